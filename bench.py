@@ -2,22 +2,28 @@
 """bench.py -- triplets/sec of P-Companion's two embedding-learning hot paths on MI355X
 (BASELINE.json metric: "Product2Vec pretrain + P-Companion joint step").
 
-Default run (no flags), one process per GPU:
-  * phase 1 = BASELINE configs[1] -- the headline `value`: 100k products, 100 types, D=128, B=4096 triplets per GPU
+Plain run (no flags besides --gpus / --steps / --warmup), one process per GPU: set-up, `--warmup` steps, `--steps` timed
+steps and the line -- nothing else:
+  * BASELINE configs[1] -- the headline `value` and `ms_per_step`: 100k products, 100 types, D=128, B=4096 triplets per GPU
     and step, 5 negatives, neighbours padded to the batch max (<=32), synthetic BPG, random-init weights.  One step =
     device batch build (Philox negative sampling + CSR neighbour rows) + gather + 4 FFN/BatchNorm call groups +
     attention + triplet hinge + full backward + Adam, everything inside the timed region.
-  * phase 2 = configs[2] -- object `joint` of the same JSON line: the P-Companion joint step (forward, type + item
-    hinge, backward, Adam over both type tables and the four Linears), B=4096 per GPU, T = --types (100) and, as
-    `joint_num_types_34800`, the reference's own config.py:27 NUM_TYPES.
+  * --dump-outputs DIR: after the timed steps, what the last of them computed (the loss, the updated parameters and BatchNorm
+    buffers, Adam's moments) as DIR/<name>.npy; the inputs depend only on the arguments, so two builds compare output for output.
 
-    python bench.py --gpus 1 --steps 50 --warmup 10
+--full adds everything else the line has carried, measured as before: the HIP-event `roofline` of the headline's timed
+region, `sustained`, `cpu_baseline`, the DROPOUT = 0.1 legs, `dropin_dense`, configs[2] -- object `joint`: the P-Companion
+joint step (forward, type + item hinge, backward, Adam over both type tables and the four Linears), B=4096 per GPU,
+T = --types (100) and, as `joint_num_types_34800`, the reference's own config.py:27 NUM_TYPES -- and `large_catalogue`
+(configs[3] / [4]).  The --no-* switches below turn single legs of --full off.
+
+    python bench.py --gpus 1 --steps 50 --warmup 10 [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
-ONE JSON line on rank 0.  `roofline` is for the dominant kernel family of the headline phase (gemm_nt_kernel):
+ONE JSON line on rank 0.  `roofline` (--full) is for the dominant kernel family of the headline phase (gemm_nt_kernel):
 algorithmic FLOPs and bytes / HIP-event time on the launch stream; BOTH fractions are printed (matrix cores: fp32-grade
 products as six v_mfma_f32_32x32x16_bf16 over a three-way bf16 split, i.e. dense bf16 peak / 6; HBM: 8 TB/s) and
-`bound` names the roof that is nearer (the larger lower bound on the launch time).  `cpu_baseline` = the oracle port
+`bound` names the roof that is nearer (the larger lower bound on the launch time).  `cpu_baseline` (--full) = the oracle port
 timed on this box's host cores (compute-only over >= 20 steps, and end to end with the host loader).
 """
 import argparse
@@ -108,6 +114,40 @@ def two_roof(flops, nbytes, seconds, peak_tflops):
     t_hbm = nbytes / (HBM_PEAK_GBS * 1e9)
     fm, fh = (t_mfma / seconds, t_hbm / seconds) if seconds > 0 else (0.0, 0.0)
     return ("mfma" if t_mfma >= t_hbm else "hbm"), fm, fh
+
+
+DUMP_CAP_BYTES = 64 << 20
+
+
+def step_outputs(loss, model, opt, skip=()):
+    """What a caller of the timed step holds after it, copied to the host: the loss (the joint step: its loss vector), every
+    parameter and buffer the step updated (module state_dict, inputs named in `skip` left out) and Adam's two moment buffers."""
+    out = {"loss": loss.detach().cpu()}
+    for k, v in model.state_dict().items():
+        if k not in skip:
+            out[k] = v.detach().cpu()
+    out["adam.exp_avg"] = opt.exp_avg.detach().cpu()
+    out["adam.exp_avg_sq"] = opt.exp_avg_sq.detach().cpu()
+    return out
+
+
+def dump_outputs(d, outs, cap=DUMP_CAP_BYTES):
+    """--dump-outputs: one DIR/<name>.npy per array, float64 for float64 / integer tensors, float32 otherwise.  If the arrays
+    exceed `cap` bytes in all, each one over an even share of it is replaced by a fixed sample of its flattened elements (the
+    same seeded indices in every run, sorted)."""
+    os.makedirs(d, exist_ok=True)
+    arrs = {}
+    for k, v in outs.items():
+        a = v.numpy() if torch.is_tensor(v) else np.asarray(v)
+        arrs[k] = np.atleast_1d(a.astype(np.float64 if a.dtype in (np.float64, np.int64, np.int32) else np.float32))
+    if sum(a.nbytes for a in arrs.values()) > cap:
+        share = cap // len(arrs)
+        for k, a in arrs.items():
+            if a.nbytes > share:
+                idx = np.sort(np.random.default_rng(0).choice(a.size, share // a.itemsize, replace=False))
+                arrs[k] = a.reshape(-1)[idx]
+    for k, a in arrs.items():
+        np.save(os.path.join(d, k + ".npy"), a)
 
 
 # ----------------------------------------------------------------------------------------------- CPU legs
@@ -217,9 +257,9 @@ LOADER_OPTS = {}             # developer A/B (PC_BENCH_SET_OPTIONS "rows=0"): at
 EXCHANGE = {"ex": None}      # the replicas' gradient exchange (distributed.make_exchange), set once in main() when N > 1
 
 
-def run_joint(args, rank, world, dev, types, steps, warmup, want_cpu, dropout=0.0, exchange=None):
+def run_joint(args, rank, world, dev, types, steps, warmup, want_cpu, dropout=0.0, exchange=None, dump=None):
     """BASELINE configs[2]: 100k products, T types, B pairs per GPU: PCompanion forward + both hinge losses + backward
-    + Adam (pc_joint_train_step + pc_adam_step), loader batch construction included."""
+    + Adam (pc_joint_train_step + pc_adam_step), loader batch construction included.  dump: --dump-outputs of the last timed step."""
     from types import SimpleNamespace
     from p_companion_amd import distributed as pdist
     from p_companion_amd.data import ComplementaryIndexDataset, ComplementaryIndexLoader, generate_scaled_bpg
@@ -323,6 +363,8 @@ def run_joint(args, rank, world, dev, types, steps, warmup, want_cpu, dropout=0.
     el = float(t)
     if rank != 0:
         return None
+    if dump:
+        dump_outputs(dump, step_outputs(losses, model, opt, skip=("product_embeddings.weight",)))
     value = world * args.batch * steps / el
     dev_ms = ev[0].elapsed_time(ev[1]) / steps               # HIP events on the launch stream, around the timed steps
     alg = joint_algorithmic_bytes(args.batch, types)
@@ -390,9 +432,10 @@ def run_joint(args, rank, world, dev, types, steps, warmup, want_cpu, dropout=0.
 
 # ----------------------------------------------------------------------------------------------- P2V phase
 def run_p2v(args, rank, world, dev, products, steps, warmup, want_cpu, profile_kernels=True, sustained=False, dim=None,
-            negatives=None, table_mode=None, dropout=0.0, pmc_kind="", exchange=None, hot_rows=0):
+            negatives=None, table_mode=None, dropout=0.0, pmc_kind="", exchange=None, hot_rows=0, dump=None):
     """One Product2Vec leg.  dim / negatives / table_mode default to the command line's; dropout = config.py:12's DROPOUT of
-    the attention probabilities (0.0: the parity setting, every golden test; 0.1: the reference as shipped)."""
+    the attention probabilities (0.0: the parity setting, every golden test; 0.1: the reference as shipped).  dump:
+    --dump-outputs of the last timed step."""
     from types import SimpleNamespace
     from p_companion_amd import distributed as pdist
     from p_companion_amd import ops
@@ -449,8 +492,9 @@ def run_p2v(args, rank, world, dev, products, steps, warmup, want_cpu, profile_k
                 yield b
 
     it = batches()
-    prof = ops.KernelProfile(capacity=32 * max(steps, 1))
-    if not args.profile_all:
+    # (the event pool, 64 HIP events per timed step, only for a leg that brackets launches)
+    prof = ops.KernelProfile(capacity=32 * max(steps, 1)) if profile_kernels else None
+    if prof is not None and not args.profile_all:
         prof.set_kinds(["gemm_nt_kernel"])
     n_sum = real_sum = slot_sum = 0
 
@@ -501,6 +545,8 @@ def run_p2v(args, rank, world, dev, products, steps, warmup, want_cpu, profile_k
     if multi:
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
     el = float(t)
+    if dump and rank == 0:                                    # (before the roofline's extra steps below move the parameters on)
+        dump_outputs(dump, step_outputs(loss, model, opt))
     hot_served = None
     if sharded is not None:
         sharded.raise_if_overflowed()
@@ -655,7 +701,8 @@ def run_p2v(args, rank, world, dev, products, steps, warmup, want_cpu, profile_k
                         "similarity_pairs": len(loader) * args.batch}
     if want_cpu and sharded is None and not on_device and dim == 128:    # (the oracle reads host arrays; a sharded batch indexes its own gathered table)
         res["cpu_baseline"] = p2v_cpu_baseline(bpg, last, dropout=float(dropout))
-    prof.close()
+    if prof is not None:
+        prof.close()
     if tn_prof is not None:
         tn_prof.close()
     return res
@@ -831,7 +878,7 @@ def guarded(name, fn, world):
     res = None
     # The line goes out only when every leg is through, and the harness ends the job at ITS limit (600 s, line or no line): a run in
     # which set-up, first contact and the legs before this one were slow -- not hung: the watchdogs see nothing -- must stop adding
-    # legs while the line can still be printed.  Past PC_BENCH_TOTAL_BUDGET_S (default 330 s since the process started; a default
+    # legs while the line can still be printed.  Past PC_BENCH_TOTAL_BUDGET_S (default 330 s since the process started; a --full
     # one-GPU run takes ~180 s) a secondary leg is not started and says so in its place; at N > 1 the ranks agree (MAX of the
     # elapsed times, on the drained device: the previous leg ended behind a synchronize), so that all of them skip the same legs.
     elapsed = time.monotonic() - BENCH_T0
@@ -901,7 +948,7 @@ def main():
                     help="both (default) = BASELINE's whole metric: configs[1] as the headline value + configs[2] as `joint`")
     ap.add_argument("--dropout", type=float, default=0.0,
                     help="DROPOUT of the headline legs (config.py:12 ships 0.1; 0.0 is the parity setting of every golden test). "
-                         "The default line carries the 0.1 legs beside the 0.0 ones either way")
+                         "A --full line carries the 0.1 legs beside the 0.0 ones either way")
     ap.add_argument("--sync-bn", action="store_true",
                     help="N > 1: BatchNorm statistics over all replicas' rows (two 16 KB all-reduces per step) instead of "
                          "each replica's own batch")
@@ -927,7 +974,15 @@ def main():
                          "this many most popular products live on every rank; 0 = off")
     ap.add_argument("--no-dropin", action="store_true", help="skip the `dropin_dense` leg (the reference's loop body over reference-format batches)")
     ap.add_argument("--no-sustained", action="store_true", help="skip the `sustained` leg (3 x >= 300 P2V steps across epoch boundaries)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, every other figure of the line: roofline, sustained, cpu_baseline, the dropout legs, "
+                         "dropin_dense, the joint legs and large_catalogue (the --no-* switches above act on this run)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them computed (loss, updated parameters and buffers, Adam "
+                         "moments) as DIR/<name>.npy, float32 / float64, at most 64 MB in all")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args.gpus, sys.argv[1:]))           # (nothing has touched the GPU in this process)
@@ -952,7 +1007,8 @@ def main():
     local = int(os.environ.get("PC_FORCE_DEVICE", local))
     torch.cuda.set_device(local)
     dev = torch.device("cuda", local)
-    want_cpu = not args.no_cpu_baseline and world == 1
+    full = args.full
+    want_cpu = full and not args.no_cpu_baseline and world == 1
     plain = args.products == 100_000 and args.dim == 128 and args.table == "replicated" and args.negatives == "uniform"
     rccl = rccl_info(world, dev)
     if pdist.collectives_on(world) and args.exchange != "hook":
@@ -1003,8 +1059,9 @@ def main():
             out.update(extra)
             print(json.dumps(out), flush=True)
             return
+        # (the same name with and without --full: the `joint` object it points at is measured by --full)
         out = {"metric": "triplets/sec (Product2Vec pretrain step: gather+fwd+bwd+Adam)" +
-                         (" + P-Companion joint step under `joint`" if joint else ""),
+                         (" + P-Companion joint step under `joint`" if args.phase == "both" else ""),
                "value": round(p2v["value"], 1), **common, "ms_per_step": round(p2v["ms_per_step"], 4),
                "host_enqueue_ms_per_step": p2v.get("host_enqueue_ms_per_step"),
                "host_enqueue_note": "wall time of the host between the region's two clocks / steps: its own work (loader hand-out, step wrapper, "
@@ -1018,7 +1075,7 @@ def main():
                           "dropout": args.dropout,
                           "dropout_note": "DROPOUT = 0.0 is the parity setting (ATen's mask stream cannot be reproduced: every golden-vector "
                                           "test runs at 0); the reference ships config.py:12 DROPOUT = 0.1 -- legs `p2v_dropout_0p1`, "
-                                          "`joint_dropout_0p1`, `joint_num_types_34800_dropout_0p1` of this line run that setting",
+                                          "`joint_dropout_0p1`, `joint_num_types_34800_dropout_0p1` of a --full line run that setting",
                           "table": args.table, "sharded_lookup": p2v.get("sharded_lookup"), "parallelism": f"dp{world}",
                           "batchnorm": "cross-replica" if (args.sync_bn and pdist.collectives_on(world)) else "per-replica",
                           "final_loss": round(p2v["final_loss"], 5),
@@ -1046,7 +1103,8 @@ def main():
         FINAL["emit"] = emit
     headline_dog = leg_watchdog("headline", world)               # (N > 1: a headline leg that hangs ends the job with an error line)
     if args.phase in ("both", "p2v"):
-        p2v = run_p2v(args, rank, world, dev, args.products, args.steps, args.warmup, want_cpu, sustained=not args.no_sustained,
+        p2v = run_p2v(args, rank, world, dev, args.products, args.steps, args.warmup, want_cpu, profile_kernels=full,
+                      sustained=full and not args.no_sustained, dump=args.dump_outputs,
                       dropout=args.dropout, pmc_kind="" if plain else ("big" if args.products == 100_000_000 else "cfg3" if args.products == 10_000_000 else "none"))
         if headline_dog is not None:
             headline_dog.cancel()
@@ -1054,32 +1112,32 @@ def main():
         if args.large_catalogue:
             large = run_p2v(args, rank, world, dev, args.large_catalogue, max(args.steps // 2, 5), args.warmup, False,
                             profile_kernels=False)
-        if plain and not args.no_dropout_legs and args.dropout == 0.0:
+        if full and plain and not args.no_dropout_legs and args.dropout == 0.0:
             r = guarded("p2v_dropout_0p1", lambda: run_p2v(args, rank, world, dev, args.products, max(args.steps, 30), args.warmup, want_cpu,
                                                            dropout=0.1, pmc_kind="p2vd"), world)
             if rank == 0:
                 extra["p2v_dropout_0p1"] = leg(r)
-        if plain and world == 1 and not args.no_dropin:
+        if full and plain and world == 1 and not args.no_dropin:
             # the literal plug-in surface: the reference's loop body over reference-format batches (one process: the reference has no N > 1)
             extra["dropin_dense"] = guarded("dropin_dense", lambda: run_dropin_dense(args, dev, max(args.steps, 20), 5), world)
     if headline_dog is not None:
         headline_dog.cancel()
-    if args.phase in ("both", "joint"):
+    if args.phase == "joint" or (full and args.phase == "both"):
         # (with the Product2Vec phase in front, the joint legs are secondary to the headline value: guarded like the others)
         first = (lambda name, fn: fn()) if args.phase == "joint" else (lambda name, fn: guarded(name, fn, world))
         joint = first("joint", lambda: run_joint(args, rank, world, dev, args.types, max(args.steps * 4, JOINT_MIN_STEPS), max(args.warmup, 10), want_cpu,
-                                                 dropout=args.dropout))
-        if not args.no_dropout_legs and args.dropout == 0.0:
+                                                 dropout=args.dropout, dump=args.dump_outputs if args.phase == "joint" else None))
+        if full and not args.no_dropout_legs and args.dropout == 0.0:
             extra["joint_dropout_0p1"] = guarded("joint_dropout_0p1", lambda: run_joint(args, rank, world, dev, args.types, max(args.steps * 4, JOINT_MIN_STEPS),
                                                                                          max(args.warmup, 10), want_cpu, dropout=0.1), world)
-        if not args.no_ref_types and args.types != 34800:
+        if full and not args.no_ref_types and args.types != 34800:
             joint_ref = guarded("joint_num_types_34800", lambda: run_joint(args, rank, world, dev, 34800, max(args.steps, JOINT_REF_MIN_STEPS), max(args.warmup, 10),
                                                                            want_cpu, dropout=args.dropout), world)
             if not args.no_dropout_legs and args.dropout == 0.0:
                 extra["joint_num_types_34800_dropout_0p1"] = guarded(
                     "joint_num_types_34800_dropout_0p1",
                     lambda: run_joint(args, rank, world, dev, 34800, max(args.steps, JOINT_REF_MIN_STEPS), max(args.warmup, 10), want_cpu, dropout=0.1), world)
-    if args.phase in ("both", "p2v") and plain and not args.no_large:
+    if full and args.phase in ("both", "p2v") and plain and not args.no_large:
         # BASELINE configs[3] / [4] at their real sizes, catalogue generated in HBM (this rank's shard of the table when N > 1).
         # One GPU holds configs[4] whole (102 GB of 288); the smaller catalogues are released first.
         run_joint.bpg = None

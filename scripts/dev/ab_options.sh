@@ -8,7 +8,7 @@ OUT=$R/gpurun_out/$TAG; mkdir -p $OUT
 for i in $(seq 1 $ROUNDS); do
   for v in a b; do
     if [ $v = a ]; then O=$A; else O=$B; fi
-    PC_BENCH_SET_OPTIONS=$O python3 $R/bench.py --phase p2v --steps 100 --warmup 20 --no-cpu-baseline --no-large --no-dropout-legs --no-dropin "$@" > $OUT/${v}_$i.json 2> $OUT/${v}_$i.err
+    PC_BENCH_SET_OPTIONS=$O python3 $R/bench.py --full --phase p2v --steps 100 --warmup 20 --no-cpu-baseline --no-large --no-dropout-legs --no-dropin "$@" > $OUT/${v}_$i.json 2> $OUT/${v}_$i.err
     python3 - <<PY
 import json
 d=json.load(open("$OUT/${v}_$i.json"))

@@ -6,7 +6,7 @@ OUT=$R/gpurun_out/${1:-forced}; mkdir -p $OUT
 export PC_DIST_FORCE=1 WORLD_SIZE=1 RANK=0 LOCAL_RANK=0 MASTER_ADDR=127.0.0.1
 for v in native hook; do
   export MASTER_PORT=$((29600 + RANDOM % 300))
-  python3 $R/bench.py --gpus 1 --steps 50 --warmup 10 --no-cpu-baseline --no-large --no-sustained --no-dropout-legs --exchange $v > $OUT/$v.json 2> $OUT/$v.err
+  python3 $R/bench.py --gpus 1 --full --steps 50 --warmup 10 --no-cpu-baseline --no-large --no-sustained --no-dropout-legs --exchange $v > $OUT/$v.json 2> $OUT/$v.err
   python3 - <<PY
 import json
 d=json.loads(open("$OUT/$v.json").read().strip().splitlines()[-1])      # (RCCL prints its version banner on stdout first)

@@ -1,13 +1,13 @@
 #!/bin/bash
 # Developer probe (GPU box): the driver's N > 1 command line -- torch.distributed.run, one process per rank -- rehearsed with TWO ranks
-# on the one card of the box (gloo; two ranks cannot share a GPU under RCCL), every leg of the default line included: the
+# on the one card of the box (gloo; two ranks cannot share a GPU under RCCL), every leg of the --full line included: the
 # large_catalogue legs then run their N > 1 form (each rank generates ITS shard of the 10 M / 100 M-product table in HBM, the
 # loader's all-to-all lookup crosses ranks).  Prints the line's keys and per-leg ms_per_step.
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$R/gpurun_out/${1:-torchrun2}; mkdir -p $OUT
 export PC_DIST_BACKEND=gloo PC_FORCE_DEVICE=0 HSA_ENABLE_IPC_MODE_LEGACY=0
 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port $((29700 + RANDOM % 200)) \
-    $R/bench.py --gpus 2 --steps 10 --warmup 3 --no-sustained > $OUT/line.out 2> $OUT/line.err
+    $R/bench.py --gpus 2 --full --steps 10 --warmup 3 --no-sustained > $OUT/line.out 2> $OUT/line.err
 echo "rc=$?"
 python3 - <<PY
 import json

@@ -22,7 +22,7 @@ OUT=$R/gpurun_out/$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 if [ -z "$NO_BENCH" ]; then
-python3 $R/bench.py > $OUT/bench.json 2> $OUT/bench.err
+python3 $R/bench.py --full > $OUT/bench.json 2> $OUT/bench.err
 fi
 if [ -z "$NO_TRACE" ]; then
 rocprofv3 --kernel-trace --stats -d $OUT/prof -o $TAG -- python3 $R/bench.py --phase p2v --steps 30 --warmup 5 --no-cpu-baseline --no-sustained --no-large --no-dropout-legs --no-dropin > $OUT/bench_under_rocprof.json 2> $OUT/rocprof.err

@@ -22,7 +22,7 @@ def test_bench_self_launches_its_ranks():
     env = dict(os.environ, PC_DIST_BACKEND="gloo", PC_FORCE_DEVICE="0", HSA_ENABLE_IPC_MODE_LEGACY="0")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "PC_DIST_FORCE"):
         env.pop(k, None)
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--full", "--steps", "4", "--warmup", "2",
                           "--products", "20000", "--batch", "512", "--no-cpu-baseline", "--no-sustained", "--no-large",
                           "--no-dropout-legs", "--no-ref-types"], env=env, capture_output=True, text=True, timeout=800, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-3000:]
@@ -52,7 +52,7 @@ def test_bench_world2_drives_the_large_legs():
     env = dict(os.environ, PC_DIST_BACKEND="gloo", PC_FORCE_DEVICE="0", HSA_ENABLE_IPC_MODE_LEGACY="0")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "PC_DIST_FORCE"):
         env.pop(k, None)
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2", "--phase", "p2v",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--full", "--steps", "4", "--warmup", "2", "--phase", "p2v",
                           "--no-cpu-baseline", "--no-sustained", "--no-dropout-legs"], env=env, capture_output=True, text=True,
                          timeout=800, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-3000:]
@@ -75,7 +75,7 @@ def test_bench_world2_leg_watchdog_keeps_the_headline():
     env = dict(os.environ, PC_DIST_BACKEND="gloo", PC_FORCE_DEVICE="0", HSA_ENABLE_IPC_MODE_LEGACY="0", PC_BENCH_LEG_DEADLINE_S="0.25")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "PC_DIST_FORCE"):
         env.pop(k, None)
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--full", "--steps", "4", "--warmup", "2",
                           "--products", "20000", "--batch", "512", "--no-cpu-baseline", "--no-sustained", "--no-large",
                           "--no-dropout-legs", "--no-ref-types"], env=env, capture_output=True, text=True, timeout=500, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-3000:]
@@ -92,7 +92,7 @@ def test_bench_world2_total_budget_skips_secondary_legs():
     env = dict(os.environ, PC_DIST_BACKEND="gloo", PC_FORCE_DEVICE="0", HSA_ENABLE_IPC_MODE_LEGACY="0", PC_BENCH_TOTAL_BUDGET_S="0.5")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "PC_DIST_FORCE"):
         env.pop(k, None)
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--full", "--steps", "4", "--warmup", "2",
                           "--products", "20000", "--batch", "512", "--no-cpu-baseline", "--no-sustained", "--no-large",
                           "--no-ref-types"], env=env, capture_output=True, text=True, timeout=500, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-3000:]
@@ -100,3 +100,28 @@ def test_bench_world2_total_budget_skips_secondary_legs():
     assert line["n_gpus"] == 2 and line["value"] > 0
     assert line["joint"]["error"].startswith("skipped:") and line["joint_dropout_0p1"]["error"].startswith("skipped:"), line.get("joint")
     assert "not started" in out.stderr
+
+
+@pytest.mark.timeout(600)
+def test_plain_run_is_the_headline_alone_and_dumps_its_last_step(tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W`: the Product2Vec headline over exactly K timed steps and nothing the --full run
+    adds; --dump-outputs writes the last timed step's loss, parameters, BatchNorm buffers and Adam moments."""
+    env = dict(os.environ)
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "PC_DIST_FORCE", "PC_FORCE_DEVICE"):
+        env.pop(k, None)
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "3",
+                          "--dump-outputs", str(tmp_path)], env=env, capture_output=True, text=True, timeout=500, cwd=ROOT)
+    assert out.returncode == 0, out.stderr[-3000:]
+    line = json.loads(out.stdout.strip().splitlines()[-1])
+    assert line["steps"] == 7 and line["warmup"] == 3 and line["value"] > 0 and line["ms_per_step"] > 0
+    assert line["unit"] == "triplets/s" and line["higher_is_better"] is True and line["dtype"] == "f32"
+    for k in ("joint", "joint_num_types_34800", "p2v_dropout_0p1", "dropin_dense", "large_catalogue"):
+        assert k not in line, k
+    assert line["roofline"] is None and line["sustained"] is None and line["cpu_baseline"] is None
+    import numpy as np
+    loss = np.load(tmp_path / "loss.npy")
+    assert loss.dtype == np.float32 and abs(float(loss[0]) - line["config"]["final_loss"]) < 1e-5
+    for k in ("ffn.0.weight", "ffn.1.running_mean", "adam.exp_avg", "adam.exp_avg_sq"):
+        a = np.load(tmp_path / f"{k}.npy")
+        assert a.dtype == np.float32 and a.size > 0 and np.isfinite(a).all(), k
+    assert sum(os.path.getsize(tmp_path / f) for f in os.listdir(tmp_path)) <= 64 << 20
