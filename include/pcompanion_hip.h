@@ -230,6 +230,19 @@ int pc_p2v_attention_backward(const pc_p2v_tensors *p, const pc_p2v_tensors *g,
                               float *dkeys, int accumulate, void *ws, size_t ws_bytes,
                               void *stream);
 
+/* P11 over a device CSR: Product2Vec.generate_all_embeddings (product2vec.py:83-111), eval mode, the whole table.
+ *   e1[i]  = ffn(features[i])                                      every product (written; the caller keeps or drops it)
+ *   out[i] = e1[i]                                                 cv_rowptr[i+1] == cv_rowptr[i]
+ *   out[i] = attn(query = ffn(e1[i]), keys = e1[cv_col[cv_rowptr[i] : cv_rowptr[i+1]]])   otherwise (exact list, no padding)
+ * features, e1, out [n_products, D] (D = p->dim: 128 or 256); cv_rowptr [n_products + 1], cv_col [cv_rowptr[n_products]],
+ * int32, device-resident; neighbour ids are trusted (as in pc_gather_rows).  Any degree.  Products are processed in chunks
+ * of chunk_rows (1 .. 2^20) on `stream`, a handful of launches per chunk, no host readback; the workspace depends on
+ * chunk_rows only: pc_p2v_export_workspace_bytes(chunk_rows, D). */
+size_t pc_p2v_export_workspace_bytes(int chunk_rows, int dim);
+int pc_p2v_export_embeddings(const pc_p2v_tensors *p, const float *features, int64_t n_products,
+                             const int32_t *cv_rowptr, const int32_t *cv_col, float *e1, float *out,
+                             int chunk_rows, void *ws, size_t ws_bytes, void *stream);
+
 /* P9: the loss of Product2Vec.train_model (product2vec.py:137-154), forward + backward:
  *   d+ = ||a - p + 1e-6||, d- = mean_j ||a - n_j + 1e-6||, loss = mean_b relu(margin - d+ + d-)
  * a[B,D], p[B,D], n[B*K,D] (row b*K+j).  Outputs: loss[1], d_pos[B], d_neg[B] and, when

@@ -100,6 +100,8 @@ SIGNATURES = {
     "pc_p2v_attention_forward": (_i, [_P(P2VTensors), _vp, _vp, _i, _i, _vp, _P(AttnSaved), _vp, _sz, _vp]),
     "pc_p2v_attention_backward": (_i, [_P(P2VTensors), _P(P2VTensors), _vp, _vp, _i, _i, _vp, _P(AttnSaved), _vp,
                                        _vp, _i, _vp, _sz, _vp]),
+    "pc_p2v_export_workspace_bytes": (_sz, [_i, _i]),
+    "pc_p2v_export_embeddings": (_i, [_P(P2VTensors), _vp, _i64, _vp, _vp, _vp, _vp, _i, _vp, _sz, _vp]),
     "pc_p2v_triplet_loss": (_i, [_vp, _vp, _vp, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "pc_p2v_triplet_loss_dim": (_i, [_vp, _vp, _vp, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "pc_adam_step": (_i, [_vp, _vp, _vp, _vp, _sz, _vp, _vp, _d, _d, _d, _d, _vp]),

@@ -8,6 +8,7 @@ with CSR arrays that live on the device: neighbours are an O(deg) row of (cv_row
 a batch is a handful of int32 index arrays, and the feature gather happens inside the HIP
 kernels.  Product i is the reference's "P%06d" % i (synthetic_data.py:43).
 """
+from collections.abc import Mapping
 from dataclasses import dataclass, field
 from typing import Dict, Optional
 
@@ -187,6 +188,42 @@ class DeviceBPG:
                       cv_rowptr=c("cv_rowptr"), cv_col=c("cv_col"), similarity_pairs=c("sim_pairs"),
                       complementary_pairs=(c("comp_pairs") if "comp_pairs" in a else np.zeros((0, 2), np.int32)),
                       n_types=self.n_types, sim_rowptr=c("sim_rowptr"), sim_col=c("sim_col"))
+
+
+class EmbeddingMapping(Mapping):
+    """The embedding table of a DeviceBPG export as a read-only Mapping[str, Tensor]: keys P{i:06d} in product order (the
+    ids IntBPG's export uses), a lookup copies that ONE row to the host.  `table` is the [P,D] tensor itself (on the
+    device); a P-entry dict of host tensors is never built."""
+
+    def __init__(self, table):
+        if not isinstance(table, torch.Tensor) or table.dim() != 2:
+            raise TypeError("EmbeddingMapping: expected a [P, D] tensor")
+        self.table = table
+
+    def _index(self, key):
+        if isinstance(key, str) and len(key) > 1 and key[0] == "P" and key[1:].isdigit():
+            i = int(key[1:])
+            if i < self.table.shape[0] and key == f"P{i:06d}":
+                return i
+        return -1
+
+    def __getitem__(self, key):
+        i = self._index(key)
+        if i < 0:
+            raise KeyError(key)
+        return self.table[i].cpu()
+
+    def __contains__(self, key):
+        return self._index(key) >= 0
+
+    def __len__(self):
+        return int(self.table.shape[0])
+
+    def __iter__(self):
+        return (f"P{i:06d}" for i in range(int(self.table.shape[0])))
+
+    def __repr__(self):
+        return f"EmbeddingMapping({len(self)} x {int(self.table.shape[1])} on {self.table.device})"
 
 
 def generate_device_bpg(num_products=100_000, num_types=100, seed=0, mean_degree=16.0, degree_cap=32, dim=128,

@@ -1258,6 +1258,58 @@ def hadamard_backward(dproj, pi, tp):
     return dpi, dtp
 
 
+# ----------------------------------------------------------------------------- P11 over a device CSR
+EXPORT_CHUNK_ROWS = 65536          # products per chunk of pc_p2v_export_embeddings (workspace 0.78 GB at D = 128)
+EXPORT_MAX_CHUNK_ROWS = 1 << 20
+
+
+def export_embeddings(params, features, cv_rowptr, cv_col, chunk_rows=None, out=None):
+    """Product2Vec.generate_all_embeddings (product2vec.py:83-111), eval mode, over a co-view CSR that stays on the device:
+    features [P,D] fp32, cv_rowptr [P+1] / cv_col [E] int32, all CUDA -> the embedding table [P,D] (into `out` when given).
+    One call of pc_p2v_export_embeddings: chunks of `chunk_rows` products, workspace bounded by the chunk, not by P.
+    Neighbour ids are trusted (as in gather_rows); the CSR's shape is checked here, before anything is launched."""
+    st, dev = p2v_struct(params)
+    d = st.dim
+    _req(features, torch.float32, "features")
+    _req(cv_rowptr, torch.int32, "cv_rowptr")
+    _req(cv_col, torch.int32, "cv_col")
+    if features.dim() != 2 or features.shape[1] != d:
+        raise ValueError(f"features: expected [P, {d}], got {tuple(features.shape)}")
+    P = int(features.shape[0])
+    if P == 0:
+        raise ValueError("features: no products")
+    if cv_rowptr.dim() != 1 or cv_rowptr.numel() != P + 1:
+        raise ValueError(f"cv_rowptr: expected {P + 1} offsets for {P} products, got shape {tuple(cv_rowptr.shape)}")
+    if cv_col.dim() != 1:
+        raise ValueError(f"cv_col: expected a 1-D id list, got shape {tuple(cv_col.shape)}")
+    for name, t in (("features", features), ("cv_rowptr", cv_rowptr), ("cv_col", cv_col)):
+        if t.device != dev:
+            raise ValueError(f"{name}: on {t.device}, the parameters are on {dev}")
+    ends = cv_rowptr[[0, P]].cpu()                    # (the one readback: a CSR that does not close is refused before launch)
+    if int(ends[0]) != 0 or int(ends[1]) != cv_col.numel():
+        raise ValueError(f"cv_rowptr must run from 0 to len(cv_col) = {cv_col.numel()}, got {int(ends[0])} .. {int(ends[1])}")
+    chunk = EXPORT_CHUNK_ROWS if chunk_rows is None else int(chunk_rows)
+    if not 1 <= chunk <= EXPORT_MAX_CHUNK_ROWS:
+        raise ValueError(f"chunk_rows must be in [1, {EXPORT_MAX_CHUNK_ROWS}], got {chunk}")
+    chunk = min(chunk, P)
+    if out is not None:
+        _req(out, torch.float32, "out", (P, d))
+    nbytes = _lib.lib().pc_p2v_export_workspace_bytes(chunk, d)
+    need = nbytes + P * d * 4 * (2 if out is None else 1)         # workspace, e1, (out)
+    free = torch.cuda.mem_get_info(dev)[0] + torch.cuda.memory_reserved(dev) - torch.cuda.memory_allocated(dev)   # (+ torch's cache)
+    if need > free:
+        raise MemoryError(f"export of {P} x {d} embeddings needs {need / 2**30:.1f} GiB more device memory "
+                          f"(e1 and the output table, {P * d * 4 / 2**30:.1f} GiB each, plus the chunk workspace), "
+                          f"{free / 2**30:.1f} GiB free on {dev}")
+    if out is None:
+        out = torch.empty(P, d, dtype=torch.float32, device=dev)
+    e1 = torch.empty(P, d, dtype=torch.float32, device=dev)
+    ws = alloc(nbytes, torch.uint8, dev)
+    check(_lib.lib().pc_p2v_export_embeddings(ctypes.byref(st), _p(features), P, _p(cv_rowptr), _p(cv_col), _p(e1), _p(out),
+                                              chunk, _p(ws), nbytes, _stream()), "pc_p2v_export_embeddings")
+    return out
+
+
 def gather_rows(table, idx):
     rows = idx.numel()
     width = table.shape[1]

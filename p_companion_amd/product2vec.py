@@ -482,13 +482,28 @@ class Product2Vec(nn.Module, _FlatParamsMixin):
 
     # ------------------------------------------------------------------ P11
     @torch.no_grad()
-    def generate_embedding_table(self, features: torch.Tensor, cv_rowptr: np.ndarray, cv_col: np.ndarray):
+    def generate_embedding_table(self, features: torch.Tensor, cv_rowptr, cv_col, chunk_rows=None):
         """Batched device pass of generate_all_embeddings (product2vec.py:83-111), eval mode:
         pass 1 e1 = ffn(x) for every product; pass 2, for products with co-view out-neighbours,
         attention(query = ffn(e1)  [the reference re-applies the FFN to the stored embedding,
         :105-108 -> :73], keys = ffn(neighbour features) = e1[neighbours]) over the product's
-        exact neighbour list (no padding in this pass).  Products are grouped by degree so each
-        group is one rectangular attention launch."""
+        exact neighbour list (no padding in this pass).
+        cv_rowptr / cv_col as CUDA int32 tensors: the CSR stays on the device and the export is one chunked call
+        (ops.export_embeddings; chunk_rows products per chunk).  As host numpy arrays: products are grouped by degree on
+        the host so each group is one rectangular attention launch."""
+        if isinstance(cv_rowptr, torch.Tensor) or isinstance(cv_col, torch.Tensor):
+            for name, t in (("cv_rowptr", cv_rowptr), ("cv_col", cv_col)):
+                if not isinstance(t, torch.Tensor) or not t.is_cuda:
+                    raise TypeError(f"generate_embedding_table: {name} must be a CUDA int32 tensor when the CSR is on the "
+                                    "device (or both host numpy arrays)")
+            was_training = self.training
+            self.eval()
+            try:
+                out = ops.export_embeddings(self._tensor_dict(), self._dev(features), cv_rowptr, cv_col, chunk_rows=chunk_rows)
+            finally:
+                self.train(was_training)
+            self.last_embedding_table = out
+            return out
         was_training = self.training
         self.eval()
         params = self._tensor_dict()
@@ -519,8 +534,21 @@ class Product2Vec(nn.Module, _FlatParamsMixin):
         """Generate embeddings for all products in the BPG (product2vec.py:83-111).
         Accepts the integer BPG (p_companion_amd.data.IntBPG) or a reference-style
         BehaviorProductGraph (nodes dict + edges['co_view'] set).  Returns Dict[str, Tensor[128]]
-        on the CPU like the reference; the device table stays in self.last_embedding_table."""
-        from .data import IntBPG
+        on the CPU like the reference; the device table stays in self.last_embedding_table.
+        A DeviceBPG (world = 1) takes the device-CSR export and returns a read-only Mapping keyed P{i:06d} over the device
+        table (data.EmbeddingMapping); a sharded one (world > 1) is refused."""
+        from .data import DeviceBPG, EmbeddingMapping, IntBPG
+        if isinstance(bpg, DeviceBPG):
+            # the large-catalogue path: CSR and features stay in HBM; the result is a read-only Mapping over the device
+            # table (one row read per lookup) -- a P-entry dict of host tensors is not built
+            if bpg.world != 1:
+                raise ValueError(f"generate_all_embeddings: this DeviceBPG holds a cyclic 1/{bpg.world} shard of the features "
+                                 f"(rank {bpg.rank}); the export needs the whole table on one device -- generate it with world = 1")
+            g = bpg.cuda(self._device())
+            if "features" not in g:
+                raise ValueError("generate_all_embeddings: the DeviceBPG was generated without features")
+            table = self.generate_embedding_table(g["features"], g["cv_rowptr"], g["cv_col"])
+            return EmbeddingMapping(table)
         if isinstance(bpg, IntBPG):
             ids = [f"P{i:06d}" for i in range(bpg.num_products)]
             feats = bpg.cuda(self._device())["features"]
