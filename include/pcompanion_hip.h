@@ -925,6 +925,20 @@ int pc_retrieve_topk(const float *proj, const int32_t *types, int rows, const in
 int pc_retrieve_topk_dim(const float *proj, const int32_t *types, int rows, const int32_t *type_rowptr,
                         const int32_t *type_col, const float *table, int n_types, int n, int dim, int32_t *out_idx,
                         float *out_score, void *stream);
+/* The same contract over a catalogue of any size (ABI 8, additive; inference.py:90-118 for a 10 M / 100 M catalogue): the
+ * rows are grouped by type on the device and each type's candidates are scored as an fp32 GEMM on v_mfma_f32_16x16x4_f32
+ * (tiles of 64 rows at dim 128, 32 at dim 256), so a candidate row is read once per tile instead of once per row.  A type's
+ * candidates are split over at most `slices` slices (0 = automatic, 16; at most 64; a slice takes at least 4096
+ * candidates), each writing a partial top-n per row that one wave per row merges.  Same out_idx / out_score as
+ * pc_retrieve_topk_dim, equal scores to the lower product index; bitwise deterministic and independent of `slices` and of
+ * the order of type_col inside a type.  No host readback: the launch geometry and the workspace
+ * (pc_retrieve_topk_grouped_workspace_bytes, 0 for arguments out of range) depend on rows, n_types, n and slices only.
+ * PC_EINVAL: null pointer, rows or n_types <= 0; PC_ESHAPE: n outside [1, 16], dim not 128 / 256, slices outside [0, 64];
+ * PC_EWORKSPACE: ws_bytes too small. */
+size_t pc_retrieve_topk_grouped_workspace_bytes(int rows, int n_types, int n, int slices);
+int pc_retrieve_topk_grouped(const float *proj, const int32_t *types, int rows, const int32_t *type_rowptr,
+                             const int32_t *type_col, const float *table, int n_types, int n, int dim, int slices,
+                             int32_t *out_idx, float *out_score, void *ws, size_t ws_bytes, void *stream);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,377 @@
+// Type-filtered top-n retrieval over a catalogue of any size (PCompanionInference.recommend, inference.py:90-118), grouped by
+// type: the same contract as pc_retrieve_topk_dim (joint.hip), a different schedule.
+//
+// pc_retrieve_topk scores one (query, type) row per wave, so every row reads all candidate rows of its type again; at 10 M
+// products / 100 types a 4096-query batch reads about 0.6 TB.  Here the rows of one type are gathered into tiles of TM
+// rows (64 at D = 128, 32 at D = 256) and each tile scores its type's candidates as an fp32 GEMM on v_mfma_f32_16x16x4_f32:
+// every candidate row is read once per tile, not once per row.  A large type's candidate range is split into up to S
+// slices; every (tile, slice) work item keeps a running top-n per row and writes it as a partial list, and one wave per
+// row merges the slices' lists.
+//
+//   count   rank[r] = atomic position of row r among the rows of its type, cnt[t] = rows of type t
+//   scan    (one workgroup) row_start[t] = exclusive sum of cnt, item_start[t] = exclusive sum of tiles(t) * slices(t)
+//   place   order[row_start[t] + rank[r]] = r
+//   score   grid-stride over the work items (count read on the device): query tile -> LDS, candidates in chunks of 64
+//           (one 16-candidate column group per wave, rows straight from global into registers, the next chunk's in
+//           flight while this one is scored), scores -> LDS, a threshold test per (row, candidate), partial top-n per row
+//   merge   one wave per row: the ns * n partial entries of its slices, n rounds of a wave-wide arg-max
+//
+// Determinism: a score is an MFMA k-chain whose order depends on the dimension index alone (step j, element e, k-lane h
+// cover dimension 16 j + 4 h + e), never on the tile, the slice or the candidate's position, so a (row, product) pair has
+// the same bits wherever it is scored.  Every selection is under the total order (score descending, product index
+// ascending), so the top n of the union does not depend on how the candidates were split, on the order of the rows in a
+// tile (the one thing the planning atomics decide), or on the order of type_col inside a type.  No float atomics.
+#include "common.h"
+
+#define RG_NONE 0x7fffffff
+#define RG_MAX_N 16
+#define RG_AUTO_SLICES 16
+#define RG_MAX_SLICES 64
+#define RG_SLICE_MIN 4096          // candidates a slice gets at least (fewer slices for a small type)
+#define RG_CHUNK 64                // candidates per chunk: four waves x 16
+#define RG_MAX_GRID 4096
+
+// Slices of a type with C candidates at most S slices: ns slices of L candidates (L a multiple of the chunk, the last slice
+// shorter), none empty.  Host and device use the same arithmetic.
+__host__ __device__ __forceinline__ void rg_slice_plan(int C, int S, int& ns, int& L) {
+    if (C <= 0) { ns = 0; L = 0; return; }
+    int want = (C + RG_SLICE_MIN - 1) / RG_SLICE_MIN;
+    if (want > S) want = S;
+    const int per = (C + want - 1) / want;
+    L = (per + RG_CHUNK - 1) / RG_CHUNK * RG_CHUNK;
+    ns = (C + L - 1) / L;
+}
+
+__device__ __forceinline__ bool rg_better(float x, int xi, float y, int yi) { return x > y || (x == y && xi < yi); }
+
+// insert (x, xi) into the descending list v / ix of length n (the caller has checked it beats the n-th entry)
+__device__ __forceinline__ void rg_insert(float* v, int* ix, int n, float x, int xi) {
+#pragma unroll
+    for (int j = 0; j < RG_MAX_N; j++) {
+        if (j < n && rg_better(x, xi, v[j], ix[j])) {
+            const float tv = v[j]; const int ti = ix[j];
+            v[j] = x; ix[j] = xi; x = tv; xi = ti;
+        }
+    }
+}
+__device__ __forceinline__ void rg_nth(const float* v, const int* ix, int n, float& tv, int& ti) {
+#pragma unroll
+    for (int j = 0; j < RG_MAX_N; j++)
+        if (j == n - 1) { tv = v[j]; ti = ix[j]; }
+}
+__device__ __forceinline__ void rg_pop(float* v, int* ix) {
+#pragma unroll
+    for (int j = 0; j < RG_MAX_N - 1; j++) { v[j] = v[j + 1]; ix[j] = ix[j + 1]; }
+    v[RG_MAX_N - 1] = -INFINITY; ix[RG_MAX_N - 1] = RG_NONE;
+}
+
+__global__ __launch_bounds__(256) void rg_count_kernel(const int32_t* __restrict__ types, int rows, int n_types,
+                                                       int32_t* __restrict__ cnt, int32_t* __restrict__ rank) {
+    const int r = blockIdx.x * 256 + threadIdx.x;
+    if (r >= rows) return;
+    const int t = types[r];
+    if (t >= 0 && t < n_types) rank[r] = atomicAdd(&cnt[t], 1);
+}
+
+// One workgroup: each thread sums a contiguous run of types, a block scan of the run totals, then the run is written.
+__global__ __launch_bounds__(1024) void rg_scan_kernel(const int32_t* __restrict__ cnt, const int32_t* __restrict__ type_rowptr,
+                                                       int n_types, int S, int TM, int32_t* __restrict__ row_start,
+                                                       int64_t* __restrict__ item_start) {
+    __shared__ int64_t sr[1024], si[1024];
+    const int tid = threadIdx.x;
+    const int per = (n_types + 1023) / 1024;
+    const int t0 = min(tid * per, n_types), t1 = min(t0 + per, n_types);
+    auto items = [&](int t, int c) -> int64_t {
+        int ns, L;
+        rg_slice_plan(type_rowptr[t + 1] - type_rowptr[t], S, ns, L);
+        return c > 0 ? (int64_t)((c + TM - 1) / TM) * ns : 0;
+    };
+    int64_t a = 0, b = 0;
+    for (int t = t0; t < t1; t++) { const int c = cnt[t]; a += c; b += items(t, c); }
+    sr[tid] = a; si[tid] = b;
+    __syncthreads();
+    for (int o = 1; o < 1024; o <<= 1) {                  // inclusive Hillis-Steele scan
+        const int64_t xa = tid >= o ? sr[tid - o] : 0, xb = tid >= o ? si[tid - o] : 0;
+        __syncthreads();
+        sr[tid] += xa; si[tid] += xb;
+        __syncthreads();
+    }
+    int64_t ra = sr[tid] - a, rb = si[tid] - b;
+    for (int t = t0; t < t1; t++) {
+        const int c = cnt[t];
+        row_start[t] = (int32_t)ra; item_start[t] = rb;
+        ra += c; rb += items(t, c);
+    }
+    if (tid == 1023) { row_start[n_types] = (int32_t)sr[1023]; item_start[n_types] = si[1023]; }
+}
+
+__global__ __launch_bounds__(256) void rg_place_kernel(const int32_t* __restrict__ types, int rows, int n_types,
+                                                       const int32_t* __restrict__ rank, const int32_t* __restrict__ row_start,
+                                                       int32_t* __restrict__ order) {
+    const int r = blockIdx.x * 256 + threadIdx.x;
+    if (r >= rows) return;
+    const int t = types[r];
+    if (t >= 0 && t < n_types) order[row_start[t] + rank[r]] = r;
+}
+
+// Work item w = (type t, slice s, tile j), items of one type ordered slice-major so that the tiles running side by side read
+// the same candidates (L2).  Lane l of wave wv: column c = l & 15 (candidate wv * 16 + c of the chunk, query row g * 16 + c
+// of the A operand), k-lane h = l >> 4.  Partial lists: pv / pi [rows][S][n] at the row's grouped position.
+template <int D>
+// three waves per SIMD at D = 128 (the LDS allows three workgroups per CU); at D = 256 two, which it needs to keep its
+// registers out of scratch
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(D == 128 ? 3 : 2))) void rg_score_kernel(const float* __restrict__ proj, const int32_t* __restrict__ type_rowptr,
+                                                       const int32_t* __restrict__ type_col, const float* __restrict__ table,
+                                                       int n_types, int n, int S, const int32_t* __restrict__ cnt,
+                                                       const int32_t* __restrict__ row_start,
+                                                       const int64_t* __restrict__ item_start,
+                                                       const int32_t* __restrict__ order, float* __restrict__ pv,
+                                                       int32_t* __restrict__ pi) {
+    constexpr int TM = 8192 / D;             // rows per tile: 64 (D = 128) or 32 (D = 256): a 32 KB query tile
+    constexpr int RG = TM / 16;              // 16-row groups
+    constexpr int QS = D + 4;                // padded LDS row
+    constexpr int TPR = 256 / TM;            // threads per row in the selection phase
+    constexpr int CPT = RG_CHUNK / TPR;      // candidates per thread per chunk
+    constexpr int NB = D / 16;               // float4 operands per lane per candidate
+    __shared__ __attribute__((aligned(16))) float q[TM * QS];
+    __shared__ float sc[TM][RG_CHUNK + 1];
+    __shared__ int cid[RG_CHUNK];
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, c = lane & 15, h = lane >> 4;
+    const int rr = tid / TPR, qq = tid % TPR;
+    const int64_t n_items = item_start[n_types];
+    for (int64_t w = blockIdx.x; w < n_items; w += gridDim.x) {
+        int lo = 0, hi = n_types - 1;                     // the largest t with item_start[t] <= w (< n_types: w < n_items)
+        while (lo < hi) {
+            const int mid = (lo + hi + 1) >> 1;
+            if (item_start[mid] <= w) lo = mid; else hi = mid - 1;
+        }
+        const int t = lo;
+        const int rows_t = cnt[t];
+        const int tiles = (rows_t + TM - 1) / TM;
+        const int local = (int)(w - item_start[t]);
+        const int s = local / tiles, j = local - s * tiles;
+        const int p0 = row_start[t] + j * TM;
+        const int valid = min(TM, rows_t - j * TM);
+        const int rg = (valid + 15) >> 4;
+        const int c0 = type_rowptr[t], C = type_rowptr[t + 1] - c0;
+        int ns, L;
+        rg_slice_plan(C, S, ns, L);
+        const int cb0 = c0 + s * L, ce = c0 + min(C, (s + 1) * L);
+
+        __syncthreads();                                  // the previous item's readers of q are done
+        for (int e = tid; e < rg * 16 * (D / 4); e += 256) {          // (rows past the last 16-row group are never read)
+            const int row = e / (D / 4), d4 = e - row * (D / 4);
+            float4 x = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (row < valid) x = reinterpret_cast<const float4*>(proj + (size_t)order[p0 + row] * D)[d4];
+            *reinterpret_cast<float4*>(&q[row * QS + 4 * d4]) = x;
+        }
+        float v[RG_MAX_N];
+        int ix[RG_MAX_N];
+#pragma unroll
+        for (int k = 0; k < RG_MAX_N; k++) { v[k] = -INFINITY; ix[k] = RG_NONE; }
+        float tv = -INFINITY, hv = -INFINITY;             // this thread's n-th entry; the row's threshold
+        int ti = RG_NONE, hix = RG_NONE;
+
+        auto load_pid = [&](int cb) { const int cc = cb + wv * 16 + c; return cc < ce ? type_col[cc] : -1; };
+        auto load_b = [&](float4* b, int pid) {
+            if (pid >= 0) {
+                const float4* f = reinterpret_cast<const float4*>(table + (size_t)pid * D) + h;
+#pragma unroll
+                for (int k = 0; k < NB; k++) b[k] = f[4 * k];
+            } else {
+#pragma unroll
+                for (int k = 0; k < NB; k++) b[k] = make_float4(0.f, 0.f, 0.f, 0.f);
+            }
+        };
+        float4 bn[NB];
+        int pidn = load_pid(cb0);
+        load_b(bn, pidn);
+        int pidnn = load_pid(cb0 + RG_CHUNK);
+        __syncthreads();                                  // query tile in LDS
+
+        for (int cb = cb0; cb < ce; cb += RG_CHUNK) {
+            float4 b[NB];
+#pragma unroll
+            for (int k = 0; k < NB; k++) b[k] = bn[k];
+            const int pid = pidn;
+            pidn = pidnn;
+            if (cb + RG_CHUNK < ce) load_b(bn, pidn);     // the next chunk's rows in flight while this one is scored
+            pidnn = load_pid(cb + 2 * RG_CHUNK);
+            f32x4 acc[RG];
+#pragma unroll
+            for (int g = 0; g < RG; g++) acc[g] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int k = 0; k < NB; k++) {
+#pragma unroll
+                for (int g = 0; g < RG; g++) {
+                    if (g < rg) {
+                        const float4 a = *reinterpret_cast<const float4*>(&q[(g * 16 + c) * QS + 16 * k + 4 * h]);
+                        acc[g] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, b[k].x, acc[g], 0, 0, 0);
+                        acc[g] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, b[k].y, acc[g], 0, 0, 0);
+                        acc[g] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, b[k].z, acc[g], 0, 0, 0);
+                        acc[g] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, b[k].w, acc[g], 0, 0, 0);
+                    }
+                }
+            }
+            // C/D map of the 16x16 f32 MFMA: column lane & 15 (the candidate), row 4 (lane >> 4) + reg (the query row)
+#pragma unroll
+            for (int g = 0; g < RG; g++)
+                if (g < rg) {
+#pragma unroll
+                    for (int k = 0; k < 4; k++) sc[g * 16 + 4 * h + k][wv * 16 + c] = acc[g][k];
+                }
+            if (h == 0) cid[wv * 16 + c] = pid < 0 ? RG_NONE : pid;
+            __syncthreads();
+            // a candidate that does not beat the row's threshold -- the best of the TPR threads' n-th entries, so n products
+            // of the row beat it -- is out.  The test is cheap; the insertions then run as a loop over each lane's own
+            // survivors, so a wave pays for its busiest lane, not for every candidate some lane keeps.
+            unsigned keep = 0;
+            if (rr < valid) {
+#pragma unroll
+                for (int k = 0; k < CPT; k++) {
+                    const int col = qq + TPR * k;
+                    const int xi = cid[col];
+                    if (xi != RG_NONE && rg_better(sc[rr][col], xi, hv, hix)) keep |= 1u << k;
+                }
+            }
+            while (keep) {
+                const int k = __builtin_ctz(keep);
+                keep &= keep - 1;
+                const int col = qq + TPR * k;
+                const int xi = cid[col];
+                const float x = sc[rr][col];
+                if (rg_better(x, xi, hv, hix)) {
+                    rg_insert(v, ix, n, x, xi);
+                    rg_nth(v, ix, n, tv, ti);
+                    if (rg_better(tv, ti, hv, hix)) { hv = tv; hix = ti; }
+                }
+            }
+#pragma unroll
+            for (int o = TPR / 2; o >= 1; o >>= 1) {
+                const float ov = __shfl_xor(hv, o, 64);
+                const int oi = __shfl_xor(hix, o, 64);
+                if (rg_better(ov, oi, hv, hix)) { hv = ov; hix = oi; }
+            }
+            __syncthreads();
+        }
+        // the TPR lists of a row (adjacent lanes) -> the slice's top n of the row
+        for (int k = 0; k < n; k++) {
+            float bv = v[0];
+            int bi = ix[0];
+#pragma unroll
+            for (int o = TPR / 2; o >= 1; o >>= 1) {
+                const float ov = __shfl_xor(bv, o, 64);
+                const int oi = __shfl_xor(bi, o, 64);
+                if (rg_better(ov, oi, bv, bi)) { bv = ov; bi = oi; }
+            }
+            if (ix[0] == bi && bi != RG_NONE) rg_pop(v, ix);
+            if (qq == 0 && rr < valid) {
+                const size_t o = ((size_t)(p0 + rr) * S + s) * n + k;
+                pv[o] = bv;
+                pi[o] = bi;
+            }
+        }
+    }
+}
+
+// One wave per row: the top n of its slices' partial lists (retrieve_topk_kernel's wave-wide arg-max pop).
+__global__ __launch_bounds__(256) void rg_merge_kernel(const int32_t* __restrict__ types, int rows,
+                                                       const int32_t* __restrict__ type_rowptr, int n_types, int n, int S,
+                                                       const int32_t* __restrict__ rank, const int32_t* __restrict__ row_start,
+                                                       const float* __restrict__ pv, const int32_t* __restrict__ pi,
+                                                       int32_t* __restrict__ out_idx, float* __restrict__ out_score) {
+    const int lane = threadIdx.x & 63;
+    const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (r >= rows) return;                                // wave-uniform
+    const int t = types[r];
+    int ns = 0, L = 0, p = 0;
+    if (t >= 0 && t < n_types) {
+        rg_slice_plan(type_rowptr[t + 1] - type_rowptr[t], S, ns, L);
+        if (ns > 0) p = row_start[t] + rank[r];
+    }
+    float v[RG_MAX_N];
+    int ix[RG_MAX_N];
+#pragma unroll
+    for (int k = 0; k < RG_MAX_N; k++) { v[k] = -INFINITY; ix[k] = RG_NONE; }
+    const size_t base = (size_t)p * S * n;
+    for (int e = lane; e < ns * n; e += 64) {
+        const int xi = pi[base + e];
+        if (xi != RG_NONE) rg_insert(v, ix, n, pv[base + e], xi);
+    }
+    for (int k = 0; k < n; k++) {
+        float bv = v[0];
+        int bi = ix[0];
+#pragma unroll
+        for (int o = 32; o >= 1; o >>= 1) {
+            const float ov = __shfl_xor(bv, o, 64);
+            const int oi = __shfl_xor(bi, o, 64);
+            if (rg_better(ov, oi, bv, bi)) { bv = ov; bi = oi; }
+        }
+        if (ix[0] == bi && bi != RG_NONE) rg_pop(v, ix);
+        if (lane == 0) {
+            out_idx[(size_t)r * n + k] = bi == RG_NONE ? -1 : bi;
+            out_score[(size_t)r * n + k] = bi == RG_NONE ? -INFINITY : bv;
+        }
+    }
+}
+
+namespace {
+struct RgWs {
+    int32_t *cnt, *rank, *row_start, *order, *pi;
+    int64_t* item_start;
+    float* pv;
+    size_t bytes;
+};
+inline size_t rg_align(size_t x) { return (x + 255) & ~(size_t)255; }
+inline int rg_slices(int slices) { return slices == 0 ? RG_AUTO_SLICES : slices; }
+RgWs rg_layout(void* ws, int rows, int n_types, int n, int S) {
+    RgWs w;
+    char* p = (char*)ws;
+    size_t o = 0;
+    auto take = [&](size_t nbytes) { char* q = p ? p + o : nullptr; o += rg_align(nbytes); return q; };
+    w.cnt = (int32_t*)take((size_t)n_types * 4);
+    w.rank = (int32_t*)take((size_t)rows * 4);
+    w.row_start = (int32_t*)take((size_t)(n_types + 1) * 4);
+    w.item_start = (int64_t*)take((size_t)(n_types + 1) * 8);
+    w.order = (int32_t*)take((size_t)rows * 4);
+    w.pv = (float*)take((size_t)rows * S * n * 4);
+    w.pi = (int32_t*)take((size_t)rows * S * n * 4);
+    w.bytes = o;
+    return w;
+}
+}  // namespace
+
+extern "C" size_t pc_retrieve_topk_grouped_workspace_bytes(int rows, int n_types, int n, int slices) {
+    if (rows <= 0 || n_types <= 0 || n < 1 || n > RG_MAX_N || slices < 0 || slices > RG_MAX_SLICES) return 0;
+    return rg_layout(nullptr, rows, n_types, n, rg_slices(slices)).bytes;
+}
+
+extern "C" int pc_retrieve_topk_grouped(const float* proj, const int32_t* types, int rows, const int32_t* type_rowptr,
+                                        const int32_t* type_col, const float* table, int n_types, int n, int dim, int slices,
+                                        int32_t* out_idx, float* out_score, void* ws, size_t ws_bytes, void* stream) {
+    if (!proj || !types || !type_rowptr || !type_col || !table || !out_idx || !out_score || !ws) return PC_EINVAL;
+    if (rows <= 0 || n_types <= 0) return PC_EINVAL;
+    if (n < 1 || n > RG_MAX_N || (dim != 128 && dim != 256) || slices < 0 || slices > RG_MAX_SLICES) return PC_ESHAPE;
+    const int S = rg_slices(slices);
+    const RgWs w = rg_layout(ws, rows, n_types, n, S);
+    if (ws_bytes < w.bytes) return PC_EWORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    const int TM = 8192 / dim;
+    PC_HIP_TRY(hipMemsetAsync(w.cnt, 0, (size_t)n_types * 4, st));
+    const dim3 rgrid((rows + 255) / 256);
+    PC_LAUNCH(rg_count_kernel, rgrid, dim3(256), 0, st, types, rows, n_types, w.cnt, w.rank);
+    PC_LAUNCH(rg_scan_kernel, dim3(1), dim3(1024), 0, st, w.cnt, type_rowptr, n_types, S, TM, w.row_start, w.item_start);
+    PC_LAUNCH(rg_place_kernel, rgrid, dim3(256), 0, st, types, rows, n_types, w.rank, w.row_start, w.order);
+    // at most (tiles over all rows + one partial tile per type) x S items; the kernel reads the real count
+    const int64_t cap = ((int64_t)(rows + TM - 1) / TM + (int64_t)(rows < n_types ? rows : n_types)) * S;
+    const dim3 sgrid((unsigned)(cap < RG_MAX_GRID ? cap : RG_MAX_GRID));
+    if (dim == 128)
+        PC_LAUNCH(rg_score_kernel<128>, sgrid, dim3(256), 0, st, proj, type_rowptr, type_col, table, n_types, n, S, w.cnt,
+                  w.row_start, w.item_start, w.order, w.pv, w.pi);
+    else
+        PC_LAUNCH(rg_score_kernel<256>, sgrid, dim3(256), 0, st, proj, type_rowptr, type_col, table, n_types, n, S, w.cnt,
+                  w.row_start, w.item_start, w.order, w.pv, w.pi);
+    PC_LAUNCH(rg_merge_kernel, dim3((rows + 3) / 4), dim3(256), 0, st, types, rows, type_rowptr, n_types, n, S, w.rank,
+              w.row_start, w.pv, w.pi, out_idx, out_score);
+    return pc_launch_status();
+}

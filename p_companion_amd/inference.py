@@ -5,7 +5,9 @@ feeds forward() keys it does not read), so the semantics are taken from its reco
 (:64-124): run the model on the query, then for every predicted complementary type take the products
 of that type, score them by <projected embedding, product features> and keep torch.topk of the scores.
 Here the candidate search of all (query, type) rows is one launch of pc_retrieve_topk over a
-type-grouped CSR of the product table."""
+type-grouped CSR of the product table.  Over a DeviceBPG (a 10 M / 100 M catalogue generated in HBM) the CSR is
+built on the device (ops.type_csr) and the search is pc_retrieve_topk_grouped, which scores each type's candidates
+as a tiled fp32 GEMM; neither type_idx nor the features are copied to the host."""
 import os
 from typing import Any, Dict, List
 
@@ -13,17 +15,27 @@ import numpy as np
 import torch
 
 from . import ops
-from .data import IntBPG
+from .data import DeviceBPG, IntBPG
 from .p_companion import PCompanion
 
 
 class PCompanionInference:
     def __init__(self, model, config, bpg: IntBPG, product_ids: List[str] = None):
         """model: a trained PCompanion, or the path of a best_model.pth written by train.train
-        (train.py:63-70 layout: 'model_state_dict' holds every tensor, including the frozen table)."""
+        (train.py:63-70 layout: 'model_state_dict' holds every tensor, including the frozen table).
+        bpg: an IntBPG, or a DeviceBPG generated with world = 1 and with features (a sharded one holds a 1/world cyclic
+        shard of the features and is refused, as in Product2Vec.generate_all_embeddings)."""
         self.config = config
         self.device = config.DEVICE
         self.bpg = bpg
+        self.grouped = isinstance(bpg, DeviceBPG)
+        if self.grouped:
+            if bpg.world != 1:
+                raise ValueError(f"PCompanionInference: this DeviceBPG holds a cyclic 1/{bpg.world} shard of the features "
+                                 f"(rank {bpg.rank}); serving needs the whole table on one device -- generate it with "
+                                 "world = 1")
+            if "features" not in bpg.arrays:
+                raise ValueError("PCompanionInference: the DeviceBPG was generated without features")
         if isinstance(model, (str, os.PathLike)):
             model = self._load_model(model)
         self.model = model.to(self.device)
@@ -33,6 +45,10 @@ class PCompanionInference:
         g = bpg.cuda(self.device)
         self.features = g["features"]
         self.type_idx = g["type_idx"]
+        if self.grouped:
+            # the same CSR, built on the device: no host copy of type_idx, no host sort
+            self.type_rowptr, self.type_col = ops.type_csr(self.type_idx, bpg.n_types)
+            return
         # bpg.get_products_by_type(t) (bpg.py:40-43): products of type t in node order
         order = np.argsort(bpg.type_idx, kind="stable").astype(np.int32)
         counts = np.bincount(bpg.type_idx, minlength=bpg.n_types)
@@ -72,9 +88,10 @@ class PCompanionInference:
         out = self.model(batch)
         types = out["complementary_types"]
         b, k = types.shape
-        idx, sc = ops.retrieve_topk(out["projected_embeddings"].contiguous().reshape(b * k, -1),
-                                    types.to(torch.int32).reshape(-1).contiguous(), self.type_rowptr, self.type_col,
-                                    self.features, int(num_recommendations))
+        retrieve = ops.retrieve_topk_grouped if self.grouped else ops.retrieve_topk
+        idx, sc = retrieve(out["projected_embeddings"].contiguous().reshape(b * k, -1),
+                           types.to(torch.int32).reshape(-1).contiguous(), self.type_rowptr, self.type_col,
+                           self.features, int(num_recommendations))
         return types, idx.reshape(b, k, -1), sc.reshape(b, k, -1)
 
     def recommend(self, query_id, num_recommendations: int = 10) -> Dict[str, Any]:

@@ -1579,3 +1579,51 @@ def retrieve_topk(proj, types, type_rowptr, type_col, table, n):
                                           type_rowptr.numel() - 1, int(n), d, _p(out_idx), _p(out_sc), _stream()),
           "pc_retrieve_topk_dim")
     return out_idx, out_sc
+
+
+RETRIEVE_MAX_SLICES = 64
+
+
+def retrieve_topk_grouped(proj, types, type_rowptr, type_col, table, n, slices=0):
+    """pc_retrieve_topk_grouped: retrieve_topk's contract (idx [R,n] int32, -1 = none; scores [R,n] fp32, -inf = none) for a
+    catalogue of any size -- rows grouped by type on the device, each type's candidates scored as a tiled fp32 MFMA GEMM,
+    large types split over up to `slices` candidate slices (0 = automatic).  Bitwise deterministic, the same bits for every
+    `slices`.  Nothing is read back to the host."""
+    d = _width(table.shape[1])
+    proj = _req(proj.reshape(-1, d), torch.float32, "proj")
+    r = proj.shape[0]
+    _req(types, torch.int32, "types", (r,))
+    _req(type_rowptr, torch.int32, "type_rowptr")
+    _req(type_col, torch.int32, "type_col")
+    _req(table, torch.float32, "table")
+    n, slices, t = int(n), int(slices), type_rowptr.numel() - 1
+    if not 0 <= slices <= RETRIEVE_MAX_SLICES:
+        raise ValueError(f"slices must be in [0, {RETRIEVE_MAX_SLICES}] (0 = automatic), got {slices}")
+    out_idx = torch.empty(r, n, dtype=torch.int32, device=proj.device)
+    out_sc = torch.empty(r, n, dtype=torch.float32, device=proj.device)
+    nbytes = _lib.lib().pc_retrieve_topk_grouped_workspace_bytes(r, t, n, slices)
+    ws = workspace(nbytes, proj.device, "retrieve_grouped")
+    check(_lib.lib().pc_retrieve_topk_grouped(_p(proj), _p(types), r, _p(type_rowptr), _p(type_col), _p(table), t, n, d,
+                                              slices, _p(out_idx), _p(out_sc), _p(ws), ws.numel(), _stream()),
+          "pc_retrieve_topk_grouped")
+    return out_idx, out_sc
+
+
+def type_csr(type_idx, n_types):
+    """The type-grouped product CSR of PCompanionInference (bpg.get_products_by_type, bpg.py:40-43), built on the device from
+    an int32 CUDA type_idx [P]: rowptr [T+1] int32, col [P] int32 = the products of each type in ascending node order (the
+    stable sort; equal to np.argsort(type_idx, kind='stable') / np.bincount / np.cumsum).  Torch's device stable sort and
+    bincount: this runs once per catalogue, not on the serving path.  Type ids outside [0, n_types) are refused."""
+    _req(type_idx, torch.int32, "type_idx")
+    n_types = int(n_types)
+    if type_idx.dim() != 1 or n_types <= 0:
+        raise ValueError("type_csr: expected a 1-D type_idx and n_types > 0")
+    if type_idx.numel():
+        lo, hi = (int(x) for x in torch.aminmax(type_idx))
+        if lo < 0 or hi >= n_types:
+            raise ValueError(f"type_csr: type ids must lie in [0, {n_types}), got {lo} .. {hi}")
+    counts = torch.bincount(type_idx, minlength=n_types)
+    rowptr = torch.zeros(n_types + 1, dtype=torch.int32, device=type_idx.device)
+    rowptr[1:] = torch.cumsum(counts, 0).to(torch.int32)
+    col = torch.argsort(type_idx, stable=True).to(torch.int32)
+    return rowptr, col

@@ -18,6 +18,7 @@ import torch
 import torch.nn as nn
 
 from . import ops
+from .data import EmbeddingMapping
 from .functional import embedding, hadamard, linear
 from .item_prediction import ComplementaryItemPrediction
 from .product2vec import _FlatParamsMixin
@@ -113,6 +114,9 @@ class PCompanion(nn.Module, _FlatParamsMixin):
         self.dim = int(config.PRODUCT_EMB_DIM)
         self.use_fused_joint = self.dim == ops.D
 
+        if isinstance(pretrained_embeddings, EmbeddingMapping):
+            # generate_all_embeddings(DeviceBPG): the device table itself, keys P{i:06d} = row i (no per-key host copies)
+            pretrained_embeddings = pretrained_embeddings.table
         if isinstance(pretrained_embeddings, torch.Tensor):
             # index-mode extension: row i is product i ("P%06d" % i)
             embedding_matrix = pretrained_embeddings.detach().float()
