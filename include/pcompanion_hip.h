@@ -407,6 +407,15 @@ int pc_build_complementary_batch(const int32_t *pairs, int batch, const float *f
                                  int32_t *query_idx, int32_t *query_types, int32_t *pos_types,
                                  int32_t *neg_types, float *pos_items, float *neg_items,
                                  float *target_features, void *stream);
+/* The same contract at PRODUCT_EMB_DIM = dim (ABI 8, additive; BASELINE configs[4]): features [*,dim], pos_items / neg_items /
+ * target_features [B,dim]; filler chunk t = b * (dim / 4) + c of row b is pc_filler_chunk(seed, step, t), so at dim = 128 the
+ * output is bit-identical to pc_build_complementary_batch.  PC_EINVAL as there (or batch * dim / 4 >= 2^31); PC_ESHAPE: dim
+ * not 128 / 256. */
+int pc_build_complementary_batch_dim(const int32_t *pairs, int batch, const float *features,
+                                     const int32_t *type_idx, int n_types, int dim, uint64_t seed, uint64_t step,
+                                     int32_t *query_idx, int32_t *query_types, int32_t *pos_types,
+                                     int32_t *neg_types, float *pos_items, float *neg_items,
+                                     float *target_features, void *stream);
 
 /* P2 exact (HOST pointers, host code): SimilarityDataset._get_negative_samples
  * (data_loader.py:27-40) on CPython's `random` stream: MT19937, random.seed(int) key
@@ -867,6 +876,15 @@ int pc_epoch_permutation(int n, uint64_t seed, uint64_t epoch, int32_t *out, voi
  * ComplementaryDataset, data_loader.py:113-126): one epoch's shuffled order in one launch.  out != rows. */
 int pc_shuffle_rows_i32(const int32_t *rows, int n, int width, uint64_t seed, uint64_t epoch, int32_t *out,
                         void *stream);
+/* ComplementaryDataset's shuffle and 80/10/10 split (data_loader.py:113-126) over device pair arrays (ABI 8, additive): with
+ * L = [comp_pairs[j] (label +1) for j < n_comp] + [sim_pairs[j] (label -1) for j < n_sim] and n = n_comp + n_sim,
+ * out[i] = (query, target, label) of L[perm(lo + i)] for i in [0, hi - lo), int32 [hi - lo][3], where perm is the bijection of
+ * pc_epoch_permutation(n, seed, mode) (mode 0 / 1 / 2 = train / val / test).  Neither L nor the permutation is stored: one
+ * pass writes the mode's rows only.  The caller computes lo / hi (the host split: 0.8 n, 0.9 n).  PC_EINVAL: a null pointer
+ * (comp_pairs / sim_pairs may be NULL when their count is 0), n = 0, n >= 2^31, 0 <= lo <= hi <= n violated, mode outside
+ * 0..2.  Integer work only, no atomics. */
+int pc_comp_split_pairs(const int32_t *comp_pairs, int64_t n_comp, const int32_t *sim_pairs, int64_t n_sim, int64_t lo,
+                        int64_t hi, uint64_t seed, int mode, int32_t *out, void *stream);
 /* collate_fn pads every neighbour list to the batch maximum (data_loader.py:186-198), so the host needs two integers per
  * batch to size it: plan[b] = (max, sum) of deg[order[i]] over positions i in [b*batch, (b+1)*batch), i < n
  * (order NULL: the identity).  plan: device int64 [n_batches][2]. */

@@ -134,6 +134,7 @@ SIGNATURES = {
     "pc_build_similarity_batch": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _u64, _u64, _vp, _vp, _vp,
                                        _vp, _vp]),
     "pc_build_complementary_batch": (_i, [_vp, _i, _vp, _vp, _i, _u64, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "pc_build_complementary_batch_dim": (_i, [_vp, _i, _vp, _vp, _i, _i, _u64, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "pc_mt_state_bytes": (_sz, []),
     "pc_mt_seed": (_i, [_vp, _u64]),
     "pc_mt_getrandbits": (ctypes.c_uint32, [_vp, _i]),
@@ -213,6 +214,7 @@ SIGNATURES = {
     "pc_gen_similarity": (_i, [_i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "pc_gen_complementary": (_i, [_i64, _i, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "pc_shuffle_rows_i32": (_i, [_vp, _i, _i, _u64, _u64, _vp, _vp]),
+    "pc_comp_split_pairs": (_i, [_vp, _i64, _vp, _i64, _i64, _i64, _u64, _i, _vp, _vp]),
     "pc_epoch_plan": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
     "pc_shard_bucket": (_i, [_P(ctypes.c_void_p), _P(ctypes.c_int), _P(ctypes.c_void_p), _P(ctypes.c_int), _P(ctypes.c_void_p),
                              _i, _i, _i, _vp, _vp, _vp, _vp]),

@@ -483,6 +483,58 @@ extern "C" int pc_build_complementary_batch(const int32_t* pairs, int batch, con
     return pc_launch_status();
 }
 
+// The same builder at PRODUCT_EMB_DIM = 128 or 256 (BASELINE configs[4]): one thread per 16-B chunk, t = b * (DIM / 4) + c,
+// filler chunk t -- at DIM = 128 the same threads, loads and filler counters as build_complementary_batch_kernel, so the
+// same bits.  (Box-Muller's math-library frame: the same 48-B private segment as that kernel.)
+template <int DIM>
+__global__ void build_complementary_batch_kernel_dim(const int32_t* pairs, int B, const float* features,
+                                                     const int32_t* type_idx, int n_types, uint64_t seed, uint64_t step,
+                                                     int32_t* query_idx, int32_t* query_types, int32_t* pos_types,
+                                                     int32_t* neg_types, float* pos_items, float* neg_items,
+                                                     float* target_features) {
+    constexpr int CH = DIM / 4;
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= B * CH) return;
+    const int b = t / CH, c = t % CH;
+    const int q = pairs[3 * b], tg = pairs[3 * b + 1], lab = pairs[3 * b + 2];
+    const float4 f = *reinterpret_cast<const float4*>(features + (size_t)tg * DIM + 4 * c);
+    const float4 fill = pc_filler_chunk(seed, step, (uint32_t)t);
+    const bool pos = lab == 1;
+    *reinterpret_cast<float4*>(pos_items + (size_t)b * DIM + 4 * c) = pos ? f : fill;
+    *reinterpret_cast<float4*>(neg_items + (size_t)b * DIM + 4 * c) = pos ? fill : f;
+    if (target_features) *reinterpret_cast<float4*>(target_features + (size_t)b * DIM + 4 * c) = f;
+    if (c == 0) {
+        const int tt = type_idx[tg];
+        query_idx[b] = q;
+        query_types[b] = type_idx[q];
+        pos_types[b] = pos ? tt : 0;
+        neg_types[b] = pos ? (tt + 1) % n_types : tt;
+    }
+}
+
+extern "C" int pc_build_complementary_batch_dim(const int32_t* pairs, int batch, const float* features,
+                                                const int32_t* type_idx, int n_types, int dim, uint64_t seed, uint64_t step,
+                                                int32_t* query_idx, int32_t* query_types, int32_t* pos_types,
+                                                int32_t* neg_types, float* pos_items, float* neg_items,
+                                                float* target_features, void* stream) {
+    if (!pairs || !features || !type_idx || !query_idx || !query_types || !pos_types || !neg_types || !pos_items ||
+        !neg_items || batch <= 0 || n_types <= 0)
+        return PC_EINVAL;
+    if (dim != 128 && dim != 256) return PC_ESHAPE;
+    if ((long long)batch * (dim / 4) > 0x7fffffffll) return PC_EINVAL;       // (t is an int)
+    const int total = batch * (dim / 4);
+    hipStream_t st = (hipStream_t)stream;
+    if (dim == 128)
+        PC_LAUNCH(build_complementary_batch_kernel_dim<128>, dim3((total + 255) / 256), dim3(256), 0, st, pairs, batch, features,
+                  type_idx, n_types, seed, step, query_idx, query_types, pos_types, neg_types, pos_items, neg_items,
+                  target_features);
+    else
+        PC_LAUNCH(build_complementary_batch_kernel_dim<256>, dim3((total + 255) / 256), dim3(256), 0, st, pairs, batch, features,
+                  type_idx, n_types, seed, step, query_idx, query_types, pos_types, neg_types, pos_items, neg_items,
+                  target_features);
+    return pc_launch_status();
+}
+
 
 // ---------------------------------------------------------------------------------------
 // The epoch order of the loaders (DataLoader(shuffle=True): scripts/pretrain_product2vec.py:24-30, train.py:115-121)
@@ -550,6 +602,35 @@ extern "C" int pc_shuffle_rows_i32(const int32_t* rows, int n, int width, uint64
     if (n <= 0 || width <= 0 || !rows || !out || rows == out) return PC_EINVAL;
     const FeistelKeys f = feistel_keys((uint64_t)n, seed, epoch);
     PC_LAUNCH(shuffle_rows_kernel, dim3(((unsigned)n + 255) / 256), dim3(256), 0, (hipStream_t)stream, rows, (uint32_t)n, width, f, out);
+    return pc_launch_status();
+}
+
+// ComplementaryDataset's shuffle and split (data_loader.py:113-126) over a catalogue in HBM: the labelled list
+// L = [comp_pairs (+1) ..., sim_pairs (-1) ...] is never built, nor is the permutation -- position lo + i of the mode's keyed
+// order (the epoch_perm_at bijection, epoch = mode) is mapped to its source row, which is read from whichever pair array
+// holds it.  One pass, only the mode's rows [lo, hi) are written.
+__global__ void comp_split_pairs_kernel(const int32_t* comp_pairs, uint32_t n_comp, const int32_t* sim_pairs, uint32_t n,
+                                        uint32_t lo, uint32_t m, FeistelKeys f, int32_t* out) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= m) return;
+    const uint32_t s = epoch_perm_at(lo + i, n, f);
+    const bool comp = s < n_comp;
+    const int32_t* src = comp ? comp_pairs + 2 * (size_t)s : sim_pairs + 2 * (size_t)(s - n_comp);
+    out[3 * (size_t)i] = src[0];
+    out[3 * (size_t)i + 1] = src[1];
+    out[3 * (size_t)i + 2] = comp ? 1 : -1;
+}
+
+extern "C" int pc_comp_split_pairs(const int32_t* comp_pairs, int64_t n_comp, const int32_t* sim_pairs, int64_t n_sim,
+                                   int64_t lo, int64_t hi, uint64_t seed, int mode, int32_t* out, void* stream) {
+    if (!out || n_comp < 0 || n_sim < 0 || (n_comp > 0 && !comp_pairs) || (n_sim > 0 && !sim_pairs)) return PC_EINVAL;
+    const int64_t n = n_comp + n_sim;
+    if (n <= 0 || n >= (1ll << 31) || lo < 0 || lo > hi || hi > n || mode < 0 || mode > 2) return PC_EINVAL;
+    if (hi == lo) return PC_OK;
+    const FeistelKeys f = feistel_keys((uint64_t)n, seed, (uint64_t)mode);
+    const uint32_t m = (uint32_t)(hi - lo);
+    PC_LAUNCH(comp_split_pairs_kernel, dim3((m + 255) / 256), dim3(256), 0, (hipStream_t)stream, comp_pairs, (uint32_t)n_comp,
+              sim_pairs, (uint32_t)n, (uint32_t)lo, m, f, out);
     return pc_launch_status();
 }
 

@@ -669,8 +669,14 @@ class ComplementaryIndexDataset:
         restatement (pc_mt_shuffle): after random.seed(seed) the pair order, the split and therefore every integer
         field of every sample equal the reference's (tests/golden/g9_complementary.npz).  `rng`: an
         ops.CPythonRandom to draw from instead of a fresh one -- the reference builds its train and val datasets
-        back to back from ONE global stream (train.py:111-112)."""
+        back to back from ONE global stream (train.py:111-112).
+        A DeviceBPG (a catalogue generated in HBM) takes the philox path on the device: `pairs` is then a device int32
+        [n_mode, 3] tensor (ops.comp_split_pairs: each mode its own keyed order of the labelled list, the same 80/10/10
+        sizes); the labelled list and its permutation are never built and nothing is copied to the host."""
         self.bpg = bpg
+        if isinstance(bpg, DeviceBPG):
+            self._init_device(bpg, mode, seed, sampler)
+            return
         cp, sp = bpg.complementary_pairs, bpg.similarity_pairs
         pairs = np.concatenate([np.concatenate([cp, np.ones((len(cp), 1), np.int32)], 1),
                                 np.concatenate([sp, -np.ones((len(sp), 1), np.int32)], 1)])
@@ -688,6 +694,24 @@ class ComplementaryIndexDataset:
         n = len(pairs)
         lo, hi = {"train": (0, int(0.8 * n)), "val": (int(0.8 * n), int(0.9 * n)), "test": (int(0.9 * n), n)}[mode]
         self.pairs = pairs[lo:hi]
+
+    def _init_device(self, bpg, mode, seed, sampler):
+        if sampler != "philox":
+            raise ValueError("ComplementaryIndexDataset: a DeviceBPG takes sampler='philox' (the 'cpython' parity sampler "
+                             "replays the reference's host shuffle: build it over an IntBPG)")
+        if bpg.world != 1:
+            raise ValueError(f"ComplementaryIndexDataset: this DeviceBPG holds a cyclic 1/{bpg.world} shard of the features "
+                             f"(rank {bpg.rank}); joint training needs the whole table on one device -- generate it with world = 1")
+        if "comp_pairs" not in bpg.arrays:
+            raise ValueError("ComplementaryIndexDataset: the DeviceBPG was generated without complementary pairs "
+                             "(with_complementary=False)")
+        if "features" not in bpg.arrays:
+            raise ValueError("ComplementaryIndexDataset: the DeviceBPG was generated without features")
+        if mode not in ("train", "val", "test"):
+            raise ValueError("mode must be 'train', 'val' or 'test'")
+        from . import ops
+        self.sampler = sampler
+        self.pairs = ops.comp_split_pairs(bpg.arrays["comp_pairs"], bpg.arrays["sim_pairs"], seed, mode)
 
     def __len__(self):
         return len(self.pairs)
@@ -716,8 +740,15 @@ class ComplementaryIndexLoader:
         self.features, self.type_idx = g["features"], g["type_idx"]
         self.step = 0
         bpg = dataset.bpg
-        if len(bpg.type_idx) and (int(bpg.type_idx.max()) >= int(bpg.n_types) or int(bpg.type_idx.min()) < 0):
-            raise IndexError(f"type ids of the graph reach {int(bpg.type_idx.max())} but n_types = {bpg.n_types}: the "
+        if isinstance(bpg, DeviceBPG):
+            # the same check on the device arrays: one read-back of (min, max)
+            lo, hi = (int(x) for x in torch.aminmax(self.type_idx)) if self.type_idx.numel() else (0, 0)
+        elif len(bpg.type_idx):
+            lo, hi = int(bpg.type_idx.min()), int(bpg.type_idx.max())
+        else:
+            lo, hi = 0, 0
+        if hi >= int(bpg.n_types) or lo < 0:
+            raise IndexError(f"type ids of the graph reach {hi} but n_types = {bpg.n_types}: the "
                              "batches' negative types are taken modulo n_types (data_loader.py:150)")
 
     def __len__(self):
@@ -761,7 +792,10 @@ class ComplementaryIndexLoader:
         # 141 steps of that epoch run, and the loop would wait for it at every epoch boundary.  Deterministic in (seed, epoch)
         # per device type.
         if getattr(self, "_pairs_all", None) is None:
-            self._pairs_all = torch.from_numpy(np.ascontiguousarray(self.dataset.pairs, np.int32)).to(self.device)
+            pairs = self.dataset.pairs
+            # (a DeviceBPG dataset's pairs are born on the device: used as they are)
+            self._pairs_all = pairs if torch.is_tensor(pairs) else \
+                torch.from_numpy(np.ascontiguousarray(pairs, np.int32)).to(self.device)
         e = self.epoch
         self.epoch += 1
         if not self.shuffle:

@@ -1534,12 +1534,16 @@ def cosine_rows(x, y):
 
 def build_complementary_batch(pairs, features, type_idx, n_types, seed, step, want_targets=True, out=None):
     """pairs [B,3] int32 (query, target, label) on the device -> the joint-step batch dict.  `out`: a dict of
-    preallocated tensors of those shapes to build into (fixed buffers of a graphed step)."""
+    preallocated tensors of those shapes to build into (fixed buffers of a graphed step).  The item rows are as wide as
+    `features`: 128 (pc_build_complementary_batch) or 256 (pc_build_complementary_batch_dim, BASELINE configs[4])."""
     b = pairs.shape[0]
     _req(pairs, torch.int32, "pairs", (b, 3)); _req(features, torch.float32, "features"); _req(type_idx, torch.int32, "type_idx")
+    d = features.shape[1] if features.dim() == 2 else -1
+    if d not in (D, 2 * D):
+        raise ValueError(f"build_complementary_batch: features must be [P, {D}] or [P, {2 * D}], got {tuple(features.shape)}")
     dev = pairs.device
     i32 = lambda: torch.empty(b, dtype=torch.int32, device=dev)
-    f32 = lambda: torch.empty(b, D, dtype=torch.float32, device=dev)
+    f32 = lambda: torch.empty(b, d, dtype=torch.float32, device=dev)
     if out is not None:
         out = dict(out)
         for k in ("query_idx", "query_types", "positive_types", "negative_types"):
@@ -1547,20 +1551,53 @@ def build_complementary_batch(pairs, features, type_idx, n_types, seed, step, wa
             if out[k].numel() != b:
                 raise ValueError("build_complementary_batch: out[%r] has %d elements, batch is %d" % (k, out[k].numel(), b))
         for k in ("positive_items", "negative_items"):
-            _req(out[k], torch.float32, k, (b, D))
+            _req(out[k], torch.float32, k, (b, d))
         want_targets = "target_features" in out
     else:
         out = {"query_idx": i32(), "query_types": i32(), "positive_types": i32(), "negative_types": i32(),
                "positive_items": f32(), "negative_items": f32()}
         if want_targets:
             out["target_features"] = f32()
-    check(_lib.lib().pc_build_complementary_batch(
-        _p(pairs), b, _p(features), _p(type_idx), int(n_types), int(seed), int(step), _p(out["query_idx"]),
-        _p(out["query_types"]), _p(out["positive_types"]), _p(out["negative_types"]), _p(out["positive_items"]),
-        _p(out["negative_items"]), _p(out.get("target_features")), _stream()), "pc_build_complementary_batch")
+    if d == D:
+        check(_lib.lib().pc_build_complementary_batch(
+            _p(pairs), b, _p(features), _p(type_idx), int(n_types), int(seed), int(step), _p(out["query_idx"]),
+            _p(out["query_types"]), _p(out["positive_types"]), _p(out["negative_types"]), _p(out["positive_items"]),
+            _p(out["negative_items"]), _p(out.get("target_features")), _stream()), "pc_build_complementary_batch")
+    else:
+        check(_lib.lib().pc_build_complementary_batch_dim(
+            _p(pairs), b, _p(features), _p(type_idx), int(n_types), d, int(seed), int(step), _p(out["query_idx"]),
+            _p(out["query_types"]), _p(out["positive_types"]), _p(out["negative_types"]), _p(out["positive_items"]),
+            _p(out["negative_items"]), _p(out.get("target_features")), _stream()), "pc_build_complementary_batch_dim")
     out["positive_types"] = out["positive_types"].view(b, 1)
     out["negative_types"] = out["negative_types"].view(b, 1)
     return out
+
+
+SPLIT_MODES = {"train": 0, "val": 1, "test": 2}
+
+
+def split_bounds(n, mode):
+    """[lo, hi) of a mode in the shuffled labelled list of n pairs: the host split of data.py (data_loader.py:121-126)."""
+    return {"train": (0, int(0.8 * n)), "val": (int(0.8 * n), int(0.9 * n)), "test": (int(0.9 * n), n)}[mode]
+
+
+def comp_split_pairs(comp_pairs, sim_pairs, seed, mode):
+    """pc_comp_split_pairs: the labelled pairs [n_mode,3] int32 (query, target, +1 / -1) of `mode` ('train' / 'val' / 'test')
+    on the device -- L = [comp_pairs (+1) ..., sim_pairs (-1) ...] in the keyed order of epoch_permutation(n, seed, mode),
+    rows [lo, hi) of the host split.  Neither L nor the permutation is built."""
+    _req(comp_pairs, torch.int32, "comp_pairs"); _req(sim_pairs, torch.int32, "sim_pairs")
+    for t, nm in ((comp_pairs, "comp_pairs"), (sim_pairs, "sim_pairs")):
+        if t.dim() != 2 or t.shape[1] != 2:
+            raise ValueError(f"comp_split_pairs: {nm} must be [n, 2], got {tuple(t.shape)}")
+    if mode not in SPLIT_MODES:
+        raise ValueError("comp_split_pairs: mode must be 'train', 'val' or 'test'")
+    n_comp, n_sim = comp_pairs.shape[0], sim_pairs.shape[0]
+    lo, hi = split_bounds(n_comp + n_sim, mode)
+    out = torch.empty(max(hi - lo, 1), 3, dtype=torch.int32, device=comp_pairs.device)
+    check(_lib.lib().pc_comp_split_pairs(_p(comp_pairs) if n_comp else None, n_comp, _p(sim_pairs) if n_sim else None, n_sim,
+                                         lo, hi, int(seed) & (2 ** 64 - 1), SPLIT_MODES[mode], _p(out), _stream()),
+          "pc_comp_split_pairs")
+    return out[:hi - lo]
 
 
 def retrieve_topk(proj, types, type_rowptr, type_col, table, n):

@@ -9,7 +9,8 @@ from typing import Dict
 
 import torch
 
-from .data import ComplementaryIndexDataset, ComplementaryIndexLoader, IntBPG, SimilarityIndexLoader
+from . import ops
+from .data import ComplementaryIndexDataset, ComplementaryIndexLoader, DeviceBPG, EmbeddingMapping, IntBPG, SimilarityIndexLoader
 from .metrics import Metrics
 from .p_companion import PCompanion
 from .product2vec import FusedAdam, Product2Vec
@@ -17,10 +18,13 @@ from .product2vec import FusedAdam, Product2Vec
 
 def pretrain_product2vec(config, similarity_dataset) -> Dict[str, torch.Tensor]:
     """Pretrain Product2Vec model and save embeddings (scripts/pretrain_product2vec.py:11-53).
-    `similarity_dataset`: an IntBPG (index loader built here), an index loader, or any iterable
-    of reference-style dense batches with a .dataset.bpg attribute."""
+    `similarity_dataset`: an IntBPG or a DeviceBPG (index loader built here), an index loader, or any iterable
+    of reference-style dense batches with a .dataset.bpg attribute.
+    Over a DeviceBPG the export is the device table (data.EmbeddingMapping, returned as it is); product2vec.pth then holds
+    'embeddings' as that [P, D] table in ONE CPU tensor (row i = P{i:06d}: a layout PCompanion takes) instead of a
+    P-entry dict, and 'type_to_idx' None."""
     logger = logging.getLogger(__name__)
-    if isinstance(similarity_dataset, IntBPG):
+    if isinstance(similarity_dataset, (IntBPG, DeviceBPG)):
         loader = SimilarityIndexLoader(similarity_dataset, config.BATCH_SIZE, shuffle=True, sampler="philox",
                                        device=config.DEVICE, reuse_buffers=True)     # (train_model consumes each batch before the next)
     else:
@@ -32,7 +36,7 @@ def pretrain_product2vec(config, similarity_dataset) -> Dict[str, torch.Tensor]:
     save_path = os.path.join(config.MODEL_DIR, "product2vec.pth")
     bpg = loader.dataset.bpg
     torch.save({"model_state_dict": {k: v.detach().cpu() for k, v in model.state_dict().items()},
-                "embeddings": embeddings_dict,
+                "embeddings": embeddings_dict.table.cpu() if isinstance(embeddings_dict, EmbeddingMapping) else embeddings_dict,
                 "type_to_idx": bpg.type_to_idx if hasattr(bpg, "type_to_idx") else None}, save_path)
     logger.info(f"Saved pretrained Product2Vec model and embeddings to {save_path}")
     pretrain_product2vec.last_model = model
@@ -77,8 +81,9 @@ def train(config, train_loader, val_loader, pretrained_embeddings, fused=True):
     # (GraphedJointStep.run_epoch -> pc_joint_train_epoch; same steps, same values as the loop below)
     epoch_runner = None
     loader_out = (train_loader.out, getattr(train_loader, "_prepared", None)) if isinstance(train_loader, ComplementaryIndexLoader) else None
+    # (PRODUCT_EMB_DIM = 256: no fused / fixed-buffer forms -- the loop below steps the per-op path, PCompanion.train_step)
     if fused and isinstance(train_loader, ComplementaryIndexLoader) and torch.device(config.DEVICE).type == "cuda" and \
-            train_loader.out is None and len(train_loader.dataset) >= train_loader.batch_size:
+            train_loader.out is None and len(train_loader.dataset) >= train_loader.batch_size and model.dim == ops.D:
         from .p_companion import GraphedJointStep
         step = GraphedJointStep(model, optimizer, train_loader.batch_size, warmup=0, mode="auto")
         if step.mode == "direct":
@@ -131,7 +136,9 @@ def train(config, train_loader, val_loader, pretrained_embeddings, fused=True):
 
 
 def main(config, bpg: IntBPG):
-    """train.py:74-134 on an integer BPG: Product2Vec pretrain -> embeddings -> P-Companion."""
+    """train.py:74-134 on an integer BPG: Product2Vec pretrain -> embeddings -> P-Companion.  `bpg`: an IntBPG, or a
+    DeviceBPG (world = 1, with features and complementary pairs): then every phase runs over the arrays in HBM and only
+    the checkpoints reach the host."""
     embeddings = pretrain_product2vec(config, bpg)
     table = pretrain_product2vec.last_model.last_embedding_table
     tr = ComplementaryIndexLoader(ComplementaryIndexDataset(bpg, "train"), config.BATCH_SIZE, shuffle=True,
