@@ -779,6 +779,45 @@ int pc_hit_rank(const float *sims, int rows, int cols, int32_t *rank, void *stre
 int pc_cosine_rows(const float *x, const float *y, int batch, int k, float *out, void *stream);
 int pc_cosine_rows_dim(const float *x, const float *y, int batch, int k, int dim, float *out, void *stream);
 
+/* --- ABI 8, additive: Metrics.evaluate_model without the [B*K, B] score matrix, and as one call per evaluation.
+ * pc_eval_batch_stats (metrics.py:88-109 for tensors the caller holds): proj [B,K,dim], targets [B,dim], pos_items [B,dim],
+ *   types [B,K] int32 (any integers), dim 128 or 256, k <= 8.  stats[5] (device int32) = {hits_1, hits_3, hits_10,
+ *   distinct_columns, rows = B}: for the eligible rows r in [0, B) of the flat [B*K, dim] projection (the reference compares
+ *   arange(B*K) with B columns, metrics.py:95-100: rows r >= B never hit), beat_r = #{c in [0,B): s_rc > g_r or (s_rc == g_r
+ *   and c < r)}, s_rc = proj_r . targets_c, g_r = s_rr (the same bits: a row never counts itself), and
+ *   hits_k = #{r: beat_r < min(k, B)} for k = 1, 3, min(10, B) (metrics.py:7-27, :103); the products are exact-fp32 matrix
+ *   instructions (v_mfma_f32_16x16x4_f32), nothing of size B x B is written.  distinct_columns = number of distinct columns of
+ *   `types` (metrics.py:29-42).  *cos_sum (device float) = sum over (b,k) of cosine_similarity(proj[b,k], pos_items[b]) with
+ *   torch's eps 1e-8 (metrics.py:44-60), in a fixed order.  No float atomics: bitwise repeatable.
+ *   ws: pc_joint_eval_workspace_bytes(batch, 1, k, dim) bytes.  PC_EINVAL: null pointer / non-positive size; PC_ESHAPE: dim, k;
+ *   PC_EWORKSPACE.
+ * pc_joint_eval_epoch (metrics.py:62-117 over a device-resident split): `n_pairs` labelled pairs[i] = (query, target, label)
+ *   in loader order -- full batches of `batch`, then the ragged rest -- each batch as pc_build_complementary_batch[_dim](pairs,
+ *   ..., seed, first_step + i) would build it (positive_items = features[target] for label +1, else the filler row: the same
+ *   bits; data_loader.py:133-157) and PCompanion.forward in eval mode would project it (p_companion.py:45-77; the top-K of a
+ *   sample is a function of its query type alone, so it is formed once per TYPE, not per sample).  Per batch i:
+ *   stats_out[5*i ..] and cos_sum_out[i] as above (device, one entry per batch); metrics_out (device double[5]) = {hit@1, hit@3,
+ *   hit@10, type_diversity, mean_relevance}: per batch hits_k / (B_i*k) and cos_sum / (B_i*k) in fp32, distinct / k, then the
+ *   mean over the batches in fp64, in batch order (metrics.py:101-117 adds Python floats).  Nothing is read back and the host
+ *   does not synchronise inside the call.  `features` [num_products, dim], `type_idx` [num_products]; p->product_table
+ *   [num_products, dim]; n_types: the dataset's modulus, as in the builder (> 0).  Ids outside their tables (query / target vs
+ *   num_products, the query's type vs num_types) are clamped, counted into *bad_count (may be NULL), never dereferenced.
+ *   n_types is part of the loader's source tuple (features, type_idx, n_types, seed) and is only range-checked here: the
+ *   evaluation reads no negative type, the one thing the builder uses it for.
+ *   For tests and probes ONLY (not a promise to other callers; the rest of the workspace's layout is private): after the
+ *   call the first num_types * k int32 of ws hold the plan's complementary types [num_types, k].
+ *   PC_EINVAL: null pointer / non-positive size; PC_ESHAPE: dim not 128 / 256, k (1..8, <= num_types), a ragged rest -- or a
+ *   batch -- of 1..9 pairs (metrics.py:103's key min(10, cols) is then not 'hit@10': the caller's loop reproduces what the
+ *   reference does there); PC_EWORKSPACE: ws_bytes < pc_joint_eval_workspace_bytes(batch, num_types, k, dim), which is linear
+ *   in num_types (the plan runs over row chunks of types).  All checked before anything is launched. */
+int pc_eval_batch_stats(const float *proj, const float *targets, const float *pos_items, const int32_t *types, int batch,
+                        int k, int dim, int32_t *stats, float *cos_sum, void *ws, size_t ws_bytes, void *stream);
+size_t pc_joint_eval_workspace_bytes(int batch, int num_types, int k, int dim);
+int pc_joint_eval_epoch(const pc_joint_tensors *p, const int32_t *pairs, int64_t n_pairs, const float *features,
+                        const int32_t *type_idx, int n_types, int dim, uint64_t seed, uint64_t first_step, int batch,
+                        int num_types, int k, int num_products, int32_t *stats_out, float *cos_sum_out, double *metrics_out,
+                        int32_t *bad_count, void *ws, size_t ws_bytes, void *stream);
+
 /* item_prediction.py:38: proj[b,k,:] = pi[b,:] * tp[b*K+k,:] and its backward
  * (dpi[b] = sum_k dproj[b,k]*tp[b,k]; dtp[b,k] = dproj[b,k]*pi[b]).  D = 128. */
 int pc_hadamard_forward(const float *pi, const float *tp, int batch, int k, float *proj,

@@ -190,6 +190,10 @@ SIGNATURES = {
     "pc_hit_rank": (_i, [_vp, _i, _i, _vp, _vp]),
     "pc_cosine_rows": (_i, [_vp, _vp, _i, _i, _vp, _vp]),
     "pc_cosine_rows_dim": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
+    "pc_eval_batch_stats": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    "pc_joint_eval_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "pc_joint_eval_epoch": (_i, [_P(JointTensors), _vp, _i64, _vp, _vp, _i, _i, _u64, _u64, _i, _i, _i, _i, _vp, _vp, _vp,
+                                 _vp, _vp, _sz, _vp]),
     "pc_retrieve_topk": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp]),
     "pc_retrieve_topk_dim": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
     "pc_retrieve_topk_grouped_workspace_bytes": (_sz, [_i, _i, _i, _i]),

@@ -5,7 +5,11 @@ The similarity product [B*K,128] x [128,B] is the shared NT GEMM (pc_linear_forw
 six-product bf16 MFMA for many), hit@k is a rank kernel
 (one wave per row), relevance a cosine kernel; only the final scalar means are read back.
 Reproduces the reference's quirk: ground truth is arange(B*K) against B columns, so rows >= B can
-never hit (metrics.py:95-100)."""
+never hit (metrics.py:95-100).
+
+Over a ComplementaryIndexLoader whose arrays live on the model's GPU the whole evaluation is one foreign call
+(pc_joint_eval_epoch, csrc/evaluate.hip): the top-K and the type projections once per TYPE, the hit counts from a B x B x D
+product whose epilogue compares and counts (no score matrix), the five metrics formed on the device and read back once."""
 from typing import Dict
 
 import numpy as np
@@ -39,8 +43,61 @@ class Metrics:
         return float(ops.cosine_rows(predictions.contiguous().float(), ground_truth.contiguous().float()).mean())
 
     @staticmethod
-    def evaluate_model(model: torch.nn.Module, data_loader, device) -> Dict[str, float]:
-        """metrics.py:62-117"""
+    def _fused_refusal(model, data_loader):
+        """Why the one-call evaluation (pc_joint_eval_epoch) does not serve (model, data_loader); None: it does."""
+        from .data import ComplementaryIndexLoader
+        from .p_companion import PCompanion
+        if not isinstance(data_loader, ComplementaryIndexLoader):
+            return "the loader is not a ComplementaryIndexLoader"
+        if not isinstance(model, PCompanion):
+            return "the model is not a PCompanion"
+        feats, table = data_loader.features, model.product_embeddings.weight
+        if not (torch.is_tensor(feats) and feats.is_cuda and table.is_cuda and feats.device == table.device):
+            return "the loader's arrays and the model are not on the same GPU"
+        if tuple(feats.shape) != tuple(table.shape) or data_loader.type_idx.dtype != torch.int32:
+            return "the loader's feature table and the model's product table differ in shape"
+        pairs = data_loader.dataset.pairs
+        if torch.is_tensor(pairs) and pairs.device != table.device:
+            return "the dataset's pairs live on another device"
+        n, b = len(data_loader.dataset), data_loader.batch_size
+        if n == 0 or b < 10 or 0 < n % b < 10:
+            return "an empty split, or a batch of fewer than 10 rows (the existing loop reproduces metrics.py:103 there)"
+        if not 1 <= int(model.config.NUM_COMP_TYPES) <= min(8, model.query_type_embeddings.weight.shape[0]):
+            return "NUM_COMP_TYPES outside 1..8"
+        return None
+
+    @staticmethod
+    def evaluate_on_device(model, loader) -> Dict[str, torch.Tensor]:
+        """metrics.py:62-117 as one foreign call with NOTHING read back: ops.joint_eval_epoch's dict of device tensors
+        ("metrics" double[5] in the order hit@1, hit@3, hit@10, type_diversity, mean_relevance; per-batch "stats" / "cos_sum";
+        the plan's "topk_table").  Leaves the loader as iterating it would: epoch + 1, step + number of batches."""
+        why = Metrics._fused_refusal(model, loader)
+        if why is not None:
+            raise ValueError("evaluate_on_device: " + why)
+        model.eval()
+        params = model._tensor_dict()
+        params["product_embeddings.weight"] = model.product_embeddings.weight
+        pairs = loader.epoch_pairs()                       # (advances loader.epoch; the loop's shuffled order)
+        source = (loader.features, loader.type_idx, int(loader.dataset.bpg.n_types), int(loader.seed))
+        with torch.no_grad():
+            out = ops.joint_eval_epoch(params, pairs.contiguous(), source, loader.step, loader.batch_size,
+                                       int(model.config.NUM_COMP_TYPES), bad=model._bad_counter())
+        loader.step += len(loader)
+        return out
+
+    @staticmethod
+    def evaluate_model(model: torch.nn.Module, data_loader, device, fused=None) -> Dict[str, float]:
+        """metrics.py:62-117.  fused=None: over a ComplementaryIndexLoader whose arrays live on the model's GPU the whole
+        evaluation is ONE foreign call (pc_joint_eval_epoch: the batches are never built, no [B*K, B] score matrix, one
+        read-back of the five metrics); any other loader -- and a last batch of 1..9 rows -- takes the loop below.
+        fused=False forces the loop; fused=True raises ValueError where the one-call form does not apply."""
+        if fused is None or fused:
+            why = Metrics._fused_refusal(model, data_loader)
+            if why is None:
+                m = Metrics.evaluate_on_device(model, data_loader)["metrics"].cpu().tolist()      # the ONE read-back
+                return dict(zip(("hit@1", "hit@3", "hit@10", "type_diversity", "mean_relevance"), m))
+            if fused:
+                raise ValueError("evaluate_model(fused=True): " + why)
         model.eval()
         metrics = {"hit@1": 0.0, "hit@3": 0.0, "hit@10": 0.0, "type_diversity": 0.0, "mean_relevance": 0.0}
         num_batches = 0

@@ -1532,6 +1532,58 @@ def cosine_rows(x, y):
     return out
 
 
+def eval_batch_stats(proj, targets, pos_items, types):
+    """metrics.py:88-109 for one batch without the [B*K, B] score matrix (pc_eval_batch_stats): proj [B,K,d], targets [B,d],
+    pos_items [B,d], types [B,K] int32 -> (stats int32[5] = {hits_1, hits_3, hits_10, distinct_columns, rows}, cos_sum float[1]),
+    both on the device; nothing is read back."""
+    b, k, d = proj.shape
+    _width(d)
+    _req(proj, torch.float32, "projected_embeddings", (b, k, d)); _req(targets, torch.float32, "target_features", (b, d))
+    _req(pos_items, torch.float32, "positive_items", (b, d)); _req(types, torch.int32, "complementary_types", (b, k))
+    dev = proj.device
+    stats = torch.empty(5, dtype=torch.int32, device=dev)
+    cos_sum = torch.empty(1, dtype=torch.float32, device=dev)
+    nbytes = _lib.lib().pc_joint_eval_workspace_bytes(b, 1, k, d)
+    if nbytes == 0:
+        raise ValueError(f"eval_batch_stats: batch {b}, k {k} (1..8), width {d} not served")
+    ws = workspace(nbytes, dev, "eval")
+    check(_lib.lib().pc_eval_batch_stats(_p(proj), _p(targets), _p(pos_items), _p(types), b, k, d, _p(stats), _p(cos_sum),
+                                         _p(ws), ws.numel(), _stream()), "pc_eval_batch_stats")
+    return stats, cos_sum
+
+
+def joint_eval_epoch(params, pairs, source, first_step, batch, k, bad=None):
+    """Metrics.evaluate_model (metrics.py:62-117) over `pairs` [n,3] int32 (loader order, on the device) as ONE foreign call
+    (pc_joint_eval_epoch).  params: the model's tensors plus "product_embeddings.weight"; source = (features, type_idx,
+    n_types, seed) of the loader; first_step: its step counter.  Returns a dict of device tensors -- "metrics" double[5] =
+    (hit@1, hit@3, hit@10, type_diversity, mean_relevance), "stats" int32[n_batches,5], "cos_sum" float[n_batches],
+    "topk_table" int32[T,k] (the plan's complementary types, a view into the workspace: valid until the next evaluation on
+    this stream) -- and nothing is read back here."""
+    st, dev = joint_struct(params)
+    features, type_idx, n_types, seed = source
+    table = params["product_embeddings.weight"]
+    n_products, d = table.shape
+    _width(d)
+    _req(features, torch.float32, "features", (n_products, d)); _req(type_idx, torch.int32, "type_idx", (n_products,))
+    n = int(pairs.shape[0])
+    _req(pairs, torch.int32, "pairs", (n, 3))
+    if bad is not None:
+        _req(bad, torch.int32, "bad", (1,))
+    t = params["query_type_embeddings.weight"].shape[0]
+    b = int(batch)
+    n_batches = (n + b - 1) // b
+    stats = torch.empty(max(n_batches, 1), 5, dtype=torch.int32, device=dev)
+    cos_sum = torch.empty(max(n_batches, 1), dtype=torch.float32, device=dev)
+    metrics = torch.empty(5, dtype=torch.float64, device=dev)
+    nbytes = _lib.lib().pc_joint_eval_workspace_bytes(b, t, int(k), d)
+    ws = workspace(max(nbytes, 256), dev, "eval")
+    check(_lib.lib().pc_joint_eval_epoch(ctypes.byref(st), _p(pairs), n, _p(features), _p(type_idx), int(n_types), d, int(seed),
+                                         int(first_step), b, t, int(k), n_products, _p(stats), _p(cos_sum), _p(metrics),
+                                         _p(bad), _p(ws), ws.numel(), _stream()), "pc_joint_eval_epoch")
+    topk_table = ws[:t * int(k) * 4].view(torch.int32).view(t, int(k))
+    return {"metrics": metrics, "stats": stats[:n_batches], "cos_sum": cos_sum[:n_batches], "topk_table": topk_table}
+
+
 def build_complementary_batch(pairs, features, type_idx, n_types, seed, step, want_targets=True, out=None):
     """pairs [B,3] int32 (query, target, label) on the device -> the joint-step batch dict.  `out`: a dict of
     preallocated tensors of those shapes to build into (fixed buffers of a graphed step).  The item rows are as wide as

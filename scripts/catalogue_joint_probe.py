@@ -8,12 +8,15 @@ profiles/catalogue_joint_probe.json (and prints it as one JSON line).
                at T = 100 and T = 34 800 types.  The product table is a Product2Vec export of the catalogue (a second
                [P,128] array beside the features: 5.1 GB each at 10 M).  The loader's per-epoch shuffle is timed on its own
                (epoch_pairs_ms); the timed runs reuse one shuffled order, so steps_ms is the steps alone.
-  evaluate     Metrics.evaluate_model over the 10 M val split (host clock around the call, which reads back every batch)
+  evaluate     Metrics.evaluate_model over the 10 M val split of every 10 M leg: the existing per-batch loop (fused=False) and the
+               one-call form (pc_joint_eval_epoch) alternating in one process, a host clock around calls that end in a
+               synchronise, each once untimed first; --kernel-stats CSV merges the count kernel's traced time afterwards
 
 ms from device events around `--reps` calls after one untimed call (median and min).
 
   python scripts/catalogue_joint_probe.py [--legs dev100k_100,dev100k_34800,host100k_100,host100k_34800,dev10M_100,dev10M_34800]
-                                          [--steps 200] [--reps 5] [--no-evaluate]
+                                          [--steps 200] [--reps 5] [--loop-reps 2] [--no-evaluate]
+  python scripts/catalogue_joint_probe.py --kernel-stats profiles/eval_10M_kernel_stats.csv      (no GPU: merge a trace)
 """
 import argparse
 import json
@@ -96,17 +99,85 @@ def leg(name, args, res):
     out["step_ms"] = {"median_ms": t["median_ms"] / S, "min_ms": t["min_ms"] / S, "reps": t["reps"]}
     out["finite_losses"] = bool(torch.isfinite(losses).all())
     out["index_errors"] = m.index_errors()
-    if src == "device" and P >= 10_000_000 and T == 100 and args.evaluate:
-        va = ComplementaryIndexLoader(ComplementaryIndexDataset(bpg, "val", seed=0), B, shuffle=False)
-        torch.cuda.synchronize()
-        t0 = time.time()
-        met = Metrics.evaluate_model(m, va, c.DEVICE)
-        torch.cuda.synchronize()
-        res["evaluate"] = {"products": P, "types": T, "val_pairs": len(va.dataset), "batches": len(va),
-                           "s": round(time.time() - t0, 3), "hit@10": met["hit@10"]}
+    if src == "device" and P >= 10_000_000 and args.evaluate:
+        va_ds = ComplementaryIndexDataset(bpg, "val", seed=0)
+        if 0 < len(va_ds) % B < 10:                                   # (a rest of 1..9 rows: both paths would take the loop)
+            va_ds.pairs = va_ds.pairs[:len(va_ds) - len(va_ds) % B].contiguous()
+        res.setdefault("evaluate", {})[f"T{T}"] = evaluate_leg(m, va_ds, c, P, T, args)
     del step, ld, ds, m, table, p2v, bpg, pairs
     torch.cuda.empty_cache()
     return out
+
+
+def evaluate_leg(m, va_ds, c, P, T, args):
+    """Metrics.evaluate_model over the val split: the existing per-batch loop (fused=False) and the one-call form
+    (pc_joint_eval_epoch) alternating in THIS process, a host clock around calls that end in a synchronise, each path once
+    untimed first.  FLOPs of the count product from the shapes."""
+    from p_companion_amd import _lib
+    from p_companion_amd.data import ComplementaryIndexLoader
+    from p_companion_amd.metrics import Metrics
+    n, K, D = len(va_ds), int(c.NUM_COMP_TYPES), int(c.PRODUCT_EMB_DIM)
+    nb = (n + B - 1) // B
+
+    def run(fused):
+        va = ComplementaryIndexLoader(va_ds, B, shuffle=False)
+        torch.cuda.synchronize()
+        t0 = time.time()
+        met = Metrics.evaluate_model(m, va, c.DEVICE, fused=fused)
+        torch.cuda.synchronize()
+        return time.time() - t0, met
+
+    loop_reps = max(0, min(args.reps, args.loop_reps))                # (0: the one-call form alone, e.g. under a kernel trace)
+    run(True)                                                         # untimed
+    if loop_reps:
+        run(False)
+    one, loop, met_one, met_loop = [], [], None, None
+    for i in range(args.reps):
+        s, met_one = run(True)
+        one.append(s)
+        if i < loop_reps:
+            s, met_loop = run(False)
+            loop.append(s)
+    sizes = [B] * (n // B) + ([n % B] if n % B else [])
+    flops = float(sum(2.0 * b * b * D for b in sizes))                # the B x B x D count product of every batch
+    peak = 157.3e12                                                   # fp32 MFMA peak of one MI355X
+    e = {"products": P, "types": T, "val_pairs": n, "batches": nb, "B": B, "K": K,
+         "loop_s": {"median": float(np.median(loop)), "min": float(min(loop)), "reps": len(loop)} if loop else None,
+         "one_call_s": {"median": float(np.median(one)), "min": float(min(one)), "reps": len(one)},
+         "loop_ms_per_batch": 1e3 * float(np.median(loop)) / nb if loop else None,
+         "one_call_ms_per_batch": 1e3 * float(np.median(one)) / nb,
+         "speedup": float(np.median(loop)) / float(np.median(one)) if loop else None,
+         "count_product_flops": flops, "fp32_mfma_peak_tflops": peak / 1e12,
+         # (lower bound on the count kernel's rate: the whole call's time, not the kernel's -- its own time comes from a
+         # kernel trace, profiles/eval_10M_kernel_stats.csv)
+         "count_tflops_over_whole_call": flops / float(np.median(one)) / 1e12,
+         "metrics_one_call": met_one, "metrics_loop": met_loop,
+         "workspace_bytes": int(_lib.lib().pc_joint_eval_workspace_bytes(B, T, K, D))}
+    return e
+
+
+def merge_kernel_stats(path_json, path_csv, leg="T100"):
+    """No GPU: adds the count kernel's own rate to an existing result file from the `rocprofv3 --kernel-trace --stats` table of a
+    run of the evaluate leg (a run of its own: tracing slows the host down).  Mean ns per launch of eval_count_kernel ->
+    TFLOP/s and share of the fp32 MFMA peak, FLOPs per launch from the shapes."""
+    import csv
+    res = json.load(open(path_json))
+    rows = [r for r in csv.DictReader(open(path_csv)) if "eval_count_kernel" in r["Name"]]
+    if not rows:
+        raise SystemExit(f"{path_csv}: no eval_count_kernel row")
+    calls = sum(int(r["Calls"]) for r in rows)
+    mean_ns = sum(float(r["TotalDurationNs"]) for r in rows) / calls
+    for name, e in res.get("evaluate", {}).items():
+        if name != leg:                                               # (the trace is of ONE leg's evaluation)
+            continue
+        per_launch = e["count_product_flops"] / e["batches"]
+        e["count_kernel_us_traced"] = mean_ns / 1e3
+        e["count_kernel_tflops"] = per_launch / (mean_ns * 1e-9) / 1e12
+        e["count_kernel_share_of_fp32_peak"] = e["count_kernel_tflops"] / e["fp32_mfma_peak_tflops"]
+    line = json.dumps(res)
+    with open(path_json, "w") as f:
+        f.write(line + "\n")
+    print(line, flush=True)
 
 
 def main():
@@ -115,8 +186,12 @@ def main():
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--no-evaluate", dest="evaluate", action="store_false")
+    ap.add_argument("--loop-reps", type=int, default=2, help="timed runs of the existing evaluation loop (9.6 s each at 10 M)")
+    ap.add_argument("--kernel-stats", default=None, help="merge a rocprofv3 kernel-stats CSV of the evaluate leg into --out and exit")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "catalogue_joint_probe.json"))
     args = ap.parse_args()
+    if args.kernel_stats:
+        return merge_kernel_stats(args.out, args.kernel_stats)
     if not torch.cuda.is_available():
         raise SystemExit("catalogue_joint_probe: no GPU (nothing here is measured on the CPU)")
     res = {"probe": "catalogue_joint", "device": torch.cuda.get_device_name(0), "legs": {}}
