@@ -58,6 +58,42 @@ def build(force=False, verbose=False):
 LLVM_BIN = os.environ.get("PC_LLVM_BIN", "/opt/rocm/lib/llvm/bin")
 
 
+def _llvm_tools(what):
+    for tool in ("llvm-objcopy", "clang-offload-bundler", "llvm-readelf"):
+        if not os.path.exists(os.path.join(LLVM_BIN, tool)):
+            raise RuntimeError(f"{what} unavailable: {tool} missing under {LLVM_BIN}")
+
+
+def code_objects(tmp, what="spill gate"):
+    """(unit, path) of the gfx950 code object of every compiled translation unit with device code, unbundled from the object's
+    .hip_fatbin into directory `tmp`."""
+    _llvm_tools(what)
+    for s in sources():
+        if not s.endswith(".hip"):
+            continue
+        unit = os.path.splitext(s)[0]
+        obj = os.path.join(OBJ, unit + ".o")
+        fat, co = os.path.join(tmp, unit + ".fat"), os.path.join(tmp, unit + ".co")
+        r = subprocess.run([os.path.join(LLVM_BIN, "llvm-objcopy"), "--dump-section", ".hip_fatbin=" + fat, obj],
+                           capture_output=True, text=True)
+        if r.returncode != 0 or not os.path.exists(fat):
+            if "hip_fatbin" in (r.stderr or "") or not os.path.exists(obj):
+                continue                                      # (a unit without device code / not built: no section to dump)
+            raise RuntimeError(f"{what}: llvm-objcopy failed on {obj}: {(r.stderr or '').strip()[:300]}")
+        subprocess.run([os.path.join(LLVM_BIN, "clang-offload-bundler"), "--unbundle", "--type=o", "--input=" + fat,
+                        "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", "--output=" + co], check=True, capture_output=True)
+        yield unit, co
+
+
+def code_object_digests():
+    """{unit: sha256 of its unbundled gfx950 code object}: equal digests before and after a host-only change say that no
+    device code moved."""
+    import hashlib
+    import tempfile
+    with tempfile.TemporaryDirectory() as tmp:
+        return {unit: hashlib.sha256(open(co, "rb").read()).hexdigest() for unit, co in code_objects(tmp, "digests")}
+
+
 def kernel_resources():
     """Per kernel of every compiled translation unit: the code object's own metadata (llvm-readelf --notes on the gfx950 image
     unbundled from the object's .hip_fatbin): {name: {vgpr_count, agpr_count, sgpr_count, vgpr_spill_count, sgpr_spill_count,
@@ -68,25 +104,9 @@ def kernel_resources():
         import yaml
     except ImportError as e:
         raise RuntimeError("spill gate unavailable: PyYAML missing (the code objects' metadata note is YAML)") from e
-    for tool in ("llvm-objcopy", "clang-offload-bundler", "llvm-readelf"):
-        if not os.path.exists(os.path.join(LLVM_BIN, tool)):
-            raise RuntimeError(f"spill gate unavailable: {tool} missing under {LLVM_BIN}")
     out = {}
     with tempfile.TemporaryDirectory() as tmp:
-        for s in sources():
-            if not s.endswith(".hip"):
-                continue
-            unit = os.path.splitext(s)[0]
-            obj = os.path.join(OBJ, unit + ".o")
-            fat, co = os.path.join(tmp, unit + ".fat"), os.path.join(tmp, unit + ".co")
-            r = subprocess.run([os.path.join(LLVM_BIN, "llvm-objcopy"), "--dump-section", ".hip_fatbin=" + fat, obj],
-                               capture_output=True, text=True)
-            if r.returncode != 0 or not os.path.exists(fat):
-                if "hip_fatbin" in (r.stderr or "") or not os.path.exists(obj):
-                    continue                                      # (a unit without device code / not built: no section to dump)
-                raise RuntimeError(f"spill gate: llvm-objcopy failed on {obj}: {(r.stderr or '').strip()[:300]}")
-            subprocess.run([os.path.join(LLVM_BIN, "clang-offload-bundler"), "--unbundle", "--type=o", "--input=" + fat,
-                            "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", "--output=" + co], check=True, capture_output=True)
+        for unit, co in code_objects(tmp):
             notes = subprocess.run([os.path.join(LLVM_BIN, "llvm-readelf"), "--notes", co], check=True, capture_output=True,
                                    text=True).stdout
             # the note is YAML between '---' and '...'
@@ -112,5 +132,8 @@ if __name__ == "__main__":
     if "--resources" in sys.argv:
         for n, r in sorted(kernel_resources().items()):
             print(r["unit"], n, {k: v for k, v in r.items() if k != "unit"})
+    if "--digests" in sys.argv:
+        for unit, h in sorted(code_object_digests().items()):
+            print(h, unit)
     bad = spilling_kernels()
     print("kernels with scratch:", bad if bad else "none")

@@ -586,3 +586,70 @@ static inline void tn_defer_init(TnDefer* d) { d->r = TnReduceGroup{}; d->rblock
 int scatter_add_slab_blocks(int table_rows, int rows, int width);
 int launch_scatter_add_slabs(const int32_t* idx, int rows, int width, int table_rows, const float* src, float* slabs,
                              hipStream_t st);
+
+// ---- host helpers shared by the translation units ----------------------------------------
+// The workspace carver every *_ws_layout walks its buffers with: base == null only measures, every take starts on a
+// 256-byte boundary, total = the bytes taken so far.
+struct WsCarver {
+    char* base; size_t total;
+    explicit WsCarver(void* b) : base(static_cast<char*>(b)), total(0) {}
+    void* bytes(size_t n) {
+        void* p = base ? base + total : nullptr;
+        total += (n + 255) & ~(size_t)255;
+        return p;
+    }
+    float* floats(size_t n) { return static_cast<float*>(bytes(n * sizeof(float))); }
+};
+
+// the ten trainable tensors of a pc_joint_tensors, in the order of the fused step's finish jobs
+static inline void joint_fields(const pc_joint_tensors* t, float* (&out)[10]) {
+    float* const f[10] = {t->itm_w, t->itm_b, t->typ_w, t->typ_b, t->dec_w, t->dec_b, t->enc_w, t->enc_b, t->comp_types, t->query_types};
+    for (int i = 0; i < 10; i++) out[i] = f[i];
+}
+static inline bool joint_tensors_ok(const pc_joint_tensors* t, bool need_table) {
+    if (!t || (need_table && !t->product_table)) return false;
+    float* f[10];
+    joint_fields(t, f);
+    for (float* x : f)
+        if (!x) return false;
+    return true;
+}
+
+// ---- internal functions one unit defines and another calls: declared HERE only, and the defining unit includes this
+// header too, so a signature that drifts fails to compile
+// gemm_tn.hip (pc_set_option)
+int pc_opt_sorted_tables();
+int pc_opt_bn_finalize_side();
+int pc_opt_fused_loss();
+int pc_opt_fused_out_chain();
+// misc.hip
+int triplet_loss_launch(const float* a, const float* p, const float* n, int batch, int k_neg, int dim, float margin,
+                        float* loss, float* d_pos, float* d_neg, float* da, float* dp, float* dn, void* stream, int with_mean);
+int launch_dropout(const float* x, size_t n, const pc_dropout& d, unsigned stream_id, float* y, hipStream_t st);
+// ffn.hip
+int launch_transpose(const float* in, int rows, int cols, float* out, hipStream_t st);
+int ffn_forward_part1(const pc_p2v_tensors* p, const float* table, const int32_t* idx, int rows, const pc_segments* seg,
+                      const pc_ffn_saved* sv, double* local_sums, void* ws, size_t ws_bytes, void* stream);
+int ffn_forward_part2(const pc_p2v_tensors* p, int rows, const pc_segments* seg, int update_running, float* y,
+                      const pc_ffn_saved* sv, const double* global_sums, void* ws, size_t ws_bytes, void* stream,
+                      const TransposeBatch* ride = nullptr);
+int ffn_backward_part1(const pc_p2v_tensors* p, const pc_p2v_tensors* g, const float* table, const int32_t* idx,
+                       int rows, const pc_segments* seg, const float* dy, const pc_ffn_saved* sv, int with_dx,
+                       int accumulate, double* local_sums, void* ws, size_t ws_bytes, void* stream, int transposed,
+                       TnDefer* defer);
+int ffn_backward_part2(const pc_p2v_tensors* g, const float* table, const int32_t* idx, int rows,
+                       const pc_segments* seg, const pc_ffn_saved* sv, float* dx, int accumulate,
+                       const double* local_sums, const double* global_sums, void* ws, size_t ws_bytes, void* stream,
+                       TnDefer* defer);
+int ffn_transposes(const pc_p2v_tensors* p, void* ws, int rows, int with_dx, TransposeBatch* tb);
+// attention.hip
+int attention_transposes(const pc_p2v_tensors* p, void* ws, int B, int N, int key_rows, TransposeBatch* tb, float* zero_bk);
+int attention_forward_impl(const pc_p2v_tensors* p, const float* query, const float* keys, int B, int N,
+                           int key_rows, const int32_t* slot_row, float* out, const pc_attn_saved* sv, void* ws,
+                           size_t ws_bytes, void* stream, int transposed, NtArgs* defer_out_chain);
+int attention_backward_impl(const pc_p2v_tensors* p, const pc_p2v_tensors* g, const float* query, const float* keys,
+                            int B, int N, int key_rows, const int32_t* slot_row, int pad_row, const float* dout,
+                            const pc_attn_saved* sv, float* dquery, float* dkeys, int accumulate, void* ws,
+                            size_t ws_bytes, void* stream, const int32_t* ref_off, const int32_t* ref_slot,
+                            int transposed, TnDefer* defer, const HingeMeanJob* rider, const LossPro* lossp,
+                            const NtArgs* fwd_out_chain);

@@ -38,8 +38,6 @@
 #endif
 #define EV_MIN_ROWS 10             // a batch of fewer rows makes metrics.py:103's key min(10, cols) a new one
 
-static inline size_t ev_align(size_t x) { return (x + 255) & ~(size_t)255; }
-
 struct EvalWs {
     int32_t* topk_table;           // [T, K]        (FIRST: tests and probes read the plan's types back from ws)
     float* tp_table;               // [T, K, D]
@@ -53,12 +51,8 @@ struct EvalWs {
 
 static EvalWs eval_ws_layout(void* base, int B, int T, int K, int D) {
     EvalWs w;
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        char* p = base ? reinterpret_cast<char*>(base) + off : nullptr;
-        off += ev_align(bytes);
-        return p;
-    };
+    WsCarver cv(base);
+    auto take = [&](size_t bytes) { return cv.bytes(bytes); };
     const size_t pr = T < EV_PLAN_ROWS ? T : EV_PLAN_ROWS;
     w.topk_table = (int32_t*)take((size_t)T * K * 4);
     w.tp_table = (float*)take((size_t)T * K * D * 4);
@@ -73,7 +67,7 @@ static EvalWs eval_ws_layout(void* base, int B, int T, int K, int D) {
     w.pi = (float*)take((size_t)B * D * 4);
     w.proj = (float*)take((size_t)B * D * 4);
     w.cos = (float*)take((size_t)B * K * 4);
-    w.total = off;
+    w.total = cv.total;
     return w;
 }
 
@@ -407,9 +401,7 @@ extern "C" int pc_joint_eval_epoch(const pc_joint_tensors* p, const int32_t* pai
                                    const int32_t* type_idx, int n_types, int dim, uint64_t seed, uint64_t first_step, int batch,
                                    int num_types, int k, int num_products, int32_t* stats_out, float* cos_sum_out,
                                    double* metrics_out, int32_t* bad_count, void* ws, size_t ws_bytes, void* stream) {
-    if (!p || !p->product_table || !p->enc_w || !p->enc_b || !p->dec_w || !p->dec_b || !p->typ_w || !p->typ_b || !p->itm_w ||
-        !p->itm_b || !p->query_types || !p->comp_types)
-        return PC_EINVAL;
+    if (!joint_tensors_ok(p, true)) return PC_EINVAL;
     if (!pairs || !features || !type_idx || !stats_out || !cos_sum_out || !metrics_out || !ws) return PC_EINVAL;
     if (n_pairs <= 0 || batch <= 0 || num_types <= 0 || n_types <= 0 || num_products <= 0) return PC_EINVAL;
     if (dim != 128 && dim != 256) return PC_ESHAPE;

@@ -180,8 +180,6 @@ __global__ __launch_bounds__(256) void export_select_kernel(const int32_t* __res
 }
 
 // ---------------------------------------------------------------------------------------
-static inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 struct ExportWs {
     void* ffn; size_t ffn_bytes;           // pc_p2v_ffn_forward_eval's own workspace for `chunk` rows
     float *e2, *q, *qt, *c, *sp, *ctx;     // [C,D], [C,D], [C,HEADS,D], [C,HEADS,D], [C,HEADS], [C,D]
@@ -191,15 +189,10 @@ struct ExportWs {
 
 static ExportWs export_ws_layout(void* base, int chunk, int D) {
     ExportWs w;
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        void* p = base ? reinterpret_cast<char*>(base) + off : nullptr;
-        off += align256(bytes);
-        return p;
-    };
-    auto takef = [&](size_t floats) { return reinterpret_cast<float*>(take(floats * sizeof(float))); };
+    WsCarver cv(base);
+    auto takef = [&](size_t floats) { return cv.floats(floats); };
     w.ffn_bytes = pc_p2v_ffn_workspace_bytes(chunk);
-    w.ffn = take(w.ffn_bytes);
+    w.ffn = cv.bytes(w.ffn_bytes);
     w.e2 = takef((size_t)chunk * D);
     w.q = takef((size_t)chunk * D);
     w.qt = takef((size_t)chunk * PC_HEADS * D);
@@ -207,7 +200,7 @@ static ExportWs export_ws_layout(void* base, int chunk, int D) {
     w.sp = takef((size_t)chunk * PC_HEADS);
     w.ctx = takef((size_t)chunk * D);
     w.wkvt = takef((size_t)2 * D * D);
-    w.total = off;
+    w.total = cv.total;
     return w;
 }
 

@@ -14,7 +14,6 @@
 // BatchNorm statistics are per SEGMENT (= per reference FFN call), see pc_segments.
 #include "common.h"
 
-int pc_opt_bn_finalize_side();     // (gemm_tn.hip: pc_set_option)
 
 #define BN_EPS 1e-5f
 #define BN_MOMENTUM 0.1f
@@ -327,8 +326,6 @@ int launch_transpose(const float* in, int rows, int cols, float* out, hipStream_
 }
 
 // ---------------------------------------------------------------------------------------
-static inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 struct FfnWs {
     float *stat_a, *stat_b;     // [ntiles][H] each
     float *dz2, *dz1;           // [R,H] each (backward; also h0/a2 scratch for eval)
@@ -344,12 +341,8 @@ struct FfnWs {
 static FfnWs ffn_ws_layout(void* base, int rows) {
     FfnWs w;
     const int max_tiles = (rows + 127) / 128 + PC_MAX_SEG;
-    size_t off = 0;
-    auto take = [&](size_t floats) {
-        float* p = base ? reinterpret_cast<float*>(reinterpret_cast<char*>(base) + off) : nullptr;
-        off += align256(floats * sizeof(float));
-        return p;
-    };
+    WsCarver cv(base);
+    auto take = [&](size_t floats) { return cv.floats(floats); };
     w.stat_a = take((size_t)max_tiles * PC_H);
     w.stat_b = take((size_t)max_tiles * PC_H);
     w.dz2 = take((size_t)rows * PC_H);
@@ -364,7 +357,7 @@ static FfnWs ffn_ws_layout(void* base, int rows) {
     for (size_t f : {gemm_tn_workspace_floats(rows, PC_D, PC_H), gemm_tn_workspace_floats(rows, PC_H, PC_D)})
         if (f > w.slab_floats) w.slab_floats = f;
     for (int i = 0; i < 4; i++) w.slabs[i] = take(w.slab_floats);
-    w.total = off;
+    w.total = cv.total;
     return w;
 }
 

@@ -10,15 +10,9 @@
 // [B,T] zero gradient and a dense [T,B]x[B,L] product for it).
 #include "common.h"
 
-int launch_transpose(const float* in, int rows, int cols, float* out, hipStream_t st);
-int launch_dropout(const float* x, size_t n, const pc_dropout& d, unsigned stream_id, float* y, hipStream_t st);
-extern "C" int pc_scatter_add_rows_small(float* table, int table_rows, const int32_t* idx, int rows, int width,
-                                         const float* src, void* stream);
 
 #define JMAX_K 8   /* top-k capacity of topk_rows_kernel (NUM_COMP_TYPES = 3 in config.py:24) */
 #define LH (PC_L / 2)
-
-static inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 static NtArgs nt_plain(const float* A, int lda, const float* W, int ldw, const float* bias, float* C, int ldc, int M,
                        int N, int K) {
@@ -486,12 +480,8 @@ struct JointWs {
 
 static JointWs joint_ws_layout(void* base, int B, int T, int K) {
     JointWs w;
-    size_t off = 0;
-    auto take = [&](size_t floats) {
-        float* p = base ? reinterpret_cast<float*>(reinterpret_cast<char*>(base) + off) : nullptr;
-        off += align256(floats * sizeof(float));
-        return p;
-    };
+    WsCarver cv(base);
+    auto take = [&](size_t floats) { return cv.floats(floats); };
     w.dpi = take((size_t)B * PC_D);
     w.dtp = take((size_t)B * K * PC_D);
     w.dce = take((size_t)B * K * PC_L);
@@ -535,7 +525,7 @@ static JointWs joint_ws_layout(void* base, int B, int T, int K) {
             for (int i = 0; i < 2; i++) w.tslabs[i] = take((size_t)w.tblocks[i] * T * PC_L);
         }
     }
-    w.total = off;
+    w.total = cv.total;
     return w;
 }
 

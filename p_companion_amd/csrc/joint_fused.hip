@@ -31,8 +31,6 @@
 #define T_SMALL 512   /* largest table the per-tile similarity row (LDS) and the one-hot gradients serve */
 #define T_WGRAD 128   /* largest table whose one-hot gradient blocks (8 per wave and table) the tile kernel carries itself */
 
-static inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 struct FusedArgs {
     const float *table, *enc_w, *enc_b, *dec_w, *dec_b, *typ_w, *typ_b, *itm_w, *itm_b, *eq, *ec;
     const int32_t *query_idx, *query_types, *pos_types, *neg_types;
@@ -2390,8 +2388,6 @@ __global__ __launch_bounds__(256) void table_segsum_kernel(SegList l0, SegList l
     }
 }
 
-int pc_opt_sorted_tables();     // (gemm_tn.hip: pc_set_option)
-
 struct FusedWs {
     float *part, *h, *dpi, *dtp, *dc, *dh, *dt, *ecsrc;
     int32_t *ecidx, *cids, *ulist, *n_u, *topk_by_type;
@@ -2410,13 +2406,9 @@ struct FusedWs {
 };
 
 static FusedWs fused_ws_layout(void* base, int B, int T, int K) {
-    FusedWs w;
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        void* p = base ? reinterpret_cast<char*>(base) + off : nullptr;
-        off += align256(bytes);
-        return p;
-    };
+    FusedWs w = {};                                             // (what a small table does not use stays null / 0)
+    WsCarver cv(base);
+    auto take = [&](size_t bytes) { return cv.bytes(bytes); };
     w.small = T <= T_SMALL;
     w.part = (float*)take((size_t)2 * B * 4);
     w.h = (float*)take((size_t)B * LH * 4);
@@ -2431,19 +2423,7 @@ static FusedWs fused_ws_layout(void* base, int B, int T, int K) {
     w.wg_blocks = (B + WG_S - 1) / WG_S;
     w.wslab_floats = wg_slab_floats(w.small ? T : 0);      // (large tables: their gradients go by row scatter-add)
     w.wslabs = (float*)take((size_t)w.wg_blocks * w.wslab_floats * 4);
-    w.nchunks_s = w.ucap = 0;
-    w.ulist = w.n_u = w.topk_by_type = nullptr;
-    w.tl_c = w.tp_c = w.tl_q = w.tp_q = w.n_touch = nullptr;
-    w.tslab_c = w.tslab_q = nullptr;
-    w.srt_c = w.srt_q = nullptr;
-    w.med_c = w.med_q = w.lng_c = w.lng_q = nullptr;
-    w.gnt_c = w.gnt_q = nullptr; w.gct_c = w.gct_q = nullptr; w.gpr_c = w.gpr_q = nullptr;
-    w.seg_c = w.seg_q = nullptr;
-    w.sorted_path = false;
-    w.part_val = nullptr;
-    w.csamp = w.gmat = w.g0 = w.gnmax = nullptr;
-    if (w.small) {
-    } else {
+    if (!w.small) {
         const int nc = B * (K + 2);
         w.tl_c = (int32_t*)take((size_t)(nc < T ? nc : T) * 4);
         w.tp_c = (int32_t*)take((size_t)T * 4);
@@ -2479,7 +2459,7 @@ static FusedWs fused_ws_layout(void* base, int B, int T, int K) {
         w.g0 = (float*)take((size_t)T * 4);
         w.gnmax = (float*)take((size_t)2 * ((T + UT - 1) / UT) * 4);     // the sub-chunks' largest |G[t]|, then their largest |g0[t]|
     }
-    w.total = off;
+    w.total = cv.total;
     return w;
 }
 
@@ -2509,40 +2489,68 @@ extern "C" int pc_joint_fused_supported(int num_types, int k, float dropout_p) {
     return 1;
 }
 
-static bool tensors_ok(const pc_joint_tensors* t, bool need_table) {
-    return t && (!need_table || t->product_table) && t->enc_w && t->enc_b && t->dec_w && t->dec_b && t->typ_w && t->typ_b &&
-           t->itm_w && t->itm_b && t->query_types && t->comp_types;
-}
-
-extern "C" int pc_build_complementary_batch(const int32_t* pairs, int batch, const float* features,
-                                            const int32_t* type_idx, int n_types, uint64_t seed, uint64_t step,
-                                            int32_t* query_idx, int32_t* query_types, int32_t* pos_types,
-                                            int32_t* neg_types, float* pos_items, float* neg_items,
-                                            float* target_features, void* stream);
-
 struct PairsSrc { const int32_t* pairs; const float* features; const int32_t* type_idx; int n_types; uint64_t seed, step; };
 // Across the steps of ONE epoch call (num_types > 512, no hidden-layer dropout): `have` -- the previous step of this call formed
 // this step's distinct-query-type list into half `parity` of the double buffer; next_pairs -- the labelled pairs of the next step
 // (same batch size: the workspace layout, hence the buffer, is the same), whose list this step forms into the other half.
 struct JointLookahead { bool have; int parity; const int32_t* next_pairs; };
 
-static int fused_step_impl(const pc_joint_tensors* p, const pc_joint_tensors* g, const pc_joint_tensors* exp_avg,
-                           const pc_joint_tensors* exp_avg_sq, int64_t* step_count, double lr, double beta1,
-                           double beta2, double eps, const PairsSrc* src, const int32_t* query_idx, const int32_t* query_types,
-                           const int32_t* pos_types, const int32_t* neg_types, const float* pos_items,
-                           const float* neg_items, int B, int T, int K, int num_products, float margin, float alpha,
-                           float* losses, int32_t* topk, int32_t* bad_count, void* ws, size_t ws_bytes,
-                           void* stream, JointLookahead* la = nullptr) {
-    if (!tensors_ok(p, true) || !tensors_ok(g, false)) return PC_EINVAL;
-    const bool adam = exp_avg != nullptr;
-    if (adam && (!tensors_ok(exp_avg, false) || !tensors_ok(exp_avg_sq, false) || !step_count)) return PC_EINVAL;
-    if (!query_idx || !query_types || !pos_types || !neg_types || !pos_items || !neg_items || !losses || !topk || !ws)
+// One call of the fused step, by name.
+struct JointStepCall {
+    const pc_joint_tensors *p = nullptr, *g = nullptr;
+    const pc_joint_tensors *exp_avg = nullptr, *exp_avg_sq = nullptr;      // both null: gradients only, no optimizer step
+    int64_t* step_count = nullptr;
+    double lr = 0, beta1 = 0, beta2 = 0, eps = 0;
+    const PairsSrc* src = nullptr;                  // the batch from labelled pairs (the batch buffers are then outputs)
+    const int32_t *query_idx = nullptr, *query_types = nullptr, *pos_types = nullptr, *neg_types = nullptr;
+    const float *pos_items = nullptr, *neg_items = nullptr;
+    int B = 0, T = 0, K = 0, num_products = 0;
+    float margin = 0.f, alpha = 0.f;
+    float* losses = nullptr;
+    int32_t *topk = nullptr, *bad_count = nullptr;
+    void* ws = nullptr;
+    size_t ws_bytes = 0;
+    void* stream = nullptr;
+    JointLookahead* la = nullptr;
+};
+
+// Every instantiation of the tile kernel and of the row-buffer gradient kernel, named once: the dynamic-LDS attribute and the
+// launch both go through these tables.  Tile kernel: TILE_* + (K == 3 ? 0 : 1).
+typedef void (*TileKernel)(FusedArgs, int);
+typedef void (*WgradKernel)(WgradArgs);
+enum { TILE_PAIRS_LARGE = 0, TILE_PAIRS_SMALL = 2, TILE_SMALL_WGRAD = 4, TILE_SMALL = 6, TILE_LARGE = 8 };
+static const TileKernel tile_kernels[10] = {
+    joint_tile_kernel<false, 3, true, true>, joint_tile_kernel<false, 0, true, true>,
+    joint_tile_kernel<true, 3, true, true>,  joint_tile_kernel<true, 0, true, true>,
+    joint_tile_kernel<true, 3, true>,        joint_tile_kernel<true, 0, true>,
+    joint_tile_kernel<true, 3, false>,       joint_tile_kernel<true, 0, false>,
+    joint_tile_kernel<false, 3, true>,       joint_tile_kernel<false, 0, true>};
+static const WgradKernel wgrad_kernels[2] = {joint_wgrad_kernel<16, 3>, joint_wgrad_kernel<16, 0>};
+template <class Kernel, int N>
+static bool allow_max_dynamic_lds(const Kernel (&k)[N]) {
+    for (int i = 0; i < N; i++)
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k[i]), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    return true;
+}
+
+static int fused_step_impl(const JointStepCall& c) {
+    const pc_joint_tensors *p = c.p, *g = c.g;
+    const PairsSrc* src = c.src;
+    JointLookahead* la = c.la;
+    const int32_t *query_idx = c.query_idx, *query_types = c.query_types, *pos_types = c.pos_types, *neg_types = c.neg_types;
+    const float *pos_items = c.pos_items, *neg_items = c.neg_items;
+    const int B = c.B, T = c.T, K = c.K, num_products = c.num_products;
+    int32_t* topk = c.topk;
+    if (!joint_tensors_ok(p, true) || !joint_tensors_ok(g, false)) return PC_EINVAL;
+    const bool adam = c.exp_avg != nullptr;
+    if (adam && (!joint_tensors_ok(c.exp_avg, false) || !joint_tensors_ok(c.exp_avg_sq, false) || !c.step_count)) return PC_EINVAL;
+    if (!query_idx || !query_types || !pos_types || !neg_types || !pos_items || !neg_items || !c.losses || !topk || !c.ws)
         return PC_EINVAL;
     if (B <= 0 || T <= 0 || num_products <= 0) return PC_EINVAL;
     if (!pc_joint_fused_supported(T, K, p->dropout.p)) return PC_ESHAPE;
-    if (ws_bytes < pc_joint_fused_workspace_bytes(B, T, K)) return PC_EWORKSPACE;
-    hipStream_t st = (hipStream_t)stream;
-    FusedWs w = fused_ws_layout(ws, B, T, K);
+    if (c.ws_bytes < pc_joint_fused_workspace_bytes(B, T, K)) return PC_EWORKSPACE;
+    hipStream_t st = (hipStream_t)c.stream;
+    FusedWs w = fused_ws_layout(c.ws, B, T, K);
     // the batch from labelled pairs: inside the tile kernel (T <= 128, and T > 512 where present_types_kernel takes the query
     // types from the pairs as well); for 128 < T <= 512 by the builder's own launch, then the step as usual
     const bool pairs_in_tile = src && (!w.small || T <= T_WGRAD);
@@ -2550,7 +2558,7 @@ static int fused_step_impl(const pc_joint_tensors* p, const pc_joint_tensors* g,
         PC_TRY(pc_build_complementary_batch(src->pairs, B, src->features, src->type_idx, src->n_types, src->seed, src->step,
                                             const_cast<int32_t*>(query_idx), const_cast<int32_t*>(query_types),
                                             const_cast<int32_t*>(pos_types), const_cast<int32_t*>(neg_types),
-                                            const_cast<float*>(pos_items), const_cast<float*>(neg_items), nullptr, stream));
+                                            const_cast<float*>(pos_items), const_cast<float*>(neg_items), nullptr, c.stream));
 
     const bool per_sample = !w.small && p->dropout.p > 0.f;      // hidden-layer dropout: c is a function of the SAMPLE
     const int32_t* look_pairs = nullptr; int32_t *look_ulist = nullptr, *look_n_u = nullptr;      // JointLookahead: see joint_finish_kernel
@@ -2605,12 +2613,12 @@ static int fused_step_impl(const pc_joint_tensors* p, const pc_joint_tensors* g,
     fa.query_idx = query_idx; fa.query_types = query_types; fa.pos_types = pos_types; fa.neg_types = neg_types;
     fa.pos_items = pos_items; fa.neg_items = neg_items;
     fa.B = B; fa.T = T; fa.K = K; fa.P = num_products;
-    fa.margin = margin; fa.g_type = (1.0f - alpha) / (float)B; fa.g_item = alpha / ((float)B * (float)K);
+    fa.margin = c.margin; fa.g_type = (1.0f - c.alpha) / (float)B; fa.g_item = c.alpha / ((float)B * (float)K);
     fa.drop = make_dropcfg(p->dropout);
     fa.topk_by_type = w.topk_by_type; fa.topk_per_sample = per_sample ? 1 : 0;
     fa.topk = topk; fa.part_type = w.part; fa.part_item = w.part + B;
     fa.h = w.h; fa.dpi = w.dpi; fa.dtp = w.dtp; fa.dc = w.dc; fa.dh = w.dh; fa.dt = w.dt;
-    fa.ecsrc = w.ecsrc; fa.ecidx = w.ecidx; fa.cids = w.cids; fa.bad = bad_count; fa.step_count = adam ? step_count : nullptr;
+    fa.ecsrc = w.ecsrc; fa.ecidx = w.ecidx; fa.cids = w.cids; fa.bad = c.bad_count; fa.step_count = adam ? c.step_count : nullptr;
     fa.run_counts = (!w.small && w.sorted_path) ? w.n_touch + 2 : nullptr;
     fa.slabs = w.wslabs; fa.slab_floats = w.wslab_floats;
     if (pairs_in_tile) {
@@ -2626,34 +2634,12 @@ static int fused_step_impl(const pc_joint_tensors* p, const pc_joint_tensors* g,
     // rows go by scatter-add) or, for 128 < T <= 512, in joint_wgrad_kernel over the row buffers
     const bool wgrad_in_tile = !w.small || T <= T_WGRAD;
     const size_t lds = tile_lds_bytes(T, w.small, w.small && wgrad_in_tile);
-    static const hipError_t attr[10] = {
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&joint_tile_kernel<false, 3, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024),
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&joint_tile_kernel<false, 0, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024),
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&joint_tile_kernel<true, 3, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024),
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&joint_tile_kernel<true, 0, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024),
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&joint_tile_kernel<true, 3, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024),
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&joint_tile_kernel<true, 0, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024),
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&joint_tile_kernel<true, 3, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024),
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&joint_tile_kernel<true, 0, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024),
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&joint_tile_kernel<false, 3, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024),
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&joint_tile_kernel<false, 0, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)};
-    (void)attr;
-    if (pairs_in_tile && w.small) {
-        if (K == 3) PC_LAUNCH((joint_tile_kernel<true, 3, true, true>), dim3(tiles), dim3(256), lds, st, fa, ldsims);
-        else PC_LAUNCH((joint_tile_kernel<true, 0, true, true>), dim3(tiles), dim3(256), lds, st, fa, ldsims);
-    } else if (pairs_in_tile) {
-        if (K == 3) PC_LAUNCH((joint_tile_kernel<false, 3, true, true>), dim3(tiles), dim3(256), lds, st, fa, ldsims);
-        else PC_LAUNCH((joint_tile_kernel<false, 0, true, true>), dim3(tiles), dim3(256), lds, st, fa, ldsims);
-    } else if (w.small && wgrad_in_tile) {
-        if (K == 3) PC_LAUNCH((joint_tile_kernel<true, 3, true>), dim3(tiles), dim3(256), lds, st, fa, ldsims);
-        else PC_LAUNCH((joint_tile_kernel<true, 0, true>), dim3(tiles), dim3(256), lds, st, fa, ldsims);
-    } else if (w.small) {
-        if (K == 3) PC_LAUNCH((joint_tile_kernel<true, 3, false>), dim3(tiles), dim3(256), lds, st, fa, ldsims);
-        else PC_LAUNCH((joint_tile_kernel<true, 0, false>), dim3(tiles), dim3(256), lds, st, fa, ldsims);
-    } else {
-        if (K == 3) PC_LAUNCH((joint_tile_kernel<false, 3, true>), dim3(tiles), dim3(256), lds, st, fa, ldsims);
-        else PC_LAUNCH((joint_tile_kernel<false, 0, true>), dim3(tiles), dim3(256), lds, st, fa, ldsims);
-    }
+    static const bool tile_attr = allow_max_dynamic_lds(tile_kernels);       // (the first call sets all of them)
+    (void)tile_attr;
+    const int variant = pairs_in_tile ? (w.small ? TILE_PAIRS_SMALL : TILE_PAIRS_LARGE)
+                        : w.small    ? (wgrad_in_tile ? TILE_SMALL_WGRAD : TILE_SMALL)
+                                     : TILE_LARGE;
+    PC_LAUNCH(tile_kernels[variant + (K == 3 ? 0 : 1)], dim3(tiles), dim3(256), lds, st, fa, ldsims);
     PC_TRY(pc_launch_status());
 
     // ---- gradient products over the row buffers: one launch, one slab per workgroup, summed by the finish kernel
@@ -2664,13 +2650,9 @@ static int fused_step_impl(const pc_joint_tensors* p, const pc_joint_tensors* g,
     wa.B = B; wa.T = w.small ? T : 0; wa.K = K; wa.slabs = w.wslabs; wa.slab_floats = w.wslab_floats;
     if (!wgrad_in_tile) {
         // (only 128 < T <= 512 comes here: 16 type blocks per wave and table)
-        static const hipError_t wattr[2] = {
-            hipFuncSetAttribute(reinterpret_cast<const void*>(&joint_wgrad_kernel<16, 3>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024),
-            hipFuncSetAttribute(reinterpret_cast<const void*>(&joint_wgrad_kernel<16, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)};
-        (void)wattr;
-        const size_t wl = wgrad_lds_bytes();
-        if (K == 3) PC_LAUNCH((joint_wgrad_kernel<16, 3>), dim3(w.wg_blocks), dim3(512), wl, st, wa);
-        else PC_LAUNCH((joint_wgrad_kernel<16, 0>), dim3(w.wg_blocks), dim3(512), wl, st, wa);
+        static const bool wgrad_attr = allow_max_dynamic_lds(wgrad_kernels);
+        (void)wgrad_attr;
+        PC_LAUNCH(wgrad_kernels[K == 3 ? 0 : 1], dim3(w.wg_blocks), dim3(512), wgrad_lds_bytes(), st, wa);
         PC_TRY(pc_launch_status());
     }
     // which form sums the table gradients (PC_OPT_SORTED_TABLE_GRADIENTS in the header): the sorted one wherever the lists fit
@@ -2740,16 +2722,10 @@ static int fused_step_impl(const pc_joint_tensors* p, const pc_joint_tensors* g,
         const int off[10] = {wg_off_itm_w(), wg_off_itm_b(), wg_off_typ_w(), wg_off_typ_b(), wg_off_dec_w(), wg_off_dec_b(),
                              wg_off_enc_w(), wg_off_enc_b(), wg_off_ec(), wg_off_eq(Tt)};
         const int cnt[10] = {PC_D * PC_D, PC_D, PC_D * PC_L, PC_D, PC_L * LH, PC_L, LH * PC_L, LH, Tt * PC_L, Tt * PC_L};
-        float* const gq[10] = {g->itm_w, g->itm_b, g->typ_w, g->typ_b, g->dec_w, g->dec_b, g->enc_w, g->enc_b, g->comp_types, g->query_types};
-        float* const pq[10] = {p->itm_w, p->itm_b, p->typ_w, p->typ_b, p->dec_w, p->dec_b, p->enc_w, p->enc_b, p->comp_types, p->query_types};
-        float *mq[10] = {}, *vq[10] = {};
-        if (adam) {
-            float* const m_[10] = {exp_avg->itm_w, exp_avg->itm_b, exp_avg->typ_w, exp_avg->typ_b, exp_avg->dec_w, exp_avg->dec_b,
-                                   exp_avg->enc_w, exp_avg->enc_b, exp_avg->comp_types, exp_avg->query_types};
-            float* const v_[10] = {exp_avg_sq->itm_w, exp_avg_sq->itm_b, exp_avg_sq->typ_w, exp_avg_sq->typ_b, exp_avg_sq->dec_w,
-                                   exp_avg_sq->dec_b, exp_avg_sq->enc_w, exp_avg_sq->enc_b, exp_avg_sq->comp_types, exp_avg_sq->query_types};
-            for (int i = 0; i < 10; i++) { mq[i] = m_[i]; vq[i] = v_[i]; }
-        }
+        float *gq[10], *pq[10], *mq[10] = {}, *vq[10] = {};
+        joint_fields(g, gq);
+        joint_fields(p, pq);
+        if (adam) { joint_fields(c.exp_avg, mq); joint_fields(c.exp_avg_sq, vq); }
         for (int i = 0; i < 10; i++) {
             if (cnt[i] > 0) add(w.wslabs + off[i], (size_t)w.wslab_floats, w.wg_blocks, cnt[i], gq[i], pq[i], mq[i], vq[i]);
             else if (adam)                                             // big tables: gradient complete already, Adam only
@@ -2758,8 +2734,8 @@ static int fused_step_impl(const pc_joint_tensors* p, const pc_joint_tensors* g,
     }
     fin.njobs = nj;
     for (int k = nj; k <= FIN_JOBS; k++) fin.block0[k] = blocks;
-    fin.part_type = w.part; fin.part_item = w.part + B; fin.B = B; fin.K = K; fin.alpha = alpha; fin.losses = losses;
-    fin.step_count = step_count; fin.lr = lr; fin.beta1 = beta1; fin.beta2 = beta2; fin.eps = eps; fin.adam = adam ? 1 : 0;
+    fin.part_type = w.part; fin.part_item = w.part + B; fin.B = B; fin.K = K; fin.alpha = c.alpha; fin.losses = c.losses;
+    fin.step_count = c.step_count; fin.lr = c.lr; fin.beta1 = c.beta1; fin.beta2 = c.beta2; fin.eps = c.eps; fin.adam = adam ? 1 : 0;
     if (look_pairs) {
         fin.next_pairs = look_pairs; fin.type_idx = src->type_idx; fin.P = num_products; fin.next_B = B; fin.T = T;
         fin.next_ulist = look_ulist; fin.next_n_u = look_n_u;
@@ -2768,6 +2744,15 @@ static int fused_step_impl(const pc_joint_tensors* p, const pc_joint_tensors* g,
     return pc_launch_status();
 }
 
+// what the entry points below pass through unchanged (their parameters carry the fields' names)
+#define JOINT_STEP_COMMON(c)                                                                                         \
+    c.p = p; c.g = g; c.lr = lr; c.beta1 = beta1; c.beta2 = beta2; c.eps = eps;                                      \
+    c.query_idx = query_idx; c.query_types = query_types; c.pos_types = pos_types; c.neg_types = neg_types;          \
+    c.pos_items = pos_items; c.neg_items = neg_items; c.B = B; c.T = T; c.K = K; c.num_products = num_products;      \
+    c.margin = margin; c.alpha = alpha; c.topk = topk; c.bad_count = bad_count; c.ws = ws; c.ws_bytes = ws_bytes;    \
+    c.stream = stream
+#define JOINT_STEP_ADAM(c) c.exp_avg = exp_avg; c.exp_avg_sq = exp_avg_sq; c.step_count = step_count
+
 extern "C" int pc_joint_fused_step(const pc_joint_tensors* p, const pc_joint_tensors* g, const pc_joint_tensors* exp_avg,
                                    const pc_joint_tensors* exp_avg_sq, int64_t* step_count, double lr, double beta1,
                                    double beta2, double eps, const int32_t* query_idx, const int32_t* query_types,
@@ -2775,9 +2760,10 @@ extern "C" int pc_joint_fused_step(const pc_joint_tensors* p, const pc_joint_ten
                                    const float* neg_items, int B, int T, int K, int num_products, float margin, float alpha,
                                    float* losses, int32_t* topk, int32_t* bad_count, void* ws, size_t ws_bytes,
                                    void* stream) {
-    return fused_step_impl(p, g, exp_avg, exp_avg_sq, step_count, lr, beta1, beta2, eps, nullptr, query_idx, query_types,
-                           pos_types, neg_types, pos_items, neg_items, B, T, K, num_products, margin, alpha, losses, topk,
-                           bad_count, ws, ws_bytes, stream);
+    JointStepCall c;
+    JOINT_STEP_COMMON(c); JOINT_STEP_ADAM(c);
+    c.losses = losses;
+    return fused_step_impl(c);
 }
 
 extern "C" int pc_joint_fused_step_pairs(const pc_joint_tensors* p, const pc_joint_tensors* g, const pc_joint_tensors* exp_avg,
@@ -2790,9 +2776,39 @@ extern "C" int pc_joint_fused_step_pairs(const pc_joint_tensors* p, const pc_joi
                                          void* ws, size_t ws_bytes, void* stream) {
     if (!pairs || !features || !type_idx || n_types <= 0) return PC_EINVAL;
     const PairsSrc src = {pairs, features, type_idx, n_types, seed, step};
-    return fused_step_impl(p, g, exp_avg, exp_avg_sq, step_count, lr, beta1, beta2, eps, &src, query_idx, query_types,
-                           pos_types, neg_types, pos_items, neg_items, B, T, K, num_products, margin, alpha, losses, topk,
-                           bad_count, ws, ws_bytes, stream);
+    JointStepCall c;
+    JOINT_STEP_COMMON(c); JOINT_STEP_ADAM(c);
+    c.src = &src; c.losses = losses;
+    return fused_step_impl(c);
+}
+
+// The epoch loop of pc_joint_train_epoch and of the data-parallel epochs: full batches of c.B pairs in the order of
+// src.pairs, then -- unless drop_last -- the ragged rest; after_step(i) follows step i on the same stream (the replicas'
+// exchange plus Adam; nothing for the single-device epoch, whose optimizer rides in the step).
+template <class StepHook>
+static int joint_epoch_loop(JointStepCall c, PairsSrc src, int64_t n_pairs, int drop_last, float* losses_out, StepHook after_step) {
+    const pc_joint_tensors* p = c.p;
+    const int32_t* pairs = src.pairs;
+    const uint64_t first_step = src.step;
+    const int B = c.B;
+    pc_joint_tensors pl = *p;
+    JointLookahead la = {false, 0, nullptr};
+    c.p = &pl; c.src = &src; c.la = &la;
+    int64_t done = 0;
+    for (int64_t i = 0; done < n_pairs; i++) {
+        const int64_t left = n_pairs - done;
+        const int b = left >= B ? B : (int)left;
+        if (b < B && drop_last) break;
+        src.pairs = pairs + 3 * done; src.step = first_step + (uint64_t)i;
+        pl.dropout.offset = p->dropout.offset + (uint64_t)i;
+        // (the next step's list only when that step has this one's batch size: the workspace layout is a function of it)
+        la.next_pairs = (left - b >= b && b == B) ? pairs + 3 * (done + b) : nullptr;
+        c.B = b; c.losses = losses_out + 3 * i;
+        PC_TRY(fused_step_impl(c));
+        PC_TRY(after_step(i));
+        done += b;
+    }
+    return PC_OK;
 }
 
 // train.py:36-57 (train_epoch: for batch in loader: forward, loss, zero_grad, backward, optimizer.step) for `n_pairs`
@@ -2811,23 +2827,10 @@ extern "C" int pc_joint_train_epoch(const pc_joint_tensors* p, const pc_joint_te
                                     void* ws, size_t ws_bytes, void* stream) {
     if (!p || !pairs || !features || !type_idx || n_types <= 0 || n_pairs < 0 || B <= 0 || !losses_out) return PC_EINVAL;
     if (!exp_avg || !exp_avg_sq) return PC_EINVAL;               // an epoch without the optimizer step trains nothing
-    pc_joint_tensors pl = *p;
-    int64_t done = 0;
-    JointLookahead la = {false, 0, nullptr};
-    for (int64_t i = 0; done < n_pairs; i++) {
-        const int64_t left = n_pairs - done;
-        const int b = left >= B ? B : (int)left;
-        if (b < B && drop_last) break;
-        const PairsSrc src = {pairs + 3 * done, features, type_idx, n_types, seed, first_step + (uint64_t)i};
-        pl.dropout.offset = p->dropout.offset + (uint64_t)i;
-        // (the next step's list only when that step has this one's batch size: the workspace layout is a function of it)
-        la.next_pairs = (left - b >= b && b == B) ? pairs + 3 * (done + b) : nullptr;
-        PC_TRY(fused_step_impl(&pl, g, exp_avg, exp_avg_sq, step_count, lr, beta1, beta2, eps, &src, query_idx, query_types,
-                               pos_types, neg_types, pos_items, neg_items, b, T, K, num_products, margin, alpha,
-                               losses_out + 3 * i, topk, bad_count, ws, ws_bytes, stream, &la));
-        done += b;
-    }
-    return PC_OK;
+    JointStepCall c;
+    JOINT_STEP_COMMON(c); JOINT_STEP_ADAM(c);
+    return joint_epoch_loop(c, {pairs, features, type_idx, n_types, seed, first_step}, n_pairs, drop_last, losses_out,
+                            [](int64_t) { return (int)PC_OK; });
 }
 
 // The same epoch for a REPLICA of a data-parallel job (ABI 6): per step the fused step without its Adam (gradients only), the
@@ -2848,31 +2851,20 @@ extern "C" int pc_joint_train_epoch_plan(const pc_joint_tensors* p, const pc_joi
     if (!param_flat || !grad_flat || !exp_avg_flat || !exp_avg_sq_flat || n_flat == 0 || t_first < 0) return PC_EINVAL;
     if (t_first == 0 && (!step_count || !adam_scalars)) return PC_EINVAL;
     // p / g are views into the flat buffers: what the exchange averages and Adam updates must be what the step reads and writes
-    const float* const gp[10] = {g->itm_w, g->itm_b, g->typ_w, g->typ_b, g->dec_w, g->dec_b, g->enc_w, g->enc_b, g->comp_types, g->query_types};
-    const float* const pp[10] = {p->itm_w, p->itm_b, p->typ_w, p->typ_b, p->dec_w, p->dec_b, p->enc_w, p->enc_b, p->comp_types, p->query_types};
+    float *gp[10], *pp[10];
+    joint_fields(g, gp);
+    joint_fields(p, pp);
     for (int i = 0; i < 10; i++) {
         if (!gp[i] || !pp[i]) return PC_EINVAL;
         if (gp[i] < grad_flat || gp[i] >= grad_flat + n_flat || pp[i] < param_flat || pp[i] >= param_flat + n_flat) return PC_EINVAL;
         if (gp[i] - grad_flat != pp[i] - param_flat) return PC_EINVAL;
     }
-    pc_joint_tensors pl = *p;
-    int64_t done = 0;
-    JointLookahead la = {false, 0, nullptr};
-    for (int64_t i = 0; done < n_pairs; i++) {
-        const int64_t left = n_pairs - done;
-        const int b = left >= B ? B : (int)left;
-        if (b < B && drop_last) break;
-        const PairsSrc src = {pairs + 3 * done, features, type_idx, n_types, seed, first_step + (uint64_t)i};
-        pl.dropout.offset = p->dropout.offset + (uint64_t)i;
-        la.next_pairs = (left - b >= b && b == B) ? pairs + 3 * (done + b) : nullptr;
-        PC_TRY(fused_step_impl(&pl, g, nullptr, nullptr, nullptr, lr, beta1, beta2, eps, &src, query_idx, query_types, pos_types,
-                               neg_types, pos_items, neg_items, b, T, K, num_products, margin, alpha, losses_out + 3 * i, topk,
-                               bad_count, ws, ws_bytes, stream, &la));
-        PC_TRY(pc_exchange_adam_plan(plan, param_flat, grad_flat, exp_avg_flat, exp_avg_sq_flat, n_flat, step_count,
-                                     t_first > 0 ? t_first + i : 0, adam_scalars, lr, beta1, beta2, eps, stream));
-        done += b;
-    }
-    return PC_OK;
+    JointStepCall c;                                             // (no moments: the step leaves gradients, the hook does the rest)
+    JOINT_STEP_COMMON(c);
+    return joint_epoch_loop(c, {pairs, features, type_idx, n_types, seed, first_step}, n_pairs, drop_last, losses_out, [&](int64_t i) {
+        return pc_exchange_adam_plan(plan, param_flat, grad_flat, exp_avg_flat, exp_avg_sq_flat, n_flat, step_count,
+                                     t_first > 0 ? t_first + i : 0, adam_scalars, lr, beta1, beta2, eps, stream);
+    });
 }
 
 extern "C" int pc_joint_train_epoch_dp(const pc_joint_tensors* p, const pc_joint_tensors* g, float* param_flat, float* grad_flat,

@@ -5,8 +5,6 @@
 // (= optimizer.zero_grad() + loss.backward()); the optimizer step is pc_adam_step.
 #include "common.h"
 
-static inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 struct StepWs {
     int32_t* idx_all;
     float *y, *h0, *a2, *a1, *bn;     // bn: mean, invstd, scale, shift  [4][MAX_SEG][H]
@@ -20,12 +18,8 @@ struct StepWs {
 static StepWs step_ws_layout(void* base, int B, int N, int K, int D) {
     StepWs w;
     const size_t R = (size_t)B * (2 + N + K) + 1;          // +1: the shared padding row of the compact layout
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        void* p = base ? reinterpret_cast<char*>(base) + off : nullptr;
-        off += align256(bytes);
-        return p;
-    };
+    WsCarver cv(base);
+    auto take = [&](size_t bytes) { return cv.bytes(bytes); };
     w.idx_all = (int32_t*)take(R * 4);
     w.y = (float*)take(R * D * 4);
     w.h0 = (float*)take(R * PC_H * 4);
@@ -47,7 +41,7 @@ static StepWs step_ws_layout(void* base, int B, int N, int K, int D) {
     w.ffn_ws = take(w.ffn_bytes);
     w.attn_bytes = N > 0 ? pc_p2v_attention_workspace_bytes_dim(B, N, D) : 0;
     w.attn_ws = take(w.attn_bytes);
-    w.total = off;
+    w.total = cv.total;
     return w;
 }
 
@@ -58,11 +52,6 @@ extern "C" size_t pc_p2v_train_step_workspace_bytes_dim(int batch, int n_nbr, in
 extern "C" size_t pc_p2v_train_step_workspace_bytes(int batch, int n_nbr, int k_neg) {
     return pc_p2v_train_step_workspace_bytes_dim(batch, n_nbr, k_neg, PC_D);
 }
-extern "C" size_t pc_p2v_attention_workspace_bytes_dim(int batch, int n_keys, int dim);
-extern "C" int pc_p2v_triplet_loss_dim(const float* a, const float* p, const float* n, int batch, int k_neg, int dim,
-                                       float margin, float* loss, float* d_pos, float* d_neg, float* da, float* dp,
-                                       float* dn, void* stream);
-
 __device__ __forceinline__ void concat_idx_body(const int32_t* a, int na, const int32_t* b, int nb, const int32_t* c, int nc,
                                                 const int32_t* d, int nd, int32_t* out, int i) {
     if (i < na) out[i] = a[i];
@@ -110,67 +99,68 @@ __global__ __launch_bounds__(256) void p2v_prologue_kernel(const int32_t* a, int
     transpose_tile_body<256>(tb, (int)blockIdx.x - concat_blocks, tiles_x, tiles_y, t, threadIdx.x);
 }
 
-int ffn_forward_part1(const pc_p2v_tensors* p, const float* table, const int32_t* idx, int rows, const pc_segments* seg,
-                      const pc_ffn_saved* sv, double* local_sums, void* ws, size_t ws_bytes, void* stream);
-int ffn_forward_part2(const pc_p2v_tensors* p, int rows, const pc_segments* seg, int update_running, float* y,
-                      const pc_ffn_saved* sv, const double* global_sums, void* ws, size_t ws_bytes, void* stream,
-                      const TransposeBatch* ride = nullptr);
-int ffn_backward_part1(const pc_p2v_tensors* p, const pc_p2v_tensors* g, const float* table, const int32_t* idx,
-                       int rows, const pc_segments* seg, const float* dy, const pc_ffn_saved* sv, int with_dx,
-                       int accumulate, double* local_sums, void* ws, size_t ws_bytes, void* stream, int transposed,
-                       TnDefer* defer);
-int ffn_backward_part2(const pc_p2v_tensors* g, const float* table, const int32_t* idx, int rows,
-                       const pc_segments* seg, const pc_ffn_saved* sv, float* dx, int accumulate,
-                       const double* local_sums, const double* global_sums, void* ws, size_t ws_bytes, void* stream,
-                       TnDefer* defer);
-int ffn_transposes(const pc_p2v_tensors* p, void* ws, int rows, int with_dx, TransposeBatch* tb);
-int attention_transposes(const pc_p2v_tensors* p, void* ws, int B, int N, int key_rows, TransposeBatch* tb, float* zero_bk);
-int attention_forward_impl(const pc_p2v_tensors* p, const float* query, const float* keys, int B, int N,
-                           int key_rows, const int32_t* slot_row, float* out, const pc_attn_saved* sv, void* ws,
-                           size_t ws_bytes, void* stream, int transposed, NtArgs* defer_out_chain);
-int attention_backward_impl(const pc_p2v_tensors* p, const pc_p2v_tensors* g, const float* query, const float* keys,
-                            int B, int N, int key_rows, const int32_t* slot_row, int pad_row, const float* dout,
-                            const pc_attn_saved* sv, float* dquery, float* dkeys, int accumulate, void* ws,
-                            size_t ws_bytes, void* stream, const int32_t* ref_off, const int32_t* ref_slot,
-                            int transposed, TnDefer* defer, const HingeMeanJob* rider, const LossPro* lossp,
-                            const NtArgs* fwd_out_chain);
-int pc_opt_fused_loss();       // (gemm_tn.hip: pc_set_option)
-int pc_opt_fused_out_chain();
-int triplet_loss_launch(const float* a, const float* p, const float* n, int batch, int k_neg, int dim, float margin,
-                        float* loss, float* d_pos, float* d_neg, float* da, float* dp, float* dn, void* stream, int with_mean);
-
-// nb_idx: neighbour rows of the step, nbc of them.  Dense layout: nbc = B*N slots in slot order
-// (slot_row NULL).  Compact layout: the M real neighbours then one -1 row (nbc = M + 1), slot_row[B*N]
-// maps every slot to its row and the -1 row carries the weight of all padding slots.
-static int p2v_step_impl(const pc_p2v_tensors* p, const pc_p2v_tensors* g, const float* table,
-                         const int32_t* anchor_idx, const int32_t* positive_idx, const int32_t* negative_idx,
-                         const int32_t* nb_idx, int nbc, const int32_t* slot_row, int B, int N, int K, float margin,
-                         float* loss, float* d_pos, float* d_neg, float* anchor_emb, void* profile, void* ws,
-                         size_t ws_bytes, void* stream, int phase = -1, double* fwd_sums = nullptr,
-                         double* bwd_local = nullptr, const double* bwd_global = nullptr,
-                         const float* nb_weight = nullptr, const int32_t* ref_off = nullptr,
-                         const int32_t* ref_slot = nullptr, const pc_adam_fused* adam = nullptr,
-                         const int32_t* rows_ready = nullptr) {
-    // nb_weight (unique-neighbour layout): multiplicity of each of the nbc neighbour rows (its last entry = the
-    // number of padding slots); replaces the single weighted row of the compact layout
-    // phase -1: the whole step with this replica's BatchNorm statistics; 0/1/2: see pc_p2v_train_step_compact_sync
-    const bool p0 = phase <= 0, p1 = phase == -1 || phase == 1, p2 = phase == -1 || phase == 2;
-    if (adam && phase != -1) return PC_EINVAL;               // (the optimizer rides in the unsplit step's last launch only)
-    // rows_ready: [anchor | neighbour rows | positive | negatives] as the loader concatenated them (pc_p2v_concat_step_rows).  The
-    // step then has no launch of its own in front of Linear0: the transposed weights, which nothing needs before the attention,
+// One call of the step, by name.  nb_idx: neighbour rows of the step, nbc of them.  Dense layout: nbc = B*N slots in slot
+// order (slot_row NULL).  Compact layout: the M real neighbours then one -1 row (nbc = M + 1), slot_row[B*N] maps every slot
+// to its row and the -1 row carries the weight of all padding slots.
+struct P2VStepCall {
+    const pc_p2v_tensors *p = nullptr, *g = nullptr;
+    const float* table = nullptr;
+    const int32_t *anchor_idx = nullptr, *positive_idx = nullptr, *negative_idx = nullptr, *nb_idx = nullptr;
+    int nbc = 0;
+    const int32_t* slot_row = nullptr;
+    // (unique-neighbour layout) multiplicity of each of the nbc neighbour rows (its last entry = the number of padding
+    // slots): replaces the single weighted row of the compact layout; ref_off / ref_slot: row -> slots
+    const float* nb_weight = nullptr;
+    const int32_t *ref_off = nullptr, *ref_slot = nullptr;
+    // [anchor | neighbour rows | positive | negatives] as the loader concatenated them (pc_p2v_concat_step_rows).  The step
+    // then has no launch of its own in front of Linear0: the transposed weights, which nothing needs before the attention,
     // ride in the BatchNorm finalize launch of the FFN forward.
-    if (rows_ready && phase != -1) return PC_EINVAL;
-    ProfileScope prof_scope((pc_profile*)profile);
-    if (!p || !g || !table || !anchor_idx || !positive_idx || !negative_idx || !loss || !ws) return PC_EINVAL;
-    if (B <= 0 || N < 0 || K <= 0 || (N > 0 && !nb_idx) || nbc < 0 || nbc > B * N + 1) return PC_EINVAL;
+    const int32_t* rows_ready = nullptr;
+    int B = 0, N = 0, K = 0;
+    float margin = 0.f;
+    float *loss = nullptr, *d_pos = nullptr, *d_neg = nullptr, *anchor_emb = nullptr;
+    void* ws = nullptr;
+    size_t ws_bytes = 0;
+    // -1: the whole step with this replica's BatchNorm statistics; 0/1/2: see pc_p2v_train_step_compact_sync
+    int phase = -1;
+    double *fwd_sums = nullptr, *bwd_local = nullptr;
+    const double* bwd_global = nullptr;
+    const pc_adam_fused* adam = nullptr;     // the optimizer rides in the unsplit step's last launch only
+    void* profile = nullptr;
+    void* stream = nullptr;
+};
+
+// the compact and unique layouts: n_real real neighbour rows in front of the padding row, every slot mapped (and a slot count
+// that an int holds: the step indexes slots with one)
+static bool nb_layout_ok(const int32_t* slot_row, const int32_t* nb_rows, int n_real, int B, int N) {
+    const long long slots = (long long)B * N;
+    return slot_row && nb_rows && N > 0 && n_real >= 0 && n_real <= slots && slots < INT32_MAX;
+}
+
+static int p2v_step_impl(const P2VStepCall& c) {
+    const pc_p2v_tensors *p = c.p, *g = c.g;
+    const int32_t *slot_row = c.slot_row, *rows_ready = c.rows_ready;
+    const int B = c.B, N = c.N, K = c.K, nbc = c.nbc, phase = c.phase;
+    void* const stream = c.stream;
+    const bool p0 = phase <= 0, p1 = phase == -1 || phase == 1, p2 = phase == -1 || phase == 2;
+    if ((c.adam || rows_ready) && phase != -1) return PC_EINVAL;
+    if (c.adam && g) {
+        // the gradient tensors must be views of the flat buffer the optimizer updates
+        const float* gt[4] = {g->w0, g->w3, g->w5, g->out_proj_w};
+        for (const float* x : gt)
+            if (!x || x < c.adam->grad || x >= c.adam->grad + c.adam->n) return PC_EINVAL;
+    }
+    ProfileScope prof_scope((pc_profile*)c.profile);
+    if (!p || !g || !c.table || !c.anchor_idx || !c.positive_idx || !c.negative_idx || !c.loss || !c.ws) return PC_EINVAL;
+    if (B <= 0 || N < 0 || K <= 0 || (N > 0 && !c.nb_idx) || nbc < 0 || nbc > B * N + 1) return PC_EINVAL;
     // the anchor and positive calls are [B,128] BatchNorm inputs: the reference raises for a single row in training
     // mode (torch/nn/functional.py _verify_batch_size); so does a [1,5,128] negative block when K = 1
     if (B == 1) return PC_EBATCHNORM;
     if (p->dim != 0 && p->dim != 128 && p->dim != 256) return PC_ESHAPE;
     const int D = p->dim == 256 ? 256 : PC_D;
-    if (ws_bytes < pc_p2v_train_step_workspace_bytes_dim(B, N, K, D)) return PC_EWORKSPACE;
+    if (c.ws_bytes < pc_p2v_train_step_workspace_bytes_dim(B, N, K, D)) return PC_EWORKSPACE;
     hipStream_t st = (hipStream_t)stream;
-    StepWs w = step_ws_layout(ws, B, N, K, D);
+    StepWs w = step_ws_layout(c.ws, B, N, K, D);
     const int32_t* rows = rows_ready ? rows_ready : w.idx_all;
     const int R = 2 * B + nbc + B * K;
     const int rA = 0, rN = B, rP = B + nbc, rG = rP + B;
@@ -182,7 +172,7 @@ static int p2v_step_impl(const pc_p2v_tensors* p, const pc_p2v_tensors* g, const
     if (N > 0) {
         seg.nseg = 4; seg.start[0] = rA; seg.start[1] = rN; seg.start[2] = rP; seg.start[3] = rG; seg.start[4] = R;
         seg.count[1] = B * N;                                  // BatchNorm sees every padded slot
-        if (nb_weight) { seg.row_weight = nb_weight; seg.row_weight_start = rN; seg.row_weight_rows = nbc; }
+        if (c.nb_weight) { seg.row_weight = c.nb_weight; seg.row_weight_start = rN; seg.row_weight_rows = nbc; }
         else if (slot_row) { seg.weighted_row = rN + nbc - 1; seg.weight = (float)(B * N - (nbc - 1)); }
     } else {
         seg.nseg = 3; seg.start[0] = rA; seg.start[1] = rP; seg.start[2] = rG; seg.start[3] = R; seg.start[4] = R;
@@ -207,22 +197,22 @@ static int p2v_step_impl(const pc_p2v_tensors* p, const pc_p2v_tensors* g, const
             int tiles_x, tiles_y;
             transpose_batch_tiles(tb, &tiles_x, &tiles_y);
             const int cb = (R + 255) / 256;
-            PC_LAUNCH(p2v_prologue_kernel, dim3(cb + tiles_x * tiles_y * tb.n), dim3(256), 0, st, anchor_idx, B, nb_idx, nbc,
-                      positive_idx, B, negative_idx, B * K, w.idx_all, cb, tb, tiles_x, tiles_y);
+            PC_LAUNCH(p2v_prologue_kernel, dim3(cb + tiles_x * tiles_y * tb.n), dim3(256), 0, st, c.anchor_idx, B, c.nb_idx, nbc,
+                      c.positive_idx, B, c.negative_idx, B * K, w.idx_all, cb, tb, tiles_x, tiles_y);
         } else {
-            PC_LAUNCH(concat_idx_kernel, dim3((R + 255) / 256), dim3(256), 0, st, anchor_idx, B, nb_idx, nbc, positive_idx, B,
-                      negative_idx, B * K, w.idx_all);
+            PC_LAUNCH(concat_idx_kernel, dim3((R + 255) / 256), dim3(256), 0, st, c.anchor_idx, B, c.nb_idx, nbc, c.positive_idx, B,
+                      c.negative_idx, B * K, w.idx_all);
         }
         PC_TRY(pc_launch_status());
-        PC_TRY(ffn_forward_part1(p, table, rows, R, &seg, &sv, phase == 0 ? fwd_sums : nullptr, w.ffn_ws, w.ffn_bytes,
+        PC_TRY(ffn_forward_part1(p, c.table, rows, R, &seg, &sv, phase == 0 ? c.fwd_sums : nullptr, w.ffn_ws, w.ffn_bytes,
                                  stream));
         if (phase == 0) return PC_OK;
     }
     if (p2 && !p1)
-        return ffn_backward_part2(g, table, rows, R, &seg, &sv, nullptr, 0, bwd_local, bwd_global, w.ffn_ws,
+        return ffn_backward_part2(g, c.table, rows, R, &seg, &sv, nullptr, 0, c.bwd_local, c.bwd_global, w.ffn_ws,
                                   w.ffn_bytes, stream, nullptr);
     if (phase == 1) PC_TRY(launch_transpose_batch(tb, st));      // (the split step: phase 0 ran the concatenation alone)
-    PC_TRY(ffn_forward_part2(p, R, &seg, 1, w.y, &sv, phase == 1 ? fwd_sums : nullptr, w.ffn_ws, w.ffn_bytes, stream,
+    PC_TRY(ffn_forward_part2(p, R, &seg, 1, w.y, &sv, phase == 1 ? c.fwd_sums : nullptr, w.ffn_ws, w.ffn_bytes, stream,
                              rows_ready ? &tb : nullptr));
 
     pc_attn_saved as;
@@ -237,29 +227,29 @@ static int p2v_step_impl(const pc_p2v_tensors* p, const pc_p2v_tensors* g, const
         emb = w.emb;
     }
 
-    float* dp_out = d_pos ? d_pos : w.dpos_tmp;
-    float* dn_out = d_neg ? d_neg : w.dneg_tmp;
+    float* dp_out = c.d_pos ? c.d_pos : w.dpos_tmp;
+    float* dn_out = c.d_neg ? c.d_neg : w.dneg_tmp;
     float* demb = N > 0 ? w.demb : w.dy + (size_t)rA * D;
     // the hinge mean rides on the first launch of the attention backward (D = 128 with neighbours); nothing in the step reads it
     const bool mean_rides = N > 0 && D == 128;
     // ... and so does the hinge itself (round 6): the prologue of the attention backward's first chain (LossPro, common.h) --
     // pc_set_option(PC_OPT_FUSED_LOSS, 0) keeps its own launch
     const bool loss_rides = mean_rides && K <= 8 && pc_opt_fused_loss();
-    const LossPro lp = {emb, w.y + (size_t)rP * D, w.y + (size_t)rG * D, B, K, margin, dp_out, dn_out,
+    const LossPro lp = {emb, w.y + (size_t)rP * D, w.y + (size_t)rG * D, B, K, c.margin, dp_out, dn_out,
                         w.dy + (size_t)rP * D, w.dy + (size_t)rG * D, w.demb};
     if (!loss_rides)
-        PC_TRY(triplet_loss_launch(emb, w.y + (size_t)rP * D, w.y + (size_t)rG * D, B, K, D, margin, loss, dp_out,
+        PC_TRY(triplet_loss_launch(emb, w.y + (size_t)rP * D, w.y + (size_t)rG * D, B, K, D, c.margin, c.loss, dp_out,
                                    dn_out, demb, w.dy + (size_t)rP * D, w.dy + (size_t)rG * D, stream, mean_rides ? 0 : 1));
-    const HingeMeanJob hm = {dp_out, dn_out, B, margin, loss};
-    if (anchor_emb && !out_chain_rides)
-        PC_HIP_TRY(hipMemcpyAsync(anchor_emb, emb, (size_t)B * D * 4, hipMemcpyDeviceToDevice, st));
+    const HingeMeanJob hm = {dp_out, dn_out, B, c.margin, c.loss};
+    if (c.anchor_emb && !out_chain_rides)
+        PC_HIP_TRY(hipMemcpyAsync(c.anchor_emb, emb, (size_t)B * D * 4, hipMemcpyDeviceToDevice, st));
 
     // the slab sums of ALL weight gradients of the step (attention: 10 few-row products, FFN: dW5, dW3 x 2, dW0) fold in
     // one launch at the end of the call
     TnDefer df;
     tn_defer_init(&df);
     if (phase == -1) df.fork = pc_fork_get(st);              // (the unsplit step: two small launches leave the main queue, common.h PcFork)
-    df.adam = adam;                                          // torch.optim.Adam inside the final slab reduce (pc_p2v_train_step_unique_adam)
+    df.adam = c.adam;                                          // torch.optim.Adam inside the final slab reduce (pc_p2v_train_step_unique_adam)
     // an error return below must not leave work on the side queue that nothing orders before the caller's next use (or
     // free) of the workspace and gradient buffers: join it into the main queue on the way out (a no-op after the normal
     // end of the step, whose reduce launch has joined already)
@@ -270,31 +260,40 @@ static int p2v_step_impl(const pc_p2v_tensors* p, const pc_p2v_tensors* g, const
     if (N > 0) {
         PC_TRY(attention_backward_impl(p, g, w.y + (size_t)rA * D, w.y + (size_t)rN * D, B, N, nbc, slot_row,
                                        slot_row ? nbc - 1 : -1, w.demb, &as, w.dy + (size_t)rA * D,
-                                       w.dy + (size_t)rN * D, 0, w.attn_ws, w.attn_bytes, stream, ref_off, ref_slot, 1, &df,
+                                       w.dy + (size_t)rN * D, 0, w.attn_ws, w.attn_bytes, stream, c.ref_off, c.ref_slot, 1, &df,
                                        mean_rides ? &hm : nullptr, loss_rides ? &lp : nullptr,
                                        out_chain_rides ? fwd_out_chain : nullptr));
-        if (anchor_emb && out_chain_rides)                    // (the embedding exists once the backward's first launch has run)
-            PC_HIP_TRY(hipMemcpyAsync(anchor_emb, emb, (size_t)B * D * 4, hipMemcpyDeviceToDevice, st));
+        if (c.anchor_emb && out_chain_rides)                    // (the embedding exists once the backward's first launch has run)
+            PC_HIP_TRY(hipMemcpyAsync(c.anchor_emb, emb, (size_t)B * D * 4, hipMemcpyDeviceToDevice, st));
     } else {
         PC_HIP_TRY(hipMemsetAsync(g->in_proj_w, 0, 3 * D * D * 4, st));
         PC_HIP_TRY(hipMemsetAsync(g->in_proj_b, 0, 3 * D * 4, st));
         PC_HIP_TRY(hipMemsetAsync(g->out_proj_w, 0, D * D * 4, st));
         PC_HIP_TRY(hipMemsetAsync(g->out_proj_b, 0, D * 4, st));
     }
-    PC_TRY(ffn_backward_part1(p, g, table, rows, R, &seg, w.dy, &sv, 0, 0, phase == 1 ? bwd_local : nullptr, w.ffn_ws,
+    PC_TRY(ffn_backward_part1(p, g, c.table, rows, R, &seg, w.dy, &sv, 0, 0, phase == 1 ? c.bwd_local : nullptr, w.ffn_ws,
                               w.ffn_bytes, stream, 1, &df));
     if (phase == 1) return launch_tn_reduce_deferred(&df, st);
-    PC_TRY(ffn_backward_part2(g, table, rows, R, &seg, &sv, nullptr, 0, nullptr, nullptr, w.ffn_ws, w.ffn_bytes, stream, &df));
+    PC_TRY(ffn_backward_part2(g, c.table, rows, R, &seg, &sv, nullptr, 0, nullptr, nullptr, w.ffn_ws, w.ffn_bytes, stream, &df));
     return launch_tn_reduce_deferred(&df, st);
 }
+
+// what every entry point passes through unchanged
+#define P2V_STEP_COMMON(c)                                                                              \
+    c.p = p; c.g = g; c.table = table; c.B = B; c.N = N; c.K = K; c.margin = margin;                    \
+    c.loss = loss; c.d_pos = d_pos; c.d_neg = d_neg; c.anchor_emb = anchor_emb;                         \
+    c.ws = ws; c.ws_bytes = ws_bytes; c.stream = stream
+#define P2V_STEP_TRIPLET(c) c.anchor_idx = anchor_idx; c.positive_idx = positive_idx; c.negative_idx = negative_idx
 
 extern "C" int pc_p2v_train_step(const pc_p2v_tensors* p, const pc_p2v_tensors* g, const float* table,
                                  const int32_t* anchor_idx, const int32_t* positive_idx,
                                  const int32_t* negative_idx, const int32_t* neighbor_idx, int B, int N, int K,
                                  float margin, float* loss, float* d_pos, float* d_neg, float* anchor_emb,
                                  void* profile, void* ws, size_t ws_bytes, void* stream) {
-    return p2v_step_impl(p, g, table, anchor_idx, positive_idx, negative_idx, neighbor_idx, B * N, nullptr, B, N, K,
-                         margin, loss, d_pos, d_neg, anchor_emb, profile, ws, ws_bytes, stream);
+    P2VStepCall c;
+    P2V_STEP_COMMON(c); P2V_STEP_TRIPLET(c);
+    c.nb_idx = neighbor_idx; c.nbc = B * N; c.profile = profile;
+    return p2v_step_impl(c);
 }
 
 extern "C" int pc_p2v_train_step_compact(const pc_p2v_tensors* p, const pc_p2v_tensors* g, const float* table,
@@ -303,9 +302,11 @@ extern "C" int pc_p2v_train_step_compact(const pc_p2v_tensors* p, const pc_p2v_t
                                          const int32_t* slot_row, int B, int N, int K, float margin, float* loss,
                                          float* d_pos, float* d_neg, float* anchor_emb, void* profile, void* ws,
                                          size_t ws_bytes, void* stream) {
-    if (!slot_row || !nb_rows || N <= 0 || n_real < 0 || n_real > B * N) return PC_EINVAL;
-    return p2v_step_impl(p, g, table, anchor_idx, positive_idx, negative_idx, nb_rows, n_real + 1, slot_row, B, N, K,
-                         margin, loss, d_pos, d_neg, anchor_emb, profile, ws, ws_bytes, stream);
+    if (!nb_layout_ok(slot_row, nb_rows, n_real, B, N)) return PC_EINVAL;
+    P2VStepCall c;
+    P2V_STEP_COMMON(c); P2V_STEP_TRIPLET(c);
+    c.nb_idx = nb_rows; c.nbc = n_real + 1; c.slot_row = slot_row; c.profile = profile;
+    return p2v_step_impl(c);
 }
 
 extern "C" int pc_p2v_train_step_compact_sync(const pc_p2v_tensors* p, const pc_p2v_tensors* g, const float* table,
@@ -315,17 +316,24 @@ extern "C" int pc_p2v_train_step_compact_sync(const pc_p2v_tensors* p, const pc_
                                               float* d_pos, float* d_neg, float* anchor_emb, int phase,
                                               double* fwd_sums, double* bwd_local, const double* bwd_global, void* ws,
                                               size_t ws_bytes, void* stream) {
-    if (!slot_row || !nb_rows || N <= 0 || n_real < 0 || n_real > B * N) return PC_EINVAL;
+    if (!nb_layout_ok(slot_row, nb_rows, n_real, B, N)) return PC_EINVAL;
     if (phase < 0 || phase > 2 || !fwd_sums || !bwd_local || (phase == 2 && !bwd_global)) return PC_EINVAL;
     if ((((uintptr_t)fwd_sums | (uintptr_t)bwd_local | (uintptr_t)bwd_global) & 7)) return PC_ESHAPE;
-    return p2v_step_impl(p, g, table, anchor_idx, positive_idx, negative_idx, nb_rows, n_real + 1, slot_row, B, N, K,
-                         margin, loss, d_pos, d_neg, anchor_emb, nullptr, ws, ws_bytes, stream, phase, fwd_sums,
-                         bwd_local, bwd_global);
+    P2VStepCall c;
+    P2V_STEP_COMMON(c); P2V_STEP_TRIPLET(c);
+    c.nb_idx = nb_rows; c.nbc = n_real + 1; c.slot_row = slot_row;
+    c.phase = phase; c.fwd_sums = fwd_sums; c.bwd_local = bwd_local; c.bwd_global = bwd_global;
+    return p2v_step_impl(c);
 }
 
 // Unique-neighbour layout (see pcompanion_hip.h): nb_rows[n_unique + 1] distinct neighbour products then -1,
 // nb_weight[n_unique + 1] their multiplicities then the number of padding slots, slot_row[B*N] slot -> row,
 // ref_off / ref_slot row -> slots.
+#define P2V_UNIQUE_OK (nb_layout_ok(slot_row, nb_rows, n_unique, B, N) && nb_weight && ref_off && ref_slot)
+#define P2V_STEP_UNIQUE(c)                                                                              \
+    c.nb_idx = nb_rows; c.nbc = n_unique + 1; c.slot_row = slot_row; c.nb_weight = nb_weight;           \
+    c.ref_off = ref_off; c.ref_slot = ref_slot; c.profile = profile
+
 extern "C" int pc_p2v_train_step_unique(const pc_p2v_tensors* p, const pc_p2v_tensors* g, const float* table,
                                         const int32_t* anchor_idx, const int32_t* positive_idx,
                                         const int32_t* negative_idx, const int32_t* nb_rows, const float* nb_weight,
@@ -334,31 +342,14 @@ extern "C" int pc_p2v_train_step_unique(const pc_p2v_tensors* p, const pc_p2v_te
                                         float* loss, float* d_pos, float* d_neg, float* anchor_emb, void* profile,
                                         int phase, double* fwd_sums, double* bwd_local, const double* bwd_global,
                                         void* ws, size_t ws_bytes, void* stream) {
-    if (!slot_row || !nb_rows || !nb_weight || !ref_off || !ref_slot || N <= 0 || n_unique < 0 || n_unique > B * N)
-        return PC_EINVAL;
+    if (!P2V_UNIQUE_OK) return PC_EINVAL;
+    P2VStepCall c;
+    P2V_STEP_UNIQUE(c);
     if (phase < -1 || phase > 2) return PC_EINVAL;
     if (phase >= 0 && (!fwd_sums || !bwd_local || (phase == 2 && !bwd_global))) return PC_EINVAL;
-    return p2v_step_impl(p, g, table, anchor_idx, positive_idx, negative_idx, nb_rows, n_unique + 1, slot_row, B, N, K,
-                         margin, loss, d_pos, d_neg, anchor_emb, profile, ws, ws_bytes, stream, phase, fwd_sums,
-                         bwd_local, bwd_global, nb_weight, ref_off, ref_slot);
-}
-
-static int unique_adam_impl(const pc_p2v_tensors* p, const pc_p2v_tensors* g, const float* table, const int32_t* anchor_idx,
-                            const int32_t* positive_idx, const int32_t* negative_idx, const int32_t* nb_rows, const float* nb_weight,
-                            int n_unique, const int32_t* slot_row, const int32_t* ref_off, const int32_t* ref_slot, int B, int N, int K,
-                            float margin, float* loss, float* d_pos, float* d_neg, float* anchor_emb, void* profile, void* ws,
-                            size_t ws_bytes, const pc_adam_fused* adam, void* stream, const int32_t* rows_ready) {
-    if (!slot_row || !nb_rows || !nb_weight || !ref_off || !ref_slot || N <= 0 || n_unique < 0 || n_unique > B * N)
-        return PC_EINVAL;
-    if (adam && g) {
-        // the gradient tensors must be views of the flat buffer the optimizer updates
-        const float* gt[4] = {g->w0, g->w3, g->w5, g->out_proj_w};
-        for (const float* x : gt)
-            if (!x || x < adam->grad || x >= adam->grad + adam->n) return PC_EINVAL;
-    }
-    return p2v_step_impl(p, g, table, anchor_idx, positive_idx, negative_idx, nb_rows, n_unique + 1, slot_row, B, N, K,
-                         margin, loss, d_pos, d_neg, anchor_emb, profile, ws, ws_bytes, stream, -1, nullptr, nullptr, nullptr,
-                         nb_weight, ref_off, ref_slot, adam, rows_ready);
+    P2V_STEP_COMMON(c); P2V_STEP_TRIPLET(c);
+    c.phase = phase; c.fwd_sums = fwd_sums; c.bwd_local = bwd_local; c.bwd_global = bwd_global;
+    return p2v_step_impl(c);
 }
 
 extern "C" int pc_p2v_train_step_unique_adam(const pc_p2v_tensors* p, const pc_p2v_tensors* g, const float* table,
@@ -368,8 +359,12 @@ extern "C" int pc_p2v_train_step_unique_adam(const pc_p2v_tensors* p, const pc_p
                                              const int32_t* ref_slot, int B, int N, int K, float margin, float* loss,
                                              float* d_pos, float* d_neg, float* anchor_emb, void* profile, void* ws,
                                              size_t ws_bytes, const pc_adam_fused* adam, void* stream) {
-    return unique_adam_impl(p, g, table, anchor_idx, positive_idx, negative_idx, nb_rows, nb_weight, n_unique, slot_row, ref_off,
-                            ref_slot, B, N, K, margin, loss, d_pos, d_neg, anchor_emb, profile, ws, ws_bytes, adam, stream, nullptr);
+    if (!P2V_UNIQUE_OK) return PC_EINVAL;
+    P2VStepCall c;
+    P2V_STEP_UNIQUE(c);
+    P2V_STEP_COMMON(c); P2V_STEP_TRIPLET(c);
+    c.adam = adam;
+    return p2v_step_impl(c);
 }
 
 // ... with the step's row indices [anchor | nb_rows[0 .. n_unique] | positive | negatives] already concatenated
@@ -379,9 +374,12 @@ extern "C" int pc_p2v_train_step_unique_rows(const pc_p2v_tensors* p, const pc_p
                                              const int32_t* slot_row, const int32_t* ref_off, const int32_t* ref_slot, int B, int N,
                                              int K, float margin, float* loss, float* d_pos, float* d_neg, float* anchor_emb,
                                              void* profile, void* ws, size_t ws_bytes, const pc_adam_fused* adam, void* stream) {
-    if (!step_rows || B <= 0 || N <= 0 || n_unique < 0 || n_unique > B * N) return PC_EINVAL;
-    const int32_t* a = step_rows;
-    return unique_adam_impl(p, g, table, a, a + B + n_unique + 1, a + 2 * B + n_unique + 1, nb_rows, nb_weight, n_unique, slot_row,
-                            ref_off, ref_slot, B, N, K, margin, loss, d_pos, d_neg, anchor_emb, profile, ws, ws_bytes, adam, stream,
-                            step_rows);
+    if (!step_rows || B <= 0) return PC_EINVAL;
+    if (!P2V_UNIQUE_OK) return PC_EINVAL;
+    P2VStepCall c;
+    P2V_STEP_UNIQUE(c);
+    P2V_STEP_COMMON(c);
+    c.anchor_idx = step_rows; c.positive_idx = step_rows + B + n_unique + 1; c.negative_idx = step_rows + 2 * B + n_unique + 1;
+    c.adam = adam; c.rows_ready = step_rows;
+    return p2v_step_impl(c);
 }

@@ -322,13 +322,11 @@ struct RgWs {
     float* pv;
     size_t bytes;
 };
-inline size_t rg_align(size_t x) { return (x + 255) & ~(size_t)255; }
 inline int rg_slices(int slices) { return slices == 0 ? RG_AUTO_SLICES : slices; }
 RgWs rg_layout(void* ws, int rows, int n_types, int n, int S) {
     RgWs w;
-    char* p = (char*)ws;
-    size_t o = 0;
-    auto take = [&](size_t nbytes) { char* q = p ? p + o : nullptr; o += rg_align(nbytes); return q; };
+    WsCarver cv(ws);
+    auto take = [&](size_t nbytes) { return cv.bytes(nbytes); };
     w.cnt = (int32_t*)take((size_t)n_types * 4);
     w.rank = (int32_t*)take((size_t)rows * 4);
     w.row_start = (int32_t*)take((size_t)(n_types + 1) * 4);
@@ -336,7 +334,7 @@ RgWs rg_layout(void* ws, int rows, int n_types, int n, int S) {
     w.order = (int32_t*)take((size_t)rows * 4);
     w.pv = (float*)take((size_t)rows * S * n * 4);
     w.pi = (int32_t*)take((size_t)rows * S * n * 4);
-    w.bytes = o;
+    w.bytes = cv.total;
     return w;
 }
 }  // namespace

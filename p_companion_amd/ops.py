@@ -278,25 +278,27 @@ def triplet_loss(a, p, n, margin, need_grad=True):
     return out
 
 
-def adam_step(param, grad, exp_avg, exp_avg_sq, step_count, scalars, lr=1e-3, betas=(0.9, 0.999), eps=1e-8):
+def _adam_buffers(what, param, grad, exp_avg, exp_avg_sq, step_count):
+    """The flat-buffer check of adam_step / adam_step_at: four float32 tensors of one size, an int64 step count.  Returns the size."""
     n = param.numel()
     for t, nm in ((param, "param"), (grad, "grad"), (exp_avg, "exp_avg"), (exp_avg_sq, "exp_avg_sq")):
         _req(t, torch.float32, nm)
         if t.numel() != n:
-            raise ValueError("adam_step: size mismatch")
-    _req(step_count, torch.int64, "step_count"); _req(scalars, torch.float32, "scalars", (2,))
+            raise ValueError(f"{what}: size mismatch")
+    _req(step_count, torch.int64, "step_count")
+    return n
+
+
+def adam_step(param, grad, exp_avg, exp_avg_sq, step_count, scalars, lr=1e-3, betas=(0.9, 0.999), eps=1e-8):
+    n = _adam_buffers("adam_step", param, grad, exp_avg, exp_avg_sq, step_count)
+    _req(scalars, torch.float32, "scalars", (2,))
     check(_lib.lib().pc_adam_step(_p(param), _p(grad), _p(exp_avg), _p(exp_avg_sq), n, _p(step_count), _p(scalars),
                                   float(lr), float(betas[0]), float(betas[1]), float(eps), _stream()), "pc_adam_step")
 
 
 def adam_step_at(param, grad, exp_avg, exp_avg_sq, step_count, t, lr=1e-3, betas=(0.9, 0.999), eps=1e-8):
     """pc_adam_step_at: the update of step number t (host-known) as one launch; step_count (device int64 [1]) is left = t."""
-    n = param.numel()
-    for x, nm in ((param, "param"), (grad, "grad"), (exp_avg, "exp_avg"), (exp_avg_sq, "exp_avg_sq")):
-        _req(x, torch.float32, nm)
-        if x.numel() != n:
-            raise ValueError("adam_step_at: size mismatch")
-    _req(step_count, torch.int64, "step_count")
+    n = _adam_buffers("adam_step_at", param, grad, exp_avg, exp_avg_sq, step_count)
     check(_lib.lib().pc_adam_step_at(_p(param), _p(grad), _p(exp_avg), _p(exp_avg_sq), n, _p(step_count), int(t), float(lr),
                                      float(betas[0]), float(betas[1]), float(eps), _stream()), "pc_adam_step_at")
 
@@ -569,27 +571,34 @@ def p2v_train_step(params, grads, table, anchor_idx, positive_idx, negative_idx,
         out["anchor_emb"] = torch.empty(b, st.dim, dtype=torch.float32, device=dev)
     nbytes = _lib.lib().pc_p2v_train_step_workspace_bytes_dim(b, n, k, st.dim)
     ws = workspace(nbytes, dev, "step")
+    # the argument groups the five entry points share, marshalled once (include/pcompanion_hip.h gives each one's order)
+    lib = _lib.lib()
+    head = (ctypes.byref(st), ctypes.byref(gst), _p(table))
+    sizes = (b, n, k, float(margin))
+    outs = (_p(out["loss"]), _p(out["d_pos"]), _p(out["d_neg"]), _p(out.get("anchor_emb")))
+    prof = profile.handle if profile else None
+    wsa = (_p(ws), nbytes)
+    if unique:
+        layout = (_p(nb_rows), _p(neighbor_idx["weight"]), n_real, _p(slot_row), _p(neighbor_idx["ref_off"]),
+                  _p(neighbor_idx["ref_slot"]))
+    elif compact:
+        layout = (_p(nb_rows), n_real, _p(slot_row))
     if sync_reduce is not None:
         if not compact:
             raise ValueError("cross-replica BatchNorm needs the compact neighbour layout")
+        triplet = (_p(anchor_idx), _p(positive_idx), _p(negative_idx))
         fwd = torch.zeros(BN_SYNC_DOUBLES, dtype=torch.float64, device=dev)
         bwd_local = torch.zeros(BN_SYNC_DOUBLES, dtype=torch.float64, device=dev)
         bwd_global = None
 
         def phase(ph):
+            sums = (ph, _p(fwd), _p(bwd_local), _p(bwd_global))
             if unique:
-                check(_lib.lib().pc_p2v_train_step_unique(
-                    ctypes.byref(st), ctypes.byref(gst), _p(table), _p(anchor_idx), _p(positive_idx), _p(negative_idx),
-                    _p(nb_rows), _p(neighbor_idx["weight"]), n_real, _p(slot_row), _p(neighbor_idx["ref_off"]),
-                    _p(neighbor_idx["ref_slot"]), b, n, k, float(margin), _p(out["loss"]),
-                    _p(out["d_pos"]), _p(out["d_neg"]), _p(out.get("anchor_emb")), None, ph, _p(fwd), _p(bwd_local),
-                    _p(bwd_global), _p(ws), nbytes, _stream()), "pc_p2v_train_step_unique")
-                return
-            check(_lib.lib().pc_p2v_train_step_compact_sync(
-                ctypes.byref(st), ctypes.byref(gst), _p(table), _p(anchor_idx), _p(positive_idx), _p(negative_idx),
-                _p(nb_rows), n_real, _p(slot_row), b, n, k, float(margin), _p(out["loss"]), _p(out["d_pos"]),
-                _p(out["d_neg"]), _p(out.get("anchor_emb")), ph, _p(fwd), _p(bwd_local), _p(bwd_global), _p(ws), nbytes,
-                _stream()), "pc_p2v_train_step_compact_sync")
+                check(lib.pc_p2v_train_step_unique(*head, *triplet, *layout, *sizes, *outs, None, *sums, *wsa, _stream()),
+                      "pc_p2v_train_step_unique")
+            else:
+                check(lib.pc_p2v_train_step_compact_sync(*head, *triplet, *layout, *sizes, *outs, *sums, *wsa, _stream()),
+                      "pc_p2v_train_step_compact_sync")
         phase(0)
         sync_reduce(fwd)
         phase(1)
@@ -600,57 +609,43 @@ def p2v_train_step(params, grads, table, anchor_idx, positive_idx, negative_idx,
     if adam is not None and not unique:
         raise ValueError("p2v_train_step(adam=...): the unique-neighbour layout (the device loader's) carries the fused optimizer step")
     step_rows = neighbor_idx.get("step_rows") if unique else None
-    if unique and (adam is not None or step_rows is not None):
-        af = None
-        if adam is not None:
-            af = _lib.AdamFused()
-            n_flat = adam["param"].numel()
-            for key in ("param", "grad", "exp_avg", "exp_avg_sq"):
-                _req(adam[key], torch.float32, key, (n_flat,))
-            _req(adam["step_count"], torch.int64, "step_count")
-            af.param, af.grad, af.exp_avg, af.exp_avg_sq = (adam[key].data_ptr() for key in ("param", "grad", "exp_avg", "exp_avg_sq"))
-            af.n, af.step_count, af.t = n_flat, adam["step_count"].data_ptr(), int(adam["t"])
-            af.lr, af.beta1, af.beta2, af.eps = float(adam["lr"]), float(adam["betas"][0]), float(adam["betas"][1]), float(adam["eps"])
-        afp = ctypes.byref(af) if af is not None else None
-        if step_rows is not None:
-            # the loader concatenated the step's row indices behind its builder (concat_step_rows): the step starts with Linear0
-            _req(step_rows, torch.int32, "step_rows")
-            if step_rows.numel() < b * (2 + k) + n_real + 1:
-                raise ValueError("step_rows shorter than B * (2 + K) + n_unique + 1")
-            check(_lib.lib().pc_p2v_train_step_unique_rows(
-                ctypes.byref(st), ctypes.byref(gst), _p(table), _p(step_rows), _p(nb_rows), _p(neighbor_idx["weight"]), n_real,
-                _p(slot_row), _p(neighbor_idx["ref_off"]), _p(neighbor_idx["ref_slot"]), b, n, k, float(margin), _p(out["loss"]),
-                _p(out["d_pos"]), _p(out["d_neg"]), _p(out.get("anchor_emb")), profile.handle if profile else None,
-                _p(ws), nbytes, afp, _stream()), "pc_p2v_train_step_unique_rows")
-            return out
-        check(_lib.lib().pc_p2v_train_step_unique_adam(
-            ctypes.byref(st), ctypes.byref(gst), _p(table), _p(anchor_idx), _p(positive_idx), _p(negative_idx),
-            _p(nb_rows), _p(neighbor_idx["weight"]), n_real, _p(slot_row), _p(neighbor_idx["ref_off"]),
-            _p(neighbor_idx["ref_slot"]), b, n, k, float(margin), _p(out["loss"]),
-            _p(out["d_pos"]), _p(out["d_neg"]), _p(out.get("anchor_emb")), profile.handle if profile else None,
-            _p(ws), nbytes, afp, _stream()), "pc_p2v_train_step_unique_adam")
+    if step_rows is not None:
+        # the loader concatenated the step's row indices behind its builder (concat_step_rows): the step starts with Linear0
+        _req(step_rows, torch.int32, "step_rows")
+        if step_rows.numel() < b * (2 + k) + n_real + 1:
+            raise ValueError("step_rows shorter than B * (2 + K) + n_unique + 1")
+        check(lib.pc_p2v_train_step_unique_rows(*head, _p(step_rows), *layout, *sizes, *outs, prof, *wsa, _adam_fused(adam), _stream()),
+              "pc_p2v_train_step_unique_rows")
         return out
-    if unique:
-        check(_lib.lib().pc_p2v_train_step_unique(
-            ctypes.byref(st), ctypes.byref(gst), _p(table), _p(anchor_idx), _p(positive_idx), _p(negative_idx),
-            _p(nb_rows), _p(neighbor_idx["weight"]), n_real, _p(slot_row), _p(neighbor_idx["ref_off"]),
-            _p(neighbor_idx["ref_slot"]), b, n, k, float(margin), _p(out["loss"]),
-            _p(out["d_pos"]), _p(out["d_neg"]), _p(out.get("anchor_emb")), profile.handle if profile else None, -1, None,
-            None, None, _p(ws), nbytes, _stream()), "pc_p2v_train_step_unique")
-        return out
-    if compact:
-        check(_lib.lib().pc_p2v_train_step_compact(
-            ctypes.byref(st), ctypes.byref(gst), _p(table), _p(anchor_idx), _p(positive_idx), _p(negative_idx),
-            _p(nb_rows), n_real, _p(slot_row), b, n, k, float(margin), _p(out["loss"]), _p(out["d_pos"]),
-            _p(out["d_neg"]), _p(out.get("anchor_emb")), profile.handle if profile else None, _p(ws), nbytes,
-            _stream()), "pc_p2v_train_step_compact")
-        return out
-    check(_lib.lib().pc_p2v_train_step(ctypes.byref(st), ctypes.byref(gst), _p(table), _p(anchor_idx),
-                                       _p(positive_idx), _p(negative_idx), _p(neighbor_idx) if n else None, b, n, k,
-                                       float(margin), _p(out["loss"]), _p(out["d_pos"]), _p(out["d_neg"]),
-                                       _p(out.get("anchor_emb")), profile.handle if profile else None, _p(ws),
-                                       nbytes, _stream()), "pc_p2v_train_step")
+    triplet = (_p(anchor_idx), _p(positive_idx), _p(negative_idx))
+    if unique and adam is not None:
+        check(lib.pc_p2v_train_step_unique_adam(*head, *triplet, *layout, *sizes, *outs, prof, *wsa, _adam_fused(adam), _stream()),
+              "pc_p2v_train_step_unique_adam")
+    elif unique:
+        check(lib.pc_p2v_train_step_unique(*head, *triplet, *layout, *sizes, *outs, prof, -1, None, None, None, *wsa, _stream()),
+              "pc_p2v_train_step_unique")
+    elif compact:
+        check(lib.pc_p2v_train_step_compact(*head, *triplet, *layout, *sizes, *outs, prof, *wsa, _stream()),
+              "pc_p2v_train_step_compact")
+    else:
+        check(lib.pc_p2v_train_step(*head, *triplet, _p(neighbor_idx) if n else None, *sizes, *outs, prof, *wsa, _stream()),
+              "pc_p2v_train_step")
     return out
+
+
+def _adam_fused(adam):
+    """p2v_train_step's adam= dict as a pc_adam_fused by reference (None: no optimizer rides in the step)."""
+    if adam is None:
+        return None
+    af = _lib.AdamFused()
+    n_flat = adam["param"].numel()
+    for key in ("param", "grad", "exp_avg", "exp_avg_sq"):
+        _req(adam[key], torch.float32, key, (n_flat,))
+    _req(adam["step_count"], torch.int64, "step_count")
+    af.param, af.grad, af.exp_avg, af.exp_avg_sq = (adam[key].data_ptr() for key in ("param", "grad", "exp_avg", "exp_avg_sq"))
+    af.n, af.step_count, af.t = n_flat, adam["step_count"].data_ptr(), int(adam["t"])
+    af.lr, af.beta1, af.beta2, af.eps = float(adam["lr"]), float(adam["betas"][0]), float(adam["betas"][1]), float(adam["eps"])
+    return ctypes.byref(af)
 
 
 # ----------------------------------------------------------------------------- P1-P4
@@ -945,38 +940,50 @@ def joint_fused_supported(num_types, k, dropout_p=0.0):
     return bool(_lib.lib().pc_joint_fused_supported(int(num_types), int(k), float(dropout_p)))
 
 
+class _JointStepArgs:
+    """The fused joint step's arguments, checked once and marshalled into named groups (include/pcompanion_hip.h,
+    pc_joint_fused_step, gives their order; each foreign call below assembles it from the groups beside the call):
+    tensors (parameters, gradients), opt (both moments, the step count -- all None without adam), hyper (lr, beta1, beta2, eps),
+    batch (the six batch pointers), b, sizes (num_types, k, num_products), loss (margin, alpha), bad."""
+
+    def __init__(self, params, grads, query_idx, query_types, pos_types, neg_types, pos_items, neg_items, k, margin, alpha,
+                 bad, adam):
+        table = params["product_embeddings.weight"]
+        self.st, self.dev = joint_struct(params)
+        self.gst, _ = joint_struct(grads, table=table)
+        self.b = b = query_idx.numel()
+        self.t, self.k, self.num_products = params["query_type_embeddings.weight"].shape[0], k, int(table.shape[0])
+        for x, nm in ((query_idx, "query_idx"), (query_types, "query_types"), (pos_types, "positive_types"),
+                      (neg_types, "negative_types")):
+            _req(x, torch.int32, nm, (b,))
+        _req(pos_items, torch.float32, "positive_items", (b, D)); _req(neg_items, torch.float32, "negative_items", (b, D))
+        self.tensors = (ctypes.byref(self.st), ctypes.byref(self.gst))
+        self.opt, self.hyper = (None, None, None), (0.0, 0.0, 0.0, 0.0)
+        if adam is not None:
+            self.mst, _ = joint_struct(adam["exp_avg"], table=table)
+            self.vst, _ = joint_struct(adam["exp_avg_sq"], table=table)
+            self.opt = (ctypes.byref(self.mst), ctypes.byref(self.vst), _p(_req(adam["step_count"], torch.int64, "step_count")))
+            self.hyper = (float(adam["lr"]), float(adam["betas"][0]), float(adam["betas"][1]), float(adam["eps"]))
+        if bad is not None:
+            _req(bad, torch.int32, "bad", (1,))
+        self.batch = (_p(query_idx), _p(query_types), _p(pos_types), _p(neg_types), _p(pos_items), _p(neg_items))
+        self.sizes = (self.t, k, self.num_products)
+        self.loss = (float(margin), float(alpha))
+        self.bad = _p(bad)
+        self.ws_bytes = _lib.lib().pc_joint_fused_workspace_bytes(b, self.t, k)
+
+
 def joint_fused_step(params, grads, query_idx, query_types, pos_types, neg_types, pos_items, neg_items, k, margin, alpha,
                      bad=None, adam=None):
     """pc_joint_fused_step: the joint loop body as two launches (T <= 128; the gradient products get their own kernel up to 512).  adam: None (gradients only) or a dict with
     'exp_avg' / 'exp_avg_sq' (tensor dicts keyed like `params`), 'step_count' ([1] int64), 'lr', 'betas', 'eps': the
     optimizer update then happens in the last kernel.  Returns (losses[3], complementary_types[B,K])."""
-    st, dev = joint_struct(params)
-    gst, _ = joint_struct(grads, table=params["product_embeddings.weight"])
-    b = query_idx.numel()
-    t = params["query_type_embeddings.weight"].shape[0]
-    for x, nm in ((query_idx, "query_idx"), (query_types, "query_types"), (pos_types, "positive_types"),
-                  (neg_types, "negative_types")):
-        _req(x, torch.int32, nm, (b,))
-    _req(pos_items, torch.float32, "positive_items", (b, D)); _req(neg_items, torch.float32, "negative_items", (b, D))
-    losses = torch.empty(3, dtype=torch.float32, device=dev)
-    topk = torch.empty(b, k, dtype=torch.int32, device=dev)
-    nbytes = _lib.lib().pc_joint_fused_workspace_bytes(b, t, k)
-    ws = workspace(nbytes, dev, "joint_fused")
-    m_ref = v_ref = step = None
-    lr, b1, b2, eps = 0.0, 0.0, 0.0, 0.0
-    if adam is not None:
-        mst, _ = joint_struct(adam["exp_avg"], table=params["product_embeddings.weight"])
-        vst, _ = joint_struct(adam["exp_avg_sq"], table=params["product_embeddings.weight"])
-        m_ref, v_ref = ctypes.byref(mst), ctypes.byref(vst)
-        step = _req(adam["step_count"], torch.int64, "step_count")
-        lr, (b1, b2), eps = float(adam["lr"]), adam["betas"], float(adam["eps"])
-    if bad is not None:
-        _req(bad, torch.int32, "bad", (1,))
-    check(_lib.lib().pc_joint_fused_step(
-        ctypes.byref(st), ctypes.byref(gst), m_ref, v_ref, _p(step), lr, float(b1), float(b2), eps, _p(query_idx),
-        _p(query_types), _p(pos_types), _p(neg_types), _p(pos_items), _p(neg_items), b, t, k,
-        int(params["product_embeddings.weight"].shape[0]), float(margin), float(alpha), _p(losses), _p(topk), _p(bad),
-        _p(ws), nbytes, _stream()), "pc_joint_fused_step")
+    a = _JointStepArgs(params, grads, query_idx, query_types, pos_types, neg_types, pos_items, neg_items, k, margin, alpha, bad, adam)
+    losses = torch.empty(3, dtype=torch.float32, device=a.dev)
+    topk = torch.empty(a.b, k, dtype=torch.int32, device=a.dev)
+    ws = workspace(a.ws_bytes, a.dev, "joint_fused")
+    check(_lib.lib().pc_joint_fused_step(*a.tensors, *a.opt, *a.hyper, *a.batch, a.b, *a.sizes, *a.loss, _p(losses), _p(topk), a.bad,
+                                         _p(ws), a.ws_bytes, _stream()), "pc_joint_fused_step")
     return losses, topk
 
 
@@ -1003,148 +1010,125 @@ class PreparedJointStep:
 
     def __init__(self, params, grads, batch, k, margin, alpha, bad=None, adam=None, dropout=None):
         self._keep = (params, grads, batch, bad, adam)
-        self.st, dev = joint_struct(params)
-        self.gst, _ = joint_struct(grads, table=params["product_embeddings.weight"])
         qi, qt, pt, nt = (batch[n].reshape(-1) for n in ("query_idx", "query_types", "positive_types", "negative_types"))
-        b = qi.numel()
-        t = params["query_type_embeddings.weight"].shape[0]
-        for x, nm in ((qi, "query_idx"), (qt, "query_types"), (pt, "positive_types"), (nt, "negative_types")):
-            _req(x, torch.int32, nm, (b,))
-        pos, neg = batch["positive_items"], batch["negative_items"]
-        _req(pos, torch.float32, "positive_items", (b, D)); _req(neg, torch.float32, "negative_items", (b, D))
-        self.losses = alloc(3, torch.float32, dev)
-        self.topk = alloc(b * k, torch.int32, dev).view(b, k)
-        nbytes = _lib.lib().pc_joint_fused_workspace_bytes(b, t, k)
-        self.ws = alloc(max(int(nbytes), 256), torch.uint8, dev)
-        m_ref = v_ref = step = None
-        lr = b1 = b2 = eps = 0.0
-        if adam is not None:
-            self.mst, _ = joint_struct(adam["exp_avg"], table=params["product_embeddings.weight"])
-            self.vst, _ = joint_struct(adam["exp_avg_sq"], table=params["product_embeddings.weight"])
-            m_ref, v_ref = ctypes.byref(self.mst), ctypes.byref(self.vst)
-            step = _req(adam["step_count"], torch.int64, "step_count")
-            lr, (b1, b2), eps = float(adam["lr"]), adam["betas"], float(adam["eps"])
-        if bad is not None:
-            _req(bad, torch.int32, "bad", (1,))
+        a = self._a = _JointStepArgs(params, grads, qi, qt, pt, nt, batch["positive_items"], batch["negative_items"], k, margin,
+                                     alpha, bad, adam)
+        self._idx = (qi, qt, pt, nt)
+        self.st, self.gst = a.st, a.gst
+        self.losses = alloc(3, torch.float32, a.dev)
+        self.topk = alloc(a.b * k, torch.int32, a.dev).view(a.b, k)
+        self.ws = alloc(max(int(a.ws_bytes), 256), torch.uint8, a.dev)
         self.dropout = dropout
         self.calls = 0
         if dropout is not None:
             self.st.dropout.p, self.st.dropout.seed = float(dropout[0]), int(dropout[1])
+        # the groups of _JointStepArgs, and what this object owns: the losses pointer, outs (top-k, bad count), wsa (workspace, bytes)
+        self._tensors, self._opt, self._batch, self._b, self._sizes, self._loss = a.tensors, a.opt, a.batch, a.b, a.sizes, a.loss
+        self._has_adam = adam is not None
+        self._step_hyper = a.hyper                      # what the step's own Adam uses (zeros without adam=)
+        self._hyper = (1e-3, 0.9, 0.999, 1e-8)          # what set_hyper last gave: run_epoch_dp's Adam over the flat buffers
+        self._losses_p, self._outs, self._wsa = _p(self.losses), (_p(self.topk), a.bad), (_p(self.ws), a.ws_bytes)
         self._fn = _lib.lib().pc_joint_fused_step
-        self._args = [ctypes.byref(self.st), ctypes.byref(self.gst), m_ref, v_ref, _p(step), lr, float(b1), float(b2), eps,
-                      _p(qi), _p(qt), _p(pt), _p(nt), _p(pos), _p(neg), b, t, k,
-                      int(params["product_embeddings.weight"].shape[0]), float(margin), float(alpha), _p(self.losses),
-                      _p(self.topk), _p(bad), _p(self.ws), nbytes]
-        self._idx = (qi, qt, pt, nt)
         self._pairs_fn = _lib.lib().pc_joint_fused_step_pairs
         self._pairs_src = None
-        self._hyper = (1e-3, 0.9, 0.999, 1e-8)
 
     def set_hyper(self, lr, betas, eps):
         """The optimizer's hyper-parameters are plain doubles among the resolved arguments: refreshed from
         optimizer.param_groups by the caller before a step / an epoch, so that an LR scheduler or a load_state_dict()
         after preparation reaches the fused update exactly as it reaches the eager path."""
-        self._hyper = (float(lr), float(betas[0]), float(betas[1]), float(eps))       # (run_epoch_dp: Adam over the flat buffers)
-        if self._args[2] is not None:
-            self._args[5], self._args[6], self._args[7], self._args[8] = self._hyper
+        self._hyper = (float(lr), float(betas[0]), float(betas[1]), float(eps))
+        if self._has_adam:
+            self._step_hyper = self._hyper
 
     def __call__(self, dropout_offset=0):
         if self.dropout is not None:
             self.st.dropout.offset = int(dropout_offset)
-        rc = self._fn(*self._args, _stream())
+        rc = self._fn(*self._tensors, *self._opt, *self._step_hyper, *self._batch, self._b, *self._sizes, *self._loss,
+                      self._losses_p, *self._outs, *self._wsa, _stream())
         if rc:
             check(rc, "pc_joint_fused_step")
         self.calls += 1
         return self.losses, self.topk
+
+    def _source(self, source):
+        """(features, type_idx, n_types, seed) of the dataset, checked against the catalogue's size: marshalled."""
+        features, type_idx, n_types, seed = source
+        _req(features, torch.float32, "features", (self._a.num_products, D))
+        _req(type_idx, torch.int32, "type_idx", (self._a.num_products,))
+        return (_p(features), _p(type_idx), int(n_types), int(seed))
 
     def from_pairs(self, rows_dev, source, step, dropout_offset=0):
         """The loader's batch construction and the step as one call (pc_joint_fused_step_pairs): `rows_dev` [B,3] int32
         labelled pairs, `source` = (features, type_idx, n_types, seed) of the dataset, `step` the loader's batch counter.
         The batch tensors this object was prepared with are OUTPUTS here: they hold the batch afterwards."""
         if self._pairs_src is None or self._pairs_src[0] is not source:
-            features, type_idx, n_types, seed = source
-            _req(features, torch.float32, "features", (self._args[18], D)); _req(type_idx, torch.int32, "type_idx", (self._args[18],))
-            self._pairs_src = (source, [_p(features), _p(type_idx), int(n_types), int(seed)])
-        _req(rows_dev, torch.int32, "pairs", (self._args[15], 3))
+            self._pairs_src = (source, self._source(source))
+        _req(rows_dev, torch.int32, "pairs", (self._b, 3))
         if self.dropout is not None:
             self.st.dropout.offset = int(dropout_offset)
-        rc = self._pairs_fn(*self._args[:9], ctypes.c_void_p(rows_dev.data_ptr()), *self._pairs_src[1], int(step),
-                            *self._args[9:], _stream())
+        rc = self._pairs_fn(*self._tensors, *self._opt, *self._step_hyper, ctypes.c_void_p(rows_dev.data_ptr()),
+                            *self._pairs_src[1], int(step), *self._batch, self._b, *self._sizes, *self._loss,
+                            self._losses_p, *self._outs, *self._wsa, _stream())
         if rc:
             check(rc, "pc_joint_fused_step_pairs")
         self.calls += 1
         return self.losses, self.topk
 
+    def _epoch(self, pairs_dev, drop_last, dropout_offset):
+        """What both epoch calls prepare: the pair count, the number of steps and their loss rows."""
+        n = int(pairs_dev.shape[0])
+        _req(pairs_dev, torch.int32, "pairs", (n, 3))
+        steps = n // self._b if drop_last else (n + self._b - 1) // self._b
+        losses = torch.empty(max(steps, 1), 3, dtype=torch.float32, device=pairs_dev.device)
+        if self.dropout is not None:
+            self.st.dropout.offset = int(dropout_offset)
+        return n, steps, losses
 
-def _prepared_run_epoch(self, pairs_dev, source, first_step, drop_last=False, dropout_offset=0):
-    """train.py:36-57 over `pairs_dev` [n,3] (epoch order, on the device) as one foreign call (pc_joint_train_epoch).
-    Returns the per-step losses [n_steps,3] (device) and the number of steps."""
-    if self._args[2] is None:
-        raise ValueError("run_epoch needs the optimizer state (PreparedJointStep(adam=...))")
-    features, type_idx, n_types, seed = source
-    _req(features, torch.float32, "features", (self._args[18], D)); _req(type_idx, torch.int32, "type_idx", (self._args[18],))
-    n = int(pairs_dev.shape[0])
-    _req(pairs_dev, torch.int32, "pairs", (n, 3))
-    b = self._args[15]
-    steps = n // b if drop_last else (n + b - 1) // b
-    losses = torch.empty(max(steps, 1), 3, dtype=torch.float32, device=pairs_dev.device)
-    if self.dropout is not None:
-        self.st.dropout.offset = int(dropout_offset)
-    a = self._args
-    rc = _lib.lib().pc_joint_train_epoch(*a[:9], _p(pairs_dev), n, _p(features), _p(type_idx), int(n_types), int(seed),
-                                         int(first_step), *a[9:16], int(bool(drop_last)), *a[16:21], _p(losses), *a[22:],
-                                         _stream())
-    if rc:
-        check(rc, "pc_joint_train_epoch")
-    self.calls += steps
-    self._keep_epoch = (pairs_dev, features, type_idx)
-    return losses[:steps], steps
+    def run_epoch(self, pairs_dev, source, first_step, drop_last=False, dropout_offset=0):
+        """train.py:36-57 over `pairs_dev` [n,3] (epoch order, on the device) as one foreign call (pc_joint_train_epoch).
+        Returns the per-step losses [n_steps,3] (device) and the number of steps."""
+        if not self._has_adam:
+            raise ValueError("run_epoch needs the optimizer state (PreparedJointStep(adam=...))")
+        src = self._source(source)
+        n, steps, losses = self._epoch(pairs_dev, drop_last, dropout_offset)
+        rc = _lib.lib().pc_joint_train_epoch(*self._tensors, *self._opt, *self._step_hyper, _p(pairs_dev), n, *src, int(first_step),
+                                             *self._batch, self._b, int(bool(drop_last)), *self._sizes, *self._loss, _p(losses),
+                                             *self._outs, *self._wsa, _stream())
+        if rc:
+            check(rc, "pc_joint_train_epoch")
+        self.calls += steps
+        self._keep_epoch = (pairs_dev, source)
+        return losses[:steps], steps
 
-
-PreparedJointStep.run_epoch = _prepared_run_epoch
-
-
-def _prepared_run_epoch_dp(self, pairs_dev, source, first_step, flat, gflat, exp_avg, exp_avg_sq, step_count, t_first, scalars,
-                           exchange, drop_last=True, dropout_offset=0, shard=False):
-    """pc_joint_train_epoch_plan: the epoch of a data-parallel REPLICA as one foreign call -- per step the fused step without its
-    Adam, the exchange (ops.RcclExchange / CallbackExchange / None) and Adam over the flat buffers; shard=True: reduce-scatter,
-    Adam on this rank's slice, all-gather (ABI 8).  The object must have been prepared WITHOUT adam (gradients only) over
-    parameters / gradients that are views of flat / gflat."""
-    if self._args[2] is not None:
-        raise ValueError("run_epoch_dp: prepare the step without adam= (the epoch applies Adam over the flat buffers itself)")
-    features, type_idx, n_types, seed = source
-    _req(features, torch.float32, "features", (self._args[18], D)); _req(type_idx, torch.int32, "type_idx", (self._args[18],))
-    n = int(pairs_dev.shape[0])
-    _req(pairs_dev, torch.int32, "pairs", (n, 3))
-    nf = flat.numel()
-    for x, nm in ((flat, "param_flat"), (gflat, "grad_flat"), (exp_avg, "exp_avg"), (exp_avg_sq, "exp_avg_sq")):
-        _req(x, torch.float32, nm, (nf,))
-    _req(step_count, torch.int64, "step_count")
-    b = self._args[15]
-    steps = n // b if drop_last else (n + b - 1) // b
-    losses = torch.empty(max(steps, 1), 3, dtype=torch.float32, device=pairs_dev.device)
-    if self.dropout is not None:
-        self.st.dropout.offset = int(dropout_offset)
-    a = self._args
-    if shard and (exchange is None or nf % exchange.world):
-        raise ValueError("run_epoch_dp(shard=True): an exchange, and flat buffers whose length is a multiple of its world size")
-    plan = exchange.plan(shard=bool(shard)) if exchange is not None else None
-    rc = _lib.lib().pc_joint_train_epoch_plan(a[0], a[1], _p(flat), _p(gflat), _p(exp_avg), _p(exp_avg_sq), nf, _p(step_count),
-                                              int(t_first), _p(scalars), float(self._hyper[0]), float(self._hyper[1]),
-                                              float(self._hyper[2]), float(self._hyper[3]),
-                                              ctypes.byref(plan) if plan is not None else None,
-                                              _p(pairs_dev), n, _p(features), _p(type_idx), int(n_types), int(seed), int(first_step),
-                                              *a[9:16], int(bool(drop_last)), *a[16:21], _p(losses), *a[22:], _stream())
-    if rc and isinstance(exchange, CallbackExchange):
-        exchange.reraise()
-    if rc:
-        check(rc, "pc_joint_train_epoch_plan")
-    self.calls += steps
-    self._keep_epoch = (pairs_dev, features, type_idx, flat, gflat, exp_avg, exp_avg_sq, step_count, scalars, exchange)
-    return losses[:steps], steps
-
-
-PreparedJointStep.run_epoch_dp = _prepared_run_epoch_dp
+    def run_epoch_dp(self, pairs_dev, source, first_step, flat, gflat, exp_avg, exp_avg_sq, step_count, t_first, scalars,
+                     exchange, drop_last=True, dropout_offset=0, shard=False):
+        """pc_joint_train_epoch_plan: the epoch of a data-parallel REPLICA as one foreign call -- per step the fused step without its
+        Adam, the exchange (ops.RcclExchange / CallbackExchange / None) and Adam over the flat buffers; shard=True: reduce-scatter,
+        Adam on this rank's slice, all-gather (ABI 8).  The object must have been prepared WITHOUT adam (gradients only) over
+        parameters / gradients that are views of flat / gflat."""
+        if self._has_adam:
+            raise ValueError("run_epoch_dp: prepare the step without adam= (the epoch applies Adam over the flat buffers itself)")
+        src = self._source(source)
+        n, steps, losses = self._epoch(pairs_dev, drop_last, dropout_offset)
+        nf = flat.numel()
+        for x, nm in ((flat, "param_flat"), (gflat, "grad_flat"), (exp_avg, "exp_avg"), (exp_avg_sq, "exp_avg_sq")):
+            _req(x, torch.float32, nm, (nf,))
+        _req(step_count, torch.int64, "step_count")
+        if shard and (exchange is None or nf % exchange.world):
+            raise ValueError("run_epoch_dp(shard=True): an exchange, and flat buffers whose length is a multiple of its world size")
+        plan = exchange.plan(shard=bool(shard)) if exchange is not None else None
+        rc = _lib.lib().pc_joint_train_epoch_plan(*self._tensors, _p(flat), _p(gflat), _p(exp_avg), _p(exp_avg_sq), nf, _p(step_count),
+                                                  int(t_first), _p(scalars), *self._hyper,
+                                                  ctypes.byref(plan) if plan is not None else None, _p(pairs_dev), n, *src,
+                                                  int(first_step), *self._batch, self._b, int(bool(drop_last)), *self._sizes,
+                                                  *self._loss, _p(losses), *self._outs, *self._wsa, _stream())
+        if rc and isinstance(exchange, CallbackExchange):
+            exchange.reraise()
+        if rc:
+            check(rc, "pc_joint_train_epoch_plan")
+        self.calls += steps
+        self._keep_epoch = (pairs_dev, source, flat, gflat, exp_avg, exp_avg_sq, step_count, scalars, exchange)
+        return losses[:steps], steps
 
 
 class PreparedComplementaryBuilder:
