@@ -997,6 +997,26 @@ int pc_retrieve_topk_grouped(const float *proj, const int32_t *types, int rows, 
                              const int32_t *type_col, const float *table, int n_types, int n, int dim, int slices,
                              int32_t *out_idx, float *out_score, void *ws, size_t ws_bytes, void *stream);
 
+/* The rank of a known product in the list the retrieval above orders (ABI 8, additive; PCompanionInference.rank_targets /
+ * evaluate_catalogue: is the held-out complement among what is served?).  For row r with c = types[r], y = targets[r] and
+ * g = <proj[r], table[y]>:
+ *   rank_out[r] = #{ p in type_col[type_rowptr[c] : type_rowptr[c+1]] : s_p > g or (s_p == g and p < y) },  s_p = <proj[r], table[p]>
+ * -- y need not be of type c; where it is, it does not count itself.  g and every s_p are formed through
+ * pc_retrieve_topk_grouped's own fp32 MFMA chain, so rank_out[r] < n exactly when that entry's top n holds y at position
+ * rank_out[r].  types[r] < 0 ("no type matched"): the row is skipped, rank_out[r] = -1.  A type >= n_types or a target outside
+ * [0, num_products) never reaches memory: the row gets -1 and *bad_count (a device counter the caller owns) is incremented.
+ * The same schedule as the retrieval (rows grouped by type on the device, tiles of 64 rows at dim 128 and 32 at dim 256,
+ * at most `slices` candidate slices per type, 0 = automatic), the selection replaced by a compare and an integer add: no
+ * score matrix, no float atomics, no host readback; bitwise deterministic and independent of `slices` and of the order of
+ * type_col inside a type.  The launch geometry and the workspace (pc_rank_grouped_workspace_bytes, 0 for arguments out of
+ * range) depend on rows, n_types and slices only.  PC_EINVAL: null pointer, rows, n_types or num_products <= 0; PC_ESHAPE:
+ * dim not 128 / 256, slices outside [0, 64]; PC_EWORKSPACE: ws_bytes too small -- each checked before anything is launched. */
+size_t pc_rank_grouped_workspace_bytes(int rows, int n_types, int slices);
+int pc_rank_grouped(const float *proj, const int32_t *types, const int32_t *targets, int rows,
+                    const int32_t *type_rowptr, const int32_t *type_col, const float *table,
+                    int n_types, int num_products, int dim, int slices,
+                    int32_t *rank_out, int32_t *bad_count, void *ws, size_t ws_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,326 @@
+// The rank of a known product among all products of its type (PCompanionInference.rank_targets / evaluate_catalogue): for
+// row r with type c = types[r] and target y = targets[r], g = <proj[r], table[y]> and
+//   rank_out[r] = #{ p of type c : s_p > g  or  (s_p == g and p < y) },   s_p = <proj[r], table[p]>,
+// the position y takes in the list pc_retrieve_topk_grouped serves for the row (score descending, product index ascending).
+// retrieve.hip's schedule with its selection replaced by a compare and an integer add: no score matrix, no partial lists.
+//
+//   count   pos[r] = atomic position of row r among the rows of its type, cnt[t] = rows of type t; rank_out[r] = 0, or -1
+//           for a row without a type (types[r] < 0) or with an id out of range (counted in *bad_count)
+//   scan    (one workgroup) row_start[t] = exclusive sum of cnt, item_start[t] = exclusive sum of tiles(t) * slices(t)
+//   place   order[row_start[t] + pos[r]] = r
+//   rank    grid-stride over the work items (type, slice, tile): query tile -> LDS; the tile's own targets scored first (wave
+//           w: the 16 targets of row group w as one MFMA column block, g = its diagonal); then the slice's candidates in
+//           chunks of 64 (one 16-candidate column group per wave, rows straight from global into registers, the next
+//           chunk's in flight), every accumulator register compared with its row's g, integer counts per lane; at the end a
+//           16-lane sum, the four waves' sums through LDS, one integer atomic per (row, slice).
+//
+// Determinism: g and every s_p are the MFMA k-chain of retrieve.hip's rg_score_kernel (step j, element e and k-lane h cover
+// dimension 16 j + 4 h + e; the chain's order depends on the dimension index alone), so s_y and g are the same bits and a
+// (row, product) score is bit for bit the one the retrieval orders by.  The count is a sum of integers: it does not depend
+// on the slices, on the order of the rows in a tile, or on the order of type_col inside a type.  No float atomics.
+// The three planning kernels restate retrieve.hip's; the slice plan and the order predicate are shared (grouped_plan.h).
+// (The scan moved into that header as an inlined body leaves rg_scan_kernel's registers and LDS as they are but not its
+// code object's digest, so it is restated here and retrieve.hip's code object stays byte for byte what it was.)
+#include "common.h"
+#include "grouped_plan.h"
+
+// LDS row of the query tile: D + 8 floats.  Lane (c, h) reads the 16 bytes at row c, float 16 k + 4 h, and ds_read_b128
+// serves a wave in four groups of 16 lanes (lanes 0-3, 12-15, 20-27 | 4-11, 16-19, 28-31 | the same + 32) over 16 slots of
+// 16 bytes: with a row stride of 2 slots mod 16 each group's 16 reads take 16 different slots.  (D + 4, one slot, puts
+// lanes 12 and 27 of the first group on one slot: five LDS cycles per read instead of four.)
+#define RK_QS(D) ((D) + 8)
+
+// pos[r] < 0: the row takes no part.
+__global__ __launch_bounds__(256) void rk_count_kernel(const int32_t* __restrict__ types, const int32_t* __restrict__ targets,
+                                                       int rows, int n_types, int num_products, int32_t* __restrict__ cnt,
+                                                       int32_t* __restrict__ pos, int32_t* __restrict__ rank_out,
+                                                       int32_t* __restrict__ bad_count) {
+    const int r = blockIdx.x * 256 + threadIdx.x;
+    if (r >= rows) return;
+    const int t = types[r], y = targets[r];
+    int p = -1;
+    if (t >= 0) {                                         // (t < 0: no type matched -- skipped, not an error)
+        if (t < n_types && y >= 0 && y < num_products) p = atomicAdd(&cnt[t], 1);
+        else atomicAdd(bad_count, 1);
+    }
+    pos[r] = p;
+    rank_out[r] = p < 0 ? -1 : 0;
+}
+
+// One workgroup: each thread sums a contiguous run of types, a block scan of the run totals, then the run is written.
+__global__ __launch_bounds__(1024) void rk_scan_kernel(const int32_t* __restrict__ cnt, const int32_t* __restrict__ type_rowptr,
+                                                       int n_types, int S, int TM, int32_t* __restrict__ row_start,
+                                                       int64_t* __restrict__ item_start) {
+    __shared__ int64_t sr[1024], si[1024];
+    const int tid = threadIdx.x;
+    const int per = (n_types + 1023) / 1024;
+    const int t0 = min(tid * per, n_types), t1 = min(t0 + per, n_types);
+    auto items = [&](int t, int c) -> int64_t {
+        int ns, L;
+        rg_slice_plan(type_rowptr[t + 1] - type_rowptr[t], S, ns, L);
+        return c > 0 ? (int64_t)((c + TM - 1) / TM) * ns : 0;
+    };
+    int64_t a = 0, b = 0;
+    for (int t = t0; t < t1; t++) { const int c = cnt[t]; a += c; b += items(t, c); }
+    sr[tid] = a; si[tid] = b;
+    __syncthreads();
+    for (int o = 1; o < 1024; o <<= 1) {                  // inclusive Hillis-Steele scan
+        const int64_t xa = tid >= o ? sr[tid - o] : 0, xb = tid >= o ? si[tid - o] : 0;
+        __syncthreads();
+        sr[tid] += xa; si[tid] += xb;
+        __syncthreads();
+    }
+    int64_t ra = sr[tid] - a, rb = si[tid] - b;
+    for (int t = t0; t < t1; t++) {
+        const int c = cnt[t];
+        row_start[t] = (int32_t)ra; item_start[t] = rb;
+        ra += c; rb += items(t, c);
+    }
+    if (tid == 1023) { row_start[n_types] = (int32_t)sr[1023]; item_start[n_types] = si[1023]; }
+}
+
+__global__ __launch_bounds__(256) void rk_place_kernel(const int32_t* __restrict__ types, int rows,
+                                                       const int32_t* __restrict__ pos, const int32_t* __restrict__ row_start,
+                                                       int32_t* __restrict__ order) {
+    const int r = blockIdx.x * 256 + threadIdx.x;
+    if (r >= rows) return;
+    const int p = pos[r];
+    if (p >= 0) order[row_start[types[r]] + p] = r;       // (p >= 0 only for a type inside [0, n_types))
+}
+
+// THE k-chain (rg_score_kernel's): NG row groups from g0 on against the 16 columns whose rows the lanes hold in b.  For one
+// accumulator the MFMAs run in the order of the dimension index (step k, element x y z w); unit u = (k = u / NG, group
+// u % NG) is four MFMAs on one ds_read_b128 of the query tile, read PD units ahead.  next != null: once step k's last unit
+// has read b[k], the register takes the same 16 bytes of the lane's NEXT column (next + 4 k), so a whole chunk's time
+// covers that load and one set of row registers serves both chunks.  The fence after each unit keeps the scheduler from
+// hoisting all NB * NG query reads (4 registers each) and from sinking the refills, which would push the kernel's
+// registers into scratch.
+template <int D, int NG>
+__device__ __forceinline__ void rk_chain(const float* q, int g0, float4 (&b)[D / 16], const float4* next, f32x4 (&acc)[NG],
+                                         int c, int h) {
+    constexpr int QS = RK_QS(D), NB = D / 16, U = NB * NG, PD = 3;
+    auto load_a = [&](int u) {
+        return *reinterpret_cast<const float4*>(&q[((g0 + u % NG) * 16 + c) * QS + 16 * (u / NG) + 4 * h]);
+    };
+    float4 ar[PD + 1];
+#pragma unroll
+    for (int u = 0; u < PD && u < U; u++) ar[u] = load_a(u);
+#pragma unroll
+    for (int u = 0; u < U; u++) {
+        if (u + PD < U) ar[(u + PD) % (PD + 1)] = load_a(u + PD);
+        const float4 a = ar[u % (PD + 1)];
+        const int k = u / NG, g = u % NG;
+        acc[g] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, b[k].x, acc[g], 0, 0, 0);
+        acc[g] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, b[k].y, acc[g], 0, 0, 0);
+        acc[g] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, b[k].z, acc[g], 0, 0, 0);
+        acc[g] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, b[k].w, acc[g], 0, 0, 0);
+        if (next && g == NG - 1) b[k] = next[4 * k];
+        __builtin_amdgcn_sched_barrier(0);
+    }
+}
+
+// One work item's candidate stream for a tile of NG 16-row groups (NG a template argument: the loop body is straight-line
+// code).  Lane l of wave wv: column c = l & 15 (candidate wv * 16 + c of the chunk, query row g * 16 + c of the A operand),
+// k-lane h = l >> 4; accumulator register k of row group g holds query row g * 16 + 4 h + k.  b / pid: the first chunk's
+// rows and product ids, pidn: the second chunk's ids, all already in flight (-1: a column past the slice's end; its b is
+// product 0's row and its scores are not counted).  Leaves the wave's counts in part[wv][row].
+template <int D, int NG>
+__device__ __forceinline__ void rk_stream(const float* q, const float* gs, const int* ys, int (*part)[8192 / D],
+                                          const int32_t* __restrict__ type_col, const float* __restrict__ table, int cb0,
+                                          int ce, float4 (&b)[D / 16], int pid, int pidn, int wv, int c, int h) {
+    float gv[NG][4];
+    int cn[NG][4];
+#pragma unroll
+    for (int g = 0; g < NG; g++) {
+        const float4 x = *reinterpret_cast<const float4*>(&gs[g * 16 + 4 * h]);
+        gv[g][0] = x.x; gv[g][1] = x.y; gv[g][2] = x.z; gv[g][3] = x.w;
+#pragma unroll
+        for (int k = 0; k < 4; k++) cn[g][k] = 0;
+    }
+    for (int cb = cb0; cb < ce; cb += RG_CHUNK) {
+        const int cc = cb + 2 * RG_CHUNK + wv * 16 + c;
+        const int pidnn = cc < ce ? type_col[cc] : -1;
+        // the next chunk's rows replace this one's step by step while it is scored
+        const float4* next = reinterpret_cast<const float4*>(table + (size_t)max(pidn, 0) * D) + h;
+        f32x4 acc[NG];
+#pragma unroll
+        for (int g = 0; g < NG; g++) acc[g] = f32x4{0.f, 0.f, 0.f, 0.f};
+        rk_chain<D, NG>(q, 0, b, next, acc, c, h);
+        // a score above g is counted.  Equal to g (the target itself, a copy of its row, or chance): the product index
+        // decides -- rare, so the rows' targets stay in LDS and are read only where a lane meets such a score
+        if (pid >= 0) {
+            bool tie = false;
+#pragma unroll
+            for (int g = 0; g < NG; g++)
+#pragma unroll
+                for (int k = 0; k < 4; k++) {
+                    cn[g][k] += acc[g][k] > gv[g][k] ? 1 : 0;
+                    tie |= acc[g][k] == gv[g][k];
+                }
+            if (tie) {
+#pragma unroll
+                for (int g = 0; g < NG; g++)
+#pragma unroll
+                    for (int k = 0; k < 4; k++)
+                        cn[g][k] += (acc[g][k] == gv[g][k] && pid < ys[g * 16 + 4 * h + k]) ? 1 : 0;
+            }
+        }
+        pid = pidn;
+        pidn = pidnn;
+    }
+    // the 16 columns of a (wave, k-lane) -> lane c == 0
+#pragma unroll
+    for (int g = 0; g < NG; g++)
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            int v = cn[g][k];
+#pragma unroll
+            for (int o = 8; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
+            if (c == 0) part[wv][g * 16 + 4 * h + k] = v;
+        }
+}
+
+// Work item w = (type t, slice s, tile j), items of one type ordered slice-major so that the tiles running side by side read
+// the same candidates (L2).  The four waves' counts meet in LDS: one integer atomic per (row, slice).
+template <int D>
+// three waves per SIMD at D = 128 and two at D = 256, as rg_score_kernel
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(D == 128 ? 3 : 2))) void rk_rank_kernel(
+    const float* __restrict__ proj, const int32_t* __restrict__ targets, const int32_t* __restrict__ type_rowptr,
+    const int32_t* __restrict__ type_col, const float* __restrict__ table, int n_types, int S, const int32_t* __restrict__ cnt,
+    const int32_t* __restrict__ row_start, const int64_t* __restrict__ item_start, const int32_t* __restrict__ order,
+    int32_t* __restrict__ rank_out) {
+    constexpr int TM = 8192 / D;             // rows per tile: 64 (D = 128) or 32 (D = 256): a 32 KB query tile
+    constexpr int RG = TM / 16;              // 16-row groups (at most one per wave)
+    constexpr int QS = RK_QS(D);             // padded LDS row
+    constexpr int NB = D / 16;               // float4 operands per lane per candidate
+    __shared__ __attribute__((aligned(16))) float q[TM * QS];
+    __shared__ __attribute__((aligned(16))) float gs[TM];            // the rows' target scores
+    __shared__ __attribute__((aligned(16))) int ys[TM];              // the rows' targets
+    __shared__ int part[4][TM];                                      // the waves' counts
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, c = lane & 15, h = lane >> 4;
+    const int64_t n_items = item_start[n_types];
+    for (int64_t w = blockIdx.x; w < n_items; w += gridDim.x) {
+        int lo = 0, hi = n_types - 1;                     // the largest t with item_start[t] <= w (< n_types: w < n_items)
+        while (lo < hi) {
+            const int mid = (lo + hi + 1) >> 1;
+            if (item_start[mid] <= w) lo = mid; else hi = mid - 1;
+        }
+        const int t = lo;
+        const int rows_t = cnt[t];
+        const int tiles = (rows_t + TM - 1) / TM;
+        const int local = (int)(w - item_start[t]);
+        const int s = local / tiles, j = local - s * tiles;
+        const int p0 = row_start[t] + j * TM;
+        const int valid = min(TM, rows_t - j * TM);
+        const int rg = (valid + 15) >> 4;
+        const int c0 = type_rowptr[t], C = type_rowptr[t + 1] - c0;
+        int ns, L;
+        rg_slice_plan(C, S, ns, L);
+        const int cb0 = c0 + s * L, ce = c0 + min(C, (s + 1) * L);
+
+        __syncthreads();                                  // the previous item's readers of q / part are done
+        for (int e = tid; e < rg * 16 * (D / 4); e += 256) {          // (rows past the last 16-row group are never read)
+            const int row = e / (D / 4), d4 = e - row * (D / 4);
+            float4 x = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (row < valid) x = reinterpret_cast<const float4*>(proj + (size_t)order[p0 + row] * D)[d4];
+            *reinterpret_cast<float4*>(&q[row * QS + 4 * d4]) = x;
+        }
+
+        auto load_pid = [&](int cb) { const int cc = cb + wv * 16 + c; return cc < ce ? type_col[cc] : -1; };
+        // (a lane without a product reads product 0's row: no branch, and nothing of it is used)
+        auto load_b = [&](float4* b, int pid) {
+            const float4* f = reinterpret_cast<const float4*>(table + (size_t)max(pid, 0) * D) + h;
+#pragma unroll
+            for (int k = 0; k < NB; k++) b[k] = f[4 * k];
+        };
+        float4 b[NB];
+        const int pid = load_pid(cb0);
+        load_b(b, pid);
+        const int pidn = load_pid(cb0 + RG_CHUNK);
+        // wave wv: column c = the target of query row wv * 16 + c
+        int ty = -1;
+        if (wv < rg && wv * 16 + c < valid) ty = targets[order[p0 + wv * 16 + c]];
+        __syncthreads();                                  // query tile in LDS
+        if (wv < rg) {                                    // (wave-uniform)
+            float4 bt[NB];
+            load_b(bt, ty);
+            f32x4 ag[1] = {f32x4{0.f, 0.f, 0.f, 0.f}};
+            rk_chain<D, 1>(q, wv, bt, nullptr, ag, c, h);
+            const f32x4 acc = ag[0];
+            // C/D map of the 16x16 f32 MFMA: column lane & 15, row 4 (lane >> 4) + reg; the diagonal: row == column
+            if ((c >> 2) == h) {
+                const int k = c & 3;
+                gs[wv * 16 + c] = k == 0 ? acc[0] : k == 1 ? acc[1] : k == 2 ? acc[2] : acc[3];
+                ys[wv * 16 + c] = ty;
+            }
+        }
+        __syncthreads();                                  // gs / ys in LDS
+        // the slice's candidates against the tile's NG row groups: straight-line code per NG
+        if (rg == 1) rk_stream<D, 1>(q, gs, ys, part, type_col, table, cb0, ce, b, pid, pidn, wv, c, h);
+        else if (rg == 2) rk_stream<D, 2>(q, gs, ys, part, type_col, table, cb0, ce, b, pid, pidn, wv, c, h);
+        else if constexpr (RG == 4) {
+            if (rg == 3) rk_stream<D, 3>(q, gs, ys, part, type_col, table, cb0, ce, b, pid, pidn, wv, c, h);
+            else rk_stream<D, 4>(q, gs, ys, part, type_col, table, cb0, ce, b, pid, pidn, wv, c, h);
+        }
+        __syncthreads();
+        if (tid < valid) {
+            const int v = part[0][tid] + part[1][tid] + part[2][tid] + part[3][tid];
+            if (v) atomicAdd(&rank_out[order[p0 + tid]], v);
+        }
+    }
+}
+
+namespace {
+struct RkWs {
+    int32_t *cnt, *pos, *row_start, *order;
+    int64_t* item_start;
+    size_t bytes;
+};
+inline int rk_slices(int slices) { return slices == 0 ? RG_AUTO_SLICES : slices; }
+RkWs rk_layout(void* ws, int rows, int n_types) {
+    RkWs w;
+    WsCarver cv(ws);
+    w.cnt = (int32_t*)cv.bytes((size_t)n_types * 4);
+    w.pos = (int32_t*)cv.bytes((size_t)rows * 4);
+    w.row_start = (int32_t*)cv.bytes((size_t)(n_types + 1) * 4);
+    w.item_start = (int64_t*)cv.bytes((size_t)(n_types + 1) * 8);
+    w.order = (int32_t*)cv.bytes((size_t)rows * 4);
+    w.bytes = cv.total;
+    return w;
+}
+}  // namespace
+
+extern "C" size_t pc_rank_grouped_workspace_bytes(int rows, int n_types, int slices) {
+    if (rows <= 0 || n_types <= 0 || slices < 0 || slices > RG_MAX_SLICES) return 0;
+    return rk_layout(nullptr, rows, n_types).bytes;
+}
+
+extern "C" int pc_rank_grouped(const float* proj, const int32_t* types, const int32_t* targets, int rows,
+                               const int32_t* type_rowptr, const int32_t* type_col, const float* table, int n_types,
+                               int num_products, int dim, int slices, int32_t* rank_out, int32_t* bad_count, void* ws,
+                               size_t ws_bytes, void* stream) {
+    if (!proj || !types || !targets || !type_rowptr || !type_col || !table || !rank_out || !bad_count || !ws) return PC_EINVAL;
+    if (rows <= 0 || n_types <= 0 || num_products <= 0) return PC_EINVAL;
+    if ((dim != 128 && dim != 256) || slices < 0 || slices > RG_MAX_SLICES) return PC_ESHAPE;
+    const int S = rk_slices(slices);
+    const RkWs w = rk_layout(ws, rows, n_types);
+    if (ws_bytes < w.bytes) return PC_EWORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    const int TM = 8192 / dim;
+    PC_HIP_TRY(hipMemsetAsync(w.cnt, 0, (size_t)n_types * 4, st));
+    const dim3 rgrid((rows + 255) / 256);
+    PC_LAUNCH(rk_count_kernel, rgrid, dim3(256), 0, st, types, targets, rows, n_types, num_products, w.cnt, w.pos, rank_out,
+              bad_count);
+    PC_LAUNCH(rk_scan_kernel, dim3(1), dim3(1024), 0, st, w.cnt, type_rowptr, n_types, S, TM, w.row_start, w.item_start);
+    PC_LAUNCH(rk_place_kernel, rgrid, dim3(256), 0, st, types, rows, w.pos, w.row_start, w.order);
+    // at most (tiles over all rows + one partial tile per type) x S items; the kernel reads the real count
+    const int64_t cap = ((int64_t)(rows + TM - 1) / TM + (int64_t)(rows < n_types ? rows : n_types)) * S;
+    const dim3 sgrid((unsigned)(cap < RG_MAX_GRID ? cap : RG_MAX_GRID));
+    if (dim == 128)
+        PC_LAUNCH(rk_rank_kernel<128>, sgrid, dim3(256), 0, st, proj, targets, type_rowptr, type_col, table, n_types, S, w.cnt,
+                  w.row_start, w.item_start, w.order, rank_out);
+    else
+        PC_LAUNCH(rk_rank_kernel<256>, sgrid, dim3(256), 0, st, proj, targets, type_rowptr, type_col, table, n_types, S, w.cnt,
+                  w.row_start, w.item_start, w.order, rank_out);
+    return pc_launch_status();
+}

@@ -22,27 +22,9 @@
 // ascending), so the top n of the union does not depend on how the candidates were split, on the order of the rows in a
 // tile (the one thing the planning atomics decide), or on the order of type_col inside a type.  No float atomics.
 #include "common.h"
+#include "grouped_plan.h"          // the chunk / slice constants, rg_slice_plan, rg_better (shared with rank.hip)
 
-#define RG_NONE 0x7fffffff
 #define RG_MAX_N 16
-#define RG_AUTO_SLICES 16
-#define RG_MAX_SLICES 64
-#define RG_SLICE_MIN 4096          // candidates a slice gets at least (fewer slices for a small type)
-#define RG_CHUNK 64                // candidates per chunk: four waves x 16
-#define RG_MAX_GRID 4096
-
-// Slices of a type with C candidates at most S slices: ns slices of L candidates (L a multiple of the chunk, the last slice
-// shorter), none empty.  Host and device use the same arithmetic.
-__host__ __device__ __forceinline__ void rg_slice_plan(int C, int S, int& ns, int& L) {
-    if (C <= 0) { ns = 0; L = 0; return; }
-    int want = (C + RG_SLICE_MIN - 1) / RG_SLICE_MIN;
-    if (want > S) want = S;
-    const int per = (C + want - 1) / want;
-    L = (per + RG_CHUNK - 1) / RG_CHUNK * RG_CHUNK;
-    ns = (C + L - 1) / L;
-}
-
-__device__ __forceinline__ bool rg_better(float x, int xi, float y, int yi) { return x > y || (x == y && xi < yi); }
 
 // insert (x, xi) into the descending list v / ix of length n (the caller has checked it beats the n-th entry)
 __device__ __forceinline__ void rg_insert(float* v, int* ix, int n, float x, int xi) {

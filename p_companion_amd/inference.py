@@ -7,7 +7,11 @@ of that type, score them by <projected embedding, product features> and keep tor
 Here the candidate search of all (query, type) rows is one launch of pc_retrieve_topk over a
 type-grouped CSR of the product table.  Over a DeviceBPG (a 10 M / 100 M catalogue generated in HBM) the CSR is
 built on the device (ops.type_csr) and the search is pc_retrieve_topk_grouped, which scores each type's candidates
-as a tiled fp32 GEMM; neither type_idx nor the features are copied to the host."""
+as a tiled fp32 GEMM; neither type_idx nor the features are copied to the host.
+
+rank_targets / evaluate_catalogue are not in the reference: they say where a KNOWN complement stands in what recommend_batch
+serves -- its rank among all products of its type (pc_rank_grouped: the grouped retrieval's schedule and score bits, the
+selection replaced by a count) -- and fold the held-out "test" pairs into hit@k / MRR / median rank."""
 import os
 from typing import Any, Dict, List
 
@@ -15,7 +19,8 @@ import numpy as np
 import torch
 
 from . import ops
-from .data import DeviceBPG, IntBPG
+from .data import ComplementaryIndexDataset, DeviceBPG, IntBPG
+from .metrics import Metrics
 from .p_companion import PCompanion
 
 
@@ -93,6 +98,75 @@ class PCompanionInference:
                            types.to(torch.int32).reshape(-1).contiguous(), self.type_rowptr, self.type_col,
                            self.features, int(num_recommendations))
         return types, idx.reshape(b, k, -1), sc.reshape(b, k, -1)
+
+    @torch.no_grad()
+    def rank_targets(self, query_idx: torch.Tensor, target_idx: torch.Tensor, take: torch.Tensor = None):
+        """Where does target_idx[b] stand in what is served for query_idx[b]?  The model runs in eval mode on the queries;
+        slot[b] = the k whose predicted complementary type is the target's type (the top-K types are distinct: at most
+        one), -1 if none is; rank[b] = the number of products of that type that slot's projected embedding scores above
+        the target (equal scores: the lower product index first) -- the target's position in recommend_batch's list of
+        that slot, were the list the whole type -- or -1 when slot[b] is -1.  A target outside the catalogue has no type:
+        slot -1, rank -1.  `take` [B] bool (optional): rows that are False get slot -1 / rank -1 and cost no search.
+        Returns (slot int32 [B], rank int32 [B]) on the device; nothing is read back."""
+        query_idx = query_idx.to(self.device).to(torch.int32).contiguous()
+        target_idx = target_idx.to(self.device).to(torch.int32).contiguous()
+        if query_idx.dim() != 1 or query_idx.shape != target_idx.shape:
+            raise ValueError("rank_targets: query_idx and target_idx must be 1-D and of equal length")
+        b = query_idx.shape[0]
+        if b == 0:
+            e = torch.empty(0, dtype=torch.int32, device=self.device)
+            return e, e.clone()
+        out = self.model({"query_idx": query_idx, "query_types": self.type_idx[query_idx.long()]})
+        types = out["complementary_types"]                                        # [B, K], distinct in a row
+        inside = (target_idx >= 0) & (target_idx < self.features.shape[0])
+        target_type = self.type_idx[target_idx.long().clamp(0, self.features.shape[0] - 1)].long()
+        match = (types == target_type[:, None]) & inside[:, None]
+        if take is not None:
+            match &= take.to(self.device).bool()[:, None]
+        found = match.any(1)
+        k = match.to(torch.int32).argmax(1)
+        slot = torch.where(found, k, torch.full_like(k, -1)).to(torch.int32)
+        proj = out["projected_embeddings"][torch.arange(b, device=self.device), k].contiguous()      # [B, D]
+        row_type = torch.where(found, target_type, torch.full_like(target_type, -1)).to(torch.int32)
+        rank, _ = ops.rank_grouped(proj, row_type, target_idx, self.type_rowptr, self.type_col, self.features)
+        return slot, rank
+
+    def evaluate_catalogue(self, dataset: ComplementaryIndexDataset, ks=(1, 3, 10, 100), chunk: int = 65536) -> Dict[str, Any]:
+        """Are the held-out complements among what is served?  `dataset`: a ComplementaryIndexDataset over this object's
+        graph, normally mode "test" (the 10 % of the labelled pairs no other phase reads); only its +1 pairs take part.
+        Chunks of `chunk` pairs go through rank_targets into two device vectors; Metrics.catalogue_metrics folds them
+        (integer counts, one float64 reciprocal-rank sum in a fixed order) and reads back once.  Over a DeviceBPG the -1
+        pairs stay in the chunks as rows that cost no search, so nothing is compacted or counted on the host.
+        Returns {"pairs", "type_hit", "hit@k" for k in ks, "mrr", "median_rank"}: hit@k is the share of all +1 pairs
+        whose target is among the first k products of its type under the matched slot (k <= 16: among
+        recommend_batch(query, k)'s lists), 0 for a pair whose type no slot predicted.  The candidates are every product
+        of the type, the query included, as in serving."""
+        bpg = self.bpg
+        if isinstance(bpg, DeviceBPG) and bpg.world != 1:
+            raise ValueError(f"evaluate_catalogue: this DeviceBPG holds a cyclic 1/{bpg.world} shard of the features")
+        if not isinstance(dataset, ComplementaryIndexDataset) or dataset.bpg is not bpg:
+            raise ValueError("evaluate_catalogue: the dataset was built over another graph than this object serves")
+        chunk = int(chunk)
+        if chunk < 1:
+            raise ValueError("evaluate_catalogue: chunk must be positive")
+        pairs = dataset.pairs
+        if not torch.is_tensor(pairs):
+            pairs = np.asarray(pairs)
+            pairs = torch.from_numpy(np.ascontiguousarray(pairs[pairs[:, 2] == 1], dtype=np.int32))
+        if pairs.shape[0] == 0:
+            raise ValueError("evaluate_catalogue: the dataset holds no +1 pair")
+        pairs = pairs.to(self.device)
+        n = pairs.shape[0]
+        take = pairs[:, 2] == 1
+        slot = torch.empty(n, dtype=torch.int32, device=self.device)
+        rank = torch.empty(n, dtype=torch.int32, device=self.device)
+        for lo in range(0, n, chunk):
+            hi = min(lo + chunk, n)
+            slot[lo:hi], rank[lo:hi] = self.rank_targets(pairs[lo:hi, 0], pairs[lo:hi, 1], take[lo:hi])
+        try:
+            return Metrics.catalogue_metrics(slot, rank, ks, take)
+        except ValueError as e:
+            raise ValueError("evaluate_catalogue: the dataset holds no +1 pair") from e
 
     def recommend(self, query_id, num_recommendations: int = 10) -> Dict[str, Any]:
         """Generate complementary product recommendations (inference.py:64-124): same result dict."""

@@ -9,7 +9,11 @@ never hit (metrics.py:95-100).
 
 Over a ComplementaryIndexLoader whose arrays live on the model's GPU the whole evaluation is one foreign call
 (pc_joint_eval_epoch, csrc/evaluate.hip): the top-K and the type projections once per TYPE, the hit counts from a B x B x D
-product whose epilogue compares and counts (no score matrix), the five metrics formed on the device and read back once."""
+product whose epilogue compares and counts (no score matrix), the five metrics formed on the device and read back once.
+
+Metrics.catalogue_metrics is not in the reference: it turns the ranks of held-out complements among ALL products of their
+type (PCompanionInference.rank_targets -> pc_rank_grouped) into hit@k / MRR / median rank -- what the served lists are
+worth, which the in-batch proxy above cannot say."""
 from typing import Dict
 
 import numpy as np
@@ -41,6 +45,42 @@ class Metrics:
     def mean_relevance(predictions: torch.Tensor, ground_truth: torch.Tensor) -> float:
         """metrics.py:44-60"""
         return float(ops.cosine_rows(predictions.contiguous().float(), ground_truth.contiguous().float()).mean())
+
+    @staticmethod
+    def catalogue_metrics(slot: torch.Tensor, rank: torch.Tensor, ks=(1, 3, 10, 100), take: torch.Tensor = None) -> Dict[str, float]:
+        """slot / rank [N] int32 as PCompanionInference.rank_targets returns them (slot -1: no predicted type is the
+        target's; rank: the target's position among all products of its type, -1 where there is none); take [N] bool:
+        the pairs that count (None: all).  Returns
+          pairs        the number of pairs that count
+          type_hit     the share of them with slot >= 0
+          hit@k        the share of ALL of them with 0 <= rank < k  (k <= 16: the target is in recommend_batch(query, k)'s lists)
+          mrr          the mean of 1 / (rank + 1), 0 for a pair without a rank
+          median_rank  the median rank over the pairs that have one (the mean of the two middle ranks for an even number;
+                       -1.0 when no pair has one)
+        Integer counts and one float64 sum over the [N] vector in torch's fixed reduction order, formed where the tensors
+        live; ONE read-back.  ValueError if no pair counts."""
+        ks = tuple(int(k) for k in ks)
+        if slot.shape != rank.shape or slot.dim() != 1 or any(k < 1 for k in ks):
+            raise ValueError("catalogue_metrics: slot and rank must be [N] and every k >= 1")
+        take = torch.ones_like(slot, dtype=torch.bool) if take is None else take.bool()
+        ranked = take & (rank >= 0)
+        counts = [take.sum(), (take & (slot >= 0)).sum(), ranked.sum()] + [(ranked & (rank < k)).sum() for k in ks]
+        rr = torch.where(ranked, 1.0 / (rank.double() + 1.0), torch.zeros((), dtype=torch.float64, device=rank.device)).sum()
+        # the two middle ranks: unranked pairs sort to the end
+        ordered = torch.where(ranked, rank, torch.full_like(rank, torch.iinfo(torch.int32).max)).sort().values
+        m = counts[2]
+        mid = torch.stack([(m - 1).clamp(min=0) // 2, m // 2]).clamp(max=max(rank.numel() - 1, 0))
+        middle = ordered[mid] if rank.numel() else torch.zeros(2, dtype=torch.int32, device=rank.device)
+        out = torch.cat([torch.stack(counts).double(), rr.reshape(1), middle.double()]).cpu().tolist()      # the ONE read-back
+        pairs, typed, n_ranked = (int(x) for x in out[:3])
+        if pairs == 0:
+            raise ValueError("catalogue_metrics: no pair to evaluate (an empty set of +1 pairs)")
+        res = {"pairs": pairs, "type_hit": typed / pairs}
+        for k, h in zip(ks, out[3:3 + len(ks)]):
+            res[f"hit@{k}"] = int(h) / pairs
+        res["mrr"] = out[3 + len(ks)] / pairs
+        res["median_rank"] = 0.5 * (out[-2] + out[-1]) if n_ranked else -1.0
+        return res
 
     @staticmethod
     def _fused_refusal(model, data_loader):

@@ -1682,6 +1682,37 @@ def retrieve_topk_grouped(proj, types, type_rowptr, type_col, table, n, slices=0
     return out_idx, out_sc
 
 
+def rank_grouped(proj, types, targets, type_rowptr, type_col, table, slices=0, bad=None):
+    """pc_rank_grouped: for row r the number of products of type types[r] that retrieve_topk_grouped orders in front of
+    targets[r] under proj[r] (score descending, product index ascending) -- the position of the target in the served list,
+    over the whole type, from the retrieval's own score bits: rank < n exactly when retrieve_topk_grouped(..., n) holds the
+    target at position rank.  Returns (rank [R] int32, bad [1] int32): rank -1 for a row with types[r] < 0 (skipped) and for
+    a type >= the CSR's or a target outside the table, which `bad` counts (`bad`: a device counter to add to; a fresh zero
+    otherwise).  Bitwise deterministic, the same for every `slices`.  Nothing is read back to the host."""
+    d = _width(table.shape[1])
+    proj = _req(proj.reshape(-1, d), torch.float32, "proj")
+    r = proj.shape[0]
+    _req(types, torch.int32, "types", (r,))
+    _req(targets, torch.int32, "targets", (r,))
+    _req(type_rowptr, torch.int32, "type_rowptr")
+    _req(type_col, torch.int32, "type_col")
+    _req(table, torch.float32, "table")
+    slices, t = int(slices), type_rowptr.numel() - 1
+    if not 0 <= slices <= RETRIEVE_MAX_SLICES:
+        raise ValueError(f"slices must be in [0, {RETRIEVE_MAX_SLICES}] (0 = automatic), got {slices}")
+    rank = torch.empty(r, dtype=torch.int32, device=proj.device)
+    if bad is None:
+        bad = torch.zeros(1, dtype=torch.int32, device=proj.device)
+    else:
+        _req(bad, torch.int32, "bad", (1,))
+    nbytes = _lib.lib().pc_rank_grouped_workspace_bytes(r, t, slices)
+    ws = workspace(nbytes, proj.device, "rank_grouped")
+    check(_lib.lib().pc_rank_grouped(_p(proj), _p(types), _p(targets), r, _p(type_rowptr), _p(type_col), _p(table), t,
+                                     table.shape[0], d, slices, _p(rank), _p(bad), _p(ws), ws.numel(), _stream()),
+          "pc_rank_grouped")
+    return rank, bad
+
+
 def type_csr(type_idx, n_types):
     """The type-grouped product CSR of PCompanionInference (bpg.get_products_by_type, bpg.py:40-43), built on the device from
     an int32 CUDA type_idx [P]: rowptr [T+1] int32, col [P] int32 = the products of each type in ascending node order (the

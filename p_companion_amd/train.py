@@ -135,6 +135,19 @@ def train(config, train_loader, val_loader, pretrained_embeddings, fused=True):
     return model
 
 
+def evaluate_test(config, model, bpg, seed=0):
+    """Not in the reference: the held-out "test" split of the labelled pairs (10 %, read by no other phase) against the
+    whole catalogue -- PCompanionInference.evaluate_catalogue: is the complement bought with the query among what is served
+    for it (hit@k, MRR, median rank over all products of its type)?  `model`: a PCompanion or the path of a best_model.pth;
+    `bpg`: the IntBPG or DeviceBPG (world = 1) it was trained over; `seed`: the dataset's.  Logs the dict and returns it."""
+    from .inference import PCompanionInference
+    logger = logging.getLogger(__name__)
+    metrics = PCompanionInference(model, config, bpg).evaluate_catalogue(ComplementaryIndexDataset(bpg, "test", seed=seed))
+    for name, value in metrics.items():
+        logger.info(f"test {name}: {value:.4f}" if isinstance(value, float) else f"test {name}: {value}")
+    return metrics
+
+
 def main(config, bpg: IntBPG):
     """train.py:74-134 on an integer BPG: Product2Vec pretrain -> embeddings -> P-Companion.  `bpg`: an IntBPG, or a
     DeviceBPG (world = 1, with features and complementary pairs): then every phase runs over the arrays in HBM and only
