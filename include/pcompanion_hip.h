@@ -90,6 +90,10 @@ int pc_abi_version(void);
  * product2vec.py:16; dgamma / dbeta and the coefficients dW0's loader applies).  0 (default) = on the step's own queue between
  * dZ1 and dW3 (12-14 us there, no hops); 1 = on the side queue beside dW3 (rounds 3-5: the kernel hidden, two ~7 us cross-queue hops exposed), kept for
  * comparison.
+ * PC_OPT_BN_FINALIZE_RIDES (ABI 8, additive): 1 (default) = with many rows (the full-tile weight-gradient path, rows >= 8192) and
+ * pc_ffn_saved.a1 given, that finalize has no launch of its own: eight workgroups of the dW3 launch -- which does not depend on
+ * it and has workgroups without rows to spare -- run it and leave.  The same function on the same inputs: the same bits.
+ * 0 = its own launch as described above.  PC_OPT_BN_FINALIZE_SIDE = 1 overrides it.
  * PC_OPT_FUSED_LOSS (ABI 8): 1 (default) = the fused Product2Vec step at PRODUCT_EMB_DIM = 128 forms the triplet hinge of
  * product2vec.py:137-154 and its three input gradients inside the first launch of the attention backward (the 16 samples of a
  * tile compute their own rows: the same arithmetic, the same bits); 0 = as its own launch (rounds 1-5), kept for comparison.
@@ -98,7 +102,7 @@ int pc_abi_version(void);
  * 16-sample tile: out-projection forward, hinge, out-projection backward; 0 = its own launch.  Same bits.
  * Unknown option / value: PC_EINVAL.  Thread-safe. */
 enum { PC_OPT_SIDE_QUEUE = 1, PC_OPT_SORTED_TABLE_GRADIENTS = 2, PC_OPT_BN_FINALIZE_SIDE = 3, PC_OPT_FUSED_LOSS = 4,
-       PC_OPT_FUSED_OUT_CHAIN = 5 };
+       PC_OPT_FUSED_OUT_CHAIN = 5, PC_OPT_BN_FINALIZE_RIDES = 6 };
 int pc_set_option(int option, int value);
 int pc_get_option(int option, int* value);
 /* Destroys the library-owned device state (side queues and their events) of every device; 0 or a hipError_t. */

@@ -80,6 +80,7 @@ PC_OPT_SIDE_QUEUE = 1      # pc_set_option: the fused Product2Vec step's side qu
 PC_OPT_FUSED_OUT_CHAIN = 5           # ... and the out-projection's forward chain in front of it in the same launch (default 1)
 PC_OPT_FUSED_LOSS = 4                # ... the triplet hinge inside the attention backward's first launch (default 1)
 PC_OPT_BN_FINALIZE_SIDE = 3          # ... the BatchNorm-backward finalize of the fused Product2Vec step on the side queue (default 0: on the step's own)
+PC_OPT_BN_FINALIZE_RIDES = 6         # ... that finalize as rider workgroups of the dW3 launch at rows >= 8192 (default 1)
 PC_OPT_SORTED_TABLE_GRADIENTS = 2    # ... the [T,64] table gradients of the fused joint step through the sorted form wherever it fits (default 1)
 
 # name -> (restype, argtypes).  Must list every symbol include/pcompanion_hip.h declares

@@ -539,7 +539,9 @@ struct TnArgs {
 // per Product2Vec step became one.
 struct TnDefer;
 int launch_gemm_tn(const TnArgs& a, hipStream_t st, TnDefer* defer = nullptr);
-int launch_gemm_tn_halves(const TnArgs& a, float* slabs0, float* slabs1, size_t slab_floats, hipStream_t st, TnDefer* defer);
+struct TnRider;                                                  // bn_finalize.h: workgroups of the launch that run the BatchNorm-backward finalize
+int launch_gemm_tn_halves(const TnArgs& a, float* slabs0, float* slabs1, size_t slab_floats, hipStream_t st, TnDefer* defer,
+                          const TnRider* rider = nullptr);
 size_t gemm_tn_workspace_floats(int R, int No, int Ni);
 // up to PC_TN_GROUP small independent products (disjoint slab regions) as one launch + one reduce; the reduce can
 // take PC_TN_EXTRA further slab sets that other kernels filled (the joint step's type-table scatter-adds)
@@ -620,6 +622,7 @@ static inline bool joint_tensors_ok(const pc_joint_tensors* t, bool need_table) 
 // gemm_tn.hip (pc_set_option)
 int pc_opt_sorted_tables();
 int pc_opt_bn_finalize_side();
+int pc_opt_bn_finalize_rides();
 int pc_opt_fused_loss();
 int pc_opt_fused_out_chain();
 // misc.hip

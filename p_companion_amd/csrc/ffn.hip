@@ -13,7 +13,7 @@
 //
 // BatchNorm statistics are per SEGMENT (= per reference FFN call), see pc_segments.
 #include "common.h"
-
+#include "bn_finalize.h"
 
 #define BN_EPS 1e-5f
 #define BN_MOMENTUM 0.1f
@@ -22,7 +22,6 @@
 // partial[t][j] over 128-row tiles -> per-segment statistics.  grid = H/32 blocks of
 // (32 columns x 32 tile lanes): every column is independent, so the fold is spread over 8 CUs
 // and each thread walks tiles/32 entries in two chains; fp64 accumulation.
-#define FIN_COLS 32
 #define FIN_LANES 32
 __device__ __forceinline__ void fold_partials(const float* p1, const float* p2, int t0, int t1, int j, int q,
                                               double (*red)[FIN_LANES][FIN_COLS], double* o1, double* o2) {
@@ -43,78 +42,6 @@ __device__ __forceinline__ void fold_partials(const float* p1, const float* p2, 
         *o1 = s1; *o2 = s2;
     }
     __syncthreads();
-}
-
-// All segments in ONE pass, 16-byte loads (round 6).  The folds above walk a segment's tiles with one dword load per lane and
-// tile: a wave-load moves 256 B and the kernel is bound by the address pipe of its eight CUs, not by latency (5.6 us for 4
-// tiles, 8.8 for 352, 13.1 for 704 when run alone -- scripts/dev/bn_finalize_probe.sh -- and 12-14 us inside the step, four
-// segments one after the other).  Here a thread owns FOUR adjacent columns (one float4 per tile and array), a workgroup is
-// 8 column groups x 64 tile lanes (512 threads: 128 registers per thread would spill the 64 accumulator registers' neighbours),
-// so a wave-load moves 1 KB (eight tile rows x 128 B) and a 352-tile fold is six loads per lane and array, all in flight
-// before the first use.  A value is added to its segment's accumulator by predicate (tiles never
-// straddle segments).  Lanes are reduced in a fixed order: xor-shuffles over the wave's eight tile lanes, then one LDS exchange
-// over the eight waves.  Result: thread f < 128 holds the two sums of (segment f / 32, column f % 32 of the workgroup's 32).
-#define FIN4_CG 8
-#define FIN4_LANES 64
-#define FIN4_WAVES (FIN4_CG * FIN4_LANES / 64)
-#define FIN4_BATCH 6
-__device__ __forceinline__ void fold_partials_all4(const float* __restrict__ p1, const float* __restrict__ p2, const SegInfo& si,
-                                                   int col0, double (*red)[2][PC_MAX_SEG][FIN_COLS], double* o1, double* o2) {
-    const int cg = threadIdx.x, q = threadIdx.y;
-    const int tid = q * FIN4_CG + cg, wave = tid >> 6, lane = tid & 63;
-    double a[PC_MAX_SEG][4], b[PC_MAX_SEG][4];
-#pragma unroll
-    for (int s = 0; s < PC_MAX_SEG; s++)
-#pragma unroll
-        for (int c = 0; c < 4; c++) { a[s][c] = 0.0; b[s][c] = 0.0; }
-    const int t_end = si.tile0[si.nseg];
-    const int b1 = si.nseg > 1 ? si.tile0[1] : t_end, b2 = si.nseg > 2 ? si.tile0[2] : t_end, b3 = si.nseg > 3 ? si.tile0[3] : t_end;
-    const size_t c0 = (size_t)col0 + cg * 4;
-    for (int t = si.tile0[0] + q; t < t_end; t += FIN4_BATCH * FIN4_LANES) {
-        float4 x[FIN4_BATCH], y[FIN4_BATCH];
-#pragma unroll
-        for (int u = 0; u < FIN4_BATCH; u++) {
-            const int tt = t + u * FIN4_LANES;
-            const int tc = tt < t_end ? tt : t;                    // (a lane past the end re-reads its first tile: no branch, no use)
-            x[u] = *reinterpret_cast<const float4*>(p1 + (size_t)tc * PC_H + c0);
-            y[u] = *reinterpret_cast<const float4*>(p2 + (size_t)tc * PC_H + c0);
-        }
-#pragma unroll
-        for (int u = 0; u < FIN4_BATCH; u++) {
-            const int tt = t + u * FIN4_LANES;
-            const int sg = tt < t_end ? (tt >= b1) + (tt >= b2) + (tt >= b3) : -1;
-#pragma unroll
-            for (int s = 0; s < PC_MAX_SEG; s++) {
-                const bool on = sg == s;
-                a[s][0] += on ? (double)x[u].x : 0.0; a[s][1] += on ? (double)x[u].y : 0.0;
-                a[s][2] += on ? (double)x[u].z : 0.0; a[s][3] += on ? (double)x[u].w : 0.0;
-                b[s][0] += on ? (double)y[u].x : 0.0; b[s][1] += on ? (double)y[u].y : 0.0;
-                b[s][2] += on ? (double)y[u].z : 0.0; b[s][3] += on ? (double)y[u].w : 0.0;
-            }
-        }
-    }
-    // the wave's eight tile lanes (lane bits 3..5), fixed order
-#pragma unroll
-    for (int s = 0; s < PC_MAX_SEG; s++)
-#pragma unroll
-        for (int c = 0; c < 4; c++) {
-#pragma unroll
-            for (int o = 8; o < 64; o <<= 1) { a[s][c] += __shfl_xor(a[s][c], o, 64); b[s][c] += __shfl_xor(b[s][c], o, 64); }
-        }
-    if (lane < FIN4_CG) {
-#pragma unroll
-        for (int s = 0; s < PC_MAX_SEG; s++)
-#pragma unroll
-            for (int c = 0; c < 4; c++) { red[wave][0][s][cg * 4 + c] = a[s][c]; red[wave][1][s][cg * 4 + c] = b[s][c]; }
-    }
-    __syncthreads();
-    if (tid < PC_MAX_SEG * FIN_COLS) {
-        const int s = tid / FIN_COLS, col = tid % FIN_COLS;
-        double s1 = 0.0, s2 = 0.0;
-#pragma unroll
-        for (int w = 0; w < FIN4_WAVES; w++) { s1 += red[w][0][s][col]; s2 += red[w][1][s][col]; }
-        *o1 = s1; *o2 = s2;
-    }
 }
 
 // Cross-replica BatchNorm: the per-segment sums of THIS replica, in fp64, in the
@@ -158,7 +85,7 @@ __global__ __launch_bounds__(FIN4_CG * FIN4_LANES) void bn_finalize_fwd_kernel(
         return;
     }
     double a = 0.0, b = 0.0;
-    if (!gsum) fold_partials_all4(psum, psq, si, blockIdx.x * FIN_COLS, red, &a, &b);
+    if (!gsum) fold_partials_all4(psum, psq, si, blockIdx.x * FIN_COLS, tid, red, &a, &b);
     if (tid < PC_MAX_SEG * FIN_COLS) {
         const int s = tid / FIN_COLS, col = tid % FIN_COLS, j = blockIdx.x * FIN_COLS + col;
         double n = s < si.nseg ? (double)si.count[s] : 0.0;   // logical rows (a weighted row counts wmult times)
@@ -214,42 +141,9 @@ __global__ void bn_eval_coeff_kernel(const float* gamma, const float* beta, cons
 __global__ __launch_bounds__(FIN4_CG * FIN4_LANES) void bn_finalize_bwd_kernel(
     const float* psum, const float* pdot, SegInfo si, const double* lsum, const double* gsum, const float* mean,
     const float* invstd, float* dgamma, float* dbeta, int accumulate, float* c1, float* c2) {
-    __shared__ double red[FIN4_WAVES][2][PC_MAX_SEG][FIN_COLS];
-    __shared__ double seg_g[PC_MAX_SEG][FIN_COLS], seg_b[PC_MAX_SEG][FIN_COLS];
-    const int tid = threadIdx.y * FIN4_CG + threadIdx.x;
-    double a = 0.0, b = 0.0;
-    if (!lsum) fold_partials_all4(psum, pdot, si, blockIdx.x * FIN_COLS, red, &a, &b);
-    if (tid < PC_MAX_SEG * FIN_COLS) {
-        const int s = tid / FIN_COLS, col = tid % FIN_COLS, j = blockIdx.x * FIN_COLS + col;
-        double tg = 0.0, tb = 0.0;
-        if (s < si.nseg) {
-            double n = si.count[s];                           // logical rows (a weighted row counts wmult times)
-            if (lsum) { a = lsum[(2 * s) * PC_H + j]; b = lsum[(2 * s + 1) * PC_H + j]; }
-            // the tiles carry the raw moment sum dz1*h0: sum dz1*xhat = invstd * (sum dz1*h0 - mean * sum dz1)
-            const double is = (double)invstd[s * PC_H + j], mu = (double)mean[s * PC_H + j];
-            b = is * (b - mu * a);
-            tb = a;                                           // dbeta / dgamma: this replica's rows
-            tg = b;
-            double ga = a, gb = b;                            // the BN-backward means run over ALL replicas' rows
-            if (gsum) {
-                ga = gsum[(2 * s) * PC_H + j];
-                gb = is * (gsum[(2 * s + 1) * PC_H + j] - mu * ga);
-                n = gsum[2 * PC_MAX_SEG * PC_H + s];
-            }
-            c1[s * PC_H + j] = n > 0 ? (float)(ga / n) : 0.f;
-            c2[s * PC_H + j] = n > 0 ? (float)(gb / n) : 0.f;
-        }
-        seg_g[s][col] = tg;
-        seg_b[s][col] = tb;
-    }
-    __syncthreads();
-    if (tid < FIN_COLS) {
-        const int j = blockIdx.x * FIN_COLS + tid;
-        double tg = 0.0, tb = 0.0;
-        for (int s = 0; s < si.nseg; s++) { tg += seg_g[s][tid]; tb += seg_b[s][tid]; }     // segment order, as before
-        dgamma[j] = accumulate ? dgamma[j] + (float)tg : (float)tg;
-        dbeta[j] = accumulate ? dbeta[j] + (float)tb : (float)tb;
-    }
+    __shared__ BnFinBwdScratch sm;
+    const BnFinBwd f = {psum, pdot, lsum, gsum, mean, invstd, dgamma, dbeta, accumulate, c1, c2};
+    bn_finalize_bwd_body(f, si, (int)blockIdx.x, (int)(threadIdx.y * FIN4_CG + threadIdx.x), &sm);
 }
 
 // dH0 = scale_s * (dZ1 - c1_s - xhat*c2_s), xhat = (H0 - mean_s)*invstd_s; in place over dz [R,256]
@@ -525,17 +419,26 @@ int ffn_backward_part1(const pc_p2v_tensors* p, const pc_p2v_tensors* g, const f
     b2.epilogue = NT_EPI_DTANH_BN; b2.aux = sv->h0; b2.ldaux = PC_H; b2.escale = sv->bn_scale; b2.eshift = sv->bn_shift;
     b2.stats = NT_STAT_BNBWD; b2.stat_sum = w.stat_a; b2.stat_aux = w.stat_b;
     PC_TRY(launch_gemm_nt(b2, st));
+    TnRider fin_rider = {};
     if (df->fork && !local_sums) {
         // the BatchNorm-backward finalize (only dW0 reads c1 / c2).  Rounds 3-5: on the side queue beside dW3 -- the fork and the
         // join each cost the main queue ~6.5 us (profiles/r06a_step_timeline.md) and the 8-workgroup kernel took 12-32 us there.
         // Round 6: on the step's own queue, between dZ1 and dW3: 12-14 us exposed, no hops, -8 us per step in A/B
-        // (pc_set_option(PC_OPT_BN_FINALIZE_SIDE, 1): the old placement)
+        // (pc_set_option(PC_OPT_BN_FINALIZE_SIDE, 1): the old placement).
+        // Now, with many rows and A1 saved: as eight RIDER workgroups of the dW3 launch below, which does not depend on it and
+        // leaves CUs without rows (pc_set_option(PC_OPT_BN_FINALIZE_RIDES, 0): its own launch again)
+        const BnFinBwd fin = {w.stat_a, w.stat_b, nullptr, nullptr, sv->bn_mean, sv->bn_invstd, g->gamma, g->beta, accumulate, w.c1, w.c2};
         if (pc_opt_bn_finalize_side()) {
             PC_TRY(pc_fork_begin(df->fork, 1, st));
             PC_LAUNCH(bn_finalize_bwd_kernel, dim3(PC_H / FIN_COLS), dim3(FIN4_CG, FIN4_LANES), 0, df->fork->side, w.stat_a, w.stat_b, si,
                       nullptr, nullptr, sv->bn_mean, sv->bn_invstd, g->gamma, g->beta, accumulate, w.c1, w.c2);
             PC_TRY(pc_launch_status());
             df->bn_finalized = 1;
+        } else if (pc_opt_bn_finalize_rides() && sv->a1 && rows >= 8192 && (size_t)128 * ((size_t)128 * PC_H + 128) <= w.slab_floats) {
+            fin_rider.n = PC_TN_RIDERS;                      // (the same condition as the halves launch of dW3 below)
+            fin_rider.fin = fin;
+            fin_rider.si = si;
+            df->bn_finalized = 2;                            // done by the time dW3 is: nothing to launch, nothing to join
         } else {
             PC_LAUNCH(bn_finalize_bwd_kernel, dim3(PC_H / FIN_COLS), dim3(FIN4_CG, FIN4_LANES), 0, st, w.stat_a, w.stat_b, si,
                       nullptr, nullptr, sv->bn_mean, sv->bn_invstd, g->gamma, g->beta, accumulate, w.c1, w.c2);
@@ -557,7 +460,7 @@ int ffn_backward_part1(const pc_p2v_tensors* p, const pc_p2v_tensors* g, const f
         // whole step: 1.068 -> 1.062 ms)
         // (round 4: many rows -- the two halves as ONE launch of 2 x 128 row slices: A1 comes from HBM once, half the slabs)
         if (rows >= 8192 && (size_t)128 * ((size_t)128 * PC_H + 128) <= w.slab_floats) {
-            PC_TRY(launch_gemm_tn_halves(t3, w.slabs[1], w.slabs[2], w.slab_floats, st, df));
+            PC_TRY(launch_gemm_tn_halves(t3, w.slabs[1], w.slabs[2], w.slab_floats, st, df, fin_rider.n ? &fin_rider : nullptr));
         } else {
             for (int half = 0; half < 2; half++) {
                 TnArgs th = t3;

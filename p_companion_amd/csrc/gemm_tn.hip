@@ -12,7 +12,9 @@
 // consecutive floats per half-wave, conflict-free ds_read_b32.
 #include <atomic>
 #include <mutex>
+#include <type_traits>
 #include "common.h"
+#include "bn_finalize.h"
 
 #define TM 128
 #define TK 32
@@ -201,9 +203,14 @@ __device__ __forceinline__ void tn_lds_sync() {
 // Workgroups b and b + 8 -- the same XCD: blockIdx round-robins over the eight -- take the two halves of ONE row slice, so the
 // second fetch of the slice's A rows is an L2 hit (two launches of 256 slices each read A twice from HBM and wrote twice the
 // slabs).  Half h reads Z + h * NO columns and writes its slabs at a.slabs + h * slab_half_off.
-template <int WO, int WI, int TO, int TI, int TKC, int NST, bool APRO, bool ZPRO>
+// RIDER: the workgroups rider.block[i], i < PC_TN_RIDERS, run column block i of the BatchNorm-backward finalize and leave; their
+// scratch is the stage memory.  The launcher gives them the places of slices that own no rows, or appends them.  (Its own
+// instantiation: read in front of every launch of this family, the rider's arguments cost each one a dependent fetch, 1.4 us.)
+struct TnNoRider {};
+template <int WO, int WI, int TO, int TI, int TKC, int NST, bool APRO, bool ZPRO, bool RIDER = false>
 __global__ __launch_bounds__(64 * WO * WI, WO * WI / 4) void gemm_tn8_kernel(TnArgs a, int nsplit, int rows_per_split, int halves,
-                                                                             size_t slab_half_off) {
+                                                                             size_t slab_half_off,
+                                                                             std::conditional_t<RIDER, TnRider, TnNoRider> rider) {
     constexpr int NWV = WO * WI, THREADS = 64 * NWV;            // 8 waves (2 per SIMD) or 16 (4 per SIMD)
     constexpr int NO = WO * TO * 32, NI = WI * TI * 32;
     // Image rows must not start on the same LDS bank two rows apart in the MFMA's k pair (lanes 0-31 read row k,
@@ -237,6 +244,16 @@ __global__ __launch_bounds__(64 * WO * WI, WO * WI / 4) void gemm_tn8_kernel(TnA
     const int r_end = min(a.R, r_begin + rows_per_split);
     const float* const zsrc0 = pc_tn_zero_chunk;
     const unsigned lds0 = (unsigned)(uintptr_t)(tn_lptr_t)&smem[0];
+    if constexpr (RIDER) {                                       // (uniform: scalar compares on the kernel arguments)
+        int rid = -1;
+#pragma unroll
+        for (int i = 0; i < PC_TN_RIDERS; i++) rid = (int)blockIdx.x == rider.block[i] ? i : rid;
+        if (rid >= 0) {
+            static_assert(sizeof(smem) >= sizeof(BnFinBwdScratch) && THREADS == FIN4_CG * FIN4_LANES, "a finalize workgroup");
+            bn_finalize_bwd_body(rider.fin, rider.si, rid, (int)threadIdx.x, reinterpret_cast<BnFinBwdScratch*>(smem));
+            return;
+        }
+    }
 
     // DMA geometry: instruction g = w + NWV j of an image covers its floats [256 g, 256 g + 256)
     // (zc / ac: the GLOBAL column this lane fetches; zd / ad: byte offset of the instruction inside the image)
@@ -625,10 +642,10 @@ int launch_gemm_tn(const TnArgs& a, hipStream_t st, TnDefer* defer) {
         // chunks in three stages like the ZPRO forms (same steady-state rate: these kernels do not wait for HBM)
 #define TN8(WO, WI, TO, TI, TKC, NST)                                                                         \
     do {                                                                                                      \
-        if (apro) PC_LAUNCH((gemm_tn8_kernel<WO, WI, TO, TI, TKC, NST, true, false>), dim3(nsplit), dim3(64 * WO * WI), 0, st, a, nsplit, rps, 1, (size_t)0);    \
-        else if (zpro && a.Ni > 128) PC_LAUNCH((gemm_tn8_kernel<2, 4, 4, 2, 16, 3, false, true>), dim3(nsplit), dim3(512), 0, st, a, nsplit, rps, 1, (size_t)0);  \
-        else if (zpro) PC_LAUNCH((gemm_tn8_kernel<4, 2, 2, 2, 16, 3, false, true>), dim3(nsplit), dim3(512), 0, st, a, nsplit, rps, 1, (size_t)0);  \
-        else PC_LAUNCH((gemm_tn8_kernel<WO, WI, TO, TI, TKC, NST, false, false>), dim3(nsplit), dim3(64 * WO * WI), 0, st, a, nsplit, rps, 1, (size_t)0);        \
+        if (apro) PC_LAUNCH((gemm_tn8_kernel<WO, WI, TO, TI, TKC, NST, true, false>), dim3(nsplit), dim3(64 * WO * WI), 0, st, a, nsplit, rps, 1, (size_t)0, TnNoRider{});    \
+        else if (zpro && a.Ni > 128) PC_LAUNCH((gemm_tn8_kernel<2, 4, 4, 2, 16, 3, false, true>), dim3(nsplit), dim3(512), 0, st, a, nsplit, rps, 1, (size_t)0, TnNoRider{});  \
+        else if (zpro) PC_LAUNCH((gemm_tn8_kernel<4, 2, 2, 2, 16, 3, false, true>), dim3(nsplit), dim3(512), 0, st, a, nsplit, rps, 1, (size_t)0, TnNoRider{});  \
+        else PC_LAUNCH((gemm_tn8_kernel<WO, WI, TO, TI, TKC, NST, false, false>), dim3(nsplit), dim3(64 * WO * WI), 0, st, a, nsplit, rps, 1, (size_t)0, TnNoRider{});        \
     } while (0)
         if (a.No > 128 && a.Ni > 128) TN8(2, 4, 4, 2, 16, 3);
         else if (a.No > 128) TN8(4, 2, 2, 2, 32, 2);
@@ -649,7 +666,8 @@ int launch_gemm_tn(const TnArgs& a, hipStream_t st, TnDefer* defer) {
 
 // dW[2 x 128, 256] = Z[:, 0:256]^T A as ONE launch of 2 x 128 row slices (see gemm_tn8_kernel, halves == 2); slabs0 / slabs1: the two
 // halves' slab regions (each >= 128 x (128 x 256 + 128) floats), reduced as two jobs of the caller's deferred list
-int launch_gemm_tn_halves(const TnArgs& a, float* slabs0, float* slabs1, size_t slab_floats, hipStream_t st, TnDefer* defer) {
+int launch_gemm_tn_halves(const TnArgs& a, float* slabs0, float* slabs1, size_t slab_floats, hipStream_t st, TnDefer* defer,
+                          const TnRider* rider) {
     if (!a.Z || !a.A || !a.dW || !slabs0 || !slabs1 || !defer || a.R <= 0) return PC_EINVAL;
     if (a.No != 256 || a.Ni != 256 || a.ldz % 4 || a.lda % 4 || a.lddw != a.Ni || a.prologue != NT_PRO_NONE || a.zaux || a.z_onehot || a.gather)
         return PC_ESHAPE;
@@ -660,16 +678,36 @@ int launch_gemm_tn_halves(const TnArgs& a, float* slabs0, float* slabs1, size_t 
     const int used = (a.R + rps - 1) / rps;                      // (<= 128: trailing slices own no rows and write zero slabs)
     const size_t per = (size_t)128 * a.Ni + 128;
     if ((size_t)nsplit * per > slab_floats) return PC_EWORKSPACE;
-    (void)used;
     TnArgs h = a;
     h.No = 128; h.slabs = slabs0; h.slab_floats = slab_floats;
+    // Riders take the places of workgroups whose slice owns no rows (R = 86.4 k: 123 of 128 slices used, ten such workgroups
+    // on the 256 CUs); the slabs those would have zeroed are then left out of the sums (a sum starts at +0 and never becomes
+    // -0: the same bits with or without a zero slab).  With fewer than PC_TN_RIDERS of them the riders are appended to the grid.
+    TnRider rd = {};
+    int blocks = 2 * nsplit, nred = nsplit;
+    if (rider && rider->n) {
+        if (rider->n != PC_TN_RIDERS) return PC_EINVAL;
+        rd = *rider;
+        int k = 0;
+        for (int b = 0; b < 2 * nsplit && k < rd.n; b++)
+            if (((b >> 4) << 3) + (b & 7) >= used) rd.block[k++] = b;        // (the kernel's own block -> slice map)
+        if (k == rd.n) nred = used;
+        else {
+            for (k = 0; k < rd.n; k++) rd.block[k] = blocks + k;
+            blocks += rd.n;
+        }
+    }
     const int pb = pc_prof_begin(PC_KIND_GEMM_TN, 2.0 * a.R * (double)a.No * a.Ni, st);
-    PC_LAUNCH((gemm_tn8_kernel<2, 4, 2, 2, 32, 2, false, false>), dim3(2 * nsplit), dim3(512), 0, st, h, nsplit, rps, 2,
-              (size_t)(slabs1 - slabs0));
+    if (rd.n)
+        PC_LAUNCH((gemm_tn8_kernel<2, 4, 2, 2, 32, 2, false, false, true>), dim3(blocks), dim3(512), 0, st, h, nsplit, rps, 2,
+                  (size_t)(slabs1 - slabs0), rd);
+    else
+        PC_LAUNCH((gemm_tn8_kernel<2, 4, 2, 2, 32, 2, false, false>), dim3(blocks), dim3(512), 0, st, h, nsplit, rps, 2,
+                  (size_t)(slabs1 - slabs0), TnNoRider{});
     pc_prof_end(pb, st);
     PC_TRY(pc_launch_status());
-    PC_TRY(tn_defer_push(defer, slabs0, slab_floats, nsplit, 128 * a.Ni, 128, a.dW, a.db, a.accumulate));
-    return tn_defer_push(defer, slabs1, slab_floats, nsplit, 128 * a.Ni, 128, a.dW + (size_t)128 * a.Ni, a.db ? a.db + 128 : nullptr,
+    PC_TRY(tn_defer_push(defer, slabs0, slab_floats, nred, 128 * a.Ni, 128, a.dW, a.db, a.accumulate));
+    return tn_defer_push(defer, slabs1, slab_floats, nred, 128 * a.Ni, 128, a.dW + (size_t)128 * a.Ni, a.db ? a.db + 128 : nullptr,
                          a.accumulate);
 }
 
@@ -684,6 +722,7 @@ std::mutex g_fork_mu;
 std::atomic<int> g_opt_side_queue{1};
 std::atomic<int> g_opt_sorted_tables{1};
 std::atomic<int> g_opt_bn_finalize_side{0};
+std::atomic<int> g_opt_bn_finalize_rides{1};
 std::atomic<int> g_opt_fused_loss{1};
 std::atomic<int> g_opt_fused_out_chain{1};
 std::atomic<int>* opt_slot(int option) {
@@ -693,12 +732,14 @@ std::atomic<int>* opt_slot(int option) {
         case PC_OPT_BN_FINALIZE_SIDE: return &g_opt_bn_finalize_side;
         case PC_OPT_FUSED_LOSS: return &g_opt_fused_loss;
         case PC_OPT_FUSED_OUT_CHAIN: return &g_opt_fused_out_chain;
+        case PC_OPT_BN_FINALIZE_RIDES: return &g_opt_bn_finalize_rides;
         default: return nullptr;
     }
 }
 }
 int pc_opt_sorted_tables() { return g_opt_sorted_tables.load(std::memory_order_relaxed); }
 int pc_opt_bn_finalize_side() { return g_opt_bn_finalize_side.load(std::memory_order_relaxed); }
+int pc_opt_bn_finalize_rides() { return g_opt_bn_finalize_rides.load(std::memory_order_relaxed); }
 int pc_opt_fused_loss() { return g_opt_fused_loss.load(std::memory_order_relaxed); }
 int pc_opt_fused_out_chain() { return g_opt_fused_out_chain.load(std::memory_order_relaxed); }
 
