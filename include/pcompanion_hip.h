@@ -660,6 +660,11 @@ int pc_exchange_adam(pc_exchange_fn exchange, void *exchange_ctx, float *param, 
  * the same order (always for world = 2; a ring all-reduce is this reduce-scatter + all-gather).
  * plan->shard_optimizer == 0 (or world == 1 with reduce_scatter_mean == NULL): the plain form -- all_reduce_mean (may be NULL:
  * no exchange) then Adam over all n.  n must be a multiple of world when sharded (the host pads the flat buffers), else PC_EINVAL.
+ * SLICE ALIGNMENT: the Adam kernels move 16-byte chunks, so every slice must start on a 16-byte boundary: (n / world) % 4 != 0 is
+ * PC_ESHAPE -- on EVERY rank (rank 0's slice starts aligned whatever n is) and BEFORE the reduce-scatter is issued, so that no
+ * rank is left waiting in a collective its peers never enter.  The host pads the flat buffers to a multiple of 4 * world floats.
+ * The moments of the other slices are neither read nor written: a checkpoint of the whole optimizer state needs an all-gather of
+ * exp_avg / exp_avg_sq over the same slices first (the all_gather member serves it).
  * pc_rccl_reduce_scatter_mean / pc_rccl_all_gather are the native members: ncclReduceScatter(ncclAvg) / ncclAllGather in place
  * on the library's communicator, chained like its other collectives. */
 typedef int (*pc_shard_collective_fn)(void *ctx, float *buf, size_t n_per_rank, void *stream);
@@ -697,7 +702,9 @@ int pc_joint_train_epoch_dp(const pc_joint_tensors *p, const pc_joint_tensors *g
                             int32_t *topk, int32_t *bad_count, void *ws, size_t ws_bytes, void *stream);
 
 /* pc_joint_train_epoch_dp with a plan in place of (exchange, exchange_ctx): per step the fused step without its Adam, then
- * pc_exchange_adam_plan -- at num_types > 512 p_companion_amd passes shard_optimizer = 1. */
+ * pc_exchange_adam_plan -- at num_types > 512 p_companion_amd passes shard_optimizer = 1.  The sharded form's conditions on
+ * n_flat (a multiple of world: PC_EINVAL; slices of a multiple of 4 floats: PC_ESHAPE) are checked at entry, before the first
+ * step's first launch. */
 int pc_joint_train_epoch_plan(const pc_joint_tensors *p, const pc_joint_tensors *g, float *param_flat, float *grad_flat,
                               float *exp_avg_flat, float *exp_avg_sq_flat, size_t n_flat, int64_t *step_count,
                               int64_t t_first, float *adam_scalars, double lr, double beta1, double beta2, double eps,

@@ -269,6 +269,10 @@ extern "C" int pc_exchange_adam_plan(const pc_exchange_plan* plan, float* param,
         if (plan->world < 1 || plan->rank < 0 || plan->rank >= plan->world || n % (size_t)plan->world) return PC_EINVAL;
         if (!plan->reduce_scatter_mean || !plan->all_gather) return PC_EINVAL;
         len = n / (size_t)plan->world;
+        // pc_adam_step[_at] moves 16-byte chunks: slice `rank` starts at param + rank * len.  The same answer on EVERY rank (rank
+        // 0's slice is aligned whatever len is) and BEFORE the reduce-scatter: a rank that refused behind it would leave its
+        // peers waiting in the all-gather.
+        if (len % 4) return PC_ESHAPE;
         lo = (size_t)plan->rank * len;
         PC_TRY(plan->reduce_scatter_mean(plan->ctx, grad, len, stream));
     } else if (plan && plan->all_reduce_mean) {

@@ -2850,6 +2850,13 @@ extern "C" int pc_joint_train_epoch_plan(const pc_joint_tensors* p, const pc_joi
     if (!p || !g || !pairs || !features || !type_idx || n_types <= 0 || n_pairs < 0 || B <= 0 || !losses_out) return PC_EINVAL;
     if (!param_flat || !grad_flat || !exp_avg_flat || !exp_avg_sq_flat || n_flat == 0 || t_first < 0) return PC_EINVAL;
     if (t_first == 0 && (!step_count || !adam_scalars)) return PC_EINVAL;
+    // the sharded optimizer's conditions on n_flat (pc_exchange_adam_plan's own, which would otherwise speak up behind the first
+    // step's launches): here, before anything is enqueued, and the same on every rank
+    if (plan && plan->shard_optimizer && (plan->world > 1 || plan->reduce_scatter_mean)) {
+        if (plan->world < 1 || plan->rank < 0 || plan->rank >= plan->world || n_flat % (size_t)plan->world) return PC_EINVAL;
+        if (!plan->reduce_scatter_mean || !plan->all_gather) return PC_EINVAL;
+        if ((n_flat / (size_t)plan->world) % 4) return PC_ESHAPE;
+    }
     // p / g are views into the flat buffers: what the exchange averages and Adam updates must be what the step reads and writes
     float *gp[10], *pp[10];
     joint_fields(g, gp);

@@ -338,6 +338,20 @@ class Exchange:
         check(rc, "pc_exchange_fn")
         return t
 
+    def all_gather_(self, t):
+        """The all-gather half of the sharded pair applied to a device tensor of world equal slices, in place, on the current
+        stream: every rank's slice `rank` -> all ranks' t (FusedAdam.gather_state: the moments of a sharded optimizer)."""
+        _req(t, torch.float32, "buf")
+        if self.ag_fn is None:
+            raise ValueError("this exchange has no reduce-scatter / all-gather pair")
+        if t.numel() % self.world:
+            raise ValueError("all_gather_: a multiple of the world size")
+        rc = EXCHANGE_FN(self.ag_fn.value)(self.ctx, _p(t), t.numel() // self.world, _stream())
+        if rc and isinstance(self, CallbackExchange):
+            self.reraise()
+        check(rc, "pc_shard_collective_fn (all_gather)")
+        return t
+
 
 def rccl_available():
     return bool(_lib.lib().pc_rccl_available())
@@ -457,7 +471,9 @@ def exchange_adam(exchange, param, grad, exp_avg, exp_avg_sq, step_count, t, sca
     """pc_exchange_adam: the replicas' mean gradient (exchange may be None: single process), then Adam -- optimizer.step() of a
     replica as one foreign call.  t >= 1: the host-known step number; t == 0: the device counter (scalars required).
     shard=True (pc_exchange_adam_plan, ABI 8): reduce-scatter of the flat gradient, Adam on this rank's 1/world of the flat
-    buffers, all-gather of the updated parameters; the buffers' length must be a multiple of exchange.world."""
+    buffers, all-gather of the updated parameters; the buffers' length must be a multiple of 4 * exchange.world (world slices,
+    each a whole number of the Adam kernel's 16-byte chunks: the library answers PC_ESHAPE on every rank, before the
+    reduce-scatter, for slices that are not)."""
     n = param.numel()
     if shard:
         if exchange is None:
@@ -465,8 +481,9 @@ def exchange_adam(exchange, param, grad, exp_avg, exp_avg_sq, step_count, t, sca
         for x, nm in ((param, "param"), (grad, "grad"), (exp_avg, "exp_avg"), (exp_avg_sq, "exp_avg_sq")):
             _req(x, torch.float32, nm, (n,))
         if n % exchange.world:
-            raise ValueError(f"exchange_adam(shard=True): {n} floats are not a multiple of the world size {exchange.world} "
-                             "(flatten_parameters(pad_multiple=world))")
+            raise ValueError(f"exchange_adam(shard=True): {n} floats are not a multiple of the world size {exchange.world}; pad "
+                             f"the flat buffers to a multiple of 4 * world = {4 * exchange.world} "
+                             "(flatten_parameters(pad_multiple=4 * world): 16-byte aligned slices)")
         _req(step_count, torch.int64, "step_count")
         plan = exchange.plan(shard=True)
         rc = _lib.lib().pc_exchange_adam_plan(ctypes.byref(plan), _p(param), _p(grad), _p(exp_avg), _p(exp_avg_sq), n, _p(step_count),
@@ -1115,7 +1132,8 @@ class PreparedJointStep:
             _req(x, torch.float32, nm, (nf,))
         _req(step_count, torch.int64, "step_count")
         if shard and (exchange is None or nf % exchange.world):
-            raise ValueError("run_epoch_dp(shard=True): an exchange, and flat buffers whose length is a multiple of its world size")
+            raise ValueError("run_epoch_dp(shard=True): an exchange, and flat buffers whose length is a multiple of its world size "
+                             "(padded to a multiple of 4 * world: flatten_parameters(pad_multiple=4 * world))")
         plan = exchange.plan(shard=bool(shard)) if exchange is not None else None
         rc = _lib.lib().pc_joint_train_epoch_plan(*self._tensors, _p(flat), _p(gflat), _p(exp_avg), _p(exp_avg_sq), nf, _p(step_count),
                                                   int(t_first), _p(scalars), *self._hyper,

@@ -356,7 +356,9 @@ class GraphedJointStep:
         reduce-scatter of the flat gradient, Adam on this rank's 1/world of the flat buffers, all-gather of the parameters)
         instead of an all-reduce and the whole dense Adam on every rank.  None = automatic: at NUM_TYPES > 512, where the two
         [NUM_TYPES,64] tables make the flat buffer megabytes (17.8 MB at config.py:27's 34800: the full update is 125 MB of
-        traffic per rank and step), when the exchange offers the pair."""
+        traffic per rank and step), when the exchange offers the pair.  The flat buffers are padded to a multiple of
+        4 * exchange.world floats (16-byte aligned slices); a checkpoint of the optimizer needs optimizer.gather_state(exchange)
+        on every rank before state_dict() (each rank keeps current moments for its slice only)."""
         from .product2vec import FusedAdam
         if not isinstance(optimizer, FusedAdam):
             raise TypeError("GraphedJointStep drives pc_adam_step / the fused step's Adam: pass a FusedAdam")
@@ -395,9 +397,10 @@ class GraphedJointStep:
             raise ValueError("shard_optimizer needs an exchange with the reduce-scatter / all-gather pair")
         self.shard_optimizer = bool(shard_optimizer)
         if exchange is not None:
-            # the slices of the sharded form are world equal parts of the flat buffers; a host-driven exchange finds the
-            # buffers by address
-            flat, gflat = model.flatten_parameters(pad_multiple=exchange.world if self.shard_optimizer else None)
+            # the slices of the sharded form are world equal parts of the flat buffers, each a multiple of 4 floats (the Adam
+            # kernel moves 16-byte chunks: a slice that starts off a 16-byte boundary is refused -- by every rank, before the
+            # reduce-scatter); a host-driven exchange finds the buffers by address
+            flat, gflat = model.flatten_parameters(pad_multiple=4 * exchange.world if self.shard_optimizer else None)
             if hasattr(exchange, "register"):
                 exchange.register(gflat)
                 exchange.register(flat)
@@ -525,7 +528,7 @@ def _graphed_run_epoch(self, loader, drop_last=False, max_steps=None):
         losses, steps = self.prepared.run_epoch_dp(pairs, loader._source, loader.step, flat, gflat, m, v, step_count, t_first,
                                                    scalars, self.exchange, drop_last=drop_last, dropout_offset=tt._dropout_step,
                                                    shard=self.shard_optimizer)
-        self.optimizer.advance(steps)
+        self.optimizer.advance(steps, exchange=self.exchange, shard=self.shard_optimizer)
     else:
         losses, steps = self.prepared.run_epoch(pairs, loader._source, loader.step, drop_last=drop_last, dropout_offset=tt._dropout_step)
     tt._dropout_step += steps

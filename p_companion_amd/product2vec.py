@@ -153,11 +153,14 @@ class FusedAdam(torch.optim.Optimizer):
         self.module = module
         super().__init__(list(module.parameters()), dict(lr=lr, betas=betas, eps=eps))
         self._state_ready = False
+        # the sharded optimizer (step(shard=True) / a sharded epoch call): (rank, world, floats per slice) as of the latest sharded
+        # step, and whether the moments of the OTHER ranks' slices are behind (only this rank's slice is updated)
+        self._shard = None
+        self._shard_stale = False
 
     def _ensure(self):
         flat, gflat = self.module.flatten_parameters()
-        if not self._state_ready or self.exp_avg.data_ptr() == 0 or self.exp_avg.numel() != flat.numel() \
-                or self.exp_avg.device != flat.device:
+        if not self._state_ready or self.exp_avg.data_ptr() == 0:
             self.exp_avg = ops.alloc(flat.numel(), torch.float32, flat.device, zero=True)
             self.exp_avg_sq = ops.alloc(flat.numel(), torch.float32, flat.device, zero=True)
             self.step_count = torch.zeros(1, dtype=torch.int64, device=flat.device)
@@ -168,15 +171,49 @@ class FusedAdam(torch.optim.Optimizer):
             # (fused_state()) -- the two-launch form then reads the device counter
             self._host_step = 0
             self._device_counter_only = False     # True once the device counter has been advanced behind the host's back
+        elif self.exp_avg.numel() != flat.numel() or self.exp_avg.device != flat.device:
+            self._follow(flat)
         return flat, gflat
+
+    def _follow(self, flat):
+        """The module's flat buffers are no longer the ones the moments were laid out for.  A change of the PADDING only
+        (flatten_parameters(pad_multiple=...) behind a load_state_dict(): what GraphedJointStep(shard_optimizer=True) does on
+        resume) carries moments, step counter and the host's step number over -- the real prefix is copied, the pad region stays
+        zero.  Anything else is an error once the optimizer has stepped or loaded a state: a silent fresh start would run every
+        later update with zero moments and the wrong bias corrections."""
+        n_real = sum(p.numel() for _, p in self.module._named_flat())
+        started = self._host_step != 0                 # (None: the device counter runs on its own -- steps have been taken)
+        if self.exp_avg.device != flat.device:
+            if started:
+                raise RuntimeError(f"FusedAdam: the module moved from {self.exp_avg.device} to {flat.device} after the optimizer "
+                                   "had stepped; its moments and step count would be lost (build a new optimizer and "
+                                   "load_state_dict() what this one's state_dict() returns)")
+            self._state_ready = False
+            self._ensure()
+            return
+        if flat.numel() < n_real or self.exp_avg.numel() < n_real:
+            raise RuntimeError(f"FusedAdam: flat buffers of {flat.numel()} floats (moments: {self.exp_avg.numel()}) cannot hold "
+                               f"the module's {n_real} parameters")
+        if started and self._shard is not None and self._shard_stale:
+            raise RuntimeError("FusedAdam: the flat buffers' padding changed while this rank holds current moments for its own "
+                               "slice only (sharded optimizer): call gather_state(exchange) on every rank first")
+        m, v = self.exp_avg, self.exp_avg_sq
+        self.exp_avg = ops.alloc(flat.numel(), torch.float32, flat.device, zero=True)
+        self.exp_avg_sq = ops.alloc(flat.numel(), torch.float32, flat.device, zero=True)
+        self.exp_avg[:n_real].copy_(m[:n_real])
+        self.exp_avg_sq[:n_real].copy_(v[:n_real])
+        self._shard, self._shard_stale = None, False              # (the slices are those of the new length from the next step on)
 
     @torch.no_grad()
     def step(self, closure=None, exchange=None, shard=False):
         """exchange (ops.Exchange, optional): a data-parallel replica's gradient exchange, issued from the same foreign call as
-        the update (pc_exchange_adam) -- the flat gradient buffer holds the replicas' mean afterwards.
+        the update (pc_exchange_adam) -- the flat gradient buffer holds the replicas' mean afterwards (shard=False).
         shard=True: the optimizer sharded over the replicas (pc_exchange_adam_plan: reduce-scatter, Adam on this rank's slice of
-        the flat buffers, all-gather of the parameters); the module's flat buffers must be padded to a multiple of the world
-        size (module.flatten_parameters(pad_multiple=exchange.world) before the first step)."""
+        the flat buffers, all-gather of the parameters).  The flat gradient buffer then holds the mean in THIS rank's slice only
+        (the other slices are unspecified), and only this rank's slice of the moments is current: gather_state(exchange) before
+        state_dict().  The Adam kernel moves 16-byte chunks, so every slice must be a multiple of 4 floats: pad the module's
+        flat buffers to a multiple of 4 * world (module.flatten_parameters(pad_multiple=4 * exchange.world) before the first
+        step); any other length is refused by every rank before a collective is issued."""
         flat, gflat = self._ensure()
         g = self.param_groups[0]
         if self._host_step is not None and flat.is_cuda and torch.cuda.is_current_stream_capturing():
@@ -187,33 +224,44 @@ class FusedAdam(torch.optim.Optimizer):
             self._host_step = None
             self._device_counter_only = True
         if self._host_step is not None:
-            self._host_step += 1
+            # (counted once the call has been accepted: a refused update leaves the host where the device counter is)
+            t = self._host_step + 1
             if exchange is not None:
-                ops.exchange_adam(exchange, flat, gflat, self.exp_avg, self.exp_avg_sq, self.step_count, self._host_step,
+                ops.exchange_adam(exchange, flat, gflat, self.exp_avg, self.exp_avg_sq, self.step_count, t,
                                   self.scalars, g["lr"], g["betas"], g["eps"], shard=shard)
-                return
-            ops.adam_step_at(flat, gflat, self.exp_avg, self.exp_avg_sq, self.step_count, self._host_step, g["lr"],
-                             g["betas"], g["eps"])
+                self._sharded_step(exchange, shard, flat.numel())
+            else:
+                ops.adam_step_at(flat, gflat, self.exp_avg, self.exp_avg_sq, self.step_count, t, g["lr"], g["betas"], g["eps"])
+            self._host_step = t
             return
         if exchange is not None:
             ops.exchange_adam(exchange, flat, gflat, self.exp_avg, self.exp_avg_sq, self.step_count, 0, self.scalars, g["lr"],
                               g["betas"], g["eps"], shard=shard)
+            self._sharded_step(exchange, shard, flat.numel())
             return
         ops.adam_step(flat, gflat, self.exp_avg, self.exp_avg_sq, self.step_count, self.scalars, g["lr"],
                       g["betas"], g["eps"])
 
+    def _sharded_step(self, exchange, shard, n):
+        """Behind a step over an exchange: a sharded one updated this rank's slice of the moments only."""
+        if shard:
+            world = int(exchange.world)
+            self._shard = (int(exchange.rank), world, n // world)
+            self._shard_stale = world > 1
+
     def riding_state(self):
         """For a step that applies this optimizer's update in its own last gradient launch (Product2Vec.train_step_indexed(
         optimizer=...): pc_p2v_train_step_unique_adam): the flat buffers, the hyper-parameters and the step number t of THIS
-        update.  Counts the step (the caller must not call step() for it).  None when the host does not know the step number
-        (a captured graph / a fused joint step has advanced the device counter on its own): the caller then steps separately."""
+        update.  Does NOT count the step: the caller reports it with advance(1) once the launch that carries the update has been
+        accepted (and must not call step() for it) -- a call refused in between leaves the step number where the device counter
+        and the moments are.  None when the host does not know the step number (a captured graph / a fused joint step has
+        advanced the device counter on its own): the caller then steps separately."""
         flat, gflat = self._ensure()
         if self._host_step is None or (flat.is_cuda and torch.cuda.is_current_stream_capturing()):
             return None
-        self._host_step += 1
         g = self.param_groups[0]
         return {"param": flat, "grad": gflat, "exp_avg": self.exp_avg, "exp_avg_sq": self.exp_avg_sq, "step_count": self.step_count,
-                "t": self._host_step, "lr": g["lr"], "betas": g["betas"], "eps": g["eps"]}
+                "t": self._host_step + 1, "lr": g["lr"], "betas": g["betas"], "eps": g["eps"]}
 
     def epoch_state(self):
         """What an epoch-in-one-call of a replica (ops.PreparedJointStep.run_epoch_dp) needs: the flat moment buffers, the device
@@ -223,9 +271,13 @@ class FusedAdam(torch.optim.Optimizer):
         t_first = self._host_step + 1 if self._host_step is not None else 0
         return self.exp_avg, self.exp_avg_sq, self.step_count, self.scalars, t_first
 
-    def advance(self, steps):
+    def advance(self, steps, exchange=None, shard=False):
+        """Report `steps` updates that another call applied over this optimizer's buffers (riding_state() / epoch_state());
+        exchange / shard: as given to that call (a sharded epoch leaves only this rank's slice of the moments current)."""
         if self._host_step is not None:
             self._host_step += int(steps)
+        if exchange is not None and int(steps) > 0:
+            self._sharded_step(exchange, shard, self.exp_avg.numel())
 
     def zero_grad(self, set_to_none=False):
         _, gflat = self._ensure()
@@ -263,7 +315,14 @@ class FusedAdam(torch.optim.Optimizer):
         """The dict torch.optim.Adam.state_dict() would return for the same parameters after the same steps
         (train.py:66 saves it as 'optimizer_state_dict'): per-parameter 'step' / 'exp_avg' / 'exp_avg_sq' sliced out
         of the flat moment buffers, parameters without a gradient (the frozen product table, p_companion.py:26-29)
-        hold no state, like in torch.  torch.optim.Adam(model.parameters()).load_state_dict() reads it."""
+        hold no state, like in torch.  torch.optim.Adam(model.parameters()).load_state_dict() reads it.
+        A sharded optimizer (step(shard=True)) holds current moments for this rank's slice only: RuntimeError until
+        gather_state(exchange) has brought the other slices in -- zeros are never exported as moments."""
+        if self._shard is not None and self._shard_stale:
+            rank, world, _ = self._shard
+            raise RuntimeError(f"FusedAdam.state_dict(): the optimizer is sharded over {world} replicas and rank {rank} holds "
+                               "current moments for its own slice only; call gather_state(exchange) on EVERY rank first "
+                               "(a collective: it is not run from here, where one rank may be alone)")
         n = len(self.param_groups[0]["params"])
         group = {"lr": self.param_groups[0]["lr"], "betas": tuple(self.param_groups[0]["betas"]),
                  "eps": self.param_groups[0]["eps"], "weight_decay": 0, "amsgrad": False, "maximize": False,
@@ -278,9 +337,30 @@ class FusedAdam(torch.optim.Optimizer):
                               "exp_avg_sq": self.exp_avg_sq[off:off + m].view(shape).clone()}
         return {"state": state, "param_groups": [group]}
 
+    @torch.no_grad()
+    def gather_state(self, exchange):
+        """The sharded optimizer's checkpoint collective: all-gather of exp_avg and exp_avg_sq over `exchange` (the one the steps
+        ran over), after which every rank holds the whole state and state_dict() works -- until the next sharded step.  EVERY
+        rank must call it (at the same point of the program, like a step).  Deliberately not part of state_dict(): a checkpoint
+        written by rank 0 alone must not turn into a collective the other ranks never enter.  Nothing to do (and no collective)
+        for an optimizer that has not taken a sharded step -- the same on every rank."""
+        self._ensure()
+        if self._shard is None:
+            return
+        rank, world, length = self._shard
+        if (int(exchange.rank), int(exchange.world)) != (rank, world) or length * world != self.exp_avg.numel():
+            raise ValueError(f"FusedAdam.gather_state: the optimizer stepped as rank {rank} of {world} over slices of {length} "
+                             f"floats; the exchange is rank {exchange.rank} of {exchange.world}")
+        for buf in (self.exp_avg, self.exp_avg_sq):
+            if hasattr(exchange, "register"):                      # (a host-driven exchange finds its buffers by address)
+                exchange.register(buf)
+            exchange.all_gather_(buf)
+        self._shard_stale = False
+
     def load_state_dict(self, state_dict):
         """Accepts torch.optim.Adam's layout (also what state_dict() above emits): a resumed run continues with the
-        saved moments and step count."""
+        saved moments and step count.  On a sharded optimizer too: every rank loads the whole state and steps on from its
+        own slice."""
         groups = state_dict["param_groups"]
         if len(groups) != 1:
             raise ValueError("FusedAdam: one parameter group expected")
@@ -314,6 +394,7 @@ class FusedAdam(torch.optim.Optimizer):
         # a prepared fused step (fused_state()) or a captured graph keeps advancing the DEVICE counter: the host's copy would
         # drift from it after the next such step, so it stays out of the picture once that has happened
         self._host_step = None if self._device_counter_only else loaded
+        self._shard_stale = False                  # (every slice holds the loaded state)
 
 
 class _FlatParamsMixin:
@@ -603,7 +684,9 @@ class Product2Vec(nn.Module, _FlatParamsMixin):
         out = ops.p2v_train_step(params, grads, table, batch["anchor_idx"], batch["positive_idx"],
                                  batch["negative_idx"], nbr, float(self.config.MARGIN), profile=profile,
                                  sync_reduce=sync_reduce, adam=adam, structs=structs)
-        if optimizer is not None and adam is None:
+        if adam is not None:
+            optimizer.advance(1)                   # (only now: the step that carried update number adam["t"] has been accepted)
+        elif optimizer is not None:
             optimizer.step()
         after = batch.get("_after_step")           # the device loader's look-ahead builder, queued behind this step's launches
         if after is not None:

@@ -105,7 +105,9 @@ def hot_set_check(rank, dev, bpg, table):
 def sharded_optimizer_check(rank, dev):
     """ABI 8 at world 2: the joint step's optimizer sharded over the replicas (reduce-scatter of the flat gradient, Adam on this
     rank's half of the flat buffers, all-gather of the parameters) against the all-reduce + whole-Adam form -- the same
-    parameters bit for bit (two addends commute), moments untouched outside this rank's half, both ranks identical."""
+    parameters bit for bit (two addends commute), moments untouched outside this rank's half, both ranks identical.  Then the
+    checkpoint: state_dict() refuses while the other half's moments are behind, gather_state(exchange) (both ranks) makes it the
+    all-reduce twin's state_dict entry for entry, and fresh twins resumed from the two stay bit-identical for two more steps."""
     from types import SimpleNamespace
     import torch
     import torch.distributed as dist
@@ -162,7 +164,49 @@ def sharded_optimizer_check(rank, dev):
                        and int(o_a.step_count) == int(o_b.step_count) == 7),
                same=bool(same), moments_outside_own_half=float(other.abs().max()), ranks_equal=bool(torch.equal(both[0], both[1])),
                steps=int(o_b.step_count), flat=int(flat_b.numel()), real=int(n_real))
+    # ---- the checkpoint of a sharded optimizer.  (No assert from here on: a rank that raised would leave its peer in a collective.)
+    try:
+        o_b.state_dict()
+        refused = False
+    except RuntimeError as e:
+        refused = "gather_state" in str(e)                            # this rank's moments cover its half only: nothing is exported
+    o_b.gather_state(g_b.exchange)                                    # the collective, both ranks: all-gather of both moments
+    sd_a, sd_b = o_a.state_dict(), o_b.state_dict()
+    out.update(state_dict_refused_before_gather=bool(refused), state_dict_equal=_same_state(sd_a, sd_b),
+               state_entries=len(sd_b["state"]))
+    # a fresh sharded twin resumes from it, a fresh all-reduce twin from the all-reduce run's: two more steps, the same bits
+    m_c, o_c, g_c, ld_c = make(True)
+    m_d, o_d, g_d, ld_d = make(False)
+    m_c.load_state_dict({k: t.detach().clone() for k, t in m_b.state_dict().items()})
+    m_d.load_state_dict({k: t.detach().clone() for k, t in m_a.state_dict().items()})
+    o_c.load_state_dict(sd_b)
+    o_d.load_state_dict(sd_a)
+    resumed, more = True, 0
+    for bc, bd in zip(ld_c, ld_d):
+        if bc["query_idx"].numel() != B:
+            continue
+        lc, _ = g_c(bc)
+        l_d, _ = g_d(bd)
+        resumed = resumed and torch.equal(lc, l_d)
+        more += 1
+        if more == 2:
+            break
+    for (k, pc), (_, pd) in zip(m_c.named_parameters(), m_d.named_parameters()):
+        resumed = resumed and torch.equal(pc, pd)
+    resumed = resumed and torch.equal(o_c.exp_avg[lo:hi], o_d.exp_avg[lo:hi]) and torch.equal(o_c.exp_avg_sq[lo:hi], o_d.exp_avg_sq[lo:hi])
+    out.update(resumed_equal=bool(resumed), resumed_steps=[int(o_c.step_count), int(o_d.step_count)])
+    out["ok"] = bool(out["ok"] and out["state_dict_refused_before_gather"] and out["state_dict_equal"] and out["state_entries"] > 0
+                     and out["resumed_equal"] and out["resumed_steps"] == [9, 9])
     return out
+
+
+def _same_state(a, b):
+    """Two optimizer state dicts, entry for entry (step included) with torch.equal."""
+    import torch
+    if a["param_groups"] != b["param_groups"] or sorted(a["state"]) != sorted(b["state"]):
+        return False
+    return all(sa.keys() == b["state"][i].keys() and all(torch.equal(sa[k], b["state"][i][k]) for k in sa)
+               for i, sa in a["state"].items())
 
 
 if __name__ == "__main__":

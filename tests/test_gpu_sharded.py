@@ -129,6 +129,10 @@ def test_sharded_step_world2_on_one_card(world2_job):
         so = r["sharded_optimizer"]
         assert so["ok"] and so["same"] and so["moments_outside_own_half"] == 0.0 and so["ranks_equal"], so
         assert so["steps"] == 7 and so["flat"] == so["real"]
+        # its checkpoint: refused while this rank's moments cover its half only; after gather_state() the all-reduce twin's
+        # state_dict entry for entry; fresh twins resumed from the two run two more steps to the same bits
+        assert so["state_dict_refused_before_gather"] and so["state_dict_equal"] and so["state_entries"] > 0, so
+        assert so["resumed_equal"] and so["resumed_steps"] == [9, 9], so
         # the replicated hot set under the sharded table at world 2: same rows, same step, shorter request lists
         hs = r["hot_set"]
         assert hs["ok"] and hs["same"] and hs["served"] == hs["request_slots_saved"] > 0 and hs["table_rows"] == 2 * hs["capacity"] + 512, hs
