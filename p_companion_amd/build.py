@@ -86,12 +86,39 @@ def code_objects(tmp, what="spill gate"):
 
 
 def code_object_digests():
-    """{unit: sha256 of its unbundled gfx950 code object}: equal digests before and after a host-only change say that no
-    device code moved."""
+    """{unit: sha256 of its unbundled gfx950 code object}, every byte of it: the instructions, but also the metadata note, the
+    symbol and string tables and what the compiler derives from the source's path and line numbers.  Equal digests show that
+    nothing in a unit's device image changed; unequal digests show nothing about its instructions (a helper that moves
+    into a header, a renamed variable or another checkout directory changes them) -- kernel_text_digests() answers that."""
     import hashlib
     import tempfile
     with tempfile.TemporaryDirectory() as tmp:
         return {unit: hashlib.sha256(open(co, "rb").read()).hexdigest() for unit, co in code_objects(tmp, "digests")}
+
+
+def kernel_text_digests():
+    """{symbol: sha256 of its instruction text} for every function symbol in the code objects' text sections (the kernels: this
+    build inlines every device function).  The text is llvm-objdump's disassembly of the symbol without addresses, encoding
+    comments and file names, so it depends on the instructions and their operands alone: equal digests under the same name
+    before and after a change say that the kernel executes what it executed."""
+    import hashlib
+    import tempfile
+    objdump = os.path.join(LLVM_BIN, "llvm-objdump")
+    if not os.path.exists(objdump):
+        raise RuntimeError(f"text digests unavailable: llvm-objdump missing under {LLVM_BIN}")
+    out = {}
+    with tempfile.TemporaryDirectory() as tmp:
+        for unit, co in code_objects(tmp, "text digests"):
+            dis = subprocess.run([objdump, "-d", co], check=True, capture_output=True, text=True).stdout
+            name, text = None, None
+            for ln in dis.splitlines() + ["0 <>:"]:               # (the sentinel closes the last symbol)
+                if ln[:1].isalnum() and ln.endswith(">:"):        # "0000000000001900 <symbol>:"
+                    if name:
+                        out[name] = text.hexdigest()
+                    name, text = ln[ln.index("<") + 1:-2], hashlib.sha256()
+                elif name and ln[:1].isspace() and ln.strip():    # "\tinstruction operands    // address: encoding"
+                    text.update((" ".join(ln.split("//")[0].split()) + "\n").encode())
+    return out
 
 
 def kernel_resources():
@@ -135,5 +162,8 @@ if __name__ == "__main__":
     if "--digests" in sys.argv:
         for unit, h in sorted(code_object_digests().items()):
             print(h, unit)
+    if "--text-digests" in sys.argv:
+        for name, h in sorted(kernel_text_digests().items()):
+            print(h, name)
     bad = spilling_kernels()
     print("kernels with scratch:", bad if bad else "none")

@@ -11,37 +11,7 @@
 // saved probabilities (eval only), and the scores are RECOMPUTED instead of kept in LDS -- pass 1 takes the maximum,
 // pass 2 the exp-sum, pass 3 the weighted sums -- so any degree works (the key rows are L2 hits after the first pass).
 #include "common.h"
-
-// lane = 16 g + l owns dims [DL l, DL l + DL) of row n0 + g (DL = D / 16: 8 or 16), as in attn_core_fwd4_kernel
-template <int DL> struct XV { float v[DL]; };
-template <int DL> __device__ __forceinline__ XV<DL> xv_load(const float* p) {
-    XV<DL> r;
-#pragma unroll
-    for (int i = 0; i < DL / 4; i++) {
-        const float4 t = *reinterpret_cast<const float4*>(p + 4 * i);
-        r.v[4 * i] = t.x; r.v[4 * i + 1] = t.y; r.v[4 * i + 2] = t.z; r.v[4 * i + 3] = t.w;
-    }
-    return r;
-}
-template <int DL> __device__ __forceinline__ void xv_store(float* p, const XV<DL>& r) {
-#pragma unroll
-    for (int i = 0; i < DL / 4; i++) *reinterpret_cast<float4*>(p + 4 * i) = make_float4(r.v[4 * i], r.v[4 * i + 1], r.v[4 * i + 2], r.v[4 * i + 3]);
-}
-// four values per lane summed over the 16 lanes of a row group: afterwards lane l holds the total of value (l >> 2), the
-// same bits in the four lanes of a head
-__device__ __forceinline__ float export_heads_reduce16(float v0, float v1, float v2, float v3, int l) {
-    const bool hi8 = (l & 8) != 0, hi4 = (l & 4) != 0;
-    float a = hi8 ? v2 : v0, b = hi8 ? v3 : v1;
-    const float sa = hi8 ? v0 : v2, sb = hi8 ? v1 : v3;
-    a += __shfl_xor(sa, 8, 64);
-    b += __shfl_xor(sb, 8, 64);
-    float k = hi4 ? b : a;
-    const float s = hi4 ? a : b;
-    k += __shfl_xor(s, 4, 64);
-    k += __shfl_xor(k, 2, 64);
-    k += __shfl_xor(k, 1, 64);
-    return k;
-}
+#include "wave_rows.h"        // LD<DL>, ld_load / ld_store, heads_reduce16, heads_fold4 (the lane layout of attn_core_fwd4_kernel)
 
 // One wave per node of the chunk [first, first + rows).  qt [rows,HEADS,D] (unscaled Wk_h^T q_h) in; c [rows,HEADS,D],
 // sp [rows,HEADS] out (zeros for a node without neighbours: the select kernel replaces its row afterwards).
@@ -60,30 +30,30 @@ __global__ __launch_bounds__(256) void export_attn_core_kernel(const float* __re
     const int64_t node = first + b;
     const int lo = rowptr[node], N = rowptr[node + 1] - lo;
     if (N <= 0) {
-        const XV<DL> z = {};
-        xv_store<DL>(c + ((size_t)b * PC_HEADS + g) * D + DL * l, z);
+        const LD<DL> z = {};
+        ld_store<DL>(c + ((size_t)b * PC_HEADS + g) * D + DL * l, z);
         if (lane < PC_HEADS) sp[(size_t)b * PC_HEADS + lane] = 0.f;
         return;
     }
     const int32_t* ids = col + lo;
     const float scale = DL == 8 ? 0.17677669529663687f : 0.125f;       // 1/sqrt(head dim)
-    XV<DL> qv[PC_HEADS];
+    LD<DL> qv[PC_HEADS];
 #pragma unroll
     for (int hh = 0; hh < PC_HEADS; hh++) {
-        qv[hh] = xv_load<DL>(qt + ((size_t)b * PC_HEADS + hh) * D + DL * l);
+        qv[hh] = ld_load<DL>(qt + ((size_t)b * PC_HEADS + hh) * D + DL * l);
 #pragma unroll
         for (int d = 0; d < DL; d++) qv[hh].v[d] *= scale;
     }
     // one trip: the rows n0 + 4u + g (u < UF) and, in lane l, the score of head l >> 2 of each.  The node's ids are read 64
     // at a time into a register and handed out by shuffles; a dead slot loads the node's first row and is masked afterwards.
     int idreg = 0;
-    auto trip = [&](int n0, XV<DL>* yu, float* s) {
+    auto trip = [&](int n0, LD<DL>* yu, float* s) {
         if ((n0 & 63) == 0) idreg = n0 + lane < N ? ids[n0 + lane] : ids[0];
 #pragma unroll
         for (int u = 0; u < UF; u++) {
             const int n = n0 + 4 * u + g;
             const int row = __shfl(idreg, (n & 63), 64);
-            yu[u] = xv_load<DL>(e1 + (size_t)row * D + DL * l);
+            yu[u] = ld_load<DL>(e1 + (size_t)row * D + DL * l);
         }
 #pragma unroll
         for (int u = 0; u < UF; u++) {
@@ -95,13 +65,13 @@ __global__ __launch_bounds__(256) void export_attn_core_kernel(const float* __re
                 for (int d = 0; d < DL; d++) t += qv[hh].v[d] * yu[u].v[d];
                 p[hh] = t;
             }
-            s[u] = export_heads_reduce16(p[0], p[1], p[2], p[3], l);
+            s[u] = heads_reduce16(p[0], p[1], p[2], p[3], l);
         }
     };
     // pass 1: maximum of head l >> 2
     float m = -INFINITY;
     for (int n0 = 0; n0 < N; n0 += TRIP) {
-        XV<DL> yu[UF];
+        LD<DL> yu[UF];
         float s[UF];
         trip(n0, yu, s);
 #pragma unroll
@@ -113,7 +83,7 @@ __global__ __launch_bounds__(256) void export_attn_core_kernel(const float* __re
     // pass 2: exp-sum of head l >> 2 (the recomputed scores are the same bits as in pass 1)
     float sum = 0.f;
     for (int n0 = 0; n0 < N; n0 += TRIP) {
-        XV<DL> yu[UF];
+        LD<DL> yu[UF];
         float s[UF];
         trip(n0, yu, s);
 #pragma unroll
@@ -125,14 +95,14 @@ __global__ __launch_bounds__(256) void export_attn_core_kernel(const float* __re
     const float inv = 1.0f / sum;
     // pass 3: c[h] = sum_n p_{n,h} y_n over this lane's dims for all four heads (head hh's probability of the group's row
     // comes from lane 4 hh of the group), sp of head l >> 2
-    XV<DL> o[PC_HEADS];
+    LD<DL> o[PC_HEADS];
 #pragma unroll
     for (int hh = 0; hh < PC_HEADS; hh++)
 #pragma unroll
         for (int d = 0; d < DL; d++) o[hh].v[d] = 0.f;
     float spa = 0.f;
     for (int n0 = 0; n0 < N; n0 += TRIP) {
-        XV<DL> yu[UF];
+        LD<DL> yu[UF];
         float s[UF];
         trip(n0, yu, s);
 #pragma unroll
@@ -151,21 +121,9 @@ __global__ __launch_bounds__(256) void export_attn_core_kernel(const float* __re
     spa += __shfl_xor(spa, 16, 64);
     spa += __shfl_xor(spa, 32, 64);
     if (lane < 16 && (l & 3) == 0) sp[(size_t)b * PC_HEADS + (l >> 2)] = spa;
-    // fold the four row groups: lane group g ends with head g (as attn_core_fwd4_kernel)
-    const bool hi32 = (lane & 32) != 0, hi16 = (lane & 16) != 0;
-    XV<DL> out;
-#pragma unroll
-    for (int d = 0; d < DL; d++) {
-        float a = hi32 ? o[2].v[d] : o[0].v[d], bb = hi32 ? o[3].v[d] : o[1].v[d];
-        const float sa = hi32 ? o[0].v[d] : o[2].v[d], sb = hi32 ? o[1].v[d] : o[3].v[d];
-        a += __shfl_xor(sa, 32, 64);
-        bb += __shfl_xor(sb, 32, 64);
-        float k = hi16 ? bb : a;
-        const float s2 = hi16 ? a : bb;
-        k += __shfl_xor(s2, 16, 64);
-        out.v[d] = k;
-    }
-    xv_store<DL>(c + ((size_t)b * PC_HEADS + g) * D + DL * l, out);
+    // the four row groups fold: lane group g ends with head g
+    const LD<DL> out = heads_fold4<DL>(o[0], o[1], o[2], o[3], (lane & 32) != 0, (lane & 16) != 0);
+    ld_store<DL>(c + ((size_t)b * PC_HEADS + g) * D + DL * l, out);
 }
 
 // out[first + r] = e1[first + r] for the chunk's nodes without co-view out-neighbours (one float4 per thread)

@@ -31,6 +31,7 @@
 // Operands are fetched with a permuted k order (lanes 0-31 take k = 8j..8j+3, lanes 32-63
 // k = 8j+4..8j+7, identically for A and W) so one ds_read_b128 feeds four MFMAs.
 #include "common.h"
+#include "lds_dma.h"          // dma16, lds_sync, PC_SPLIT / PC_MFMA
 #include "mfma16.h"
 
 #define PLD 36          // row stride (floats) of the per-wave epilogue transposition patch
@@ -39,18 +40,6 @@
 int gemm_nt_tiles(const SegInfo& si) { return si.tile0[PC_MAX_SEG]; }
 
 __device__ __attribute__((aligned(64))) float pc_zero_chunk[16];   // source of every zero-filled 16-B chunk
-
-typedef __attribute__((address_space(3))) void* lptr_t;
-
-// 64 lanes x 16 B from per-lane global addresses to LDS [lds_addr + 16 * lane].  In-order with every
-// other vector-memory operation of the wave (vmcnt), so compiler-placed waits stay correct (at worst
-// they wait for this too); the data is visible after s_waitcnt vmcnt(0) + a workgroup barrier.
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Winline-asm"
-__device__ __forceinline__ void dma16(const float* gsrc, unsigned lds_addr) {
-    asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(gsrc), "s"(lds_addr) : "memory", "m0");
-}
-#pragma clang diagnostic pop
 
 // C and aux are streams (written / read once per launch, far larger than the 4 MB L2 of an XCD): moved
 // with the non-temporal hint they do not push W and the A rows in flight out of L2 (measured on the dZ2
@@ -76,14 +65,6 @@ __device__ __forceinline__ float4 load_stream(const float* p) {
     typedef float v4f __attribute__((ext_vector_type(4)));
     const v4f v = __builtin_nontemporal_load(reinterpret_cast<const v4f*>(p));
     return make_float4(v.x, v.y, v.z, v.w);
-}
-
-// LDS-only hand-off between waves: no global-memory fence (a __syncthreads() would also wait for
-// this wave's outstanding C stores and for the next stage's DMA)
-__device__ __forceinline__ void lds_sync() {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
 }
 
 // NWM x NWN waves of 64x64 each: BM = 64*NWM rows, BN = 64*NWN columns.
@@ -247,16 +228,6 @@ __global__ __launch_bounds__(64 * NWM * NWN, WPS) void gemm_nt_kernel(NtArgs a, 
 #define PC_FRAG(PTR, OFF) make_float4(__int_as_float(a.M), __int_as_float(a.N), __int_as_float(a.K), __int_as_float(a.lda))
 #else
 #define PC_FRAG(PTR, OFF) (*reinterpret_cast<const float4*>((PTR) + (OFF)))
-#endif
-#if defined(PC_EXP_NO_SPLIT) || defined(PC_EXP_NO_LDSREAD)
-#define PC_SPLIT(LO, HI) Split3{__builtin_bit_cast(bf16x8, LO), __builtin_bit_cast(bf16x8, HI), __builtin_bit_cast(bf16x8, LO)}
-#else
-#define PC_SPLIT(LO, HI) split3(LO, HI)
-#endif
-#if defined(PC_EXP_NO_MFMA)
-#define PC_MFMA(A, B, C) ([&]() { asm volatile("" ::"v"(A), "v"(B)); return C; }())
-#else
-#define PC_MFMA(A, B, C) mfma_bf16(A, B, C)
 #endif
             Split3 sa[2];
 #pragma unroll
@@ -860,11 +831,6 @@ __device__ __forceinline__ void chain16_body(const NtArgs& a0, const NtArgs& a1,
     const int tid = threadIdx.x, lane = tid & 63, ci = lane & 15, rh = lane >> 4;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int M = a0.M;
-    auto lds_sync = [&]() {
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-    };
     // a PLAIN stage over the 16 x 128 LDS tile `src`: wave w owns the column blocks 2 w, 2 w + 1
     // (biases and per-row bias scales are requested at entry with the weight fragments: a load in an epilogue is one more
     // L2 round trip on the critical path of a kernel that is nothing but such round trips)
@@ -1014,11 +980,6 @@ __global__ __launch_bounds__(256) void gemm_nt_chain16_d256_kernel(NtChain c) {
     const NtArgs& a0 = c.a[0];
     const NtArgs& a1 = c.a[1];
     const int row0 = blockIdx.x * 16, M = a0.M;
-    auto lds_sync = [&]() {
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-    };
     // PLAIN over the 16 x 256 LDS tile `src`: wave w owns the column blocks 4 w .. 4 w + 3, fragments one block ahead
     // (two blocks' fragments in flight: 128 VGPRs; the biases with them)
     auto plain = [&](const NtArgs& a, const float* src, float* keep) {

@@ -15,6 +15,7 @@
 #include <type_traits>
 #include "common.h"
 #include "bn_finalize.h"
+#include "lds_dma.h"          // dma16, lds_sync, PC_SPLIT / PC_MFMA
 
 #define TM 128
 #define TK 32
@@ -177,7 +178,7 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_group_kernel(TnGroup g) {
 // once per row tile: 2x the traffic for a 256x256 gradient, and these products sit near the
 // HBM roofline at the fp32 MFMA rate).  Wave grid WO x WI, each wave TO x TI MFMA tiles.
 //   <2,4,4,2> 256x256 (dW3)   <2,4,2,2> 128x256 (dW5)   <4,2,2,2> 256x128 (dW0, dW_kv)
-// The operands go global -> LDS directly (global_load_lds_dwordx4, see gemm_nt.hip): the stage is
+// The operands go global -> LDS directly (dma16, lds_dma.h): the stage is
 // [TK rows][NO | NI] row-major exactly as the rows lie in HBM, so one wave instruction drops 1 KB
 // of consecutive row floats and the MFMA fragments are conflict-free ds_read_b32 (32 consecutive
 // floats per half-wave).  The fused loaders run IN PLACE on the landed stage:
@@ -185,19 +186,7 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_group_kernel(TnGroup g) {
 //   ZPRO  Z' = scale_s * (Z - m (c1_s + (H - mean_s) invstd_s c2_s))  (dW0: BatchNorm backward of dZ1,
 //         H = H0 staged beside Z)
 // db is folded from the Z fragments the wi == 0 waves read anyway.
-typedef __attribute__((address_space(3))) void* tn_lptr_t;
 __device__ __attribute__((aligned(64))) float pc_tn_zero_chunk[16];
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Winline-asm"
-__device__ __forceinline__ void tn_dma16(const float* gsrc, unsigned lds_addr) {
-    asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(gsrc), "s"(lds_addr) : "memory", "m0");
-}
-#pragma clang diagnostic pop
-__device__ __forceinline__ void tn_lds_sync() {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-}
 
 // halves == 2 (round 4: dW3): ONE launch computes the two NO-wide halves of a 2 NO-wide gradient over nsplit row slices each.
 // Workgroups b and b + 8 -- the same XCD: blockIdx round-robins over the eight -- take the two halves of ONE row slice, so the
@@ -243,7 +232,7 @@ __global__ __launch_bounds__(64 * WO * WI, WO * WI / 4) void gemm_tn8_kernel(TnA
     const int r_begin = split * rows_per_split;
     const int r_end = min(a.R, r_begin + rows_per_split);
     const float* const zsrc0 = pc_tn_zero_chunk;
-    const unsigned lds0 = (unsigned)(uintptr_t)(tn_lptr_t)&smem[0];
+    const unsigned lds0 = (unsigned)(uintptr_t)(lptr_t)&smem[0];
     if constexpr (RIDER) {                                       // (uniform: scalar compares on the kernel arguments)
         int rid = -1;
 #pragma unroll
@@ -287,14 +276,14 @@ __global__ __launch_bounds__(64 * WO * WI, WO * WI / 4) void gemm_tn8_kernel(TnA
         for (int j = 0; j < JZ; j++) {
             const int r = r0 + zr[j];
             const bool v = r < r_end && zc[j] < a.No;
-            tn_dma16(v ? a.Z + (size_t)r * a.ldz + zc[j] : zsrc0, base + zd[j]);
-            if (ZPRO) tn_dma16(v ? a.zaux + (size_t)r * a.ldzaux + zc[j] : zsrc0, base + ZF * 4 + zd[j]);
+            dma16(v ? a.Z + (size_t)r * a.ldz + zc[j] : zsrc0, base + zd[j]);
+            if (ZPRO) dma16(v ? a.zaux + (size_t)r * a.ldzaux + zc[j] : zsrc0, base + ZF * 4 + zd[j]);
         }
 #pragma unroll
         for (int j = 0; j < JA; j++) {
             const int r = r0 + ar[j];
             const bool v = r < r_end && ac[j] < a.Ni && gidx[j] >= 0;
-            tn_dma16(v ? a.A + (size_t)gidx[j] * a.lda + ac[j] : zsrc0, base + (ZPRO ? 2 : 1) * ZF * 4 + ad[j]);
+            dma16(v ? a.A + (size_t)gidx[j] * a.lda + ac[j] : zsrc0, base + (ZPRO ? 2 : 1) * ZF * 4 + ad[j]);
         }
     };
 
@@ -410,7 +399,7 @@ __global__ __launch_bounds__(64 * WO * WI, WO * WI / 4) void gemm_tn8_kernel(TnA
         }
 #endif
         float* stage = smem + cur * STAGE;
-        if (APRO || ZPRO) { transform(stage, r_begin + c * TKC); tn_lds_sync(); }
+        if (APRO || ZPRO) { transform(stage, r_begin + c * TKC); lds_sync(); }
         const float* Zs = stage + fz;
         const float* As = stage + (ZPRO ? 2 : 1) * ZF + fa;
 #pragma unroll
@@ -424,23 +413,13 @@ __global__ __launch_bounds__(64 * WO * WI, WO * WI / 4) void gemm_tn8_kernel(TnA
 #else
 #define PC_TNV(PTR, OFF) (PTR)[OFF]
 #endif
-#if defined(PC_EXP_NO_SPLIT) || defined(PC_EXP_NO_LDSREAD)
-#define PC_TNSPLIT(LO, HI) Split3{__builtin_bit_cast(bf16x8, LO), __builtin_bit_cast(bf16x8, HI), __builtin_bit_cast(bf16x8, LO)}
-#else
-#define PC_TNSPLIT(LO, HI) split3(LO, HI)
-#endif
-#if defined(PC_EXP_NO_MFMA)
-#define PC_TNMFMA(A, B, C) ([&]() { asm volatile("" ::"v"(A), "v"(B)); return C; }())
-#else
-#define PC_TNMFMA(A, B, C) mfma_bf16(A, B, C)
-#endif
             Split3 sx[TI];
 #pragma unroll
             for (int j = 0; j < TI; j++) {
                 float v[8];
 #pragma unroll
                 for (int t = 0; t < 8; t++) v[t] = PC_TNV(As, (16 * g + t) * ARS + xo[j]);
-                sx[j] = PC_TNSPLIT(make_float4(v[0], v[1], v[2], v[3]), make_float4(v[4], v[5], v[6], v[7]));
+                sx[j] = PC_SPLIT(make_float4(v[0], v[1], v[2], v[3]), make_float4(v[4], v[5], v[6], v[7]));
             }
 #pragma unroll
             for (int i = 0; i < TO; i++) {
@@ -448,8 +427,8 @@ __global__ __launch_bounds__(64 * WO * WI, WO * WI / 4) void gemm_tn8_kernel(TnA
 #pragma unroll
                 for (int t = 0; t < 8; t++) v[t] = PC_TNV(Zs, (16 * g + t) * ZRS + zo[i]);
                 zsum[i] += ((v[0] + v[1]) + (v[2] + v[3])) + ((v[4] + v[5]) + (v[6] + v[7]));
-                const Split3 sz = PC_TNSPLIT(make_float4(v[0], v[1], v[2], v[3]), make_float4(v[4], v[5], v[6], v[7]));
-#define PC_TERM(PZ, PX) _Pragma("unroll") for (int j = 0; j < TI; j++) acc[i][j] = PC_TNMFMA(sz.PZ, sx[j].PX, acc[i][j]);
+                const Split3 sz = PC_SPLIT(make_float4(v[0], v[1], v[2], v[3]), make_float4(v[4], v[5], v[6], v[7]));
+#define PC_TERM(PZ, PX) _Pragma("unroll") for (int j = 0; j < TI; j++) acc[i][j] = PC_MFMA(sz.PZ, sx[j].PX, acc[i][j]);
                 PC_PRIO_MFMA(PC_PRIO_TN_COND, 1);
                 PC_TERM(p2, p0) PC_TERM(p0, p2) PC_TERM(p1, p1) PC_TERM(p1, p0) PC_TERM(p0, p1) PC_TERM(p0, p0)
                 PC_PRIO_MFMA(PC_PRIO_TN_COND, 0);

@@ -23,6 +23,7 @@
 // epilogue, merge) instead of per sample, the [B,T] matrix never exists, and the table gradients fall back to
 // hardware float atomics into the cleared dense gradient (row lists of B*(K+2) + B rows).
 #include "common.h"
+#include "lds_dma.h"          // lds_sync
 #include "mfma16.h"
 
 #define LH (PC_L / 2)
@@ -264,11 +265,7 @@ __host__ __device__ inline int wg_slab_floats(int T) { return wg_off_eq(T) + T *
 #define LD128 132
 
 // LDS-only hand-off between the phases (no wait for this wave's outstanding global loads / stores)
-__device__ __forceinline__ void phase_sync() {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-}
+__device__ __forceinline__ void phase_sync() { lds_sync(); }
 
 #ifdef PC_JOINT_TIMING
 // developer build (scripts/joint_phase_times.py): 100 MHz wall-clock stamps of wave 0 of workgroups 0 and 128 at the

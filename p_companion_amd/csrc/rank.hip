@@ -4,10 +4,8 @@
 // the position y takes in the list pc_retrieve_topk_grouped serves for the row (score descending, product index ascending).
 // retrieve.hip's schedule with its selection replaced by a compare and an integer add: no score matrix, no partial lists.
 //
-//   count   pos[r] = atomic position of row r among the rows of its type, cnt[t] = rows of type t; rank_out[r] = 0, or -1
-//           for a row without a type (types[r] < 0) or with an id out of range (counted in *bad_count)
-//   scan    (one workgroup) row_start[t] = exclusive sum of cnt, item_start[t] = exclusive sum of tiles(t) * slices(t)
-//   place   order[row_start[t] + pos[r]] = r
+//   plan    (grouped_plan.hip: count, scan, place) the rows grouped by type, the work items; rank_out[r] = 0, or -1 for a
+//           row without a type (types[r] < 0) or with an id out of range (counted in *bad_count)
 //   rank    grid-stride over the work items (type, slice, tile): query tile -> LDS; the tile's own targets scored first (wave
 //           w: the 16 targets of row group w as one MFMA column block, g = its diagonal); then the slice's candidates in
 //           chunks of 64 (one 16-candidate column group per wave, rows straight from global into registers, the next
@@ -18,9 +16,7 @@
 // dimension 16 j + 4 h + e; the chain's order depends on the dimension index alone), so s_y and g are the same bits and a
 // (row, product) score is bit for bit the one the retrieval orders by.  The count is a sum of integers: it does not depend
 // on the slices, on the order of the rows in a tile, or on the order of type_col inside a type.  No float atomics.
-// The three planning kernels restate retrieve.hip's; the slice plan and the order predicate are shared (grouped_plan.h).
-// (The scan moved into that header as an inlined body leaves rg_scan_kernel's registers and LDS as they are but not its
-// code object's digest, so it is restated here and retrieve.hip's code object stays byte for byte what it was.)
+// The plan (count, scan, place), the slice plan and the order predicate are retrieve.hip's (grouped_plan.h).
 #include "common.h"
 #include "grouped_plan.h"
 
@@ -29,64 +25,6 @@
 // 16 bytes: with a row stride of 2 slots mod 16 each group's 16 reads take 16 different slots.  (D + 4, one slot, puts
 // lanes 12 and 27 of the first group on one slot: five LDS cycles per read instead of four.)
 #define RK_QS(D) ((D) + 8)
-
-// pos[r] < 0: the row takes no part.
-__global__ __launch_bounds__(256) void rk_count_kernel(const int32_t* __restrict__ types, const int32_t* __restrict__ targets,
-                                                       int rows, int n_types, int num_products, int32_t* __restrict__ cnt,
-                                                       int32_t* __restrict__ pos, int32_t* __restrict__ rank_out,
-                                                       int32_t* __restrict__ bad_count) {
-    const int r = blockIdx.x * 256 + threadIdx.x;
-    if (r >= rows) return;
-    const int t = types[r], y = targets[r];
-    int p = -1;
-    if (t >= 0) {                                         // (t < 0: no type matched -- skipped, not an error)
-        if (t < n_types && y >= 0 && y < num_products) p = atomicAdd(&cnt[t], 1);
-        else atomicAdd(bad_count, 1);
-    }
-    pos[r] = p;
-    rank_out[r] = p < 0 ? -1 : 0;
-}
-
-// One workgroup: each thread sums a contiguous run of types, a block scan of the run totals, then the run is written.
-__global__ __launch_bounds__(1024) void rk_scan_kernel(const int32_t* __restrict__ cnt, const int32_t* __restrict__ type_rowptr,
-                                                       int n_types, int S, int TM, int32_t* __restrict__ row_start,
-                                                       int64_t* __restrict__ item_start) {
-    __shared__ int64_t sr[1024], si[1024];
-    const int tid = threadIdx.x;
-    const int per = (n_types + 1023) / 1024;
-    const int t0 = min(tid * per, n_types), t1 = min(t0 + per, n_types);
-    auto items = [&](int t, int c) -> int64_t {
-        int ns, L;
-        rg_slice_plan(type_rowptr[t + 1] - type_rowptr[t], S, ns, L);
-        return c > 0 ? (int64_t)((c + TM - 1) / TM) * ns : 0;
-    };
-    int64_t a = 0, b = 0;
-    for (int t = t0; t < t1; t++) { const int c = cnt[t]; a += c; b += items(t, c); }
-    sr[tid] = a; si[tid] = b;
-    __syncthreads();
-    for (int o = 1; o < 1024; o <<= 1) {                  // inclusive Hillis-Steele scan
-        const int64_t xa = tid >= o ? sr[tid - o] : 0, xb = tid >= o ? si[tid - o] : 0;
-        __syncthreads();
-        sr[tid] += xa; si[tid] += xb;
-        __syncthreads();
-    }
-    int64_t ra = sr[tid] - a, rb = si[tid] - b;
-    for (int t = t0; t < t1; t++) {
-        const int c = cnt[t];
-        row_start[t] = (int32_t)ra; item_start[t] = rb;
-        ra += c; rb += items(t, c);
-    }
-    if (tid == 1023) { row_start[n_types] = (int32_t)sr[1023]; item_start[n_types] = si[1023]; }
-}
-
-__global__ __launch_bounds__(256) void rk_place_kernel(const int32_t* __restrict__ types, int rows,
-                                                       const int32_t* __restrict__ pos, const int32_t* __restrict__ row_start,
-                                                       int32_t* __restrict__ order) {
-    const int r = blockIdx.x * 256 + threadIdx.x;
-    if (r >= rows) return;
-    const int p = pos[r];
-    if (p >= 0) order[row_start[types[r]] + p] = r;       // (p >= 0 only for a type inside [0, n_types))
-}
 
 // THE k-chain (rg_score_kernel's): NG row groups from g0 on against the 16 columns whose rows the lanes hold in b.  For one
 // accumulator the MFMAs run in the order of the dimension index (step k, element x y z w); unit u = (k = u / NG, group
@@ -200,6 +138,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(D == 128 ? 
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, c = lane & 15, h = lane >> 4;
     const int64_t n_items = item_start[n_types];
     for (int64_t w = blockIdx.x; w < n_items; w += gridDim.x) {
+        // (this decode and the tile load below are retrieve.hip's rg_score_kernel; as a shared function they move both kernels' code)
         int lo = 0, hi = n_types - 1;                     // the largest t with item_start[t] <= w (< n_types: w < n_items)
         while (lo < hi) {
             const int mid = (lo + hi + 1) >> 1;
@@ -270,29 +209,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(D == 128 ? 
     }
 }
 
-namespace {
-struct RkWs {
-    int32_t *cnt, *pos, *row_start, *order;
-    int64_t* item_start;
-    size_t bytes;
-};
-inline int rk_slices(int slices) { return slices == 0 ? RG_AUTO_SLICES : slices; }
-RkWs rk_layout(void* ws, int rows, int n_types) {
-    RkWs w;
-    WsCarver cv(ws);
-    w.cnt = (int32_t*)cv.bytes((size_t)n_types * 4);
-    w.pos = (int32_t*)cv.bytes((size_t)rows * 4);
-    w.row_start = (int32_t*)cv.bytes((size_t)(n_types + 1) * 4);
-    w.item_start = (int64_t*)cv.bytes((size_t)(n_types + 1) * 8);
-    w.order = (int32_t*)cv.bytes((size_t)rows * 4);
-    w.bytes = cv.total;
-    return w;
-}
-}  // namespace
-
 extern "C" size_t pc_rank_grouped_workspace_bytes(int rows, int n_types, int slices) {
     if (rows <= 0 || n_types <= 0 || slices < 0 || slices > RG_MAX_SLICES) return 0;
-    return rk_layout(nullptr, rows, n_types).bytes;
+    WsCarver cv(nullptr);
+    rg_plan_carve(cv, rows, n_types);
+    return cv.total;
 }
 
 extern "C" int pc_rank_grouped(const float* proj, const int32_t* types, const int32_t* targets, int rows,
@@ -302,20 +223,14 @@ extern "C" int pc_rank_grouped(const float* proj, const int32_t* types, const in
     if (!proj || !types || !targets || !type_rowptr || !type_col || !table || !rank_out || !bad_count || !ws) return PC_EINVAL;
     if (rows <= 0 || n_types <= 0 || num_products <= 0) return PC_EINVAL;
     if ((dim != 128 && dim != 256) || slices < 0 || slices > RG_MAX_SLICES) return PC_ESHAPE;
-    const int S = rk_slices(slices);
-    const RkWs w = rk_layout(ws, rows, n_types);
-    if (ws_bytes < w.bytes) return PC_EWORKSPACE;
+    const int S = rg_slices(slices);
+    WsCarver cv(ws);
+    const RgPlan w = rg_plan_carve(cv, rows, n_types);
+    if (ws_bytes < cv.total) return PC_EWORKSPACE;
     hipStream_t st = (hipStream_t)stream;
     const int TM = 8192 / dim;
-    PC_HIP_TRY(hipMemsetAsync(w.cnt, 0, (size_t)n_types * 4, st));
-    const dim3 rgrid((rows + 255) / 256);
-    PC_LAUNCH(rk_count_kernel, rgrid, dim3(256), 0, st, types, targets, rows, n_types, num_products, w.cnt, w.pos, rank_out,
-              bad_count);
-    PC_LAUNCH(rk_scan_kernel, dim3(1), dim3(1024), 0, st, w.cnt, type_rowptr, n_types, S, TM, w.row_start, w.item_start);
-    PC_LAUNCH(rk_place_kernel, rgrid, dim3(256), 0, st, types, rows, w.pos, w.row_start, w.order);
-    // at most (tiles over all rows + one partial tile per type) x S items; the kernel reads the real count
-    const int64_t cap = ((int64_t)(rows + TM - 1) / TM + (int64_t)(rows < n_types ? rows : n_types)) * S;
-    const dim3 sgrid((unsigned)(cap < RG_MAX_GRID ? cap : RG_MAX_GRID));
+    PC_TRY(rg_plan_launch(w, types, targets, rows, type_rowptr, n_types, num_products, S, TM, rank_out, bad_count, st));
+    const dim3 sgrid(rg_item_grid(rows, n_types, S, TM));
     if (dim == 128)
         PC_LAUNCH(rk_rank_kernel<128>, sgrid, dim3(256), 0, st, proj, targets, type_rowptr, type_col, table, n_types, S, w.cnt,
                   w.row_start, w.item_start, w.order, rank_out);

@@ -8,9 +8,9 @@
 // slices; every (tile, slice) work item keeps a running top-n per row and writes it as a partial list, and one wave per
 // row merges the slices' lists.
 //
-//   count   rank[r] = atomic position of row r among the rows of its type, cnt[t] = rows of type t
-//   scan    (one workgroup) row_start[t] = exclusive sum of cnt, item_start[t] = exclusive sum of tiles(t) * slices(t)
-//   place   order[row_start[t] + rank[r]] = r
+//   plan    (grouped_plan.hip) count: rank[r] = atomic position of row r among the rows of its type, cnt[t] = rows of type
+//           t; scan: row_start[t] = exclusive sum of cnt, item_start[t] = exclusive sum of tiles(t) * slices(t); place:
+//           order[row_start[t] + rank[r]] = r
 //   score   grid-stride over the work items (count read on the device): query tile -> LDS, candidates in chunks of 64
 //           (one 16-candidate column group per wave, rows straight from global into registers, the next chunk's in
 //           flight while this one is scored), scores -> LDS, a threshold test per (row, candidate), partial top-n per row
@@ -22,7 +22,7 @@
 // ascending), so the top n of the union does not depend on how the candidates were split, on the order of the rows in a
 // tile (the one thing the planning atomics decide), or on the order of type_col inside a type.  No float atomics.
 #include "common.h"
-#include "grouped_plan.h"          // the chunk / slice constants, rg_slice_plan, rg_better (shared with rank.hip)
+#include "grouped_plan.h"          // the constants, the plan, rg_better, the item decode and tile load (shared with rank.hip)
 
 #define RG_MAX_N 16
 
@@ -45,55 +45,6 @@ __device__ __forceinline__ void rg_pop(float* v, int* ix) {
 #pragma unroll
     for (int j = 0; j < RG_MAX_N - 1; j++) { v[j] = v[j + 1]; ix[j] = ix[j + 1]; }
     v[RG_MAX_N - 1] = -INFINITY; ix[RG_MAX_N - 1] = RG_NONE;
-}
-
-__global__ __launch_bounds__(256) void rg_count_kernel(const int32_t* __restrict__ types, int rows, int n_types,
-                                                       int32_t* __restrict__ cnt, int32_t* __restrict__ rank) {
-    const int r = blockIdx.x * 256 + threadIdx.x;
-    if (r >= rows) return;
-    const int t = types[r];
-    if (t >= 0 && t < n_types) rank[r] = atomicAdd(&cnt[t], 1);
-}
-
-// One workgroup: each thread sums a contiguous run of types, a block scan of the run totals, then the run is written.
-__global__ __launch_bounds__(1024) void rg_scan_kernel(const int32_t* __restrict__ cnt, const int32_t* __restrict__ type_rowptr,
-                                                       int n_types, int S, int TM, int32_t* __restrict__ row_start,
-                                                       int64_t* __restrict__ item_start) {
-    __shared__ int64_t sr[1024], si[1024];
-    const int tid = threadIdx.x;
-    const int per = (n_types + 1023) / 1024;
-    const int t0 = min(tid * per, n_types), t1 = min(t0 + per, n_types);
-    auto items = [&](int t, int c) -> int64_t {
-        int ns, L;
-        rg_slice_plan(type_rowptr[t + 1] - type_rowptr[t], S, ns, L);
-        return c > 0 ? (int64_t)((c + TM - 1) / TM) * ns : 0;
-    };
-    int64_t a = 0, b = 0;
-    for (int t = t0; t < t1; t++) { const int c = cnt[t]; a += c; b += items(t, c); }
-    sr[tid] = a; si[tid] = b;
-    __syncthreads();
-    for (int o = 1; o < 1024; o <<= 1) {                  // inclusive Hillis-Steele scan
-        const int64_t xa = tid >= o ? sr[tid - o] : 0, xb = tid >= o ? si[tid - o] : 0;
-        __syncthreads();
-        sr[tid] += xa; si[tid] += xb;
-        __syncthreads();
-    }
-    int64_t ra = sr[tid] - a, rb = si[tid] - b;
-    for (int t = t0; t < t1; t++) {
-        const int c = cnt[t];
-        row_start[t] = (int32_t)ra; item_start[t] = rb;
-        ra += c; rb += items(t, c);
-    }
-    if (tid == 1023) { row_start[n_types] = (int32_t)sr[1023]; item_start[n_types] = si[1023]; }
-}
-
-__global__ __launch_bounds__(256) void rg_place_kernel(const int32_t* __restrict__ types, int rows, int n_types,
-                                                       const int32_t* __restrict__ rank, const int32_t* __restrict__ row_start,
-                                                       int32_t* __restrict__ order) {
-    const int r = blockIdx.x * 256 + threadIdx.x;
-    if (r >= rows) return;
-    const int t = types[r];
-    if (t >= 0 && t < n_types) order[row_start[t] + rank[r]] = r;
 }
 
 // Work item w = (type t, slice s, tile j), items of one type ordered slice-major so that the tiles running side by side read
@@ -122,6 +73,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(D == 128 ? 
     const int rr = tid / TPR, qq = tid % TPR;
     const int64_t n_items = item_start[n_types];
     for (int64_t w = blockIdx.x; w < n_items; w += gridDim.x) {
+        // (this decode and the tile load below are rank.hip's rk_rank_kernel; as a shared function they move both kernels' code)
         int lo = 0, hi = n_types - 1;                     // the largest t with item_start[t] <= w (< n_types: w < n_items)
         while (lo < hi) {
             const int mid = (lo + hi + 1) >> 1;
@@ -299,23 +251,17 @@ __global__ __launch_bounds__(256) void rg_merge_kernel(const int32_t* __restrict
 
 namespace {
 struct RgWs {
-    int32_t *cnt, *rank, *row_start, *order, *pi;
-    int64_t* item_start;
-    float* pv;
+    RgPlan plan;
+    float* pv;                             // the partial lists [rows][S][n]
+    int32_t* pi;
     size_t bytes;
 };
-inline int rg_slices(int slices) { return slices == 0 ? RG_AUTO_SLICES : slices; }
 RgWs rg_layout(void* ws, int rows, int n_types, int n, int S) {
     RgWs w;
     WsCarver cv(ws);
-    auto take = [&](size_t nbytes) { return cv.bytes(nbytes); };
-    w.cnt = (int32_t*)take((size_t)n_types * 4);
-    w.rank = (int32_t*)take((size_t)rows * 4);
-    w.row_start = (int32_t*)take((size_t)(n_types + 1) * 4);
-    w.item_start = (int64_t*)take((size_t)(n_types + 1) * 8);
-    w.order = (int32_t*)take((size_t)rows * 4);
-    w.pv = (float*)take((size_t)rows * S * n * 4);
-    w.pi = (int32_t*)take((size_t)rows * S * n * 4);
+    w.plan = rg_plan_carve(cv, rows, n_types);
+    w.pv = (float*)cv.bytes((size_t)rows * S * n * 4);
+    w.pi = (int32_t*)cv.bytes((size_t)rows * S * n * 4);
     w.bytes = cv.total;
     return w;
 }
@@ -337,21 +283,16 @@ extern "C" int pc_retrieve_topk_grouped(const float* proj, const int32_t* types,
     if (ws_bytes < w.bytes) return PC_EWORKSPACE;
     hipStream_t st = (hipStream_t)stream;
     const int TM = 8192 / dim;
-    PC_HIP_TRY(hipMemsetAsync(w.cnt, 0, (size_t)n_types * 4, st));
-    const dim3 rgrid((rows + 255) / 256);
-    PC_LAUNCH(rg_count_kernel, rgrid, dim3(256), 0, st, types, rows, n_types, w.cnt, w.rank);
-    PC_LAUNCH(rg_scan_kernel, dim3(1), dim3(1024), 0, st, w.cnt, type_rowptr, n_types, S, TM, w.row_start, w.item_start);
-    PC_LAUNCH(rg_place_kernel, rgrid, dim3(256), 0, st, types, rows, n_types, w.rank, w.row_start, w.order);
-    // at most (tiles over all rows + one partial tile per type) x S items; the kernel reads the real count
-    const int64_t cap = ((int64_t)(rows + TM - 1) / TM + (int64_t)(rows < n_types ? rows : n_types)) * S;
-    const dim3 sgrid((unsigned)(cap < RG_MAX_GRID ? cap : RG_MAX_GRID));
+    const RgPlan& pl = w.plan;
+    PC_TRY(rg_plan_launch(pl, types, nullptr, rows, type_rowptr, n_types, 0, S, TM, nullptr, nullptr, st));
+    const dim3 sgrid(rg_item_grid(rows, n_types, S, TM));
     if (dim == 128)
-        PC_LAUNCH(rg_score_kernel<128>, sgrid, dim3(256), 0, st, proj, type_rowptr, type_col, table, n_types, n, S, w.cnt,
-                  w.row_start, w.item_start, w.order, w.pv, w.pi);
+        PC_LAUNCH(rg_score_kernel<128>, sgrid, dim3(256), 0, st, proj, type_rowptr, type_col, table, n_types, n, S, pl.cnt,
+                  pl.row_start, pl.item_start, pl.order, w.pv, w.pi);
     else
-        PC_LAUNCH(rg_score_kernel<256>, sgrid, dim3(256), 0, st, proj, type_rowptr, type_col, table, n_types, n, S, w.cnt,
-                  w.row_start, w.item_start, w.order, w.pv, w.pi);
-    PC_LAUNCH(rg_merge_kernel, dim3((rows + 3) / 4), dim3(256), 0, st, types, rows, type_rowptr, n_types, n, S, w.rank,
-              w.row_start, w.pv, w.pi, out_idx, out_score);
+        PC_LAUNCH(rg_score_kernel<256>, sgrid, dim3(256), 0, st, proj, type_rowptr, type_col, table, n_types, n, S, pl.cnt,
+                  pl.row_start, pl.item_start, pl.order, w.pv, w.pi);
+    PC_LAUNCH(rg_merge_kernel, dim3((rows + 3) / 4), dim3(256), 0, st, types, rows, type_rowptr, n_types, n, S, pl.pos,
+              pl.row_start, w.pv, w.pi, out_idx, out_score);
     return pc_launch_status();
 }

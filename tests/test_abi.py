@@ -98,6 +98,17 @@ def test_exchange_slot_plumbing_without_a_gpu():
     assert pdist.make_exchange(1) is None
 
 
+def test_every_kernel_has_a_stable_instruction_text_digest():
+    """build.kernel_text_digests() (llvm-objdump -d on the gfx950 images, per symbol, without addresses and encodings) covers
+    every kernel the code objects' metadata lists, and reading the same build twice gives the same digests."""
+    from p_companion_amd import build
+    build.build()
+    first, second = build.kernel_text_digests(), build.kernel_text_digests()
+    assert first == second
+    assert not [n for n in build.kernel_resources() if n not in first]
+    assert all(len(h) == 64 and int(h, 16) >= 0 for h in first.values())
+
+
 def test_no_shipped_kernel_spills_vector_registers():
     """The code objects' own metadata (llvm-readelf --notes on the gfx950 images of the compiled units): no kernel keeps vector
     registers in scratch, and the only private segments are the one-time generators' / the stand-alone batch builder's."""

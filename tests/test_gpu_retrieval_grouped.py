@@ -176,6 +176,32 @@ def test_one_row_per_type_and_a_single_product_catalogue():
     assert idx.cpu().tolist() == [[0, -1, -1]] and sc[0, 0].item() == 4.0 and torch.isneginf(sc[0, 1:]).all()
 
 
+def test_rows_without_a_valid_type_beside_a_two_tile_type_exact():
+    """The planning pass on the retrieval side: D = 128, n = 4, 300 products over 5 types of which type 3 has none, 70 rows of
+    which 65 are of type 0 (two 64-row tiles), one of type -1 and one of type 5 (out of range).  Small-integer features and
+    queries make every score exact in fp32 and fp64 alike, so the two invalid rows give -1 / -inf in every slot and every
+    other row EQUALS grouped_reference: indices equal, scores the same bits."""
+    from p_companion_amd import ops
+    D, n, P, T, R = 128, 4, 300, 5, 70
+    rng = np.random.default_rng(21)
+    type_idx = rng.choice(np.array([0, 1, 2, 4], np.int32), P)
+    features = rng.integers(-3, 4, (P, D)).astype(np.float32)
+    proj = rng.integers(-3, 4, (R, D)).astype(np.float32)
+    types = np.zeros(R, np.int32)
+    types[5], types[40], types[67:] = -1, 5, [1, 3, 4]
+    assert (types == 0).sum() == 65 and (type_idx == 3).sum() == 0
+    rowptr, col, table = upload(type_idx, features, T)
+    idx, sc = ops.retrieve_topk_grouped(torch.from_numpy(proj).cuda(), torch.from_numpy(types).cuda(), rowptr, col, table, n)
+    idx, sc = idx.cpu().numpy(), sc.cpu().numpy()
+    for r in (5, 40):
+        assert (idx[r] == -1).all() and np.isneginf(sc[r]).all(), r
+    for r, (rid, rsc) in enumerate(grouped_reference(proj, types, type_idx, features, n)):
+        want_idx, want_sc = np.full(n, -1, np.int64), np.full(n, -np.inf, np.float32)
+        want_idx[:len(rid)], want_sc[:len(rid)] = rid, rsc.astype(np.float32)
+        assert (rsc.astype(np.float32).astype(np.float64) == rsc).all()
+        assert (idx[r] == want_idx).all() and (sc[r].view(np.int32) == want_sc.view(np.int32)).all(), r
+
+
 # ---- 2. agreement with pc_retrieve_topk
 def _agree_with_old(proj, types, type_idx, features, rowptr, col, table, n):
     from p_companion_amd import ops
