@@ -809,6 +809,8 @@ def unique_neighbors(neighbor_idx):
     slot = np.full(idx.shape, len(u), np.int32)
     slot[real] = inv.astype(np.int32)
     order = np.argsort(slot.reshape(-1), kind="stable").astype(np.int32)[:int(real.sum())]   # real slots grouped by row
+    if order.size == 0:
+        order = np.zeros(1, np.int32)     # a batch of padding alone: no row lists a slot, but the C ABI refuses a NULL ref_slot
     ref_off = np.concatenate([[0], np.cumsum(cnt), [int(real.sum())]]).astype(np.int32)      # [U + 2]: padding row lists none
     dev = neighbor_idx.device
     return {"nb_rows": torch.from_numpy(nb_rows).to(dev), "weight": torch.from_numpy(weight).to(dev),
