@@ -210,8 +210,9 @@ int pc_p2v_ffn_backward(const pc_p2v_tensors *p, const pc_p2v_tensors *g, const 
                         size_t ws_bytes, void *stream);
 
 /* P7: Product2Vec.apply_attention -> nn.MultiheadAttention(128, 4 heads), ONE query token
- * per sample, keys == values == neighbour embeddings, no key-padding mask, attention-weight dropout p->dropout
- * (product2vec.py:48-68).  query[B,D], keys[B*N,D] -> out[B,D].
+ * per sample, keys == values == neighbour embeddings, attention-weight dropout p->dropout (product2vec.py:48-68).  The
+ * reference passes no key-padding mask and these two entries have none; the _masked forms below add one.
+ * query[B,D], keys[B*N,D] -> out[B,D].
  * With ONE query token the K and V projections of the key rows are absorbed into the per-sample side (exact algebra,
  * csrc/attention.hip): score = (Wk_h^T q_h / sqrt(hd)) . key + const, ctx_h = Wv_h (sum_n pm_n key_n) + bv_h sum_n pm_n;
  * no [B*N, 2D] K|V buffer exists.
@@ -233,6 +234,20 @@ int pc_p2v_attention_backward(const pc_p2v_tensors *p, const pc_p2v_tensors *g,
                               const float *dout, const pc_attn_saved *saved, float *dquery,
                               float *dkeys, int accumulate, void *ws, size_t ws_bytes,
                               void *stream);
+/* P7 with a key-padding mask -- a labelled deviation from the reference (nn.MultiheadAttention's key_padding_mask, which
+ * product2vec.py never passes); the entries above stay the parity default.  key_pad[B*N] (uint8, device): nonzero = slot (b,n)
+ * is padding and no key.  It is left out of the running maximum and of the softmax sum, its saved probability is exactly
+ * 0.0f and its key row is never multiplied in (it may hold anything); the dropout multiplier of a real slot is the one it
+ * draws without the mask (element (b,h,n) of the [B,HEADS,N] tensor).  A sample whose slots are all padding gets a zero
+ * context: out = out_proj_b, every value finite (torch gives NaN there).  Backward: dkeys rows of padding slots come back as
+ * zeros; such a sample sends nothing to dquery or to in_proj.  Same workspace and saved buffers as above. */
+int pc_p2v_attention_forward_masked(const pc_p2v_tensors *p, const float *query, const float *keys,
+                                    const uint8_t *key_pad, int batch, int n_keys, float *out,
+                                    const pc_attn_saved *saved, void *ws, size_t ws_bytes, void *stream);
+int pc_p2v_attention_backward_masked(const pc_p2v_tensors *p, const pc_p2v_tensors *g,
+                                     const float *query, const float *keys, const uint8_t *key_pad, int batch,
+                                     int n_keys, const float *dout, const pc_attn_saved *saved, float *dquery,
+                                     float *dkeys, int accumulate, void *ws, size_t ws_bytes, void *stream);
 
 /* P11 over a device CSR: Product2Vec.generate_all_embeddings (product2vec.py:83-111), eval mode, the whole table.
  *   e1[i]  = ffn(features[i])                                      every product (written; the caller keeps or drops it)
@@ -623,6 +638,33 @@ int pc_p2v_train_step_unique_rows(const pc_p2v_tensors *p, const pc_p2v_tensors 
                                   int n_nbr, int k_neg, float margin, float *loss, float *d_pos, float *d_neg,
                                   float *anchor_emb, void *profile, void *ws, size_t ws_bytes, const pc_adam_fused *adam,
                                   void *stream);
+
+/* The fused step with the key-padding mask (a labelled deviation, see pc_p2v_attention_forward_masked; the entries above stay
+ * the parity default).  A padding slot is a slot that slot_row maps to the shared padding row (the last of nb_rows).
+ *   attention: padding slots are no keys; a sample without a real slot gets out_proj_b and sends no gradient to keys or in_proj.
+ *   BatchNorm of the neighbour call: statistics, running-statistics update and backward sums span the real slots only.  The
+ *     padding row weighs 0 (nb_weight's last entry is NOT read and the array is not written: one batch serves both modes) and
+ *     adds nothing to any weight or bias gradient.
+ *   one real slot in the batch: PC_EBATCHNORM, as one row.  None (a batch of padding alone): the neighbour call did not
+ *     happen -- three BatchNorm calls update the running statistics and num_batches_tracked, nothing is divided by zero.
+ * _compact_masked: pc_p2v_train_step_compact's arguments (n_real real slots, one row each).
+ * _unique_masked: the unique layout plus n_real_slots = the number of real slots (the sum of nb_weight[0 .. n_unique), which the
+ *   host knows: the loader's n_real); step_rows optional (NULL, or pc_p2v_concat_step_rows' list, which then replaces the three
+ *   index arrays as in pc_p2v_train_step_unique_rows); adam optional (NULL, or the optimizer riding in the last launch as in
+ *   pc_p2v_train_step_unique_adam).  Unsplit step only: cross-replica masked statistics are not built. */
+int pc_p2v_train_step_compact_masked(const pc_p2v_tensors *p, const pc_p2v_tensors *g, const float *table,
+                                     const int32_t *anchor_idx, const int32_t *positive_idx,
+                                     const int32_t *negative_idx, const int32_t *nb_rows, int n_real,
+                                     const int32_t *slot_row, int batch, int n_nbr, int k_neg, float margin,
+                                     float *loss, float *d_pos, float *d_neg, float *anchor_emb, void *profile,
+                                     void *ws, size_t ws_bytes, void *stream);
+int pc_p2v_train_step_unique_masked(const pc_p2v_tensors *p, const pc_p2v_tensors *g, const float *table,
+                                    const int32_t *anchor_idx, const int32_t *positive_idx,
+                                    const int32_t *negative_idx, const int32_t *step_rows, const int32_t *nb_rows,
+                                    const float *nb_weight, int n_unique, int n_real_slots, const int32_t *slot_row,
+                                    const int32_t *ref_off, const int32_t *ref_slot, int batch, int n_nbr, int k_neg,
+                                    float margin, float *loss, float *d_pos, float *d_neg, float *anchor_emb,
+                                    void *profile, void *ws, size_t ws_bytes, const pc_adam_fused *adam, void *stream);
 
 /* ---------------------------------------------------------------------------------
  * Data-parallel replicas (the reference is single-process: train.py:46-48 is loss.backward(); optimizer.step()

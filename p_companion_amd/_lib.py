@@ -101,6 +101,13 @@ SIGNATURES = {
     "pc_p2v_attention_forward": (_i, [_P(P2VTensors), _vp, _vp, _i, _i, _vp, _P(AttnSaved), _vp, _sz, _vp]),
     "pc_p2v_attention_backward": (_i, [_P(P2VTensors), _P(P2VTensors), _vp, _vp, _i, _i, _vp, _P(AttnSaved), _vp,
                                        _vp, _i, _vp, _sz, _vp]),
+    "pc_p2v_attention_forward_masked": (_i, [_P(P2VTensors), _vp, _vp, _vp, _i, _i, _vp, _P(AttnSaved), _vp, _sz, _vp]),
+    "pc_p2v_attention_backward_masked": (_i, [_P(P2VTensors), _P(P2VTensors), _vp, _vp, _vp, _i, _i, _vp, _P(AttnSaved), _vp,
+                                              _vp, _i, _vp, _sz, _vp]),
+    "pc_p2v_train_step_compact_masked": (_i, [_P(P2VTensors), _P(P2VTensors), _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _f,
+                                              _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "pc_p2v_train_step_unique_masked": (_i, [_P(P2VTensors), _P(P2VTensors), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp,
+                                             _vp, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _P(AdamFused), _vp]),
     "pc_p2v_export_workspace_bytes": (_sz, [_i, _i]),
     "pc_p2v_export_embeddings": (_i, [_P(P2VTensors), _vp, _i64, _vp, _vp, _vp, _vp, _i, _vp, _sz, _vp]),
     "pc_p2v_triplet_loss": (_i, [_vp, _vp, _vp, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

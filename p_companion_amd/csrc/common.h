@@ -649,10 +649,11 @@ int ffn_transposes(const pc_p2v_tensors* p, void* ws, int rows, int with_dx, Tra
 int attention_transposes(const pc_p2v_tensors* p, void* ws, int B, int N, int key_rows, TransposeBatch* tb, float* zero_bk);
 int attention_forward_impl(const pc_p2v_tensors* p, const float* query, const float* keys, int B, int N,
                            int key_rows, const int32_t* slot_row, float* out, const pc_attn_saved* sv, void* ws,
-                           size_t ws_bytes, void* stream, int transposed, NtArgs* defer_out_chain);
+                           size_t ws_bytes, void* stream, int transposed, NtArgs* defer_out_chain, int masked = 0,
+                           const uint8_t* key_pad = nullptr);
 int attention_backward_impl(const pc_p2v_tensors* p, const pc_p2v_tensors* g, const float* query, const float* keys,
                             int B, int N, int key_rows, const int32_t* slot_row, int pad_row, const float* dout,
                             const pc_attn_saved* sv, float* dquery, float* dkeys, int accumulate, void* ws,
                             size_t ws_bytes, void* stream, const int32_t* ref_off, const int32_t* ref_slot,
                             int transposed, TnDefer* defer, const HingeMeanJob* rider, const LossPro* lossp,
-                            const NtArgs* fwd_out_chain);
+                            const NtArgs* fwd_out_chain, int masked = 0, const uint8_t* key_pad = nullptr);

@@ -128,6 +128,12 @@ struct P2VStepCall {
     const pc_adam_fused* adam = nullptr;     // the optimizer rides in the unsplit step's last launch only
     void* profile = nullptr;
     void* stream = nullptr;
+    // The key-padding mask (a labelled deviation from the reference, off by default; compact and unique layouts, unsplit step):
+    // the slots mapped to the padding row are no keys of the attention, and the neighbour call's BatchNorm spans the
+    // n_real_slots real slots -- the padding row weighs 0 whatever nb_weight's last entry says (the caller's array is not written:
+    // one batch serves both modes).
+    bool masked = false;
+    int n_real_slots = 0;
 };
 
 // the compact and unique layouts: n_real real neighbour rows in front of the padding row, every slot mapped (and a slot count
@@ -156,6 +162,14 @@ static int p2v_step_impl(const P2VStepCall& c) {
     // the anchor and positive calls are [B,128] BatchNorm inputs: the reference raises for a single row in training
     // mode (torch/nn/functional.py _verify_batch_size); so does a [1,5,128] negative block when K = 1
     if (B == 1) return PC_EBATCHNORM;
+    if (c.masked) {
+        if (phase != -1) return PC_EINVAL;                       // (cross-replica masked statistics: not built)
+        if (!slot_row || N <= 0 || nbc < 1) return PC_EINVAL;
+        // every real row holds at least one real slot
+        if (c.n_real_slots < nbc - 1 || (long long)c.n_real_slots > (long long)B * N) return PC_EINVAL;
+        if (!c.nb_weight && c.n_real_slots != nbc - 1) return PC_EINVAL;      // (compact layout: one row per real slot)
+        if (c.n_real_slots == 1) return PC_EBATCHNORM;           // a neighbour call of one row, as B == 1 above
+    }
     if (p->dim != 0 && p->dim != 128 && p->dim != 256) return PC_ESHAPE;
     const int D = p->dim == 256 ? 256 : PC_D;
     if (c.ws_bytes < pc_p2v_train_step_workspace_bytes_dim(B, N, K, D)) return PC_EWORKSPACE;
@@ -169,7 +183,19 @@ static int p2v_step_impl(const P2VStepCall& c) {
     pc_segments seg = {};
     seg.weighted_row = -1;
     seg.weight = 1.f;
-    if (N > 0) {
+    if (c.masked && c.n_real_slots == 0) {
+        // a batch of padding alone: the neighbour call did not happen.  Its one (padding) row is carried at the end of the
+        // anchor call's segment with weight 0 -- it enters no statistic and no gradient, and what the FFN makes of it is finite --
+        // so three BatchNorm calls update the running statistics and num_batches_tracked, and nothing is divided by 0.
+        seg.nseg = 3; seg.start[0] = rA; seg.start[1] = rP; seg.start[2] = rG; seg.start[3] = R; seg.start[4] = R;
+        seg.count[0] = B;
+        seg.weighted_row = rN; seg.weight = 0.f;
+    } else if (c.masked) {
+        seg.nseg = 4; seg.start[0] = rA; seg.start[1] = rN; seg.start[2] = rP; seg.start[3] = rG; seg.start[4] = R;
+        seg.count[1] = c.n_real_slots;                         // BatchNorm sees the real slots only
+        seg.weighted_row = rN + nbc - 1; seg.weight = 0.f;     // (looked up for rows outside row_weight's range: common.h row_multiplicity)
+        if (c.nb_weight) { seg.row_weight = c.nb_weight; seg.row_weight_start = rN; seg.row_weight_rows = nbc - 1; }
+    } else if (N > 0) {
         seg.nseg = 4; seg.start[0] = rA; seg.start[1] = rN; seg.start[2] = rP; seg.start[3] = rG; seg.start[4] = R;
         seg.count[1] = B * N;                                  // BatchNorm sees every padded slot
         if (c.nb_weight) { seg.row_weight = c.nb_weight; seg.row_weight_start = rN; seg.row_weight_rows = nbc; }
@@ -223,7 +249,8 @@ static int p2v_step_impl(const P2VStepCall& c) {
     NtArgs fwd_out_chain[2];
     if (N > 0) {
         PC_TRY(attention_forward_impl(p, w.y + (size_t)rA * D, w.y + (size_t)rN * D, B, N, nbc, slot_row, w.emb,
-                                      &as, w.attn_ws, w.attn_bytes, stream, 1, out_chain_rides ? fwd_out_chain : nullptr));
+                                      &as, w.attn_ws, w.attn_bytes, stream, 1, out_chain_rides ? fwd_out_chain : nullptr,
+                                      c.masked ? 1 : 0, nullptr));
         emb = w.emb;
     }
 
@@ -262,7 +289,7 @@ static int p2v_step_impl(const P2VStepCall& c) {
                                        slot_row ? nbc - 1 : -1, w.demb, &as, w.dy + (size_t)rA * D,
                                        w.dy + (size_t)rN * D, 0, w.attn_ws, w.attn_bytes, stream, c.ref_off, c.ref_slot, 1, &df,
                                        mean_rides ? &hm : nullptr, loss_rides ? &lp : nullptr,
-                                       out_chain_rides ? fwd_out_chain : nullptr));
+                                       out_chain_rides ? fwd_out_chain : nullptr, c.masked ? 1 : 0, nullptr));
         if (c.anchor_emb && out_chain_rides)                    // (the embedding exists once the backward's first launch has run)
             PC_HIP_TRY(hipMemcpyAsync(c.anchor_emb, emb, (size_t)B * D * 4, hipMemcpyDeviceToDevice, st));
     } else {
@@ -381,5 +408,43 @@ extern "C" int pc_p2v_train_step_unique_rows(const pc_p2v_tensors* p, const pc_p
     P2V_STEP_COMMON(c);
     c.anchor_idx = step_rows; c.positive_idx = step_rows + B + n_unique + 1; c.negative_idx = step_rows + 2 * B + n_unique + 1;
     c.adam = adam; c.rows_ready = step_rows;
+    return p2v_step_impl(c);
+}
+
+// The masked mode of the compact and unique steps (see P2VStepCall::masked; pcompanion_hip.h has the semantics).
+extern "C" int pc_p2v_train_step_compact_masked(const pc_p2v_tensors* p, const pc_p2v_tensors* g, const float* table,
+                                                const int32_t* anchor_idx, const int32_t* positive_idx,
+                                                const int32_t* negative_idx, const int32_t* nb_rows, int n_real,
+                                                const int32_t* slot_row, int B, int N, int K, float margin, float* loss,
+                                                float* d_pos, float* d_neg, float* anchor_emb, void* profile, void* ws,
+                                                size_t ws_bytes, void* stream) {
+    if (!nb_layout_ok(slot_row, nb_rows, n_real, B, N)) return PC_EINVAL;
+    P2VStepCall c;
+    P2V_STEP_COMMON(c); P2V_STEP_TRIPLET(c);
+    c.nb_idx = nb_rows; c.nbc = n_real + 1; c.slot_row = slot_row; c.profile = profile;
+    c.masked = true; c.n_real_slots = n_real;
+    return p2v_step_impl(c);
+}
+
+extern "C" int pc_p2v_train_step_unique_masked(const pc_p2v_tensors* p, const pc_p2v_tensors* g, const float* table,
+                                               const int32_t* anchor_idx, const int32_t* positive_idx,
+                                               const int32_t* negative_idx, const int32_t* step_rows, const int32_t* nb_rows,
+                                               const float* nb_weight, int n_unique, int n_real_slots, const int32_t* slot_row,
+                                               const int32_t* ref_off, const int32_t* ref_slot, int B, int N, int K, float margin,
+                                               float* loss, float* d_pos, float* d_neg, float* anchor_emb, void* profile, void* ws,
+                                               size_t ws_bytes, const pc_adam_fused* adam, void* stream) {
+    if (B <= 0 || !P2V_UNIQUE_OK || n_real_slots < 0) return PC_EINVAL;
+    if (!step_rows && (!anchor_idx || !positive_idx || !negative_idx)) return PC_EINVAL;
+    P2VStepCall c;
+    P2V_STEP_UNIQUE(c);
+    P2V_STEP_COMMON(c);
+    if (step_rows) {
+        c.anchor_idx = step_rows; c.positive_idx = step_rows + B + n_unique + 1; c.negative_idx = step_rows + 2 * B + n_unique + 1;
+        c.rows_ready = step_rows;
+    } else {
+        P2V_STEP_TRIPLET(c);
+    }
+    c.adam = adam;
+    c.masked = true; c.n_real_slots = n_real_slots;
     return p2v_step_impl(c);
 }

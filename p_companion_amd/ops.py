@@ -78,8 +78,10 @@ def workspace(nbytes, device, tag="ws"):
     return buf
 
 
-def make_segments(starts, rows):
-    """starts: row starts of each BatchNorm call group, e.g. [0, B, B+B*N]; rows = total."""
+def make_segments(starts, rows, row_weight=None, counts=None):
+    """starts: row starts of each BatchNorm call group, e.g. [0, B, B+B*N]; rows = total.
+    row_weight (optional): fp32 device tensor [rows], how many identical logical rows each row stands for (0 = the row enters no
+    statistic); counts (optional): the logical row count of each group, i.e. what BatchNorm divides by (0 = its physical rows)."""
     if not 1 <= len(starts) <= PC_MAX_SEG:
         raise ValueError("1..4 segments")
     s = Segments()
@@ -89,8 +91,16 @@ def make_segments(starts, rows):
     arr = list(starts) + [rows] * (PC_MAX_SEG + 1 - len(starts))
     for i, v in enumerate(arr):
         s.start[i] = int(v)
+    if counts is not None:
+        if len(counts) != s.nseg or any(int(c) < 0 for c in counts):
+            raise ValueError("counts: one non-negative logical row count per segment")
+        for i, c in enumerate(counts):
+            s.count[i] = int(c)
+    if row_weight is not None:
+        _req(row_weight, torch.float32, "row_weight", (rows,))
+        s.row_weight, s.row_weight_start, s.row_weight_rows = row_weight.data_ptr(), 0, rows
     for i in range(s.nseg):
-        n = s.start[i + 1] - s.start[i]
+        n = s.count[i] if s.count[i] > 0 else s.start[i + 1] - s.start[i]
         if n == 1:
             # nn.BatchNorm1d raises the same in training mode (torch/nn/functional.py _verify_batch_size)
             raise ValueError("Expected more than 1 value per channel when training, got input size "
@@ -146,20 +156,23 @@ def _new_p2v_grads(device, d=D):
 
 
 # ----------------------------------------------------------------------------- P6
-def ffn_forward_train(params, table, idx, rows, seg_starts, update_running=True):
+def ffn_forward_train(params, table, idx, rows, seg_starts, update_running=True, row_weight=None, counts=None):
     """Product2Vec.get_initial_embedding in training mode over `rows` rows made of
-    len(seg_starts) BatchNorm call groups.  Returns (y[rows,D], saved)."""
+    len(seg_starts) BatchNorm call groups.  Returns (y[rows,D], saved).
+    row_weight / counts: see make_segments (pc_segments' row multiplicities and logical counts); the backward reads them from
+    `saved`.  A row of weight 0 still gets its y, but BatchNorm's statistics do not see it."""
     st, dev = p2v_struct(params)
     _req(table, torch.float32, "table")
     if idx is not None:
         _req(idx, torch.int32, "idx", (rows,))
-    seg = make_segments(seg_starts, rows)
+    seg = make_segments(seg_starts, rows, row_weight, counts)
     y = torch.empty(rows, st.dim, dtype=torch.float32, device=dev)
     sv = {"h0": torch.empty(rows, H, dtype=torch.float32, device=dev),
           "a2": torch.empty(rows, H, dtype=torch.float32, device=dev),
           "a1": torch.empty(rows, H, dtype=torch.float32, device=dev),      # tanh(BN(h0)): written by Linear3's kernel, read by dW3
           "bn": torch.empty(4, PC_MAX_SEG, H, dtype=torch.float32, device=dev),
-          "seg_starts": list(seg_starts), "rows": rows}
+          "seg_starts": list(seg_starts), "rows": rows, "row_weight": row_weight,
+          "counts": None if counts is None else list(counts)}
     nbytes = _lib.lib().pc_p2v_ffn_workspace_bytes(rows)
     ws = workspace(nbytes, dev)
     check(_lib.lib().pc_p2v_ffn_forward_train(ctypes.byref(st), _p(table), _p(idx), rows, ctypes.byref(seg),
@@ -199,7 +212,7 @@ def ffn_backward(params, table, idx, dy, sv, need_dx=False, grads=None, accumula
         grads = _new_p2v_grads(dev, d)
         accumulate = False
     gst, _ = p2v_struct(grads, with_buffers=False)
-    seg = make_segments(sv["seg_starts"], rows)
+    seg = make_segments(sv["seg_starts"], rows, sv.get("row_weight"), sv.get("counts"))
     dx = torch.empty(rows, d, dtype=torch.float32, device=dev) if need_dx else None
     nbytes = _lib.lib().pc_p2v_ffn_workspace_bytes(rows)
     ws = workspace(nbytes, dev)
@@ -216,8 +229,22 @@ def _attn_saved(sv):
     return s
 
 
-def attention_forward(params, query, keys):
-    """query [B,D], keys [B,N,D] -> out [B,D], saved."""
+def _key_pad(key_pad, b, n):
+    """A [B,N] key-padding mask (bool or uint8, nonzero / True = padding) as the uint8 tensor the masked kernels read."""
+    if not isinstance(key_pad, torch.Tensor) or not key_pad.is_cuda:
+        raise TypeError("key_pad: expected a CUDA/ROCm tensor (the HIP path has no CPU fallback)")
+    if key_pad.dtype not in (torch.bool, torch.uint8):
+        raise TypeError(f"key_pad: expected torch.bool or torch.uint8, got {key_pad.dtype}")
+    if tuple(key_pad.shape) != (b, n):
+        raise ValueError(f"key_pad: expected shape {(b, n)}, got {tuple(key_pad.shape)}")
+    kp = key_pad.contiguous()
+    return kp.view(torch.uint8) if kp.dtype == torch.bool else kp
+
+
+def attention_forward(params, query, keys, key_pad=None):
+    """query [B,D], keys [B,N,D] -> out [B,D], saved.
+    key_pad (optional, [B,N] bool / uint8, True = padding): the key-padding mask, a labelled deviation from the reference
+    (pc_p2v_attention_forward_masked): padding slots are no keys, a sample without a real slot gets out_proj.bias."""
     st, dev = p2v_struct(params)
     b, n, _ = keys.shape
     d = st.dim
@@ -232,13 +259,20 @@ def attention_forward(params, query, keys):
           "ctx": torch.empty(b, d, dtype=torch.float32, device=dev)}
     nbytes = _lib.lib().pc_p2v_attention_workspace_bytes_dim(b, n, d)
     ws = workspace(nbytes, dev)
+    if key_pad is not None:
+        sv["key_pad"] = _key_pad(key_pad, b, n)
+        check(_lib.lib().pc_p2v_attention_forward_masked(ctypes.byref(st), _p(query), _p(keys), _p(sv["key_pad"]), b, n, _p(out),
+                                                         ctypes.byref(_attn_saved(sv)), _p(ws), nbytes, _stream()),
+              "pc_p2v_attention_forward_masked")
+        return out, sv
     check(_lib.lib().pc_p2v_attention_forward(ctypes.byref(st), _p(query), _p(keys), b, n, _p(out),
                                               ctypes.byref(_attn_saved(sv)), _p(ws), nbytes, _stream()),
           "pc_p2v_attention_forward")
     return out, sv
 
 
-def attention_backward(params, query, keys, dout, sv, grads=None, accumulate=False):
+def attention_backward(params, query, keys, dout, sv, grads=None, accumulate=False, key_pad=None):
+    """key_pad: the mask of the forward call (default: the one that call saved); dkeys of padding slots are zeros."""
     st, dev = p2v_struct(params)
     b, n, _ = keys.shape
     d = st.dim
@@ -251,6 +285,13 @@ def attention_backward(params, query, keys, dout, sv, grads=None, accumulate=Fal
     dk = torch.empty(b, n, d, dtype=torch.float32, device=dev)
     nbytes = _lib.lib().pc_p2v_attention_workspace_bytes_dim(b, n, d)
     ws = workspace(nbytes, dev)
+    kp = _key_pad(key_pad, b, n) if key_pad is not None else sv.get("key_pad")
+    if kp is not None:
+        check(_lib.lib().pc_p2v_attention_backward_masked(ctypes.byref(st), ctypes.byref(gst), _p(query), _p(keys), _p(kp), b, n,
+                                                          _p(dout), ctypes.byref(_attn_saved(sv)), _p(dq), _p(dk),
+                                                          1 if accumulate else 0, _p(ws), nbytes, _stream()),
+              "pc_p2v_attention_backward_masked")
+        return grads, dq, dk
     check(_lib.lib().pc_p2v_attention_backward(ctypes.byref(st), ctypes.byref(gst), _p(query), _p(keys), b, n,
                                                _p(dout), ctypes.byref(_attn_saved(sv)), _p(dq), _p(dk),
                                                1 if accumulate else 0, _p(ws), nbytes, _stream()),
@@ -539,7 +580,7 @@ BN_SYNC_DOUBLES = PC_MAX_SEG * 2 * H + PC_MAX_SEG
 
 
 def p2v_train_step(params, grads, table, anchor_idx, positive_idx, negative_idx, neighbor_idx, margin,
-                   want_emb=False, profile=None, sync_reduce=None, adam=None, structs=None):
+                   want_emb=False, profile=None, sync_reduce=None, adam=None, structs=None, masked=False):
     """One loop-body iteration of Product2Vec.train_model in index form (grads overwritten).
 
     sync_reduce: None = BatchNorm statistics of this batch; else a callable `reduce(buf)` that sums a
@@ -553,7 +594,18 @@ def p2v_train_step(params, grads, table, anchor_idx, positive_idx, negative_idx,
 
     structs: (st, gst, dev) built earlier by p2v_struct over the SAME tensors (a training loop whose parameters are views of
     fixed flat buffers builds them once: ~25 tensor checks per step less between a drained device and the step's first launch);
-    the dropout entry of `params` is applied to it per call."""
+    the dropout entry of `params` is applied to it per call.
+
+    masked: the key-padding mask, a labelled deviation from the reference (pc_p2v_train_step_compact_masked / _unique_masked):
+    the -1 slots are no keys of the attention and the neighbour call's BatchNorm spans the real slots only.  A dense [B,N] index
+    matrix goes through compact_neighbors (one host pass); a unique layout carries "n_real", its number of real slots
+    (unique_neighbors returns it; the device loader knows it).  Not with sync_reduce."""
+    if masked and sync_reduce is not None:
+        raise ValueError("p2v_train_step(masked=True): cross-replica (sync_reduce) masked BatchNorm statistics are not built")
+    masked = bool(masked) and neighbor_idx is not None          # (no neighbour slots: nothing to mask)
+    if masked and neighbor_idx is not None and not isinstance(neighbor_idx, dict):
+        _req(neighbor_idx, torch.int32, "neighbor_idx")
+        neighbor_idx = compact_neighbors(neighbor_idx)
     if structs is not None:
         st, gst, dev = structs
         st.dropout.p = 0.0
@@ -626,6 +678,22 @@ def p2v_train_step(params, grads, table, anchor_idx, positive_idx, negative_idx,
     if adam is not None and not unique:
         raise ValueError("p2v_train_step(adam=...): the unique-neighbour layout (the device loader's) carries the fused optimizer step")
     step_rows = neighbor_idx.get("step_rows") if unique else None
+    if masked:
+        if unique:
+            if neighbor_idx.get("n_real") is None:
+                raise ValueError('p2v_train_step(masked=True): the unique layout needs "n_real", its number of real slots')
+            if step_rows is not None:
+                _req(step_rows, torch.int32, "step_rows")
+                if step_rows.numel() < b * (2 + k) + n_real + 1:
+                    raise ValueError("step_rows shorter than B * (2 + K) + n_unique + 1")
+            triplet = (_p(anchor_idx), _p(positive_idx), _p(negative_idx))
+            check(lib.pc_p2v_train_step_unique_masked(*head, *triplet, _p(step_rows), *layout[:3], int(neighbor_idx["n_real"]),
+                                                      *layout[3:], *sizes, *outs, prof, *wsa, _adam_fused(adam), _stream()),
+                  "pc_p2v_train_step_unique_masked")
+        else:
+            check(lib.pc_p2v_train_step_compact_masked(*head, _p(anchor_idx), _p(positive_idx), _p(negative_idx), *layout, *sizes,
+                                                       *outs, prof, *wsa, _stream()), "pc_p2v_train_step_compact_masked")
+        return out
     if step_rows is not None:
         # the loader concatenated the step's row indices behind its builder (concat_step_rows): the step starts with Linear0
         _req(step_rows, torch.int32, "step_rows")
@@ -815,7 +883,7 @@ def unique_neighbors(neighbor_idx):
     dev = neighbor_idx.device
     return {"nb_rows": torch.from_numpy(nb_rows).to(dev), "weight": torch.from_numpy(weight).to(dev),
             "slot_row": torch.from_numpy(slot).to(dev), "ref_off": torch.from_numpy(ref_off).to(dev),
-            "ref_slot": torch.from_numpy(order).to(dev), "n_unique": int(len(u))}
+            "ref_slot": torch.from_numpy(order).to(dev), "n_unique": int(len(u)), "n_real": int(real.sum())}
 
 
 def compact_neighbors(neighbor_idx):

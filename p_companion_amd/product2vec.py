@@ -33,12 +33,15 @@ _ATT_KEYS = ops.P2V_KEYS[8:]
 
 
 class _FFNFunction(torch.autograd.Function):
-    """get_initial_embedding on a [R,128] block, training mode (product2vec.py:31-46)."""
+    """get_initial_embedding on a [R,128] block, training mode (product2vec.py:31-46).
+    row_weight / count (key-padding mask only, else None): fp32 [R] with 0 for a padding row and the number of real rows --
+    BatchNorm's statistics, running-statistics update and backward sums then span the real rows."""
 
     @staticmethod
-    def forward(ctx, module, x, *weights):
+    def forward(ctx, module, x, row_weight, count, *weights):
         params = module._tensor_dict()
-        y, sv = ops.ffn_forward_train(params, x, None, x.shape[0], [0], update_running=True)
+        y, sv = ops.ffn_forward_train(params, x, None, x.shape[0], [0], update_running=True, row_weight=row_weight,
+                                      counts=None if count is None else [count])
         ctx.module, ctx.sv = module, sv
         ctx.save_for_backward(x)
         return y
@@ -48,17 +51,18 @@ class _FFNFunction(torch.autograd.Function):
         (x,) = ctx.saved_tensors
         params = ctx.module._tensor_dict()
         grads, dx = ops.ffn_backward(params, x, None, dy.contiguous(), ctx.sv, need_dx=ctx.needs_input_grad[1])
-        return (None, dx) + tuple(grads[k] for k in _FFN_KEYS)
+        return (None, dx, None, None) + tuple(grads[k] for k in _FFN_KEYS)
 
 
 class _AttentionFunction(torch.autograd.Function):
-    """apply_attention (product2vec.py:48-68): query [B,D], keys [B,N,D] -> [B,D]."""
+    """apply_attention (product2vec.py:48-68): query [B,D], keys [B,N,D] -> [B,D].  key_pad: None, or the [B,N] key-padding
+    mask (True = padding; the backward reads it from the saved state)."""
 
     @staticmethod
-    def forward(ctx, module, query, keys, *weights):
+    def forward(ctx, module, query, keys, key_pad, *weights):
         ctx.dropout = module._next_dropout()                 # one fresh mask per forward; the backward regenerates it
         params = module._tensor_dict(ctx.dropout)
-        out, sv = ops.attention_forward(params, query, keys)
+        out, sv = ops.attention_forward(params, query, keys, key_pad=key_pad)
         ctx.module, ctx.sv = module, sv
         ctx.save_for_backward(query, keys)
         return out
@@ -68,7 +72,7 @@ class _AttentionFunction(torch.autograd.Function):
         query, keys = ctx.saved_tensors
         params = ctx.module._tensor_dict(ctx.dropout)
         grads, dq, dk = ops.attention_backward(params, query, keys, dout.contiguous(), ctx.sv)
-        return (None, dq, dk) + tuple(grads[k] for k in _ATT_KEYS)
+        return (None, dq, dk, None) + tuple(grads[k] for k in _ATT_KEYS)
 
 
 class _NoEvalBackward(torch.autograd.Function):
@@ -121,7 +125,7 @@ class _FusedDenseLoss(torch.autograd.Function):
     in forward and handed to autograd in backward (scaled by the incoming gradient)."""
 
     @staticmethod
-    def forward(ctx, module, anchor, positive, negative, neighbors, *weights):
+    def forward(ctx, module, anchor, positive, negative, neighbors, key_pad, *weights):
         b, k, n = anchor.shape[0], negative.shape[1], neighbors.shape[1]
         dev = anchor.device
         d = anchor.shape[1]
@@ -135,14 +139,18 @@ class _FusedDenseLoss(torch.autograd.Function):
             module._dense_idx[key] = idx
         names = [nm for nm, _ in module.named_parameters()]
         grads = {nm: torch.empty_like(w) for nm, w in zip(names, weights)}
-        out = ops.p2v_train_step(module._tensor_dict(module._next_dropout()), grads, table, idx[0], idx[1], idx[2], idx[3],
-                                 float(module.config.MARGIN))
+        nbr = idx[3]
+        if key_pad is not None:
+            # the key-padding mask (config.ATTENTION_KEY_MASK): a padding slot is index -1 of the masked step
+            nbr = torch.where(key_pad, torch.full_like(nbr, -1), nbr)
+        out = ops.p2v_train_step(module._tensor_dict(module._next_dropout()), grads, table, idx[0], idx[1], idx[2], nbr,
+                                 float(module.config.MARGIN), masked=key_pad is not None)
         ctx.grads = [grads[nm] for nm in names]
         return out["loss"].reshape(())
 
     @staticmethod
     def backward(ctx, g):
-        return (None, None, None, None, None) + tuple(torch._foreach_mul(ctx.grads, g))      # one multi-tensor launch
+        return (None, None, None, None, None, None) + tuple(torch._foreach_mul(ctx.grads, g))      # one multi-tensor launch
 
 
 class FusedAdam(torch.optim.Optimizer):
@@ -513,21 +521,47 @@ class Product2Vec(nn.Module, _FlatParamsMixin):
             return self._ffn(features.reshape(-1, D)).reshape(B, N, -1)
         raise ValueError(f"Unexpected input dimension: {features.dim()}")
 
-    def _ffn(self, x):
+    def _key_mask_on(self):
+        """config.ATTENTION_KEY_MASK, read at call time like MARGIN (a missing attribute means False): the key-padding mask, a
+        labelled deviation from the reference -- padding slots are no keys of the attention and stay out of the neighbour
+        call's BatchNorm statistics."""
+        return bool(getattr(self.config, "ATTENTION_KEY_MASK", False))
+
+    def _ffn(self, x, pad=None):
+        """pad (optional, bool [R], True = padding row): training-mode BatchNorm spans the other rows only.  Costs one host read
+        of the real-row count (this is the non-fused path).  No real row: the call does not happen (zeros come back, the
+        running statistics stay); exactly one: the error BatchNorm raises for one row."""
         x = self._dev(x)
         if self.training:
-            if x.shape[0] == 1:
+            row_weight = count = None
+            if pad is not None:
+                count = int((~pad).sum())
+                if count == 0:
+                    return torch.zeros(x.shape[0], self.dim, dtype=torch.float32, device=x.device)
+                row_weight = (~pad).to(torch.float32).contiguous()
+            if (x.shape[0] if count is None else count) == 1:
                 raise ValueError(f"Expected more than 1 value per channel when training, got input size {x.shape}")
             if torch.is_grad_enabled():
-                return _FFNFunction.apply(self, x, *self._weights(_FFN_KEYS))
-            y, _ = ops.ffn_forward_train(self._tensor_dict(), x, None, x.shape[0], [0], True)
+                return _FFNFunction.apply(self, x, row_weight, count, *self._weights(_FFN_KEYS))
+            y, _ = ops.ffn_forward_train(self._tensor_dict(), x, None, x.shape[0], [0], True, row_weight=row_weight,
+                                         counts=None if count is None else [count])
             return y
         with torch.no_grad():
             y = ops.ffn_forward_eval(self._tensor_dict(), x, None, x.shape[0])
         return _guard_eval(y, "Product2Vec.get_initial_embedding", [x] + list(self._weights(_FFN_KEYS)))
 
-    def apply_attention(self, query: torch.Tensor, key_value: torch.Tensor) -> torch.Tensor:
-        """Apply attention mechanism with proper reshaping (product2vec.py:48-68)."""
+    def _pad_mask(self, key_padding_mask, b, n):
+        m = key_padding_mask
+        if not isinstance(m, torch.Tensor) or m.dtype != torch.bool or tuple(m.shape) != (b, n):
+            raise ValueError(f"key_padding_mask: expected a bool tensor of shape {(b, n)} (True = padding)")
+        return m.to(self._device()).contiguous()
+
+    def apply_attention(self, query: torch.Tensor, key_value: torch.Tensor,
+                        key_padding_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Apply attention mechanism with proper reshaping (product2vec.py:48-68).
+        key_padding_mask (optional, bool [B,N], True = padding): nn.MultiheadAttention's argument of that name, which the
+        reference never passes -- a labelled deviation.  Padding slots are no keys; a sample without a real slot gets
+        out_proj.bias (torch gives NaN).  Training and eval mode."""
         if query.dim() == 1:
             query = query.unsqueeze(0).unsqueeze(0)
         elif query.dim() == 2:
@@ -539,11 +573,12 @@ class Product2Vec(nn.Module, _FlatParamsMixin):
                              "(the only use in product2vec.py:70-81)")
         q2 = self._dev(query[:, 0, :])
         kv = self._dev(key_value)
+        kp = None if key_padding_mask is None else self._pad_mask(key_padding_mask, kv.shape[0], kv.shape[1])
         if torch.is_grad_enabled() and self.training:
-            out = _AttentionFunction.apply(self, q2, kv, *self._weights(_ATT_KEYS))
+            out = _AttentionFunction.apply(self, q2, kv, kp, *self._weights(_ATT_KEYS))
         else:
             with torch.no_grad():
-                out, _ = ops.attention_forward(self._tensor_dict(self._next_dropout()), q2, kv)   # (dropout off in eval)
+                out, _ = ops.attention_forward(self._tensor_dict(self._next_dropout()), q2, kv, key_pad=kp)   # (dropout off in eval)
             if not self.training:
                 out = _guard_eval(out, "Product2Vec.apply_attention", [q2, kv] + list(self._weights(_ATT_KEYS)))
         out = out.unsqueeze(1)
@@ -553,10 +588,21 @@ class Product2Vec(nn.Module, _FlatParamsMixin):
             out = out.squeeze(1)
         return out
 
-    def forward(self, features: torch.Tensor, neighbors: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """Forward pass through Product2Vec model (product2vec.py:70-81)."""
+    def forward(self, features: torch.Tensor, neighbors: Optional[torch.Tensor] = None,
+                key_padding_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Forward pass through Product2Vec model (product2vec.py:70-81).
+        key_padding_mask (optional, bool [B,N] for neighbors [B,N,D], True = padding; a labelled deviation, see
+        apply_attention): the padding slots are no keys, and in training mode the neighbour call's BatchNorm spans the
+        unmasked rows only -- one host read of their count on this non-fused path."""
         embeddings = self.get_initial_embedding(features)
         if neighbors is not None and neighbors.size(0) > 0:
+            if key_padding_mask is not None:
+                if neighbors.dim() != 3:
+                    raise ValueError("key_padding_mask goes with neighbors of shape [B,N,D]")
+                B, N, D = neighbors.shape
+                kp = self._pad_mask(key_padding_mask, B, N)
+                neighbor_embeddings = self._ffn(neighbors.reshape(-1, D), pad=kp.reshape(-1)).reshape(B, N, -1)
+                return self.apply_attention(embeddings, neighbor_embeddings, kp)
             neighbor_embeddings = self.get_initial_embedding(neighbors)
             embeddings = self.apply_attention(embeddings, neighbor_embeddings)
         return embeddings
@@ -655,7 +701,8 @@ class Product2Vec(nn.Module, _FlatParamsMixin):
         sync_reduce: see ops.p2v_train_step (cross-replica BatchNorm statistics for data-parallel runs).
         optimizer (a FusedAdam over this module): product2vec.py:158's optimizer.step() as well -- inside the step's last
         gradient launch where the batch's layout carries it (the device loader's unique-neighbour batches, one process), by the
-        optimizer's own launch otherwise.  Either way the caller does NOT call optimizer.step() for this iteration."""
+        optimizer's own launch otherwise.  Either way the caller does NOT call optimizer.step() for this iteration.
+        config.ATTENTION_KEY_MASK (read per call): the masked step, see ops.p2v_train_step(masked=True); not with sync_reduce."""
         flat, gflat = self.flatten_parameters()
         # the tensor dicts and the C structs over them are rebuilt only when a buffer they describe has moved (the parameters and
         # gradients are views of the flat buffers; the BatchNorm buffers are checked by address): a module-tree walk and ~25
@@ -683,7 +730,7 @@ class Product2Vec(nn.Module, _FlatParamsMixin):
                 adam = optimizer.riding_state()
         out = ops.p2v_train_step(params, grads, table, batch["anchor_idx"], batch["positive_idx"],
                                  batch["negative_idx"], nbr, float(self.config.MARGIN), profile=profile,
-                                 sync_reduce=sync_reduce, adam=adam, structs=structs)
+                                 sync_reduce=sync_reduce, adam=adam, structs=structs, masked=self._key_mask_on())
         if adam is not None:
             optimizer.advance(1)                   # (only now: the step that carried update number adam["t"] has been accepted)
         elif optimizer is not None:
@@ -752,9 +799,17 @@ class Product2Vec(nn.Module, _FlatParamsMixin):
         return self.generate_all_embeddings(bpg)
 
     def dense_loss(self, batch):
-        """product2vec.py:132-154 on a dense reference batch (anchor/positive/negative[/anchor_neighbors])."""
+        """product2vec.py:132-154 on a dense reference batch (anchor/positive/negative[/anchor_neighbors]).
+        With config.ATTENTION_KEY_MASK the key-padding mask is the optional batch key anchor_neighbors_mask (bool [B,N], True =
+        padding) or, when the key is absent, the all-zero neighbour rows -- exactly what collate_fn appends, so a reference
+        loader works unchanged.  Without the flag the key is ignored."""
         nb = batch.get("anchor_neighbors")
         a, p, n = batch["anchor"], batch["positive"], batch["negative"]
+        kp = None
+        if self._key_mask_on() and nb is not None and nb.dim() == 3 and nb.shape[1] > 0:
+            kp = batch.get("anchor_neighbors_mask")
+            kp = (nb == 0).all(dim=-1) if kp is None else kp
+            kp = self._pad_mask(kp, nb.shape[0], nb.shape[1])
         if (self.training and torch.is_grad_enabled() and nb is not None and nb.dim() == 3 and nb.shape[0] == a.shape[0]
                 and nb.shape[1] > 0 and a.dim() == 2 and p.dim() == 2 and n.dim() == 3 and a.shape[0] > 1
                 and not any(t.requires_grad for t in (a, p, n, nb))):
@@ -762,8 +817,8 @@ class Product2Vec(nn.Module, _FlatParamsMixin):
             # sequence instead of four forward + four backward ones)
             dev = self.ffn[0].weight.device
             f = lambda t: t.to(device=dev, dtype=torch.float32).contiguous()
-            return _FusedDenseLoss.apply(self, f(a), f(p), f(n), f(nb), *[w for _, w in self.named_parameters()])
-        anchor_emb = self(batch["anchor"], batch.get("anchor_neighbors"))
+            return _FusedDenseLoss.apply(self, f(a), f(p), f(n), f(nb), kp, *[w for _, w in self.named_parameters()])
+        anchor_emb = self(batch["anchor"], batch.get("anchor_neighbors"), kp)
         positive_emb = self(batch["positive"])
         negative_emb = self(batch["negative"])
         if negative_emb.dim() == 2:
