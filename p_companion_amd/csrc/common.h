@@ -631,29 +631,73 @@ int triplet_loss_launch(const float* a, const float* p, const float* n, int batc
 int launch_dropout(const float* x, size_t n, const pc_dropout& d, unsigned stream_id, float* y, hipStream_t st);
 // ffn.hip
 int launch_transpose(const float* in, int rows, int cols, float* out, hipStream_t st);
-int ffn_forward_part1(const pc_p2v_tensors* p, const float* table, const int32_t* idx, int rows, const pc_segments* seg,
-                      const pc_ffn_saved* sv, double* local_sums, void* ws, size_t ws_bytes, void* stream);
-int ffn_forward_part2(const pc_p2v_tensors* p, int rows, const pc_segments* seg, int update_running, float* y,
-                      const pc_ffn_saved* sv, const double* global_sums, void* ws, size_t ws_bytes, void* stream,
-                      const TransposeBatch* ride = nullptr);
-int ffn_backward_part1(const pc_p2v_tensors* p, const pc_p2v_tensors* g, const float* table, const int32_t* idx,
-                       int rows, const pc_segments* seg, const float* dy, const pc_ffn_saved* sv, int with_dx,
-                       int accumulate, double* local_sums, void* ws, size_t ws_bytes, void* stream, int transposed,
-                       TnDefer* defer);
-int ffn_backward_part2(const pc_p2v_tensors* g, const float* table, const int32_t* idx, int rows,
-                       const pc_segments* seg, const pc_ffn_saved* sv, float* dx, int accumulate,
-                       const double* local_sums, const double* global_sums, void* ws, size_t ws_bytes, void* stream,
-                       TnDefer* defer);
+// One call of the FFN's launchers, by name: a caller builds one block and changes, between the four parts, only what differs.
+struct FfnCall {
+    // what every part reads (g: the backward parts)
+    const pc_p2v_tensors *p = nullptr, *g = nullptr;
+    const float* table = nullptr;
+    const int32_t* idx = nullptr;
+    int rows = 0;
+    const pc_segments* seg = nullptr;
+    const pc_ffn_saved* sv = nullptr;
+    void* ws = nullptr; size_t ws_bytes = 0; void* stream = nullptr;
+    // per part, off by default.  local_sums: forward / backward part 1 WRITE this replica's folded sums, backward part 2 reads them;
+    // global_sums: the statistics of all replicas (forward / backward part 2)
+    double* local_sums = nullptr; const double* global_sums = nullptr;
+    int update_running = 0; float* y = nullptr;                  // forward part 2
+    const TransposeBatch* ride = nullptr;                        // forward part 2: transposes riding in the BatchNorm finalize launch
+    const float* dy = nullptr; float* dx = nullptr;              // backward part 1 / part 2 (dx optional)
+    int with_dx = 0, transposed = 0;                             // backward part 1: W0^T joins the transposes / they are in the workspace already
+    int accumulate = 0;                                          // backward: 1: +=, 0: overwrite
+    TnDefer* defer = nullptr;                                    // backward: the slab sums join the caller's list
+};
+int ffn_forward_part1(const FfnCall& c);
+int ffn_forward_part2(const FfnCall& c);
+int ffn_backward_part1(const FfnCall& c);
+int ffn_backward_part2(const FfnCall& c);       // (takes the dimension from c.g: the gradient struct carries the same dim)
 int ffn_transposes(const pc_p2v_tensors* p, void* ws, int rows, int with_dx, TransposeBatch* tb);
 // attention.hip
 int attention_transposes(const pc_p2v_tensors* p, void* ws, int B, int N, int key_rows, TransposeBatch* tb, float* zero_bk);
-int attention_forward_impl(const pc_p2v_tensors* p, const float* query, const float* keys, int B, int N,
-                           int key_rows, const int32_t* slot_row, float* out, const pc_attn_saved* sv, void* ws,
-                           size_t ws_bytes, void* stream, int transposed, NtArgs* defer_out_chain, int masked = 0,
-                           const uint8_t* key_pad = nullptr);
-int attention_backward_impl(const pc_p2v_tensors* p, const pc_p2v_tensors* g, const float* query, const float* keys,
-                            int B, int N, int key_rows, const int32_t* slot_row, int pad_row, const float* dout,
-                            const pc_attn_saved* sv, float* dquery, float* dkeys, int accumulate, void* ws,
-                            size_t ws_bytes, void* stream, const int32_t* ref_off, const int32_t* ref_slot,
-                            int transposed, TnDefer* defer, const HingeMeanJob* rider, const LossPro* lossp,
-                            const NtArgs* fwd_out_chain, int masked = 0, const uint8_t* key_pad = nullptr);
+// One call of the attention block's launchers, by name; the defaults are "not used".
+struct AttnCall {
+    // both directions.  slot_row[B*N] (compact form): the key row of slot (b,n), keys[key_rows,D] holding each distinct row once
+    const pc_p2v_tensors* p = nullptr;
+    const float *query = nullptr, *keys = nullptr;
+    int B = 0, N = 0, key_rows = 0;
+    const int32_t* slot_row = nullptr;
+    const pc_attn_saved* sv = nullptr;
+    void* ws = nullptr; size_t ws_bytes = 0; void* stream = nullptr;
+    bool transposed = false;                    // attention_transposes' products are in the workspace already
+    bool masked = false;                        // the key-padding mask: slots mapped to the last key row, or flagged by key_pad[B*N] (dense)
+    const uint8_t* key_pad = nullptr;
+    // forward only
+    float* out = nullptr;
+    // backward only.  pad_row: the slot layouts' shared padding row; ref_off / ref_slot (unique-neighbour layout): row -> slots
+    const pc_p2v_tensors* g = nullptr;
+    int pad_row = -1;
+    const float* dout = nullptr;
+    float *dquery = nullptr, *dkeys = nullptr;
+    int accumulate = 0;
+    const int32_t *ref_off = nullptr, *ref_slot = nullptr;
+    // the fused step's riders: slab sums deferred to the step's reduce, hinge mean, hinge prologue, the forward's last chain
+    TnDefer* defer = nullptr;
+    const HingeMeanJob* rider = nullptr;
+    const LossPro* loss = nullptr;
+    const NtArgs* fwd_out_chain = nullptr;      // backward: runs in front of its first launch ...
+    NtArgs* defer_out_chain = nullptr;          // ... when the forward handed it back here instead of launching it (D = 128)
+};
+int attention_forward_impl(const AttnCall& c);
+int attention_backward_impl(const AttnCall& c);
+
+// ---- host helpers that several units used to restate ----------------------------------------
+// a plain C = A W^T (+ bias) product; `si`: the caller's segments, null: one segment of M rows
+static inline NtArgs nt_plain(const float* A, int lda, const float* W, int ldw, const float* bias, float* C, int ldc, int M,
+                              int N, int K, const SegInfo* si = nullptr) {
+    NtArgs a = {};
+    a.A = A; a.lda = lda; a.W = W; a.ldw = ldw; a.bias = bias; a.C = C; a.ldc = ldc;
+    a.M = M; a.N = N; a.K = K; a.seg = si ? *si : make_seginfo(nullptr, M, 128);
+    return a;
+}
+// PRODUCT_EMB_DIM of a parameter struct: dim = 0 means PC_D
+static inline bool p2v_dim_ok(const pc_p2v_tensors* p) { return p->dim == 0 || p->dim == 128 || p->dim == 256; }
+static inline int p2v_dim(const pc_p2v_tensors* p) { return p && p->dim == 256 ? 256 : PC_D; }

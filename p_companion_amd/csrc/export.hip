@@ -169,19 +169,11 @@ extern "C" size_t pc_p2v_export_workspace_bytes(int chunk_rows, int dim) {
     return export_ws_layout(nullptr, chunk_rows, dim).total;
 }
 
-static NtArgs nt_plain(const float* A, int lda, const float* W, int ldw, const float* bias, float* C, int ldc, int M,
-                       int N, int K) {
-    NtArgs a = {};
-    a.A = A; a.lda = lda; a.W = W; a.ldw = ldw; a.bias = bias; a.C = C; a.ldc = ldc;
-    a.M = M; a.N = N; a.K = K; a.seg = make_seginfo(nullptr, M, 128);
-    return a;
-}
-
 extern "C" int pc_p2v_export_embeddings(const pc_p2v_tensors* p, const float* features, int64_t n_products,
                                         const int32_t* cv_rowptr, const int32_t* cv_col, float* e1, float* out,
                                         int chunk_rows, void* ws, size_t ws_bytes, void* stream) {
     if (!p || !features || n_products <= 0 || !cv_rowptr || !cv_col || !e1 || !out || chunk_rows <= 0 || !ws) return PC_EINVAL;
-    if (p->dim != 0 && p->dim != 128 && p->dim != 256) return PC_ESHAPE;
+    if (!p2v_dim_ok(p)) return PC_ESHAPE;
     if (!p->w0 || !p->b0 || !p->gamma || !p->beta || !p->w3 || !p->b3 || !p->w5 || !p->b5 || !p->running_mean ||
         !p->running_var || !p->in_proj_w || !p->in_proj_b || !p->out_proj_w || !p->out_proj_b) return PC_EINVAL;
     if (n_products > INT32_MAX || chunk_rows > PC_EXPORT_MAX_CHUNK) return PC_ESHAPE;    // (node ids are int32)

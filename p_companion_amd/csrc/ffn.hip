@@ -260,79 +260,90 @@ extern "C" size_t pc_p2v_ffn_workspace_bytes(int rows) {
     return ffn_ws_layout(nullptr, rows).total;
 }
 
-static inline int p2v_dim(const pc_p2v_tensors* p) { return p && p->dim == 256 ? 256 : PC_D; }
-
 static int ffn_check(const pc_p2v_tensors* p, const float* table, int rows, const pc_segments* seg, void* ws,
                      size_t ws_bytes) {
     if (!p || !table || rows <= 0 || !ws) return PC_EINVAL;
-    if (p->dim != 0 && p->dim != 128 && p->dim != 256) return PC_ESHAPE;
+    if (!p2v_dim_ok(p)) return PC_ESHAPE;
     if (!p->w0 || !p->b0 || !p->gamma || !p->beta || !p->w3 || !p->b3 || !p->w5 || !p->b5) return PC_EINVAL;
     if (!seg_valid(seg, rows)) return PC_EINVAL;
     if (ws_bytes < pc_p2v_ffn_workspace_bytes(rows)) return PC_EWORKSPACE;
     return PC_OK;
 }
 
-static NtArgs nt_plain(const float* A, int lda, const float* W, int ldw, const float* bias, float* C, int ldc, int M,
-                       int N, int K, const SegInfo& si) {
-    NtArgs a = {};
-    a.A = A; a.lda = lda; a.W = W; a.ldw = ldw; a.bias = bias; a.C = C; a.ldc = ldc;
-    a.M = M; a.N = N; a.K = K; a.seg = si;
-    return a;
+// this replica's folded per-tile sums -> `local_sums` (the cross-replica exchange's input)
+static int launch_bn_fold(hipStream_t st, const FfnWs& w, const SegInfo& si, double* local_sums) {
+    PC_LAUNCH(bn_fold_kernel, dim3(PC_H / FIN_COLS), dim3(FIN_COLS, FIN_LANES), 0, st, w.stat_a, w.stat_b, si, local_sums);
+    return pc_launch_status();
+}
+
+// the BatchNorm-backward finalize as its own launch, on whichever queue the caller placed it
+static int launch_bn_finalize_bwd(hipStream_t st, const BnFinBwd& f, const SegInfo& si) {
+    PC_LAUNCH(bn_finalize_bwd_kernel, dim3(PC_H / FIN_COLS), dim3(FIN4_CG, FIN4_LANES), 0, st, f.psum, f.pdot, si, f.lsum, f.gsum, f.mean,
+              f.invstd, f.dgamma, f.dbeta, f.accumulate, f.c1, f.c2);
+    return pc_launch_status();
 }
 
 // part 1: gather + Linear0 + per-tile sums (+ this replica's folded sums into `local_sums` when exchanging);
 // part 2: statistics (from `global_sums` when given) -> BN-tanh -> Linear3 -> tanh -> Linear5
-int ffn_forward_part1(const pc_p2v_tensors* p, const float* table, const int32_t* idx, int rows, const pc_segments* seg,
-                      const pc_ffn_saved* sv, double* local_sums, void* ws, size_t ws_bytes, void* stream) {
-    PC_TRY(ffn_check(p, table, rows, seg, ws, ws_bytes));
+int ffn_forward_part1(const FfnCall& c) {
+    const pc_p2v_tensors* p = c.p;
+    const pc_ffn_saved* sv = c.sv;
+    const int rows = c.rows;
+    PC_TRY(ffn_check(p, c.table, rows, c.seg, c.ws, c.ws_bytes));
     if (!sv || !sv->h0 || !sv->a2 || !sv->bn_mean || !sv->bn_invstd || !sv->bn_scale || !sv->bn_shift) return PC_EINVAL;
-    hipStream_t st = (hipStream_t)stream;
+    hipStream_t st = (hipStream_t)c.stream;
     const int D = p2v_dim(p);
-    const SegInfo si = make_seginfo(seg, rows, 128);
-    FfnWs w = ffn_ws_layout(ws, rows);
-    NtArgs g1 = nt_plain(table, D, p->w0, D, p->b0, sv->h0, PC_H, rows, PC_H, D, si);
-    g1.gather = idx;
+    const SegInfo si = make_seginfo(c.seg, rows, 128);
+    FfnWs w = ffn_ws_layout(c.ws, rows);
+    NtArgs g1 = nt_plain(c.table, D, p->w0, D, p->b0, sv->h0, PC_H, rows, PC_H, D, &si);
+    g1.gather = c.idx;
     g1.stats = NT_STAT_SUMSQ; g1.stat_sum = w.stat_a; g1.stat_aux = w.stat_b;
     PC_TRY(launch_gemm_nt(g1, st));
-    if (local_sums) {
-        PC_LAUNCH(bn_fold_kernel, dim3(PC_H / FIN_COLS), dim3(FIN_COLS, FIN_LANES), 0, st, w.stat_a, w.stat_b, si, local_sums);
-        PC_TRY(pc_launch_status());
-    }
+    if (c.local_sums) PC_TRY(launch_bn_fold(st, w, si, c.local_sums));
     return PC_OK;
 }
 
-int ffn_forward_part2(const pc_p2v_tensors* p, int rows, const pc_segments* seg, int update_running, float* y,
-                      const pc_ffn_saved* sv, const double* global_sums, void* ws, size_t ws_bytes, void* stream,
-                      const TransposeBatch* ride) {
-    if (!y || (update_running && (!p->running_mean || !p->running_var))) return PC_EINVAL;
-    hipStream_t st = (hipStream_t)stream;
-    const SegInfo si = make_seginfo(seg, rows, 128);
-    FfnWs w = ffn_ws_layout(ws, rows);
+int ffn_forward_part2(const FfnCall& c) {
+    const pc_p2v_tensors* p = c.p;
+    const pc_ffn_saved* sv = c.sv;
+    const int rows = c.rows;
+    if (!c.y || (c.update_running && (!p->running_mean || !p->running_var))) return PC_EINVAL;
+    hipStream_t st = (hipStream_t)c.stream;
+    const SegInfo si = make_seginfo(c.seg, rows, 128);
+    FfnWs w = ffn_ws_layout(c.ws, rows);
     TransposeBatch tb = {};
     int tiles_x = 0, tiles_y = 0;
-    if (ride && ride->n > 0) { tb = *ride; transpose_batch_tiles(tb, &tiles_x, &tiles_y); }
+    if (c.ride && c.ride->n > 0) { tb = *c.ride; transpose_batch_tiles(tb, &tiles_x, &tiles_y); }
     PC_LAUNCH(bn_finalize_fwd_kernel, dim3(PC_H / FIN_COLS + tiles_x * tiles_y * tb.n), dim3(FIN4_CG, FIN4_LANES), 0, st, w.stat_a,
-              w.stat_b, si, global_sums, p->gamma, p->beta, p->running_mean, p->running_var, p->num_batches_tracked, update_running,
-              sv->bn_mean, sv->bn_invstd, sv->bn_scale, sv->bn_shift, tb, tiles_x, tiles_y);
+              w.stat_b, si, c.global_sums, p->gamma, p->beta, p->running_mean, p->running_var, p->num_batches_tracked,
+              c.update_running, sv->bn_mean, sv->bn_invstd, sv->bn_scale, sv->bn_shift, tb, tiles_x, tiles_y);
     PC_TRY(pc_launch_status());
 
-    NtArgs g2 = nt_plain(sv->h0, PC_H, p->w3, PC_H, p->b3, sv->a2, PC_H, rows, PC_H, PC_H, si);
+    NtArgs g2 = nt_plain(sv->h0, PC_H, p->w3, PC_H, p->b3, sv->a2, PC_H, rows, PC_H, PC_H, &si);
     g2.prologue = NT_PRO_BNTANH; g2.pscale = sv->bn_scale; g2.pshift = sv->bn_shift;
     g2.pro_out = sv->a1; g2.ldpo = PC_H;               // A1 = tanh(BN(H0)) leaves the kernel that forms it anyway (dW3 reads it)
     g2.epilogue = NT_EPI_TANH;
     PC_TRY(launch_gemm_nt(g2, st));
 
     const int D = p2v_dim(p);
-    NtArgs g3 = nt_plain(sv->a2, PC_H, p->w5, PC_H, p->b5, y, D, rows, D, PC_H, si);
+    NtArgs g3 = nt_plain(sv->a2, PC_H, p->w5, PC_H, p->b5, c.y, D, rows, D, PC_H, &si);
     return launch_gemm_nt(g3, st);
 }
+
+// what the train-forward and backward entries pass through unchanged
+#define FFN_COMMON(c)                                                                                   \
+    c.p = p; c.table = table; c.idx = idx; c.rows = rows; c.seg = seg; c.sv = sv;                       \
+    c.ws = ws; c.ws_bytes = ws_bytes; c.stream = stream
 
 extern "C" int pc_p2v_ffn_forward_train(const pc_p2v_tensors* p, const float* table, const int32_t* idx, int rows,
                                         const pc_segments* seg, int update_running, float* y,
                                         const pc_ffn_saved* sv, void* ws, size_t ws_bytes, void* stream) {
     if (!y) return PC_EINVAL;
-    PC_TRY(ffn_forward_part1(p, table, idx, rows, seg, sv, nullptr, ws, ws_bytes, stream));
-    return ffn_forward_part2(p, rows, seg, update_running, y, sv, nullptr, ws, ws_bytes, stream, nullptr);
+    FfnCall c;
+    FFN_COMMON(c);
+    c.update_running = update_running; c.y = y;
+    PC_TRY(ffn_forward_part1(c));
+    return ffn_forward_part2(c);
 }
 
 extern "C" int pc_p2v_ffn_forward_eval(const pc_p2v_tensors* p, const float* table, const int32_t* idx, int rows,
@@ -348,14 +359,14 @@ extern "C" int pc_p2v_ffn_forward_eval(const pc_p2v_tensors* p, const float* tab
                        p->running_var, w.coef, w.coef + PC_H);
     PC_TRY(pc_launch_status());
     const int D = p2v_dim(p);
-    NtArgs g1 = nt_plain(table, D, p->w0, D, p->b0, h0, PC_H, rows, PC_H, D, si);
+    NtArgs g1 = nt_plain(table, D, p->w0, D, p->b0, h0, PC_H, rows, PC_H, D, &si);
     g1.gather = idx;
     PC_TRY(launch_gemm_nt(g1, st));
-    NtArgs g2 = nt_plain(h0, PC_H, p->w3, PC_H, p->b3, a2, PC_H, rows, PC_H, PC_H, si);
+    NtArgs g2 = nt_plain(h0, PC_H, p->w3, PC_H, p->b3, a2, PC_H, rows, PC_H, PC_H, &si);
     g2.prologue = NT_PRO_BNTANH; g2.pscale = w.coef; g2.pshift = w.coef + PC_H;
     g2.epilogue = NT_EPI_TANH;
     PC_TRY(launch_gemm_nt(g2, st));
-    NtArgs g3 = nt_plain(a2, PC_H, p->w5, PC_H, p->b5, y, D, rows, D, PC_H, si);
+    NtArgs g3 = nt_plain(a2, PC_H, p->w5, PC_H, p->b5, y, D, rows, D, PC_H, &si);
     return launch_gemm_nt(g3, st);
 }
 
@@ -374,29 +385,30 @@ int ffn_transposes(const pc_p2v_tensors* p, void* ws, int rows, int with_dx, Tra
 
 // transposed != 0: ffn_transposes' products are in the workspace already (the fused step forms every transposed weight
 // of the step in one launch).  defer (optional): the slab sums join the caller's list instead of being launched here.
-int ffn_backward_part1(const pc_p2v_tensors* p, const pc_p2v_tensors* g, const float* table, const int32_t* idx,
-                       int rows, const pc_segments* seg, const float* dy, const pc_ffn_saved* sv, int with_dx,
-                       int accumulate, double* local_sums, void* ws, size_t ws_bytes, void* stream, int transposed,
-                       TnDefer* defer) {
-    PC_TRY(ffn_check(p, table, rows, seg, ws, ws_bytes));
+int ffn_backward_part1(const FfnCall& c) {
+    const pc_p2v_tensors *p = c.p, *g = c.g;
+    const pc_ffn_saved* sv = c.sv;
+    const float* dy = c.dy;
+    const int rows = c.rows, accumulate = c.accumulate;
+    PC_TRY(ffn_check(p, c.table, rows, c.seg, c.ws, c.ws_bytes));
     if (!g || !dy || !sv || !sv->h0 || !sv->a2) return PC_EINVAL;
     if (!g->w0 || !g->b0 || !g->gamma || !g->beta || !g->w3 || !g->b3 || !g->w5 || !g->b5) return PC_EINVAL;
-    hipStream_t st = (hipStream_t)stream;
-    const SegInfo si = make_seginfo(seg, rows, 128);
-    FfnWs w = ffn_ws_layout(ws, rows);
+    hipStream_t st = (hipStream_t)c.stream;
+    const SegInfo si = make_seginfo(c.seg, rows, 128);
+    FfnWs w = ffn_ws_layout(c.ws, rows);
     TnDefer own;
     tn_defer_init(&own);
-    TnDefer* df = defer ? defer : &own;
+    TnDefer* df = c.defer ? c.defer : &own;
 
     const int D = p2v_dim(p);
-    if (!transposed) {
+    if (!c.transposed) {
         TransposeBatch tb = {};
-        PC_TRY(ffn_transposes(p, ws, rows, with_dx, &tb));
+        PC_TRY(ffn_transposes(p, c.ws, rows, c.with_dx, &tb));
         PC_TRY(launch_transpose_batch(tb, st));
     }
 
     // dZ2 = (dY W5) * (1 - A2^2)
-    NtArgs b1 = nt_plain(dy, D, w.w5t, D, nullptr, w.dz2, PC_H, rows, PC_H, D, si);
+    NtArgs b1 = nt_plain(dy, D, w.w5t, D, nullptr, w.dz2, PC_H, rows, PC_H, D, &si);
     b1.epilogue = NT_EPI_DTANH; b1.aux = sv->a2; b1.ldaux = PC_H;
     PC_TRY(launch_gemm_nt(b1, st));
 
@@ -415,12 +427,12 @@ int ffn_backward_part1(const pc_p2v_tensors* p, const pc_p2v_tensors* g, const f
     }
 
     // dZ1 = (dZ2 W3) * (1 - A1^2), A1 = tanh(BN(H0)); plus BN-backward partial sums
-    NtArgs b2 = nt_plain(w.dz2, PC_H, w.w3t, PC_H, nullptr, w.dz1, PC_H, rows, PC_H, PC_H, si);
+    NtArgs b2 = nt_plain(w.dz2, PC_H, w.w3t, PC_H, nullptr, w.dz1, PC_H, rows, PC_H, PC_H, &si);
     b2.epilogue = NT_EPI_DTANH_BN; b2.aux = sv->h0; b2.ldaux = PC_H; b2.escale = sv->bn_scale; b2.eshift = sv->bn_shift;
     b2.stats = NT_STAT_BNBWD; b2.stat_sum = w.stat_a; b2.stat_aux = w.stat_b;
     PC_TRY(launch_gemm_nt(b2, st));
     TnRider fin_rider = {};
-    if (df->fork && !local_sums) {
+    if (df->fork && !c.local_sums) {
         // the BatchNorm-backward finalize (only dW0 reads c1 / c2).  Rounds 3-5: on the side queue beside dW3 -- the fork and the
         // join each cost the main queue ~6.5 us (profiles/r06a_step_timeline.md) and the 8-workgroup kernel took 12-32 us there.
         // Round 6: on the step's own queue, between dZ1 and dW3: 12-14 us exposed, no hops, -8 us per step in A/B
@@ -430,9 +442,7 @@ int ffn_backward_part1(const pc_p2v_tensors* p, const pc_p2v_tensors* g, const f
         const BnFinBwd fin = {w.stat_a, w.stat_b, nullptr, nullptr, sv->bn_mean, sv->bn_invstd, g->gamma, g->beta, accumulate, w.c1, w.c2};
         if (pc_opt_bn_finalize_side()) {
             PC_TRY(pc_fork_begin(df->fork, 1, st));
-            PC_LAUNCH(bn_finalize_bwd_kernel, dim3(PC_H / FIN_COLS), dim3(FIN4_CG, FIN4_LANES), 0, df->fork->side, w.stat_a, w.stat_b, si,
-                      nullptr, nullptr, sv->bn_mean, sv->bn_invstd, g->gamma, g->beta, accumulate, w.c1, w.c2);
-            PC_TRY(pc_launch_status());
+            PC_TRY(launch_bn_finalize_bwd(df->fork->side, fin, si));
             df->bn_finalized = 1;
         } else if (pc_opt_bn_finalize_rides() && sv->a1 && rows >= 8192 && (size_t)128 * ((size_t)128 * PC_H + 128) <= w.slab_floats) {
             fin_rider.n = PC_TN_RIDERS;                      // (the same condition as the halves launch of dW3 below)
@@ -440,9 +450,7 @@ int ffn_backward_part1(const pc_p2v_tensors* p, const pc_p2v_tensors* g, const f
             fin_rider.si = si;
             df->bn_finalized = 2;                            // done by the time dW3 is: nothing to launch, nothing to join
         } else {
-            PC_LAUNCH(bn_finalize_bwd_kernel, dim3(PC_H / FIN_COLS), dim3(FIN4_CG, FIN4_LANES), 0, st, w.stat_a, w.stat_b, si,
-                      nullptr, nullptr, sv->bn_mean, sv->bn_invstd, g->gamma, g->beta, accumulate, w.c1, w.c2);
-            PC_TRY(pc_launch_status());
+            PC_TRY(launch_bn_finalize_bwd(st, fin, si));
             df->bn_finalized = 2;                            // done, on the step's queue: nothing to join
         }
     }
@@ -473,35 +481,34 @@ int ffn_backward_part1(const pc_p2v_tensors* p, const pc_p2v_tensors* g, const f
     } else {
         PC_TRY(launch_gemm_tn(t3, st, df));
     }
-    if (local_sums) {
-        PC_LAUNCH(bn_fold_kernel, dim3(PC_H / FIN_COLS), dim3(FIN_COLS, FIN_LANES), 0, st, w.stat_a, w.stat_b, si, local_sums);
-        PC_TRY(pc_launch_status());
-    }
-    if (!defer) PC_TRY(launch_tn_reduce_deferred(&own, st));
+    if (c.local_sums) PC_TRY(launch_bn_fold(st, w, si, c.local_sums));
+    if (!c.defer) PC_TRY(launch_tn_reduce_deferred(&own, st));
     return PC_OK;
 }
 
-int ffn_backward_part2(const pc_p2v_tensors* g, const float* table, const int32_t* idx, int rows,
-                       const pc_segments* seg, const pc_ffn_saved* sv, float* dx, int accumulate,
-                       const double* local_sums, const double* global_sums, void* ws, size_t ws_bytes, void* stream,
-                       TnDefer* defer) {
-    hipStream_t st = (hipStream_t)stream;
-    const SegInfo si = make_seginfo(seg, rows, 128);
-    FfnWs w = ffn_ws_layout(ws, rows);
+int ffn_backward_part2(const FfnCall& c) {
+    const pc_p2v_tensors* g = c.g;
+    const pc_ffn_saved* sv = c.sv;
+    float* const dx = c.dx;
+    const int rows = c.rows, accumulate = c.accumulate;
+    TnDefer* const defer = c.defer;
+    hipStream_t st = (hipStream_t)c.stream;
+    const SegInfo si = make_seginfo(c.seg, rows, 128);
+    FfnWs w = ffn_ws_layout(c.ws, rows);
     if (defer && defer->bn_finalized) {
-        if (local_sums || global_sums) return PC_EINVAL;
+        if (c.local_sums || c.global_sums) return PC_EINVAL;
         if (defer->bn_finalized == 1) PC_TRY(pc_fork_join(defer->fork, 0, st));      // part 1 ran the finalize on the side queue
     } else {
-        PC_LAUNCH(bn_finalize_bwd_kernel, dim3(PC_H / FIN_COLS), dim3(FIN4_CG, FIN4_LANES), 0, st, w.stat_a, w.stat_b, si, local_sums,
-                  global_sums, sv->bn_mean, sv->bn_invstd, g->gamma, g->beta, accumulate, w.c1, w.c2);
-        PC_TRY(pc_launch_status());
+        const BnFinBwd fin = {w.stat_a, w.stat_b, c.local_sums, c.global_sums, sv->bn_mean, sv->bn_invstd, g->gamma, g->beta, accumulate,
+                              w.c1, w.c2};
+        PC_TRY(launch_bn_finalize_bwd(st, fin, si));
     }
 
     // dW0 = dH0^T X (rows gathered again from the table), db0.  Without a dx consumer the BatchNorm
     // backward is applied to dZ1 on the fly inside the loader and dH0 never touches HBM.
     const int D = p2v_dim(g);                                     // (the gradient struct carries the same dim)
     TnArgs t0 = {};
-    t0.Z = w.dz1; t0.ldz = PC_H; t0.A = table; t0.lda = D; t0.gather = idx; t0.R = rows; t0.No = PC_H;
+    t0.Z = w.dz1; t0.ldz = PC_H; t0.A = c.table; t0.lda = D; t0.gather = c.idx; t0.R = rows; t0.No = PC_H;
     t0.Ni = D; t0.seg = si;
     t0.dW = g->w0; t0.lddw = D; t0.db = g->b0; t0.accumulate = accumulate; t0.slabs = w.slabs[3];
     t0.slab_floats = w.slab_floats;
@@ -518,7 +525,7 @@ int ffn_backward_part2(const pc_p2v_tensors* g, const float* table, const int32_
     PC_TRY(launch_gemm_tn(t0, st, defer));
 
     if (dx) {
-        NtArgs b3 = nt_plain(w.dz1, PC_H, w.w0t, PC_H, nullptr, dx, D, rows, D, PC_H, si);
+        NtArgs b3 = nt_plain(w.dz1, PC_H, w.w0t, PC_H, nullptr, dx, D, rows, D, PC_H, &si);
         PC_TRY(launch_gemm_nt(b3, st));
     }
     return PC_OK;
@@ -530,7 +537,10 @@ extern "C" int pc_p2v_ffn_backward(const pc_p2v_tensors* p, const pc_p2v_tensors
                                    void* stream) {
     TnDefer df;
     tn_defer_init(&df);
-    PC_TRY(ffn_backward_part1(p, g, table, idx, rows, seg, dy, sv, dx != nullptr, accumulate, nullptr, ws, ws_bytes, stream, 0, &df));
-    PC_TRY(ffn_backward_part2(g, table, idx, rows, seg, sv, dx, accumulate, nullptr, nullptr, ws, ws_bytes, stream, &df));
+    FfnCall c;
+    FFN_COMMON(c);
+    c.g = g; c.dy = dy; c.dx = dx; c.with_dx = dx != nullptr; c.accumulate = accumulate; c.defer = &df;
+    PC_TRY(ffn_backward_part1(c));
+    PC_TRY(ffn_backward_part2(c));
     return launch_tn_reduce_deferred(&df, (hipStream_t)stream);
 }

@@ -14,14 +14,6 @@
 #define JMAX_K 8   /* top-k capacity of topk_rows_kernel (NUM_COMP_TYPES = 3 in config.py:24) */
 #define LH (PC_L / 2)
 
-static NtArgs nt_plain(const float* A, int lda, const float* W, int ldw, const float* bias, float* C, int ldc, int M,
-                       int N, int K) {
-    NtArgs a = {};
-    a.A = A; a.lda = lda; a.W = W; a.ldw = ldw; a.bias = bias; a.C = C; a.ldc = ldc;
-    a.M = M; a.N = N; a.K = K; a.seg = make_seginfo(nullptr, M, 128);
-    return a;
-}
-
 // ---------------------------------------------------------------------------------------
 // Generic nn.Linear pieces (exported: the Python modules build their autograd on these).
 //   y = act(x W^T + b), x row r = idx ? x[idx[r]] : x[r];  act: 0 none, 1 tanh, 2 relu

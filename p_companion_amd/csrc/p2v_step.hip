@@ -170,8 +170,8 @@ static int p2v_step_impl(const P2VStepCall& c) {
         if (!c.nb_weight && c.n_real_slots != nbc - 1) return PC_EINVAL;      // (compact layout: one row per real slot)
         if (c.n_real_slots == 1) return PC_EBATCHNORM;           // a neighbour call of one row, as B == 1 above
     }
-    if (p->dim != 0 && p->dim != 128 && p->dim != 256) return PC_ESHAPE;
-    const int D = p->dim == 256 ? 256 : PC_D;
+    if (!p2v_dim_ok(p)) return PC_ESHAPE;
+    const int D = p2v_dim(p);
     if (c.ws_bytes < pc_p2v_train_step_workspace_bytes_dim(B, N, K, D)) return PC_EWORKSPACE;
     hipStream_t st = (hipStream_t)stream;
     StepWs w = step_ws_layout(c.ws, B, N, K, D);
@@ -208,6 +208,11 @@ static int p2v_step_impl(const P2VStepCall& c) {
     sv.h0 = w.h0; sv.a2 = w.a2; sv.a1 = w.a1;
     sv.bn_mean = w.bn; sv.bn_invstd = w.bn + PC_MAX_SEG * PC_H; sv.bn_scale = w.bn + 2 * PC_MAX_SEG * PC_H;
     sv.bn_shift = w.bn + 3 * PC_MAX_SEG * PC_H;
+    // the FFN's call block: its four parts differ in the fields set in front of each (the sums are set in the split phases
+    // alone, and each of those returns before another part could read them)
+    FfnCall fc;
+    fc.p = p; fc.g = g; fc.table = c.table; fc.idx = rows; fc.rows = R; fc.seg = &seg; fc.sv = &sv;
+    fc.ws = w.ffn_ws; fc.ws_bytes = w.ffn_bytes; fc.stream = stream;
     // every transposed weight of the step (attention: Wo^T, Wq^T, [Wk;Wv]^T; FFN backward: W5^T, W3^T): one launch, which also
     // clears the key-bias gradient (exactly 0, see attention.hip); in the unsplit step it is the SAME launch as the row-index
     // concatenation
@@ -230,16 +235,18 @@ static int p2v_step_impl(const P2VStepCall& c) {
                       c.negative_idx, B * K, w.idx_all);
         }
         PC_TRY(pc_launch_status());
-        PC_TRY(ffn_forward_part1(p, c.table, rows, R, &seg, &sv, phase == 0 ? c.fwd_sums : nullptr, w.ffn_ws, w.ffn_bytes,
-                                 stream));
+        fc.local_sums = phase == 0 ? c.fwd_sums : nullptr;
+        PC_TRY(ffn_forward_part1(fc));
         if (phase == 0) return PC_OK;
     }
-    if (p2 && !p1)
-        return ffn_backward_part2(g, c.table, rows, R, &seg, &sv, nullptr, 0, c.bwd_local, c.bwd_global, w.ffn_ws,
-                                  w.ffn_bytes, stream, nullptr);
+    if (p2 && !p1) {
+        fc.local_sums = c.bwd_local; fc.global_sums = c.bwd_global;
+        return ffn_backward_part2(fc);
+    }
     if (phase == 1) PC_TRY(launch_transpose_batch(tb, st));      // (the split step: phase 0 ran the concatenation alone)
-    PC_TRY(ffn_forward_part2(p, R, &seg, 1, w.y, &sv, phase == 1 ? c.fwd_sums : nullptr, w.ffn_ws, w.ffn_bytes, stream,
-                             rows_ready ? &tb : nullptr));
+    fc.update_running = 1; fc.y = w.y; fc.global_sums = phase == 1 ? c.fwd_sums : nullptr;
+    fc.ride = rows_ready ? &tb : nullptr;
+    PC_TRY(ffn_forward_part2(fc));
 
     pc_attn_saved as;
     as.q = w.q; as.qt = w.qt; as.probs = w.probs; as.c = w.c; as.sp = w.sp; as.ctx = w.ctx;
@@ -247,10 +254,14 @@ static int p2v_step_impl(const P2VStepCall& c) {
     // (D = 128 with neighbours, the hinge riding: the forward's out-projection chain is deferred into the backward's first launch)
     const bool out_chain_rides = N > 0 && D == 128 && K <= 8 && pc_opt_fused_loss() && pc_opt_fused_out_chain();
     NtArgs fwd_out_chain[2];
+    // the attention block's call block, forward and backward
+    AttnCall ac;
+    ac.p = p; ac.query = w.y + (size_t)rA * D; ac.keys = w.y + (size_t)rN * D; ac.B = B; ac.N = N; ac.key_rows = nbc;
+    ac.slot_row = slot_row; ac.sv = &as; ac.ws = w.attn_ws; ac.ws_bytes = w.attn_bytes; ac.stream = stream;
+    ac.transposed = true; ac.masked = c.masked;
     if (N > 0) {
-        PC_TRY(attention_forward_impl(p, w.y + (size_t)rA * D, w.y + (size_t)rN * D, B, N, nbc, slot_row, w.emb,
-                                      &as, w.attn_ws, w.attn_bytes, stream, 1, out_chain_rides ? fwd_out_chain : nullptr,
-                                      c.masked ? 1 : 0, nullptr));
+        ac.out = w.emb; ac.defer_out_chain = out_chain_rides ? fwd_out_chain : nullptr;
+        PC_TRY(attention_forward_impl(ac));
         emb = w.emb;
     }
 
@@ -285,11 +296,11 @@ static int p2v_step_impl(const P2VStepCall& c) {
         ~ForkGuard() { if (f && f->pending) (void)pc_fork_join(f, 1, st); }
     } fork_guard{df.fork, st};
     if (N > 0) {
-        PC_TRY(attention_backward_impl(p, g, w.y + (size_t)rA * D, w.y + (size_t)rN * D, B, N, nbc, slot_row,
-                                       slot_row ? nbc - 1 : -1, w.demb, &as, w.dy + (size_t)rA * D,
-                                       w.dy + (size_t)rN * D, 0, w.attn_ws, w.attn_bytes, stream, c.ref_off, c.ref_slot, 1, &df,
-                                       mean_rides ? &hm : nullptr, loss_rides ? &lp : nullptr,
-                                       out_chain_rides ? fwd_out_chain : nullptr, c.masked ? 1 : 0, nullptr));
+        ac.g = g; ac.pad_row = slot_row ? nbc - 1 : -1; ac.dout = w.demb;
+        ac.dquery = w.dy + (size_t)rA * D; ac.dkeys = w.dy + (size_t)rN * D; ac.ref_off = c.ref_off; ac.ref_slot = c.ref_slot;
+        ac.defer = &df; ac.rider = mean_rides ? &hm : nullptr; ac.loss = loss_rides ? &lp : nullptr;
+        ac.fwd_out_chain = out_chain_rides ? fwd_out_chain : nullptr;
+        PC_TRY(attention_backward_impl(ac));
         if (c.anchor_emb && out_chain_rides)                    // (the embedding exists once the backward's first launch has run)
             PC_HIP_TRY(hipMemcpyAsync(c.anchor_emb, emb, (size_t)B * D * 4, hipMemcpyDeviceToDevice, st));
     } else {
@@ -298,10 +309,10 @@ static int p2v_step_impl(const P2VStepCall& c) {
         PC_HIP_TRY(hipMemsetAsync(g->out_proj_w, 0, D * D * 4, st));
         PC_HIP_TRY(hipMemsetAsync(g->out_proj_b, 0, D * 4, st));
     }
-    PC_TRY(ffn_backward_part1(p, g, c.table, rows, R, &seg, w.dy, &sv, 0, 0, phase == 1 ? c.bwd_local : nullptr, w.ffn_ws,
-                              w.ffn_bytes, stream, 1, &df));
+    fc.dy = w.dy; fc.transposed = 1; fc.defer = &df; fc.local_sums = phase == 1 ? c.bwd_local : nullptr;
+    PC_TRY(ffn_backward_part1(fc));
     if (phase == 1) return launch_tn_reduce_deferred(&df, st);
-    PC_TRY(ffn_backward_part2(g, c.table, rows, R, &seg, &sv, nullptr, 0, nullptr, nullptr, w.ffn_ws, w.ffn_bytes, stream, &df));
+    PC_TRY(ffn_backward_part2(fc));
     return launch_tn_reduce_deferred(&df, st);
 }
 

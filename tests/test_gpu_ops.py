@@ -216,6 +216,29 @@ def test_ffn_backward(ops, starts, rows):
     close(dx, xin.grad, 2e-5, what="dx")
 
 
+def test_ffn_backward_without_the_saved_a1(ops):
+    """The optional saved A1 = tanh(BN(H0)) left out: dW3 is then ONE plain product whose loader recomputes A1 from H0 (with it,
+    dW3 runs as two halves).  The smallest of the shapes above with several segments and row tiles; the bounds of the test above."""
+    starts, rows = SEGS[2]
+    st = _state()
+    x, dy = rnd(rows, 128, seed=40), rnd(rows, 128, seed=41, scale=0.1)
+    leaves = {k: st[k].clone().requires_grad_(True) for k in p2v_oracle.TRAINABLE if k.startswith("ffn")}
+    work = {k: v.clone() for k, v in st.items()}
+    work.update(leaves)
+    bounds = list(starts) + [rows]
+    y = torch.cat([p2v_oracle.ffn(x[bounds[i]:bounds[i + 1]], work, True, update_running=False) for i in range(len(starts))])
+    (y * dy).sum().backward()
+    dst = _to_dev(st)
+    _, sv = ops.ffn_forward_train(dst, dev(x), None, rows, starts, update_running=False)
+    with_a1, _ = ops.ffn_backward(dst, dev(x), None, dev(dy), sv)
+    sv["a1"] = None
+    grads, _ = ops.ffn_backward(dst, dev(x), None, dev(dy), sv)
+    for k, leaf in leaves.items():
+        close(grads[k], leaf.grad, 2e-5 * max(1.0, float(leaf.grad.abs().max())), what=k)
+    # only dW3 / db3 read A1; everything else is the same launches on the same inputs
+    assert all(torch.equal(grads[k], with_a1[k]) for k in leaves if not k.startswith("ffn.3"))
+
+
 # ------------------------------------------------------------------ P7 attention
 @pytest.mark.parametrize("B,N", [(1, 1), (8, 6), (70, 33), (5, 48)])
 def test_attention(ops, B, N):
