@@ -1070,6 +1070,42 @@ int pc_rank_grouped(const float *proj, const int32_t *types, const int32_t *targ
                     int n_types, int num_products, int dim, int slices,
                     int32_t *rank_out, int32_t *bad_count, void *ws, size_t ws_bytes, void *stream);
 
+/* The two entries above with named products kept out (ABI 8, additive; PCompanionInference.set_exclusions: a complementary
+ * recommender must not serve the query itself, its co-viewed substitutes or what is in the basket, and the caller cannot strike
+ * them out afterwards -- a list of at most 16 whose head is taken comes back short, and a rank counts them in front of the
+ * held-out complement).  An exclusion set is a CSR over KEYS: ex_rowptr [n_keys + 1], ex_col [E], the ids of one key strictly
+ * ascending (searched by bisection; ops.exclusion_csr builds one from any device CSR).  row_key[r] in [-1, n_keys) names row r's
+ * list, -1 = none; a key outside that range is served as -1, never indexes memory and is counted in *bad_count (a device
+ * counter the caller owns; added to).  List ids outside the table are passed over.
+ *
+ * pc_retrieve_topk_grouped_excluding: out_idx / out_score = the first n products of the row's type that are NOT in the row's
+ * list, under pc_retrieve_topk_grouped's total order (score descending, product index ascending), -1 / -inf past the end.  The
+ * same plan, merge, tiling and score chain; a candidate is looked up in the list only after it has beaten its row's running
+ * threshold and is dropped before it enters a list, so it never moves the threshold.  The filter is a predicate of
+ * (row, product): the same bits for every `slices`, every placement of the rows and every order of type_col.  Error codes and
+ * workspace as pc_retrieve_topk_grouped (pc_retrieve_topk_grouped_excluding_workspace_bytes: the same size), PC_EINVAL also for
+ * a null row_key / ex_rowptr / ex_col / bad_count or n_keys < 0.
+ *
+ * pc_rank_grouped_excluding: cand_type [num_products] = the type under which product p is a candidate, -1 if it is none; it
+ * must agree with type_rowptr / type_col.  rank_out[r] = the number of NON-excluded products of type types[r] ordered in front
+ * of the target; -1 if the target is in the row's list or cand_type[targets[r]] != types[r]; -1 and *bad_count as
+ * pc_rank_grouped otherwise.  pc_rank_grouped's launches as they are, then one wave per row scores the row's list and its
+ * target through the same MFMA chain and takes the excluded products of the type that stand in front of the target off the
+ * count: rank_out[r] < n exactly when pc_retrieve_topk_grouped_excluding's top n holds the target at that position.  Workspace:
+ * pc_rank_grouped_workspace_bytes.  Error codes as pc_rank_grouped, PC_EINVAL also for a null row_key / ex_rowptr / ex_col /
+ * cand_type or n_keys < 0. */
+size_t pc_retrieve_topk_grouped_excluding_workspace_bytes(int rows, int n_types, int n, int slices);
+int pc_retrieve_topk_grouped_excluding(const float *proj, const int32_t *types, const int32_t *row_key, int rows,
+                                       const int32_t *type_rowptr, const int32_t *type_col, const float *table, int n_types,
+                                       const int32_t *ex_rowptr, const int32_t *ex_col, int n_keys, int n, int dim, int slices,
+                                       int32_t *out_idx, float *out_score, int32_t *bad_count, void *ws, size_t ws_bytes,
+                                       void *stream);
+int pc_rank_grouped_excluding(const float *proj, const int32_t *types, const int32_t *targets, const int32_t *row_key, int rows,
+                              const int32_t *type_rowptr, const int32_t *type_col, const float *table, int n_types,
+                              int num_products, const int32_t *ex_rowptr, const int32_t *ex_col, int n_keys,
+                              const int32_t *cand_type, int dim, int slices, int32_t *rank_out, int32_t *bad_count, void *ws,
+                              size_t ws_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,7 +11,9 @@ as a tiled fp32 GEMM; neither type_idx nor the features are copied to the host.
 
 rank_targets / evaluate_catalogue are not in the reference: they say where a KNOWN complement stands in what recommend_batch
 serves -- its rank among all products of its type (pc_rank_grouped: the grouped retrieval's schedule and score bits, the
-selection replaced by a count) -- and fold the held-out "test" pairs into hit@k / MRR / median rank."""
+selection replaced by a count) -- and fold the held-out "test" pairs into hit@k / MRR / median rank.
+set_exclusions / set_eligible keep the query, its co-viewed substitutes and unservable products out of both
+(pc_retrieve_topk_grouped_excluding / pc_rank_grouped_excluding)."""
 import os
 from typing import Any, Dict, List
 
@@ -50,9 +52,14 @@ class PCompanionInference:
         g = bpg.cuda(self.device)
         self.features = g["features"]
         self.type_idx = g["type_idx"]
+        self._graph = g
+        self.exclusions = None                 # (ex_rowptr, ex_col) keyed by query id: set_exclusions
+        self.eligible = None                   # [P] bool: set_eligible
+        self.cand_type = self.type_idx         # the type under which a product is a candidate (-1: none)
         if self.grouped:
             # the same CSR, built on the device: no host copy of type_idx, no host sort
             self.type_rowptr, self.type_col = ops.type_csr(self.type_idx, bpg.n_types)
+            self._all_products = (self.type_rowptr, self.type_col)
             return
         # bpg.get_products_by_type(t) (bpg.py:40-43): products of type t in node order
         order = np.argsort(bpg.type_idx, kind="stable").astype(np.int32)
@@ -60,6 +67,63 @@ class PCompanionInference:
         rowptr = np.concatenate([[0], np.cumsum(counts)]).astype(np.int32)
         self.type_rowptr = torch.from_numpy(rowptr).to(self.device)
         self.type_col = torch.from_numpy(order).to(self.device)
+        self._all_products = (self.type_rowptr, self.type_col)
+
+    def set_exclusions(self, rowptr=None, col=None, include_self=True):
+        """Keep named products out of what is served and ranked for a query: an exclusion set keyed by the QUERY product id.
+        Default: the graph's own co-view CSR (co-viewed products are substitutes) and, with include_self, the query itself,
+        through ops.exclusion_csr; rowptr / col: any device CSR over the products instead (a basket, say).  With a set installed
+        recommend_batch, rank_targets and evaluate_catalogue go through pc_retrieve_topk_grouped_excluding /
+        pc_rank_grouped_excluding with the query id as the row key of its K slots -- an uploaded IntBPG too: its arrays are on
+        the device, and the per-row kernel has no filter.  set_exclusions(False) removes the set.  Once per catalogue, off the
+        serving path."""
+        if rowptr is False:
+            self.exclusions = None
+            return self
+        if (rowptr is None) != (col is None):
+            raise ValueError("set_exclusions: pass rowptr and col together, or neither for the co-view graph")
+        if rowptr is None:
+            rowptr, col = self._graph["cv_rowptr"], self._graph["cv_col"]
+        p = int(self.features.shape[0])
+        if rowptr.numel() != p + 1:
+            raise ValueError(f"set_exclusions: the set is keyed by query id: rowptr must hold {p + 1} entries, got {rowptr.numel()}")
+        self.exclusions = ops.exclusion_csr(rowptr.to(self.device), col.to(self.device), include_self=include_self, num_products=p)
+        return self
+
+    def set_eligible(self, mask=None):
+        """Serve and rank over the eligible products only (in stock, not withdrawn): mask [P] bool on the device, None = all.
+        Rebuilds type_rowptr / type_col over the eligible products (ops.type_csr on the filtered ids) and forms
+        cand_type = where(mask, type_idx, -1); a held-out target that is not eligible gets rank -1."""
+        if mask is None:
+            self.eligible, self.cand_type = None, self.type_idx
+            self.type_rowptr, self.type_col = self._all_products
+            return self
+        p = int(self.features.shape[0])
+        if not torch.is_tensor(mask) or mask.dtype != torch.bool or tuple(mask.shape) != (p,):
+            raise ValueError(f"set_eligible: expected a bool tensor of shape ({p},)")
+        mask = mask.to(self.device)
+        ids = torch.nonzero(mask).reshape(-1).to(torch.int32)
+        rowptr, local = ops.type_csr(self.type_idx[ids.long()].contiguous(), self.bpg.n_types)
+        self.type_rowptr, self.type_col = rowptr, ids[local.long()].contiguous()
+        self.eligible = mask
+        self.cand_type = torch.where(mask, self.type_idx, torch.full_like(self.type_idx, -1))
+        return self
+
+    def _excluded(self, query_idx, target_idx):
+        """[B] bool: target_idx[b] is in query_idx[b]'s exclusion list (a bisection per pair, as vector operations; the lists
+        are strictly ascending)."""
+        ex_rowptr, ex_col = self.exclusions
+        q = query_idx.long()
+        lo, end = ex_rowptr[q].long(), ex_rowptr[q + 1].long()
+        hi = end.clone()
+        if ex_col.numel() == 0:
+            return torch.zeros_like(q, dtype=torch.bool)
+        y = target_idx.long()
+        for _ in range(max(int(ex_col.numel()).bit_length(), 1)):
+            mid = (lo + hi) >> 1
+            below = (lo < hi) & (ex_col[mid.clamp(max=ex_col.numel() - 1)].long() < y)
+            lo, hi = torch.where(below, mid + 1, lo), torch.where(below | (lo >= hi), hi, mid)
+        return (lo < end) & (ex_col[lo.clamp(max=ex_col.numel() - 1)].long() == y)
 
     def _load_model(self, model_path):
         """Load trained model weights (inference.py:28-36)"""
@@ -93,10 +157,16 @@ class PCompanionInference:
         out = self.model(batch)
         types = out["complementary_types"]
         b, k = types.shape
-        retrieve = ops.retrieve_topk_grouped if self.grouped else ops.retrieve_topk
-        idx, sc = retrieve(out["projected_embeddings"].contiguous().reshape(b * k, -1),
-                           types.to(torch.int32).reshape(-1).contiguous(), self.type_rowptr, self.type_col,
-                           self.features, int(num_recommendations))
+        proj = out["projected_embeddings"].contiguous().reshape(b * k, -1)
+        row_types = types.to(torch.int32).reshape(-1).contiguous()
+        if self.exclusions is not None:
+            # the per-row kernel has no filter: the grouped search, whatever the graph's kind
+            exclude = (query_idx.repeat_interleave(k).contiguous(),) + self.exclusions
+            idx, sc = ops.retrieve_topk_grouped(proj, row_types, self.type_rowptr, self.type_col, self.features,
+                                                int(num_recommendations), exclude=exclude)
+        else:
+            retrieve = ops.retrieve_topk_grouped if self.grouped else ops.retrieve_topk
+            idx, sc = retrieve(proj, row_types, self.type_rowptr, self.type_col, self.features, int(num_recommendations))
         return types, idx.reshape(b, k, -1), sc.reshape(b, k, -1)
 
     @torch.no_grad()
@@ -105,7 +175,8 @@ class PCompanionInference:
         slot[b] = the k whose predicted complementary type is the target's type (the top-K types are distinct: at most
         one), -1 if none is; rank[b] = the number of products of that type that slot's projected embedding scores above
         the target (equal scores: the lower product index first) -- the target's position in recommend_batch's list of
-        that slot, were the list the whole type -- or -1 when slot[b] is -1.  A target outside the catalogue has no type:
+        that slot, were the list the whole type -- or -1 when slot[b] is -1.  With set_exclusions / set_eligible the products
+        they keep out are not counted, and a target they keep out has rank -1 (its slot stays).  A target outside the catalogue has no type:
         slot -1, rank -1.  `take` [B] bool (optional): rows that are False get slot -1 / rank -1 and cost no search.
         Returns (slot int32 [B], rank int32 [B]) on the device; nothing is read back."""
         query_idx = query_idx.to(self.device).to(torch.int32).contiguous()
@@ -128,7 +199,15 @@ class PCompanionInference:
         slot = torch.where(found, k, torch.full_like(k, -1)).to(torch.int32)
         proj = out["projected_embeddings"][torch.arange(b, device=self.device), k].contiguous()      # [B, D]
         row_type = torch.where(found, target_type, torch.full_like(target_type, -1)).to(torch.int32)
+        if self.exclusions is not None:
+            # a target in the query's list, or not eligible: -1 from the entry itself
+            rank, _ = ops.rank_grouped(proj, row_type, target_idx, self.type_rowptr, self.type_col, self.features,
+                                       exclude=(query_idx,) + self.exclusions, cand_type=self.cand_type)
+            return slot, rank
         rank, _ = ops.rank_grouped(proj, row_type, target_idx, self.type_rowptr, self.type_col, self.features)
+        if self.eligible is not None:
+            kept = self.eligible[target_idx.long().clamp(0, self.features.shape[0] - 1)]
+            rank = torch.where(kept, rank, torch.full_like(rank, -1))
         return slot, rank
 
     def evaluate_catalogue(self, dataset: ComplementaryIndexDataset, ks=(1, 3, 10, 100), chunk: int = 65536) -> Dict[str, Any]:
@@ -140,7 +219,9 @@ class PCompanionInference:
         Returns {"pairs", "type_hit", "hit@k" for k in ks, "mrr", "median_rank"}: hit@k is the share of all +1 pairs
         whose target is among the first k products of its type under the matched slot (k <= 16: among
         recommend_batch(query, k)'s lists), 0 for a pair whose type no slot predicted.  The candidates are every product
-        of the type, the query included, as in serving."""
+        of the type, the query included, as in serving.  With set_exclusions / set_eligible the candidates are what is then
+        served; a pair whose target the filters keep out (it is in its query's list, or not eligible) is a miss -- it keeps its
+        slot, its rank is -1 -- and the dict gains "filtered_targets", the number of such pairs."""
         bpg = self.bpg
         if isinstance(bpg, DeviceBPG) and bpg.world != 1:
             raise ValueError(f"evaluate_catalogue: this DeviceBPG holds a cyclic 1/{bpg.world} shard of the features")
@@ -160,13 +241,26 @@ class PCompanionInference:
         take = pairs[:, 2] == 1
         slot = torch.empty(n, dtype=torch.int32, device=self.device)
         rank = torch.empty(n, dtype=torch.int32, device=self.device)
+        filtering = self.exclusions is not None or self.eligible is not None
+        filtered = torch.zeros((), dtype=torch.int64, device=self.device)
         for lo in range(0, n, chunk):
             hi = min(lo + chunk, n)
             slot[lo:hi], rank[lo:hi] = self.rank_targets(pairs[lo:hi, 0], pairs[lo:hi, 1], take[lo:hi])
+            if filtering:
+                q, y = pairs[lo:hi, 0], pairs[lo:hi, 1]
+                out = torch.zeros_like(take[lo:hi])
+                if self.exclusions is not None:
+                    out |= self._excluded(q, y)
+                if self.eligible is not None:
+                    out |= ~self.eligible[y.long()]
+                filtered += (out & take[lo:hi]).sum()
         try:
-            return Metrics.catalogue_metrics(slot, rank, ks, take)
+            res = Metrics.catalogue_metrics(slot, rank, ks, take)
         except ValueError as e:
             raise ValueError("evaluate_catalogue: the dataset holds no +1 pair") from e
+        if filtering:
+            res["filtered_targets"] = int(filtered)
+        return res
 
     def recommend(self, query_id, num_recommendations: int = 10) -> Dict[str, Any]:
         """Generate complementary product recommendations (inference.py:64-124): same result dict."""

@@ -1745,11 +1745,49 @@ def retrieve_topk(proj, types, type_rowptr, type_col, table, n):
 RETRIEVE_MAX_SLICES = 64
 
 
-def retrieve_topk_grouped(proj, types, type_rowptr, type_col, table, n, slices=0):
+def _check_exclude(what, exclude, rows):
+    """exclude = (row_key [rows] int32, ex_rowptr [n_keys + 1] int32, ex_col [E] int32), checked on the host side alone (dtypes
+    and shapes: ValueError) before any tensor is handed to the device."""
+    if not isinstance(exclude, (tuple, list)) or len(exclude) != 3 or not all(isinstance(t, torch.Tensor) for t in exclude):
+        raise ValueError(f"{what}: exclude must be the triple (row_key, ex_rowptr, ex_col) of tensors")
+    row_key, ex_rowptr, ex_col = exclude
+    for name, t in (("row_key", row_key), ("ex_rowptr", ex_rowptr), ("ex_col", ex_col)):
+        if t.dtype != torch.int32:
+            raise ValueError(f"{what}: exclude {name} must be int32, got {t.dtype}")
+        if t.dim() != 1:
+            raise ValueError(f"{what}: exclude {name} must be 1-D, got shape {tuple(t.shape)}")
+    if row_key.shape[0] != rows:
+        raise ValueError(f"{what}: exclude row_key must hold one key per row ({rows}), got {row_key.shape[0]}")
+    if ex_rowptr.numel() < 1:
+        raise ValueError(f"{what}: exclude ex_rowptr must hold n_keys + 1 >= 1 entries")
+    return row_key, ex_rowptr, ex_col
+
+
+def _exclude_args(exclude):
+    """The triple as device arguments: (row_key, ex_rowptr, ex_col -- one unread entry where every list is empty --, n_keys)."""
+    row_key, ex_rowptr, ex_col = exclude
+    _req(row_key, torch.int32, "exclude row_key")
+    _req(ex_rowptr, torch.int32, "exclude ex_rowptr")
+    if ex_col.numel() == 0:
+        ex_col = torch.zeros(1, dtype=torch.int32, device=ex_rowptr.device)
+    _req(ex_col, torch.int32, "exclude ex_col")
+    return row_key, ex_rowptr, ex_col, ex_rowptr.numel() - 1
+
+
+def retrieve_topk_grouped(proj, types, type_rowptr, type_col, table, n, slices=0, exclude=None, bad=None):
     """pc_retrieve_topk_grouped: retrieve_topk's contract (idx [R,n] int32, -1 = none; scores [R,n] fp32, -inf = none) for a
     catalogue of any size -- rows grouped by type on the device, each type's candidates scored as a tiled fp32 MFMA GEMM,
     large types split over up to `slices` candidate slices (0 = automatic).  Bitwise deterministic, the same bits for every
-    `slices`.  Nothing is read back to the host."""
+    `slices`.  Nothing is read back to the host.
+    exclude = (row_key [R] int32, ex_rowptr [n_keys + 1] int32, ex_col [E] int32), an exclusion CSR over keys as
+    exclusion_csr builds it (the ids of a key strictly ascending): pc_retrieve_topk_grouped_excluding -- the first n products of
+    the type that are NOT in the list of row_key[r] (-1: no list), the same order and the same bits.  A key outside
+    [-1, n_keys) is served as -1 and counted in `bad` (a [1] int32 device counter the caller passes to see the count; added
+    to).  exclude=None: exactly the unfiltered call."""
+    if exclude is not None:
+        exclude = _check_exclude("retrieve_topk_grouped", exclude, types.shape[0] if isinstance(types, torch.Tensor) else -1)
+    elif bad is not None:
+        raise ValueError("retrieve_topk_grouped: bad counts keys out of range and is read with an exclude triple only")
     d = _width(table.shape[1])
     proj = _req(proj.reshape(-1, d), torch.float32, "proj")
     r = proj.shape[0]
@@ -1762,6 +1800,19 @@ def retrieve_topk_grouped(proj, types, type_rowptr, type_col, table, n, slices=0
         raise ValueError(f"slices must be in [0, {RETRIEVE_MAX_SLICES}] (0 = automatic), got {slices}")
     out_idx = torch.empty(r, n, dtype=torch.int32, device=proj.device)
     out_sc = torch.empty(r, n, dtype=torch.float32, device=proj.device)
+    if exclude is not None:
+        row_key, ex_rowptr, ex_col, n_keys = _exclude_args(exclude)
+        if bad is None:
+            bad = torch.zeros(1, dtype=torch.int32, device=proj.device)
+        else:
+            _req(bad, torch.int32, "bad", (1,))
+        nbytes = _lib.lib().pc_retrieve_topk_grouped_excluding_workspace_bytes(r, t, n, slices)
+        ws = workspace(nbytes, proj.device, "retrieve_grouped")
+        check(_lib.lib().pc_retrieve_topk_grouped_excluding(_p(proj), _p(types), _p(row_key), r, _p(type_rowptr), _p(type_col),
+                                                            _p(table), t, _p(ex_rowptr), _p(ex_col), n_keys, n, d, slices,
+                                                            _p(out_idx), _p(out_sc), _p(bad), _p(ws), ws.numel(), _stream()),
+              "pc_retrieve_topk_grouped_excluding")
+        return out_idx, out_sc
     nbytes = _lib.lib().pc_retrieve_topk_grouped_workspace_bytes(r, t, n, slices)
     ws = workspace(nbytes, proj.device, "retrieve_grouped")
     check(_lib.lib().pc_retrieve_topk_grouped(_p(proj), _p(types), r, _p(type_rowptr), _p(type_col), _p(table), t, n, d,
@@ -1770,13 +1821,27 @@ def retrieve_topk_grouped(proj, types, type_rowptr, type_col, table, n, slices=0
     return out_idx, out_sc
 
 
-def rank_grouped(proj, types, targets, type_rowptr, type_col, table, slices=0, bad=None):
+def rank_grouped(proj, types, targets, type_rowptr, type_col, table, slices=0, bad=None, exclude=None, cand_type=None):
     """pc_rank_grouped: for row r the number of products of type types[r] that retrieve_topk_grouped orders in front of
     targets[r] under proj[r] (score descending, product index ascending) -- the position of the target in the served list,
     over the whole type, from the retrieval's own score bits: rank < n exactly when retrieve_topk_grouped(..., n) holds the
     target at position rank.  Returns (rank [R] int32, bad [1] int32): rank -1 for a row with types[r] < 0 (skipped) and for
     a type >= the CSR's or a target outside the table, which `bad` counts (`bad`: a device counter to add to; a fresh zero
-    otherwise).  Bitwise deterministic, the same for every `slices`.  Nothing is read back to the host."""
+    otherwise).  Bitwise deterministic, the same for every `slices`.  Nothing is read back to the host.
+    exclude = (row_key, ex_rowptr, ex_col) as in retrieve_topk_grouped, with cand_type [P] int32 (the type under which product
+    p is a candidate, -1 if none; it must agree with type_rowptr / type_col): pc_rank_grouped_excluding -- the number of
+    NON-excluded products of the type in front of the target, -1 where the target is in the row's list or is no candidate of
+    the row's type; rank < n exactly when the filtered retrieval holds the target at position rank.  A key outside
+    [-1, n_keys) is served as -1 and counted in `bad`.  exclude=None: exactly the unfiltered call."""
+    if exclude is not None:
+        exclude = _check_exclude("rank_grouped", exclude, types.shape[0] if isinstance(types, torch.Tensor) else -1)
+        if cand_type is None:
+            raise ValueError("rank_grouped: exclude needs cand_type (the type under which each product is a candidate)")
+        if not isinstance(cand_type, torch.Tensor) or cand_type.dtype != torch.int32 or cand_type.dim() != 1 \
+                or cand_type.shape[0] != table.shape[0]:
+            raise ValueError("rank_grouped: cand_type must be an int32 tensor of one entry per product")
+    elif cand_type is not None:
+        raise ValueError("rank_grouped: cand_type is read with an exclude triple only")
     d = _width(table.shape[1])
     proj = _req(proj.reshape(-1, d), torch.float32, "proj")
     r = proj.shape[0]
@@ -1795,6 +1860,14 @@ def rank_grouped(proj, types, targets, type_rowptr, type_col, table, slices=0, b
         _req(bad, torch.int32, "bad", (1,))
     nbytes = _lib.lib().pc_rank_grouped_workspace_bytes(r, t, slices)
     ws = workspace(nbytes, proj.device, "rank_grouped")
+    if exclude is not None:
+        row_key, ex_rowptr, ex_col, n_keys = _exclude_args(exclude)
+        _req(cand_type, torch.int32, "cand_type", (table.shape[0],))
+        check(_lib.lib().pc_rank_grouped_excluding(_p(proj), _p(types), _p(targets), _p(row_key), r, _p(type_rowptr), _p(type_col),
+                                                   _p(table), t, table.shape[0], _p(ex_rowptr), _p(ex_col), n_keys,
+                                                   _p(cand_type), d, slices, _p(rank), _p(bad), _p(ws), ws.numel(), _stream()),
+              "pc_rank_grouped_excluding")
+        return rank, bad
     check(_lib.lib().pc_rank_grouped(_p(proj), _p(types), _p(targets), r, _p(type_rowptr), _p(type_col), _p(table), t,
                                      table.shape[0], d, slices, _p(rank), _p(bad), _p(ws), ws.numel(), _stream()),
           "pc_rank_grouped")
@@ -1819,3 +1892,39 @@ def type_csr(type_idx, n_types):
     rowptr[1:] = torch.cumsum(counts, 0).to(torch.int32)
     col = torch.argsort(type_idx, stable=True).to(torch.int32)
     return rowptr, col
+
+
+def exclusion_csr(rowptr, col, include_self=True, num_products=None):
+    """An exclusion set as pc_retrieve_topk_grouped_excluding / pc_rank_grouped_excluding read it, from any device CSR over keys
+    (normally the co-view graph: cv_rowptr / cv_col, key = the query product): inside every row the ids are sorted, duplicates
+    and ids outside [0, num_products) are dropped and, with include_self, the key itself is inserted (keys below num_products).
+    num_products defaults to the number of keys.  Returns (ex_rowptr [n_keys + 1] int32, ex_col [E'] int32), the ids of a key
+    strictly ascending.  Torch's device sort and scan over (key, id) pairs as one int64 each; nothing is read back per row.
+    Runs once per catalogue, off the serving path, as type_csr does.  E + num_products >= 2^31 is refused."""
+    for name, t in (("rowptr", rowptr), ("col", col)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or t.dim() != 1:
+            raise ValueError(f"exclusion_csr: {name} must be a 1-D int32 tensor")
+    n_keys = rowptr.numel() - 1
+    if n_keys < 0:
+        raise ValueError("exclusion_csr: rowptr must hold n_keys + 1 >= 1 entries")
+    p = n_keys if num_products is None else int(num_products)
+    if p < 0:
+        raise ValueError("exclusion_csr: num_products must not be negative")
+    if col.numel() + p >= 2 ** 31:
+        raise ValueError(f"exclusion_csr: {col.numel()} entries + {p} products do not fit 31 bits")
+    _req(rowptr, torch.int32, "rowptr")
+    _req(col, torch.int32, "col")
+    dev = rowptr.device
+    keys = torch.arange(n_keys, dtype=torch.int64, device=dev)
+    row = torch.repeat_interleave(keys, (rowptr[1:] - rowptr[:-1]).long(), output_size=col.numel())
+    ids = col.long()
+    if include_self:
+        own = keys[:min(n_keys, p)]
+        row, ids = torch.cat([row, own]), torch.cat([ids, own])
+    inside = (ids >= 0) & (ids < p)
+    pairs = torch.unique(row[inside] * max(p, 1) + ids[inside])              # sorted: by key, then by id; no duplicates
+    row, ids = pairs // max(p, 1), pairs % max(p, 1)
+    ex_rowptr = torch.zeros(n_keys + 1, dtype=torch.int32, device=dev)
+    if n_keys:
+        ex_rowptr[1:] = torch.cumsum(torch.bincount(row, minlength=n_keys), 0).to(torch.int32)
+    return ex_rowptr, ids.to(torch.int32).contiguous()
