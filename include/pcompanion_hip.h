@@ -1106,6 +1106,30 @@ int pc_rank_grouped_excluding(const float *proj, const int32_t *types, const int
                               const int32_t *cand_type, int dim, int slices, int32_t *rank_out, int32_t *bad_count, void *ws,
                               size_t ws_bytes, void *stream);
 
+/* Long lists (ABI 8, additive; PCompanionInference.recommend_batch above 16: a candidate generator feeds a re-ranker, a
+ * business-rule filter or a page of several slots with 50 to 200 products per type).  pc_retrieve_list_grouped is
+ * pc_retrieve_topk_grouped's contract for 1 <= n <= 256, and pc_retrieve_topk_grouped_excluding's when row_key is given:
+ * out_idx [rows, n] / out_score [rows, n] = the first n products of type types[r] that are not in the list of row_key[r], under
+ * the same total order (score descending, product index ascending), -1 / -inf past the end of a short type and for a type
+ * outside [0, n_types).  row_key == NULL: no lists (ex_rowptr, ex_col NULL, n_keys 0; bad_count may be NULL).  With row_key
+ * the exclusion set is the CSR over keys described above; a key outside [-1, n_keys) is served as -1, never indexes memory and
+ * is counted in *bad_count (required then; added to).  The scores are formed through pc_retrieve_topk_grouped's own fp32 MFMA
+ * chain and every selection is under its total order: for n <= 16 the output is that entry's bit for bit, for every n it does
+ * not depend on `slices`, on the placement of the rows or on the order of type_col inside a type, and pc_rank_grouped[_excluding]
+ * is < n exactly when the list holds the target at that position.  The same plan over tiles of 16 rows; a row keeps an
+ * unsorted candidate buffer and a threshold on chip, compacted by a sorting network when it fills; the slices' sorted partial
+ * lists are merged by one wave per row.  No float atomics, no host readback: the launch geometry and the workspace
+ * (pc_retrieve_list_grouped_workspace_bytes, 0 for arguments out of range) depend on rows, n_types, n and slices only.
+ * PC_EINVAL: null pointer, rows or n_types <= 0; with row_key a null ex_rowptr / ex_col / bad_count or n_keys < 0; without it a
+ * list or n_keys != 0; PC_ESHAPE: n outside [1, 256], dim not 128 / 256, slices outside [0, 64]; PC_EWORKSPACE: ws_bytes too
+ * small -- each checked before anything is launched. */
+size_t pc_retrieve_list_grouped_workspace_bytes(int rows, int n_types, int n, int slices);
+int pc_retrieve_list_grouped(const float *proj, const int32_t *types, const int32_t *row_key, int rows,
+                             const int32_t *type_rowptr, const int32_t *type_col, const float *table, int n_types,
+                             const int32_t *ex_rowptr, const int32_t *ex_col, int n_keys, int n, int dim, int slices,
+                             int32_t *out_idx, float *out_score, int32_t *bad_count, void *ws, size_t ws_bytes,
+                             void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -213,6 +213,9 @@ SIGNATURES = {
                                                 _sz, _vp]),
     "pc_rank_grouped_excluding": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _vp, _i, _i, _vp, _vp, _vp, _sz,
                                        _vp]),
+    "pc_retrieve_list_grouped_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "pc_retrieve_list_grouped": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz,
+                                      _vp]),
     "pc_hadamard_forward": (_i, [_vp, _vp, _i, _i, _vp, _vp]),
     "pc_hadamard_forward_dim": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
     "pc_hadamard_backward": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp]),

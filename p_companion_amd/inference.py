@@ -148,10 +148,21 @@ class PCompanionInference:
             raise ValueError(f"Product ID {query_id} not found in BPG")
         return idx
 
+    @staticmethod
+    def _list_length(num_recommendations):
+        """num_recommendations as an int; above what pc_retrieve_list_grouped serves: ValueError, before the model runs."""
+        n = int(num_recommendations)
+        if n > ops.RETRIEVE_LIST_MAX_N:
+            raise ValueError(f"recommend_batch: at most {ops.RETRIEVE_LIST_MAX_N} recommendations per (query, type), got {n}")
+        return n
+
     @torch.no_grad()
     def recommend_batch(self, query_idx: torch.Tensor, num_recommendations: int = 10):
         """All queries at once.  Returns complementary_types [B,K] int64, product indices [B,K,n] int32
-        (-1 past the end of a short type) and scores [B,K,n]."""
+        (-1 past the end of a short type) and scores [B,K,n].  Up to 16 recommendations: the entries with a sorted list per
+        thread; from 17 to ops.RETRIEVE_LIST_MAX_N (256): pc_retrieve_list_grouped, whatever the graph's kind -- an uploaded
+        IntBPG's arrays are on the device, and the per-row kernel stops at 16."""
+        n = self._list_length(num_recommendations)
         query_idx = query_idx.to(self.device).to(torch.int32).contiguous()
         batch = {"query_idx": query_idx, "query_types": self.type_idx[query_idx.long()]}
         out = self.model(batch)
@@ -159,7 +170,13 @@ class PCompanionInference:
         b, k = types.shape
         proj = out["projected_embeddings"].contiguous().reshape(b * k, -1)
         row_types = types.to(torch.int32).reshape(-1).contiguous()
-        if self.exclusions is not None:
+        if n > 16:                                        # (RG_MAX_N / RMAX_N: the entries below refuse 17)
+            exclude = None
+            if self.exclusions is not None:
+                exclude = (query_idx.repeat_interleave(k).contiguous(),) + self.exclusions
+            idx, sc = ops.retrieve_list_grouped(proj, row_types, self.type_rowptr, self.type_col, self.features, n,
+                                                exclude=exclude)
+        elif self.exclusions is not None:
             # the per-row kernel has no filter: the grouped search, whatever the graph's kind
             exclude = (query_idx.repeat_interleave(k).contiguous(),) + self.exclusions
             idx, sc = ops.retrieve_topk_grouped(proj, row_types, self.type_rowptr, self.type_col, self.features,
@@ -217,7 +234,7 @@ class PCompanionInference:
         (integer counts, one float64 reciprocal-rank sum in a fixed order) and reads back once.  Over a DeviceBPG the -1
         pairs stay in the chunks as rows that cost no search, so nothing is compacted or counted on the host.
         Returns {"pairs", "type_hit", "hit@k" for k in ks, "mrr", "median_rank"}: hit@k is the share of all +1 pairs
-        whose target is among the first k products of its type under the matched slot (k <= 16: among
+        whose target is among the first k products of its type under the matched slot (k <= 256: among
         recommend_batch(query, k)'s lists), 0 for a pair whose type no slot predicted.  The candidates are every product
         of the type, the query included, as in serving.  With set_exclusions / set_eligible the candidates are what is then
         served; a pair whose target the filters keep out (it is in its query's list, or not eligible) is a miss -- it keeps its

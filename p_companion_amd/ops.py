@@ -1821,6 +1821,53 @@ def retrieve_topk_grouped(proj, types, type_rowptr, type_col, table, n, slices=0
     return out_idx, out_sc
 
 
+RETRIEVE_LIST_MAX_N = 256
+
+
+def retrieve_list_grouped(proj, types, type_rowptr, type_col, table, n, slices=0, exclude=None, bad=None):
+    """pc_retrieve_list_grouped: retrieve_topk_grouped's contract (idx [R,n] int32, -1 = none; scores [R,n] fp32, -inf = none)
+    for lists of 1 <= n <= RETRIEVE_LIST_MAX_N products -- the same plan, candidate slices and score chain; a row keeps an
+    unsorted candidate buffer and a threshold on chip in place of the per-thread lists of 16.  Bitwise deterministic, the same
+    bits for every `slices`, and for n <= 16 retrieve_topk_grouped's own bits.  Nothing is read back to the host.
+    exclude = (row_key [R] int32, ex_rowptr [n_keys + 1] int32, ex_col [E] int32) and `bad` as in retrieve_topk_grouped: the
+    first n products of the type that are NOT in the list of row_key[r].  exclude=None: the unfiltered list."""
+    n, slices = int(n), int(slices)
+    if not 1 <= n <= RETRIEVE_LIST_MAX_N:
+        raise ValueError(f"retrieve_list_grouped: n must be in [1, {RETRIEVE_LIST_MAX_N}], got {n}")
+    if not 0 <= slices <= RETRIEVE_MAX_SLICES:
+        raise ValueError(f"slices must be in [0, {RETRIEVE_MAX_SLICES}] (0 = automatic), got {slices}")
+    if exclude is not None:
+        exclude = _check_exclude("retrieve_list_grouped", exclude, types.shape[0] if isinstance(types, torch.Tensor) else -1)
+    elif bad is not None:
+        raise ValueError("retrieve_list_grouped: bad counts keys out of range and is read with an exclude triple only")
+    d = _width(table.shape[1])
+    proj = _req(proj.reshape(-1, d), torch.float32, "proj")
+    r = proj.shape[0]
+    _req(types, torch.int32, "types", (r,))
+    _req(type_rowptr, torch.int32, "type_rowptr")
+    _req(type_col, torch.int32, "type_col")
+    _req(table, torch.float32, "table")
+    t = type_rowptr.numel() - 1
+    out_idx = torch.empty(r, n, dtype=torch.int32, device=proj.device)
+    out_sc = torch.empty(r, n, dtype=torch.float32, device=proj.device)
+    row_key = ex_rowptr = ex_col = None
+    n_keys = 0
+    if exclude is not None:
+        row_key, ex_rowptr, ex_col, n_keys = _exclude_args(exclude)
+        if bad is None:
+            bad = torch.zeros(1, dtype=torch.int32, device=proj.device)
+        else:
+            _req(bad, torch.int32, "bad", (1,))
+    nbytes = _lib.lib().pc_retrieve_list_grouped_workspace_bytes(r, t, n, slices)
+    ws = workspace(nbytes, proj.device, "retrieve_list")
+    # (without a triple row_key, ex_rowptr, ex_col and bad are None: null pointers, n_keys 0)
+    check(_lib.lib().pc_retrieve_list_grouped(_p(proj), _p(types), _p(row_key), r, _p(type_rowptr), _p(type_col), _p(table), t,
+                                              _p(ex_rowptr), _p(ex_col), n_keys, n, d, slices, _p(out_idx), _p(out_sc),
+                                              _p(bad), _p(ws), ws.numel(), _stream()),
+          "pc_retrieve_list_grouped")
+    return out_idx, out_sc
+
+
 def rank_grouped(proj, types, targets, type_rowptr, type_col, table, slices=0, bad=None, exclude=None, cand_type=None):
     """pc_rank_grouped: for row r the number of products of type types[r] that retrieve_topk_grouped orders in front of
     targets[r] under proj[r] (score descending, product index ascending) -- the position of the target in the served list,
