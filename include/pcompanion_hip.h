@@ -958,6 +958,51 @@ int pc_gen_complementary(int64_t n_products, int num_types, uint64_t seed, const
                          const int32_t *cv_rowptr, const int32_t *cv_col, int32_t *count,
                          const int32_t *comp_rowptr, int32_t *comp_pairs, void *stream);
 
+/* ---- The catalogue INGESTED on the device (csrc/ingest.hip, ABI 8, additive): the same arrays from the three edge sets of a
+ * BehaviorProductGraph (src/data/bpg.py:4-22: co_view, purchase_after_view, co_purchase) given as unsorted, directed int32
+ * [E][2] lists of (source, target) with duplicates, E < 2^31, ids in [0, n_products).  Semantics (DESIGN.md "Ingestion"):
+ * self-loops dropped, duplicates collapsed, a co_view edge's number of occurrences is its weight; a co_view row keeps its
+ * degree_cap distinct targets of greatest weight (equal weights: the lower id), ascending; similarity = kept co-view & PAV -
+ * co-purchase; complementary = co-purchase - PAV - the FULL co-view set; both sorted by (s, t).  No global sort: per list,
+ * pc_ingest_count -> pc_exclusive_scan_i32 (raw row offsets) -> pc_ingest_scatter (buckets) -> pc_ingest_rows (each row
+ * sorted, run-length coded and capped in its bucket); then pc_ingest_emit (cv_col) and pc_ingest_flag -> scan ->
+ * pc_ingest_emit per pair array.  Integer atomics only; every output is a function of the lists as sets (co_view: as a
+ * multiset), bit-identical under any permutation of the input.  ops.build_catalogue is the call order. */
+/* cnt[s] += 1 (cnt zeroed by the caller) for every edge (s, t), s != t, of one list.  Every id is compared with [0, n_products)
+ * BEFORE it indexes anything: an edge with an id outside is skipped (by pc_ingest_scatter too) and ORs list_bit (> 0) into
+ * the device word *bad, which the caller reads once.  n_edges = 0: nothing is launched. */
+int pc_ingest_count(const int32_t *edges, int64_t n_edges, int64_t n_products, int list_bit, int32_t *cnt, int32_t *bad,
+                    void *stream);
+/* bucket[rowptr[s] + j] = the targets of s in arbitrary order, through the integer cursor cursor[s]: the counts of
+ * pc_ingest_count on entry, zero on exit (rowptr = their exclusive scan) */
+int pc_ingest_scatter(const int32_t *edges, int64_t n_edges, int64_t n_products, const int32_t *rowptr, int32_t *cursor,
+                      int32_t *bucket, void *stream);
+/* the raw row lengths at which pc_ingest_rows changes path: up to *wave_row_max one wave per row (bitonic network in
+ * registers), up to *lds_row_max one workgroup per row sorting in LDS, above it one workgroup per row sorting between the
+ * bucket and the scratch buffer (LSD radix, 8-bit digits); no length is refused */
+int pc_ingest_row_limits(int *wave_row_max, int *lds_row_max);
+size_t pc_ingest_rows_workspace_bytes(int64_t n_products);
+/* Every row of the bucket array in place: the row's D distinct ids ascending in bucket[rowptr[s], rowptr[s] + D),
+ * full_cnt[s] = D.  degree_cap in 1..64: bit 31 marks the kept ids, kept_cnt[s] = min(D, degree_cap), *max_kept (zeroed by
+ * the caller) = the largest of them.  degree_cap = 0: a plain set, no bits, kept_cnt / max_kept unused (may be NULL).
+ * scratch: as many int32 as the bucket array (touched only under rows longer than *lds_row_max). */
+int pc_ingest_rows(int64_t n_products, const int32_t *rowptr, int32_t *bucket, int32_t *scratch, int degree_cap,
+                   int32_t *full_cnt, int32_t *kept_cnt, int32_t *max_kept, void *ws, size_t ws_bytes, void *stream);
+/* Set algebra over sorted rows.  A set is (buf, rowptr, cnt): row s = buf[rowptr[s], rowptr[s] + cnt[s]) (cnt NULL: up to
+ * rowptr[s + 1]), ids ascending, bit 31 ignored; buf NULL = the set is not given.  Bit 31 of every entry (s, t) of src is SET
+ * when t is in need[s] (if given) and in neither forbid1[s] nor forbid2[s] (if given), cleared otherwise; count[s] = the
+ * number of entries set.  src must not be one of the three sets. */
+int pc_ingest_flag(int64_t n_products, int32_t *src, const int32_t *src_rowptr, const int32_t *src_cnt, const int32_t *need,
+                   const int32_t *need_rowptr, const int32_t *need_cnt, const int32_t *forbid1,
+                   const int32_t *forbid1_rowptr, const int32_t *forbid1_cnt, const int32_t *forbid2,
+                   const int32_t *forbid2_rowptr, const int32_t *forbid2_cnt, int32_t *count, void *stream);
+/* The entries of src with bit 31 set, row by row in order, to positions out_rowptr[s] onwards (out_rowptr = the scan of their
+ * counts) of out_col (the id), out_pairs ((s, id), [n][2]) and out_deg (deg_rowptr[s + 1] - deg_rowptr[s]: pair_deg) -- each
+ * optional, at least one given.  clear != 0: bit 31 is removed from src on the way. */
+int pc_ingest_emit(int64_t n_products, int32_t *src, const int32_t *src_rowptr, const int32_t *src_cnt,
+                   const int32_t *out_rowptr, int32_t *out_col, int32_t *out_pairs, int32_t *out_deg,
+                   const int32_t *deg_rowptr, int clear, void *stream);
+
 /* The epoch order of DataLoader(shuffle=True) (scripts/pretrain_product2vec.py:24-30, train.py:115-121) as a keyed
  * bijection: out[i] = perm_{seed,epoch}(i), i in [0, n) -- a six-round balanced Feistel network over the even number of
  * bits covering n, cycle-walked into [0, n).  No sort, no storage, deterministic in (seed, epoch); restated in

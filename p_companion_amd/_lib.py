@@ -235,6 +235,14 @@ SIGNATURES = {
     "pc_gen_coview": (_i, [_i64, _i, _u64, _vp, _vp, _vp, _vp]),
     "pc_gen_similarity": (_i, [_i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "pc_gen_complementary": (_i, [_i64, _i, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    # the catalogue from edge lists (csrc/ingest.hip; ABI 8, additive)
+    "pc_ingest_count": (_i, [_vp, _i64, _i64, _i, _vp, _vp, _vp]),
+    "pc_ingest_scatter": (_i, [_vp, _i64, _i64, _vp, _vp, _vp, _vp]),
+    "pc_ingest_row_limits": (_i, [_P(ctypes.c_int), _P(ctypes.c_int)]),
+    "pc_ingest_rows_workspace_bytes": (_sz, [_i64]),
+    "pc_ingest_rows": (_i, [_i64, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "pc_ingest_flag": (_i, [_i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "pc_ingest_emit": (_i, [_i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
     "pc_shuffle_rows_i32": (_i, [_vp, _i, _i, _u64, _u64, _vp, _vp]),
     "pc_comp_split_pairs": (_i, [_vp, _i64, _vp, _i64, _i64, _i64, _u64, _i, _vp, _vp]),
     "pc_epoch_plan": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),

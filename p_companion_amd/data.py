@@ -65,6 +65,57 @@ class IntBPG:
                    complementary_pairs=z["complementary_pairs"].astype(np.int32),
                    n_types=int(z["type_idx"].max()) + 1)
 
+    @property
+    def max_degree(self):
+        """The longest co-view row (what DeviceBPG.max_degree holds for a built graph)."""
+        return int(np.diff(self.cv_rowptr).max()) if self.num_products else 0
+
+    @classmethod
+    def from_edges(cls, features, type_idx, co_view, purchase_after_view, co_purchase, degree_cap=None, category=None):
+        """From the three edge sets of a BehaviorProductGraph (bpg.py:4-22) as integer [E, 2] arrays of (source, target):
+        unsorted, directed, duplicates allowed.  The host twin of ops.build_catalogue / device_bpg_from_edges, equal bit for
+        bit (DESIGN.md "Ingestion"): self-loops dropped, duplicates collapsed, a co_view edge's occurrences are its weight; a
+        co_view row keeps its degree_cap distinct targets of greatest weight (equal weights: the lower id; None: no cap, as the
+        reference's graph has none), ascending; similarity = kept co-view & purchase-after-view - co-purchase; complementary =
+        co-purchase - purchase-after-view - the FULL co-view set; both sorted by (s, t).  features None: a graph without
+        features ([P, 0]).  An id outside [0, P) raises ValueError naming the list."""
+        type_idx = np.ascontiguousarray(type_idx, np.int32)
+        P = int(type_idx.shape[0])
+        if degree_cap is not None and int(degree_cap) < 1:
+            raise ValueError("from_edges: degree_cap must be None or >= 1")
+
+        def keys(name, e):
+            e = np.asarray(e).reshape(-1, 2).astype(np.int64)
+            if e.size and (e.min() < 0 or e.max() >= P):
+                raise ValueError(f"from_edges: product ids outside [0, {P}) in {name}")
+            e = e[e[:, 0] != e[:, 1]]
+            return e[:, 0] * P + e[:, 1]
+
+        cv, w = np.unique(keys("co_view", co_view), return_counts=True)          # sorted by (s, t)
+        pv = np.unique(keys("purchase_after_view", purchase_after_view))
+        cp = np.unique(keys("co_purchase", co_purchase))
+        kept = cv
+        if degree_cap is not None and cv.size:
+            s, t = cv // P, cv % P
+            order = np.lexsort((t, -w, s))                                       # per source: weight descending, id ascending
+            first = np.searchsorted(s, s[order], side="left")                    # (s is sorted: the start of each row)
+            keep = np.zeros(cv.size, bool)
+            keep[order[np.arange(cv.size) - first < int(degree_cap)]] = True
+            kept = cv[keep]
+        sim = np.setdiff1d(np.intersect1d(kept, pv, assume_unique=True), cp, assume_unique=True)
+        comp = np.setdiff1d(np.setdiff1d(cp, pv, assume_unique=True), cv, assume_unique=True)
+        pairs = lambda k: np.stack([k // P, k % P], 1).astype(np.int32)
+        cv_rowptr = np.zeros(P + 1, np.int64)
+        np.add.at(cv_rowptr, kept // P + 1, 1)
+        feats = np.zeros((P, 0), np.float32) if features is None else np.ascontiguousarray(features, np.float32)
+        if feats.shape[0] != P:
+            raise ValueError(f"from_edges: features must have {P} rows")
+        return cls(features=feats, type_idx=type_idx,
+                   category=np.zeros(P, np.int32) if category is None else np.ascontiguousarray(category, np.int32),
+                   cv_rowptr=np.cumsum(cv_rowptr).astype(np.int32), cv_col=(kept % P).astype(np.int32),
+                   similarity_pairs=pairs(sim), complementary_pairs=pairs(comp),
+                   n_types=int(type_idx.max()) + 1 if P else 0)
+
     def cuda(self, device="cuda"):
         if self._dev is None:
             t = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a)).to(dt).to(device)
@@ -143,7 +194,8 @@ def generate_scaled_bpg(num_products=100_000, num_types=100, seed=0, mean_degree
 
 
 class DeviceBPG:
-    """The integer BPG with every array RESIDENT IN HBM, generated there (ops.generate_catalogue -> csrc/generator.hip):
+    """The integer BPG with every array RESIDENT IN HBM, generated there (ops.generate_catalogue -> csrc/generator.hip) or built
+    there from behaviour edge lists (device_bpg_from_edges -> ops.build_catalogue -> csrc/ingest.hip):
     BASELINE configs[3]/[4] -- 10 M and 100 M products -- cannot be built as host numpy arrays (generate_scaled_bpg's
     np.unique over src * P + tgt alone needs tens of GB of host memory and minutes).  Same attribute surface as IntBPG for
     the device paths (the throughput loaders, the fused steps, bench.py); host-side consumers (the CPython parity
@@ -184,7 +236,8 @@ class DeviceBPG:
         c = lambda k: a[k].cpu().numpy()
         per_cat = max(self.n_types // 5, 1)
         ti = c("type_idx")
-        return IntBPG(features=c("features"), type_idx=ti, category=np.minimum(ti // per_cat, 4).astype(np.int32),
+        feats = c("features") if "features" in a else np.zeros((self.num_products, 0), np.float32)   # (built without features)
+        return IntBPG(features=feats, type_idx=ti, category=np.minimum(ti // per_cat, 4).astype(np.int32),
                       cv_rowptr=c("cv_rowptr"), cv_col=c("cv_col"), similarity_pairs=c("sim_pairs"),
                       complementary_pairs=(c("comp_pairs") if "comp_pairs" in a else np.zeros((0, 2), np.int32)),
                       n_types=self.n_types, sim_rowptr=c("sim_rowptr"), sim_col=c("sim_col"))
@@ -233,6 +286,35 @@ def generate_device_bpg(num_products=100_000, num_types=100, seed=0, mean_degree
     arrays = ops.generate_catalogue(num_products, num_types, seed, mean_degree, degree_cap, dim, device, rank=rank,
                                     world=world, with_complementary=with_complementary)
     return DeviceBPG(arrays, num_types, dim, rank=rank, world=world, seed=seed)
+
+
+def device_bpg_from_edges(features, type_idx, n_types, co_view, purchase_after_view, co_purchase, degree_cap=32,
+                          device="cuda") -> DeviceBPG:
+    """A DeviceBPG from real behaviour data: the three edge sets of a BehaviorProductGraph as integer [E, 2] arrays of
+    (source, target) -- unsorted, directed, duplicates allowed -- built in HBM by ops.build_catalogue (csrc/ingest.hip;
+    IntBPG.from_edges is the host twin).  features [P, D] float32 or None (a graph without features), type_idx [P].  Host
+    arrays (numpy or torch) are uploaded once; device tensors are used as they are.  world = 1."""
+    from . import ops
+
+    def up(a, dtype):
+        if a is None:
+            return None
+        t = a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a))
+        if t.dtype != dtype:
+            raise ValueError(f"device_bpg_from_edges: expected {dtype}, got {t.dtype}")
+        return t.to(device=device, dtype=dtype).contiguous()
+
+    lists = []
+    for name, e in zip(ops.INGEST_LISTS, (co_view, purchase_after_view, co_purchase)):
+        t = up(e, torch.int32)
+        if t.numel() == 0:
+            t = t.reshape(0, 2)
+        lists.append(t)
+    feats = up(features, torch.float32)
+    arrays = ops.build_catalogue(up(type_idx, torch.int32), *lists, degree_cap=degree_cap, features=feats, n_types=n_types)
+    if n_types is None:
+        n_types = int(arrays["type_idx"].max()) + 1
+    return DeviceBPG(arrays, n_types, 0 if feats is None else feats.shape[1])
 
 
 class _LazyCount:

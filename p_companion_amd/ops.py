@@ -1490,6 +1490,110 @@ def generate_catalogue(num_products, num_types, seed, mean_degree, degree_cap, d
     return out
 
 
+INGEST_CAP_MAX = 64                # = GEN_CAP_MAX: the degree bound under which the device loaders are tested
+INGEST_WAVE_ROW_MAX = 128          # raw row length up to which pc_ingest_rows sorts a row in one wave's registers
+INGEST_LDS_ROW_MAX = 4096          # ... and up to which one workgroup sorts it in LDS (above: between two global buffers);
+#                                    pc_ingest_row_limits reports the library's own values (tests/test_ingest_host.py compares)
+INGEST_LISTS = ("co_view", "purchase_after_view", "co_purchase")
+
+
+def _check_catalogue_args(type_idx, lists, degree_cap, features, n_types):
+    """build_catalogue's checks that need neither the library nor a device."""
+    if isinstance(degree_cap, bool) or not isinstance(degree_cap, (int, np.integer)) or not 1 <= degree_cap <= INGEST_CAP_MAX:
+        raise ValueError(f"build_catalogue: degree_cap must be an integer in 1..{INGEST_CAP_MAX}, got {degree_cap!r}")
+    if n_types is not None and int(n_types) <= 0:
+        raise ValueError("build_catalogue: n_types must be positive")
+    if not isinstance(type_idx, torch.Tensor) or type_idx.dtype != torch.int32 or type_idx.dim() != 1 or type_idx.numel() < 1:
+        raise ValueError("build_catalogue: type_idx must be a 1-D int32 tensor of P >= 1 type ids")
+    P = type_idx.numel()
+    if P >= 2 ** 31:
+        raise ValueError(f"build_catalogue: {P} products do not fit int32 ids")
+    for name, e in zip(INGEST_LISTS, lists):
+        if not isinstance(e, torch.Tensor) or e.dtype != torch.int32 or e.dim() != 2 or e.shape[1] != 2:
+            raise ValueError(f"build_catalogue: {name} must be an int32 tensor of shape [E, 2] (source, target)")
+        if e.shape[0] >= 2 ** 31:
+            raise ValueError(f"build_catalogue: {name} holds {e.shape[0]} edges; a list is limited to 2^31 - 1")
+    if features is not None:
+        if not isinstance(features, torch.Tensor) or features.dtype != torch.float32 or features.dim() != 2 or features.shape[0] != P:
+            raise ValueError(f"build_catalogue: features must be a float32 tensor of shape [{P}, D] or None")
+    for name, t in zip(("type_idx",) + INGEST_LISTS, (type_idx,) + tuple(lists)):
+        _req(t, torch.int32, name)
+    if features is not None:
+        _req(features, torch.float32, "features")
+    return P
+
+
+def build_catalogue(type_idx, co_view, purchase_after_view, co_purchase, degree_cap=32, features=None, n_types=None):
+    """csrc/ingest.hip end to end: the dict of device tensors of generate_catalogue (see data.DeviceBPG) from the three edge
+    sets of a BehaviorProductGraph as unsorted, directed int32 [E, 2] device tensors of (source, target) with duplicates
+    (DESIGN.md "Ingestion" has the semantics; data.IntBPG.from_edges is the host twin, equal bit for bit).  An id outside
+    [0, P) raises ValueError naming its list: the device compares every id before using it and reports through one flag word.
+    Host synchronisations: that word, the totals of the scans (as in generate_catalogue) and max_degree."""
+    lists = (co_view, purchase_after_view, co_purchase)
+    P = _check_catalogue_args(type_idx, lists, degree_cap, features, n_types)
+    lo, hi = (int(x) for x in torch.aminmax(type_idx))
+    n_types = hi + 1 if n_types is None else int(n_types)
+    if lo < 0 or hi >= n_types:
+        raise ValueError(f"build_catalogue: type ids must lie in [0, {n_types}), got {lo} .. {hi}")
+    L = _lib.lib()
+    dev = type_idx.device
+    i32 = lambda *s: torch.empty(*s, dtype=torch.int32, device=dev)
+    z32 = lambda *s: torch.zeros(*s, dtype=torch.int32, device=dev)
+    # ---- bucket every list by source
+    bad = z32(1)
+    cnt = [z32(P) for _ in lists]
+    for k, e in enumerate(lists):
+        check(L.pc_ingest_count(_p(e), e.shape[0], P, 1 << k, _p(cnt[k]), _p(bad), _stream()), "pc_ingest_count")
+    flag = int(bad.item())
+    if flag:
+        names = ", ".join(n for k, n in enumerate(INGEST_LISTS) if flag >> k & 1)
+        raise ValueError(f"build_catalogue: product ids outside [0, {P}) in {names}")
+    rowptr, bucket = [], []
+    for k, e in enumerate(lists):
+        rp, n = exclusive_scan_i32(cnt[k])
+        b = i32(max(n, 1))
+        check(L.pc_ingest_scatter(_p(e), e.shape[0], P, _p(rp), _p(cnt[k]), _p(b), _stream()), "pc_ingest_scatter")
+        rowptr.append(rp)
+        bucket.append(b)
+    # ---- every row sorted, run-length coded and (co_view) capped in its bucket; cnt[k] becomes the distinct counts
+    scratch = i32(max(b.numel() for b in bucket))
+    nbytes = L.pc_ingest_rows_workspace_bytes(P)
+    ws = torch.empty(int(nbytes), dtype=torch.uint8, device=dev)      # (O(P): not kept in the grow-only workspace cache)
+    kept, max_kept = i32(P), z32(1)
+    for k in range(3):
+        cap = int(degree_cap) if k == 0 else 0
+        check(L.pc_ingest_rows(P, _p(rowptr[k]), _p(bucket[k]), _p(scratch), cap, _p(cnt[k]), _p(kept) if k == 0 else None,
+                               _p(max_kept) if k == 0 else None, _p(ws), nbytes, _stream()), "pc_ingest_rows")
+    del scratch
+    (cv_raw, pv_raw, cp_raw), (cv_b, pv_b, cp_b), (cv_n, pv_n, cp_n) = rowptr, bucket, cnt
+    # ---- neighbour lists: the kept ids of every co-view row
+    cv_rowptr, n_edges = exclusive_scan_i32(kept)
+    cv_col = i32(max(n_edges, 1))
+    check(L.pc_ingest_emit(P, _p(cv_b), _p(cv_raw), _p(cv_n), _p(cv_rowptr), _p(cv_col), None, None, None, 0, _stream()),
+          "pc_ingest_emit")
+    # ---- similarity = kept co-view & purchase-after-view - co-purchase
+    count = kept                                             # (free now)
+    check(L.pc_ingest_flag(P, _p(cv_col), _p(cv_rowptr), None, _p(pv_b), _p(pv_raw), _p(pv_n), _p(cp_b), _p(cp_raw), _p(cp_n),
+                           None, None, None, _p(count), _stream()), "pc_ingest_flag")
+    sim_rowptr, n_sim = exclusive_scan_i32(count)
+    sim_pairs, sim_col, pair_deg = i32(max(n_sim, 1), 2), i32(max(n_sim, 1)), i32(max(n_sim, 1))
+    check(L.pc_ingest_emit(P, _p(cv_col), _p(cv_rowptr), None, _p(sim_rowptr), _p(sim_col), _p(sim_pairs), _p(pair_deg),
+                           _p(cv_rowptr), 1, _stream()), "pc_ingest_emit")
+    # ---- complementary = co-purchase - purchase-after-view - the FULL co-view set (an edge the cap dropped is still co-viewed)
+    check(L.pc_ingest_flag(P, _p(cp_b), _p(cp_raw), _p(cp_n), None, None, None, _p(pv_b), _p(pv_raw), _p(pv_n), _p(cv_b),
+                           _p(cv_raw), _p(cv_n), _p(count), _stream()), "pc_ingest_flag")
+    comp_rowptr, n_comp = exclusive_scan_i32(count)
+    comp = i32(max(n_comp, 1), 2)
+    check(L.pc_ingest_emit(P, _p(cp_b), _p(cp_raw), _p(cp_n), _p(comp_rowptr), None, _p(comp), None, None, 0, _stream()),
+          "pc_ingest_emit")
+    out = {"n_products": P, "type_idx": type_idx}
+    if features is not None:
+        out["features"] = features
+    out.update(cv_rowptr=cv_rowptr, cv_col=cv_col[:n_edges], sim_rowptr=sim_rowptr, sim_pairs=sim_pairs[:n_sim],
+               sim_col=sim_col[:n_sim], pair_deg=pair_deg[:n_sim], max_degree=int(max_kept.item()), comp_pairs=comp[:n_comp])
+    return out
+
+
 def epoch_permutation(n, seed, epoch, device):
     """pc_epoch_permutation: the epoch's order of n dataset positions, int32 [n] on the device (keyed Feistel bijection,
     cycle-walked: no sort kernels, no torch.randperm)."""
