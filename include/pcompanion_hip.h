@@ -1175,6 +1175,31 @@ int pc_retrieve_list_grouped(const float *proj, const int32_t *types, const int3
                              int32_t *out_idx, float *out_score, int32_t *bad_count, void *ws, size_t ws_bytes,
                              void *stream);
 
+/* A bf16 copy of the catalogue (ABI 8, additive; PCompanionInference(..., catalogue=): the fp32 table is the largest thing in
+ * HBM while a model is served -- 5.1 GB at 10 M x 128 -- and the bf16 copy is half of it).  pc_retrieve_topk_grouped_bf16 is
+ * pc_retrieve_topk_grouped's contract, and pc_retrieve_topk_grouped_excluding's when row_key is given, over table_bf16
+ * [num_products, dim]: bf16 bit patterns, row-major, 16-byte aligned (the fp32 features rounded to nearest even).  The stored
+ * table is scored against the UNROUNDED query: each fp32 query row is split into three bf16 pieces by truncation
+ * (q = p0 + p1 + p2 to 2^-24 |q|) and p0 . t, p1 . t, p2 . t are accumulated in fp32 on v_mfma_f32_16x16x32_bf16.  Every
+ * product is exact, so the score is the fp32-grade dot product of proj[r] with the ROUNDED table row -- not that of the fp32
+ * table: the lists can differ from pc_retrieve_topk_grouped's wherever two products lie within bf16 rounding of each other.
+ * The same plan, work items, selection, merge and total order (score descending, product index ascending); the order of a
+ * score's chain depends on the dimension index and the piece alone, so the output is bitwise deterministic and does not
+ * depend on `slices`, on the placement of the rows or on the order of type_col inside a type.  row_key == NULL: no lists
+ * (ex_rowptr, ex_col NULL, n_keys 0; bad_count may be NULL).  With row_key the exclusion set is the CSR over keys described
+ * above; a key outside [-1, n_keys) is served as -1, never indexes memory and is counted in *bad_count (required then; added
+ * to).  No float atomics, no host readback: the launch geometry and the workspace
+ * (pc_retrieve_topk_grouped_bf16_workspace_bytes, 0 for arguments out of range; pc_retrieve_topk_grouped's size) depend on
+ * rows, n_types, n and slices only.  PC_EINVAL: null pointer, rows or n_types <= 0; with row_key a null ex_rowptr / ex_col /
+ * bad_count or n_keys < 0; without it a list or n_keys != 0; PC_ESHAPE: n outside [1, 16], dim not 128 / 256, slices outside
+ * [0, 64], table_bf16 not 16-byte aligned; PC_EWORKSPACE: ws_bytes too small -- each checked before anything is launched. */
+size_t pc_retrieve_topk_grouped_bf16_workspace_bytes(int rows, int n_types, int n, int slices);
+int pc_retrieve_topk_grouped_bf16(const float *proj, const int32_t *types, const int32_t *row_key, int rows,
+                                  const int32_t *type_rowptr, const int32_t *type_col, const uint16_t *table_bf16,
+                                  int n_types, const int32_t *ex_rowptr, const int32_t *ex_col, int n_keys, int n, int dim,
+                                  int slices, int32_t *out_idx, float *out_score, int32_t *bad_count, void *ws,
+                                  size_t ws_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -216,7 +216,10 @@ SIGNATURES = {
     "pc_retrieve_list_grouped_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "pc_retrieve_list_grouped": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz,
                                       _vp]),
-    "pc_hadamard_forward": (_i, [_vp, _vp, _i, _i, _vp, _vp]),
+    "pc_retrieve_topk_grouped_bf16_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "pc_retrieve_topk_grouped_bf16": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp,
+                                           _sz, _vp]),
+    "pc_hadamard_forward":(_i, [_vp, _vp, _i, _i, _vp, _vp]),
     "pc_hadamard_forward_dim": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
     "pc_hadamard_backward": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp]),
     "pc_hadamard_backward_dim": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),

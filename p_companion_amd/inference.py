@@ -13,7 +13,9 @@ rank_targets / evaluate_catalogue are not in the reference: they say where a KNO
 serves -- its rank among all products of its type (pc_rank_grouped: the grouped retrieval's schedule and score bits, the
 selection replaced by a count) -- and fold the held-out "test" pairs into hit@k / MRR / median rank.
 set_exclusions / set_eligible keep the query, its co-viewed substitutes and unservable products out of both
-(pc_retrieve_topk_grouped_excluding / pc_rank_grouped_excluding)."""
+(pc_retrieve_topk_grouped_excluding / pc_rank_grouped_excluding).
+catalogue= serves the lists of up to 16 from a bf16 copy of the product table (pc_retrieve_topk_grouped_bf16): half the bytes,
+scored against the unrounded query; the scores are those of the ROUNDED table."""
 import os
 from typing import Any, Dict, List
 
@@ -27,21 +29,47 @@ from .p_companion import PCompanion
 
 
 class PCompanionInference:
-    def __init__(self, model, config, bpg: IntBPG, product_ids: List[str] = None):
+    catalogue = None                           # the bf16 copy that is served from (__init__: catalogue=); None: the fp32 features
+
+    def __init__(self, model, config, bpg: IntBPG, product_ids: List[str] = None, catalogue=None):
         """model: a trained PCompanion, or the path of a best_model.pth written by train.train
         (train.py:63-70 layout: 'model_state_dict' holds every tensor, including the frozen table).
         bpg: an IntBPG, or a DeviceBPG generated with world = 1 and with features (a sharded one holds a 1/world cyclic
-        shard of the features and is refused, as in Product2Vec.generate_all_embeddings)."""
+        shard of the features and is refused, as in Product2Vec.generate_all_embeddings).
+        catalogue: what the candidates are scored against.
+          None            the graph's fp32 features (the parity setting).
+          torch.bfloat16  ops.catalogue_bf16 of the graph's features, made here once.
+          a [P, D] torch.bfloat16 device tensor: that copy, as it is; a DeviceBPG without features is then accepted.  This is
+                          how a caller gets the memory back: the fp32 features belong to the graph object (and to whoever else
+                          holds them -- the model's frozen table, say), and freeing them is the caller's business; this object
+                          keeps no reference to them.
+        With a bf16 catalogue recommend_batch (up to 16 per type) and recommend go through pc_retrieve_topk_grouped_bf16 for
+        every kind of graph: the unrounded projected query against the ROUNDED table, so a list can differ from the fp32
+        catalogue's where two products lie within bf16 rounding of each other.  set_exclusions / set_eligible work unchanged;
+        lists above 16, rank_targets and evaluate_catalogue need the fp32 catalogue and raise ValueError."""
         self.config = config
         self.device = config.DEVICE
         self.bpg = bpg
         self.grouped = isinstance(bpg, DeviceBPG)
+        given = torch.is_tensor(catalogue)
+        if catalogue is not None and catalogue is not torch.bfloat16 and not given:
+            raise ValueError(f"PCompanionInference: catalogue must be None (the fp32 features), torch.bfloat16 or a [P, D] "
+                             f"torch.bfloat16 device tensor, got {catalogue!r}")
+        if given:
+            if catalogue.dtype != torch.bfloat16:
+                raise ValueError(f"PCompanionInference: a catalogue tensor must be torch.bfloat16 (ops.catalogue_bf16), got "
+                                 f"{catalogue.dtype}; the fp32 catalogue is catalogue=None")
+            if catalogue.dim() != 2 or catalogue.shape[0] != bpg.num_products or catalogue.shape[1] not in (128, 256):
+                raise ValueError(f"PCompanionInference: the catalogue must be [{bpg.num_products}, 128 or 256], got "
+                                 f"{tuple(catalogue.shape)}")
+            if not catalogue.is_cuda or not catalogue.is_contiguous():
+                raise ValueError("PCompanionInference: the catalogue must be a contiguous device tensor")
         if self.grouped:
             if bpg.world != 1:
                 raise ValueError(f"PCompanionInference: this DeviceBPG holds a cyclic 1/{bpg.world} shard of the features "
                                  f"(rank {bpg.rank}); serving needs the whole table on one device -- generate it with "
                                  "world = 1")
-            if "features" not in bpg.arrays:
+            if "features" not in bpg.arrays and not given:
                 raise ValueError("PCompanionInference: the DeviceBPG was generated without features")
         if isinstance(model, (str, os.PathLike)):
             model = self._load_model(model)
@@ -50,7 +78,11 @@ class PCompanionInference:
         self.product_ids = product_ids
         self._index = {pid: i for i, pid in enumerate(product_ids)} if product_ids is not None else None
         g = bpg.cuda(self.device)
-        self.features = g["features"]
+        # the table the candidates are scored against: the fp32 features, or the bf16 copy (self.features is then None)
+        if catalogue is None:
+            self.features, self.catalogue = g["features"], None
+        else:
+            self.features, self.catalogue = None, (catalogue if given else ops.catalogue_bf16(g["features"]))
         self.type_idx = g["type_idx"]
         self._graph = g
         self.exclusions = None                 # (ex_rowptr, ex_col) keyed by query id: set_exclusions
@@ -84,7 +116,7 @@ class PCompanionInference:
             raise ValueError("set_exclusions: pass rowptr and col together, or neither for the co-view graph")
         if rowptr is None:
             rowptr, col = self._graph["cv_rowptr"], self._graph["cv_col"]
-        p = int(self.features.shape[0])
+        p = int(self.type_idx.shape[0])
         if rowptr.numel() != p + 1:
             raise ValueError(f"set_exclusions: the set is keyed by query id: rowptr must hold {p + 1} entries, got {rowptr.numel()}")
         self.exclusions = ops.exclusion_csr(rowptr.to(self.device), col.to(self.device), include_self=include_self, num_products=p)
@@ -98,7 +130,7 @@ class PCompanionInference:
             self.eligible, self.cand_type = None, self.type_idx
             self.type_rowptr, self.type_col = self._all_products
             return self
-        p = int(self.features.shape[0])
+        p = int(self.type_idx.shape[0])
         if not torch.is_tensor(mask) or mask.dtype != torch.bool or tuple(mask.shape) != (p,):
             raise ValueError(f"set_eligible: expected a bool tensor of shape ({p},)")
         mask = mask.to(self.device)
@@ -163,6 +195,9 @@ class PCompanionInference:
         thread; from 17 to ops.RETRIEVE_LIST_MAX_N (256): pc_retrieve_list_grouped, whatever the graph's kind -- an uploaded
         IntBPG's arrays are on the device, and the per-row kernel stops at 16."""
         n = self._list_length(num_recommendations)
+        if self.catalogue is not None and n > 16:
+            raise ValueError(f"recommend_batch: a bf16 catalogue serves at most 16 recommendations per (query, type), got {n}; "
+                             "longer lists need the fp32 catalogue (catalogue=None)")
         query_idx = query_idx.to(self.device).to(torch.int32).contiguous()
         batch = {"query_idx": query_idx, "query_types": self.type_idx[query_idx.long()]}
         out = self.model(batch)
@@ -170,7 +205,13 @@ class PCompanionInference:
         b, k = types.shape
         proj = out["projected_embeddings"].contiguous().reshape(b * k, -1)
         row_types = types.to(torch.int32).reshape(-1).contiguous()
-        if n > 16:                                        # (RG_MAX_N / RMAX_N: the entries below refuse 17)
+        if self.catalogue is not None:                    # (n <= 16) the bf16 entry, whatever the graph's kind
+            exclude = None
+            if self.exclusions is not None:
+                exclude = (query_idx.repeat_interleave(k).contiguous(),) + self.exclusions
+            idx, sc = ops.retrieve_topk_grouped(proj, row_types, self.type_rowptr, self.type_col, self.catalogue, n,
+                                                exclude=exclude)
+        elif n > 16:                                      # (RG_MAX_N / RMAX_N: the entries below refuse 17)
             exclude = None
             if self.exclusions is not None:
                 exclude = (query_idx.repeat_interleave(k).contiguous(),) + self.exclusions
@@ -196,6 +237,9 @@ class PCompanionInference:
         they keep out are not counted, and a target they keep out has rank -1 (its slot stays).  A target outside the catalogue has no type:
         slot -1, rank -1.  `take` [B] bool (optional): rows that are False get slot -1 / rank -1 and cost no search.
         Returns (slot int32 [B], rank int32 [B]) on the device; nothing is read back."""
+        if self.catalogue is not None:
+            raise ValueError("rank_targets: the rank kernels read the fp32 catalogue (catalogue=None); a bf16 catalogue serves "
+                             "recommend_batch / recommend up to 16 per type")
         query_idx = query_idx.to(self.device).to(torch.int32).contiguous()
         target_idx = target_idx.to(self.device).to(torch.int32).contiguous()
         if query_idx.dim() != 1 or query_idx.shape != target_idx.shape:
@@ -240,6 +284,9 @@ class PCompanionInference:
         served; a pair whose target the filters keep out (it is in its query's list, or not eligible) is a miss -- it keeps its
         slot, its rank is -1 -- and the dict gains "filtered_targets", the number of such pairs."""
         bpg = self.bpg
+        if self.catalogue is not None:
+            raise ValueError("evaluate_catalogue: the rank kernels read the fp32 catalogue (catalogue=None); a bf16 catalogue "
+                             "serves recommend_batch / recommend up to 16 per type")
         if isinstance(bpg, DeviceBPG) and bpg.world != 1:
             raise ValueError(f"evaluate_catalogue: this DeviceBPG holds a cyclic 1/{bpg.world} shard of the features")
         if not isinstance(dataset, ComplementaryIndexDataset) or dataset.bpg is not bpg:

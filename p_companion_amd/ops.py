@@ -1849,6 +1849,16 @@ def retrieve_topk(proj, types, type_rowptr, type_col, table, n):
 RETRIEVE_MAX_SLICES = 64
 
 
+def catalogue_bf16(features):
+    """The bf16 copy of a catalogue that retrieve_topk_grouped serves from: [P, D] fp32 on the device -> [P, D] torch.bfloat16,
+    rounded to nearest even, half the bytes.  Once per catalogue, off the serving path: no kernel of its own."""
+    _req(features, torch.float32, "features")
+    if features.dim() != 2:
+        raise ValueError(f"features: expected [P, D], got shape {tuple(features.shape)}")
+    _width(features.shape[1])
+    return features.to(torch.bfloat16)
+
+
 def _check_exclude(what, exclude, rows):
     """exclude = (row_key [rows] int32, ex_rowptr [n_keys + 1] int32, ex_col [E] int32), checked on the host side alone (dtypes
     and shapes: ValueError) before any tensor is handed to the device."""
@@ -1887,7 +1897,11 @@ def retrieve_topk_grouped(proj, types, type_rowptr, type_col, table, n, slices=0
     exclusion_csr builds it (the ids of a key strictly ascending): pc_retrieve_topk_grouped_excluding -- the first n products of
     the type that are NOT in the list of row_key[r] (-1: no list), the same order and the same bits.  A key outside
     [-1, n_keys) is served as -1 and counted in `bad` (a [1] int32 device counter the caller passes to see the count; added
-    to).  exclude=None: exactly the unfiltered call."""
+    to).  exclude=None: exactly the unfiltered call.
+    table: [P, D] fp32, or the [P, D] torch.bfloat16 copy catalogue_bf16 makes of it: pc_retrieve_topk_grouped_bf16 -- the
+    same contract, order and determinism over half the bytes, with or without exclude; the scores are the fp32-grade dot
+    products of the unrounded proj with the ROUNDED table (the query is split into three bf16 pieces, the products are
+    exact), so a list can differ from the fp32 table's where two products lie within bf16 rounding of each other."""
     if exclude is not None:
         exclude = _check_exclude("retrieve_topk_grouped", exclude, types.shape[0] if isinstance(types, torch.Tensor) else -1)
     elif bad is not None:
@@ -1898,12 +1912,30 @@ def retrieve_topk_grouped(proj, types, type_rowptr, type_col, table, n, slices=0
     _req(types, torch.int32, "types", (r,))
     _req(type_rowptr, torch.int32, "type_rowptr")
     _req(type_col, torch.int32, "type_col")
-    _req(table, torch.float32, "table")
+    bf16 = isinstance(table, torch.Tensor) and table.dtype == torch.bfloat16
+    _req(table, torch.bfloat16 if bf16 else torch.float32, "table")
     n, slices, t = int(n), int(slices), type_rowptr.numel() - 1
     if not 0 <= slices <= RETRIEVE_MAX_SLICES:
         raise ValueError(f"slices must be in [0, {RETRIEVE_MAX_SLICES}] (0 = automatic), got {slices}")
     out_idx = torch.empty(r, n, dtype=torch.int32, device=proj.device)
     out_sc = torch.empty(r, n, dtype=torch.float32, device=proj.device)
+    if bf16:
+        row_key = ex_rowptr = ex_col = None
+        n_keys = 0
+        if exclude is not None:
+            row_key, ex_rowptr, ex_col, n_keys = _exclude_args(exclude)
+            if bad is None:
+                bad = torch.zeros(1, dtype=torch.int32, device=proj.device)
+            else:
+                _req(bad, torch.int32, "bad", (1,))
+        nbytes = _lib.lib().pc_retrieve_topk_grouped_bf16_workspace_bytes(r, t, n, slices)
+        ws = workspace(nbytes, proj.device, "retrieve_grouped")
+        # (without a triple row_key, ex_rowptr, ex_col and bad are None: null pointers, n_keys 0)
+        check(_lib.lib().pc_retrieve_topk_grouped_bf16(_p(proj), _p(types), _p(row_key), r, _p(type_rowptr), _p(type_col),
+                                                       _p(table), t, _p(ex_rowptr), _p(ex_col), n_keys, n, d, slices,
+                                                       _p(out_idx), _p(out_sc), _p(bad), _p(ws), ws.numel(), _stream()),
+              "pc_retrieve_topk_grouped_bf16")
+        return out_idx, out_sc
     if exclude is not None:
         row_key, ex_rowptr, ex_col, n_keys = _exclude_args(exclude)
         if bad is None:
