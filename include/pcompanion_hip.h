@@ -1200,6 +1200,51 @@ int pc_retrieve_topk_grouped_bf16(const float *proj, const int32_t *types, const
                                   int slices, int32_t *out_idx, float *out_score, int32_t *bad_count, void *ws,
                                   size_t ws_bytes, void *stream);
 
+/* A per-product additive term on the score (ABI 8, additive; inference.SimilarProducts: Product2Vec is trained for the
+ * Euclidean order, and |q - e_p|^2 = |q|^2 - 2 (<q, e_p> - |e_p|^2 / 2), so the nearest product under L2 is the largest
+ * <q, e_p> + b_p with b_p = -|e_p|^2 / 2; the same term carries a popularity prior or a business boost).  bias
+ * [num_products] fp32; the score of row r and product p is
+ *   s(r, p) = fl(d(r, p) + bias[p]),  d(r, p) = pc_retrieve_topk_grouped's own fp32 MFMA chain over table [num_products, dim],
+ * one fp32 addition after the chain, so a zero bias gives the unbiased entries' output bit for bit.
+ *
+ * pc_half_sq_norm_bias: out[p] = -0.5f * sum_d table[p][d]^2 for p < rows, one fixed summation order per row (16 partial sums
+ * over the dimensions 4 l + 64 j + e, met in a butterfly), no atomics: the same bits for every launch geometry and run.
+ * PC_EINVAL: null pointer, rows <= 0; PC_ESHAPE: dim not 128 / 256.
+ *
+ * pc_retrieve_topk_grouped_biased: pc_retrieve_topk_grouped's contract, and pc_retrieve_topk_grouped_excluding's when row_key
+ * is given, under s: out_idx / out_score [rows, n] = the first n products of type types[r] (not in the list of row_key[r])
+ * under (s descending, product index ascending), out_score = s, -1 / -inf past the end of a short type and for a type outside
+ * [0, n_types).  row_key == NULL: no lists (ex_rowptr, ex_col NULL, n_keys 0; bad_count may be NULL).  With row_key the
+ * exclusion set is the CSR over keys described above; a key outside [-1, n_keys) is served as -1, never indexes memory and is
+ * counted in *bad_count (required then; added to).  The same plan, work items, selection, merge and workspace size
+ * (pc_retrieve_topk_grouped_biased_workspace_bytes, 0 for arguments out of range); bitwise deterministic and independent of
+ * `slices`, of the placement of the rows and of the order of type_col inside a type; no float atomics, no host readback.
+ * PC_EINVAL: null pointer, rows or n_types <= 0; with row_key a null ex_rowptr / ex_col / bad_count or n_keys < 0; without it a
+ * list or n_keys != 0; PC_ESHAPE: n outside [1, 16], dim not 128 / 256, slices outside [0, 64]; PC_EWORKSPACE: ws_bytes too
+ * small -- each checked before anything is launched.
+ *
+ * pc_rank_grouped_biased: pc_rank_grouped's contract under s -- rank_out[r] = #{ p of type types[r] : s_p > g or (s_p == g
+ * and p < y) }, g = s(r, y), y = targets[r] -- and, when row_key is given (then with ex_rowptr, ex_col and cand_type: all four
+ * or none), pc_rank_grouped_excluding's: the excluded products are not counted, and rank_out[r] = -1 where the target is in
+ * the row's list or cand_type[y] != types[r].  -1 and *bad_count for rows without a type or with an id out of range as
+ * pc_rank_grouped.  rank_out[r] < n exactly when pc_retrieve_topk_grouped_biased's top n (same lists) holds the target at
+ * that position.  Workspace: pc_rank_grouped_biased_workspace_bytes (pc_rank_grouped's size).  PC_EINVAL: null pointer, rows,
+ * n_types or num_products <= 0, n_keys < 0, half-given exclusion arguments; PC_ESHAPE: dim not 128 / 256, slices outside
+ * [0, 64]; PC_EWORKSPACE: ws_bytes too small -- each checked before anything is launched. */
+int pc_half_sq_norm_bias(const float *table, int rows, int dim, float *out, void *stream);
+size_t pc_retrieve_topk_grouped_biased_workspace_bytes(int rows, int n_types, int n, int slices);
+int pc_retrieve_topk_grouped_biased(const float *proj, const int32_t *types, const int32_t *row_key, int rows,
+                                    const int32_t *type_rowptr, const int32_t *type_col, const float *table,
+                                    const float *bias, int n_types, const int32_t *ex_rowptr, const int32_t *ex_col,
+                                    int n_keys, int n, int dim, int slices, int32_t *out_idx, float *out_score,
+                                    int32_t *bad_count, void *ws, size_t ws_bytes, void *stream);
+size_t pc_rank_grouped_biased_workspace_bytes(int rows, int n_types, int slices);
+int pc_rank_grouped_biased(const float *proj, const int32_t *types, const int32_t *targets, const int32_t *row_key, int rows,
+                           const int32_t *type_rowptr, const int32_t *type_col, const float *table, const float *bias,
+                           int n_types, int num_products, const int32_t *ex_rowptr, const int32_t *ex_col, int n_keys,
+                           const int32_t *cand_type, int dim, int slices, int32_t *rank_out, int32_t *bad_count, void *ws,
+                           size_t ws_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -219,6 +219,13 @@ SIGNATURES = {
     "pc_retrieve_topk_grouped_bf16_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "pc_retrieve_topk_grouped_bf16": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp,
                                            _sz, _vp]),
+    "pc_half_sq_norm_bias": (_i, [_vp, _i, _i, _vp, _vp]),
+    "pc_retrieve_topk_grouped_biased_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "pc_retrieve_topk_grouped_biased": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp,
+                                             _vp, _sz, _vp]),
+    "pc_rank_grouped_biased_workspace_bytes": (_sz, [_i, _i, _i]),
+    "pc_rank_grouped_biased": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _vp, _i, _i, _vp, _vp, _vp,
+                                    _sz, _vp]),
     "pc_hadamard_forward":(_i, [_vp, _vp, _i, _i, _vp, _vp]),
     "pc_hadamard_forward_dim": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
     "pc_hadamard_backward": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp]),

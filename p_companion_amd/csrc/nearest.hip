@@ -1,0 +1,658 @@
+// Grouped retrieval and grouped rank with a per-product additive term on the score (pc_retrieve_topk_grouped_biased,
+// pc_rank_grouped_biased; SimilarProducts in inference.py), and the term that makes them Euclidean (pc_half_sq_norm_bias):
+//   |q - e_p|^2 = |q|^2 - 2 (<q, e_p> - |e_p|^2 / 2),
+// so the nearest product under L2 is the largest <q, e_p> + b_p with b_p = -|e_p|^2 / 2.  retrieve.hip's contract, plan, work
+// items, chunks, selection and merge, and rank.hip's / rank_exclude.hip's counts; what differs is the score:
+//   s(r, p) = fl(d(r, p) + bias[p]),   d(r, p) = rk_chain (rank_chain.h) over the fp32 table,
+// ONE fp32 addition in the epilogue, after the chain -- the accumulator starts at zero, never at the bias -- so d is bit for bit
+// what pc_retrieve_topk_grouped orders by and a zero bias gives that entry's output.  A unit of its own: inside retrieve.hip or
+// rank.hip the new kernels move the register allocation of the existing ones, and those keep their instruction text; what
+// cannot be shared through a header (the list helpers, the item decode, the merge) is restated here.
+//
+//   plan     grouped_plan.hip as it is (tiles of TM = 8192 / D rows)
+//   score    nb_score_kernel: work item (type, slice, tile); query tile -> LDS in RK_QS rows; candidates in chunks of 64, one
+//            16-candidate column group per wave; a lane holds ONE set of row registers, which rk_chain refills with the next
+//            chunk's rows step by step (a tile of more than two 16-row groups in two passes of two accumulators); bias[pid] is
+//            a 4-byte gather per column, issued with the column's product id a chunk ahead; biased scores -> LDS, then
+//            rg_score_kernel's threshold test, per-thread lists of 16, exclusion lists
+//   merge    nb_merge_kernel: rg_merge_kernel's body
+//   rank     nb_rank_kernel: rk_rank_kernel with g = d(r, y) + bias[y] and every candidate compared as d + bias[pid] against g;
+//            nb_rank_exclude_kernel: rk_exclude_kernel's post-pass with the same biased scores
+//   bias     nb_half_sq_norm_kernel: out[p] = -0.5f * sum_d e[p][d]^2
+//
+// Determinism: the chain of a (row, product) pair runs in the order of the dimension index alone (step j, element e, k-lane h
+// cover dimension 16 j + 4 h + e), and the bias is a function of the product, so a (row, product) score has the same bits
+// wherever it is scored: in any tile, slice or column, in the retrieval and in both rank kernels.  Every selection is under the
+// total order (score descending, product index ascending), so the output does not depend on the slices, on the order of the
+// rows in a tile (the one thing the planning atomics decide) or on the order of type_col inside a type.  Counts are sums of
+// integers, one integer atomic per (row, slice).  No float atomics.
+#include <type_traits>
+#include "common.h"
+#include "grouped_plan.h"
+#include "rank_chain.h"
+
+#define NB_MAX_N 16                // (RG_MAX_N of retrieve.hip)
+
+// (retrieve.hip's rg_insert / rg_nth / rg_pop)
+__device__ __forceinline__ void nb_insert(float* v, int* ix, int n, float x, int xi) {
+#pragma unroll
+    for (int j = 0; j < NB_MAX_N; j++) {
+        if (j < n && rg_better(x, xi, v[j], ix[j])) {
+            const float tv = v[j]; const int ti = ix[j];
+            v[j] = x; ix[j] = xi; x = tv; xi = ti;
+        }
+    }
+}
+__device__ __forceinline__ void nb_nth(const float* v, const int* ix, int n, float& tv, int& ti) {
+#pragma unroll
+    for (int j = 0; j < NB_MAX_N; j++)
+        if (j == n - 1) { tv = v[j]; ti = ix[j]; }
+}
+__device__ __forceinline__ void nb_pop(float* v, int* ix) {
+#pragma unroll
+    for (int j = 0; j < NB_MAX_N - 1; j++) { v[j] = v[j + 1]; ix[j] = ix[j + 1]; }
+    v[NB_MAX_N - 1] = -INFINITY; ix[NB_MAX_N - 1] = RG_NONE;
+}
+
+// f(integral_constant<R>) for the R in [1, RMAX] that equals rg: rk_chain's group count is a template argument, so the chain is
+// straight-line code for every number of 16-row groups a tile can hold.
+template <int RMAX, class F>
+__device__ __forceinline__ void nb_dispatch_groups(int rg, F& f) {
+    if (rg == RMAX) f(std::integral_constant<int, RMAX>{});
+    else if constexpr (RMAX > 1) nb_dispatch_groups<RMAX - 1>(rg, f);
+}
+
+// Work item w = (type t, slice s, tile j) -> the tile's rows and the slice's candidates (rg_score_kernel's decode).
+struct NbItem { int s, p0, valid, rg, cb0, ce; };
+template <int TM>
+__device__ __forceinline__ NbItem nb_decode(int64_t w, const int64_t* __restrict__ item_start, const int32_t* __restrict__ cnt,
+                                            const int32_t* __restrict__ row_start, const int32_t* __restrict__ type_rowptr,
+                                            int n_types, int S) {
+    int lo = 0, hi = n_types - 1;                         // the largest t with item_start[t] <= w (< n_types: w < n_items)
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (item_start[mid] <= w) lo = mid; else hi = mid - 1;
+    }
+    const int t = lo;
+    const int rows_t = cnt[t];
+    const int tiles = (rows_t + TM - 1) / TM;
+    const int local = (int)(w - item_start[t]);
+    NbItem it;
+    it.s = local / tiles;
+    const int j = local - it.s * tiles;
+    it.p0 = row_start[t] + j * TM;
+    it.valid = min(TM, rows_t - j * TM);
+    it.rg = (it.valid + 15) >> 4;
+    const int c0 = type_rowptr[t], C = type_rowptr[t + 1] - c0;
+    int ns, L;
+    rg_slice_plan(C, S, ns, L);
+    it.cb0 = c0 + it.s * L;
+    it.ce = c0 + min(C, (it.s + 1) * L);
+    return it;
+}
+
+// the rows order[p0 .. p0 + valid) of proj as the query tile rk_chain reads (rows of RK_QS floats; rows past `valid` of the last
+// 16-row group are zero, rows past that group are never read)
+template <int D>
+__device__ __forceinline__ void nb_load_tile(float* q, const float* __restrict__ proj, const int32_t* __restrict__ order, int p0,
+                                             int valid, int rg, int tid) {
+    constexpr int QS = RK_QS(D);
+    // (opaque to the optimiser: the addresses below are formed per work item and die with the load; hoisted out of the item loop
+    // they live through the chunk loop, and the D = 128 kernels then keep three of them in scratch)
+    asm volatile("" : "+v"(tid));
+    for (int e = tid; e < rg * 16 * (D / 4); e += 256) {
+        const int row = e / (D / 4), d4 = e - row * (D / 4);
+        float4 x = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (row < valid) x = reinterpret_cast<const float4*>(proj + (size_t)order[p0 + row] * D)[d4];
+        *reinterpret_cast<float4*>(&q[row * QS + 4 * d4]) = x;
+    }
+}
+
+// Lane l of wave wv: column c = l & 15 (candidate wv * 16 + c of the chunk, query row g * 16 + c of the A operand), k-lane
+// h = l >> 4.  Partial lists: pv / pi [rows][S][n] at the row's grouped position.  EXCL: rg_score_excl_kernel's exclusion lists
+// (bisection after the threshold test, before the insertion) and the count of keys outside [-1, n_keys) in *bad_count.
+// A column past the slice's end (pid -1) reads product 0's row and bias[0]; nothing of it is used: its id in LDS is RG_NONE.
+template <int D, bool EXCL>
+// three waves per SIMD at D = 128 (the LDS allows three workgroups per CU) and two at D = 256, as rg_score_kernel
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(D == 128 ? 3 : 2))) void nb_score_kernel(
+    const float* __restrict__ proj, const int32_t* __restrict__ type_rowptr, const int32_t* __restrict__ type_col,
+    const float* __restrict__ table, const float* __restrict__ bias, int n_types, int n, int S, const int32_t* __restrict__ cnt,
+    const int32_t* __restrict__ row_start, const int64_t* __restrict__ item_start, const int32_t* __restrict__ order,
+    float* __restrict__ pv, int32_t* __restrict__ pi, const int32_t* __restrict__ row_key, int rows,
+    const int32_t* __restrict__ ex_rowptr, const int32_t* __restrict__ ex_col, int n_keys, int32_t* __restrict__ bad_count) {
+    constexpr int TM = 8192 / D;             // rows per tile: 64 (D = 128) or 32 (D = 256)
+    constexpr int RG = TM / 16;              // 16-row groups
+    constexpr int QS = RK_QS(D);             // padded LDS row
+    constexpr int TPR = 256 / TM;            // threads per row in the selection phase
+    constexpr int CPT = RG_CHUNK / TPR;      // candidates per thread per chunk
+    constexpr int NB = D / 16;               // float4 operands per lane per candidate
+    __shared__ __attribute__((aligned(16))) float q[TM * QS];
+    __shared__ float sc[TM][RG_CHUNK + 1];
+    __shared__ int cid[RG_CHUNK];
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, c = lane & 15, h = lane >> 4;
+    const int rr = tid / TPR, qq = tid % TPR;
+    const int64_t n_items = item_start[n_types];
+    if constexpr (EXCL) {
+        for (int r = blockIdx.x * 256 + tid; r < rows; r += gridDim.x * 256) {
+            const int key = row_key[r];
+            if (key < -1 || key >= n_keys) atomicAdd(bad_count, 1);
+        }
+    }
+    for (int64_t w = blockIdx.x; w < n_items; w += gridDim.x) {
+        const NbItem it = nb_decode<TM>(w, item_start, cnt, row_start, type_rowptr, n_types, S);
+        const int p0 = it.p0, valid = it.valid, rg = it.rg, cb0 = it.cb0, ce = it.ce;
+
+        __syncthreads();                                  // the previous item's readers of q are done
+        nb_load_tile<D>(q, proj, order, p0, valid, rg, tid);
+        float v[NB_MAX_N];
+        int ix[NB_MAX_N];
+#pragma unroll
+        for (int k = 0; k < NB_MAX_N; k++) { v[k] = -INFINITY; ix[k] = RG_NONE; }
+        float tv = -INFINITY, hv = -INFINITY;             // this thread's n-th entry; the row's threshold
+        int ti = RG_NONE, hix = RG_NONE;
+        int elo = 0, ehi = 0;                             // this thread's row's list: ex_col[elo, ehi)
+        if constexpr (EXCL) {
+            if (rr < valid) {
+                const int key = row_key[order[p0 + rr]];
+                if (key >= 0 && key < n_keys) { elo = ex_rowptr[key]; ehi = ex_rowptr[key + 1]; }
+            }
+        }
+
+        auto load_pid = [&](int cb) { const int cc = cb + wv * 16 + c; return cc < ce ? type_col[cc] : -1; };
+        float4 b[NB];
+        int pid = load_pid(cb0);
+        {
+            const float4* f = reinterpret_cast<const float4*>(table + (size_t)max(pid, 0) * D) + h;
+#pragma unroll
+            for (int k = 0; k < NB; k++) b[k] = f[4 * k];
+        }
+        float bs = bias[max(pid, 0)];
+        int pidn = load_pid(cb0 + RG_CHUNK);
+        __syncthreads();                                  // query tile in LDS
+
+        for (int cb = cb0; cb < ce; cb += RG_CHUNK) {
+            const int pidnn = load_pid(cb + 2 * RG_CHUNK);
+            // (the previous chunk's readers of cid are behind the barrier at the loop's end)
+            if (h == 0) cid[wv * 16 + c] = pid < 0 ? RG_NONE : pid;
+            // the next chunk's rows replace this one's step by step while it is scored
+            const float4* next = reinterpret_cast<const float4*>(table + (size_t)max(pidn, 0) * D) + h;
+            // A tile of more than two row groups is scored in two passes over the same row registers (the refill rides in the
+            // last pass): two accumulators at a time keep the D = 128 kernel inside the registers of three waves per SIMD.  An
+            // accumulator's chain is the same either way: the dimensions in index order.
+            auto score = [&](auto groups) {
+                constexpr int R = decltype(groups)::value, R1 = R > 2 ? 2 : R;
+                // C/D map of the 16x16 f32 MFMA: column lane & 15 (the candidate), row 4 (lane >> 4) + reg (the query row);
+                // the epilogue's one addition: s = fl(d + bias[pid])
+                {
+                    f32x4 acc[R1];
+#pragma unroll
+                    for (int g = 0; g < R1; g++) acc[g] = f32x4{0.f, 0.f, 0.f, 0.f};
+                    rk_chain<D, R1>(q, 0, b, R > 2 ? nullptr : next, acc, c, h);
+#pragma unroll
+                    for (int g = 0; g < R1; g++) {
+#pragma unroll
+                        for (int k = 0; k < 4; k++) sc[g * 16 + 4 * h + k][wv * 16 + c] = acc[g][k] + bs;
+                    }
+                }
+                if constexpr (R > 2) {
+                    f32x4 acc[R - 2];
+#pragma unroll
+                    for (int g = 0; g < R - 2; g++) acc[g] = f32x4{0.f, 0.f, 0.f, 0.f};
+                    rk_chain<D, R - 2>(q, 2, b, next, acc, c, h);
+#pragma unroll
+                    for (int g = 0; g < R - 2; g++) {
+#pragma unroll
+                        for (int k = 0; k < 4; k++) sc[(g + 2) * 16 + 4 * h + k][wv * 16 + c] = acc[g][k] + bs;
+                    }
+                }
+            };
+            nb_dispatch_groups<RG>(rg, score);
+            // the next chunk's term, with its product id, a chunk ahead: in flight through this chunk's selection (issued
+            // behind the chain, where a register is free for it)
+            const float bsn = bias[max(pidn, 0)];
+            __syncthreads();
+            // (rg_score_kernel's selection: the threshold test, then a loop over each lane's own survivors)
+            unsigned keep = 0;
+            if (rr < valid) {
+#pragma unroll
+                for (int k = 0; k < CPT; k++) {
+                    const int col = qq + TPR * k;
+                    const int xi = cid[col];
+                    keep |= (xi != RG_NONE && rg_better(sc[rr][col], xi, hv, hix) ? 1u : 0u) << k;
+                }
+            }
+            while (keep) {
+                const int k = __builtin_ctz(keep);
+                keep &= keep - 1;
+                const int col = qq + TPR * k;
+                const int xi = cid[col];
+                const float x = sc[rr][col];
+                if (rg_better(x, xi, hv, hix)) {
+                    if constexpr (EXCL) {
+                        int a = elo, b2 = ehi;            // the first list entry >= xi
+                        while (a < b2) {
+                            const int mid = (a + b2) >> 1;
+                            if (ex_col[mid] < xi) a = mid + 1; else b2 = mid;
+                        }
+                        if (a < ehi && ex_col[a] == xi) continue;     // excluded: never inserted, the threshold stays
+                    }
+                    nb_insert(v, ix, n, x, xi);
+                    nb_nth(v, ix, n, tv, ti);
+                    if (rg_better(tv, ti, hv, hix)) { hv = tv; hix = ti; }
+                }
+            }
+#pragma unroll
+            for (int o = TPR / 2; o >= 1; o >>= 1) {
+                const float ov = __shfl_xor(hv, o, 64);
+                const int oi = __shfl_xor(hix, o, 64);
+                if (rg_better(ov, oi, hv, hix)) { hv = ov; hix = oi; }
+            }
+            __syncthreads();
+            pid = pidn;
+            pidn = pidnn;
+            bs = bsn;
+        }
+        // the TPR lists of a row (adjacent lanes) -> the slice's top n of the row
+        for (int k = 0; k < n; k++) {
+            float bv = v[0];
+            int bi = ix[0];
+#pragma unroll
+            for (int o = TPR / 2; o >= 1; o >>= 1) {
+                const float ov = __shfl_xor(bv, o, 64);
+                const int oi = __shfl_xor(bi, o, 64);
+                if (rg_better(ov, oi, bv, bi)) { bv = ov; bi = oi; }
+            }
+            if (ix[0] == bi && bi != RG_NONE) nb_pop(v, ix);
+            if (qq == 0 && rr < valid) {
+                const size_t o = ((size_t)(p0 + rr) * S + it.s) * n + k;
+                pv[o] = bv;
+                pi[o] = bi;
+            }
+        }
+    }
+}
+
+// One wave per row: the top n of its slices' partial lists (rg_merge_kernel's contract and body).
+__global__ __launch_bounds__(256) void nb_merge_kernel(const int32_t* __restrict__ types, int rows,
+                                                       const int32_t* __restrict__ type_rowptr, int n_types, int n, int S,
+                                                       const int32_t* __restrict__ rank, const int32_t* __restrict__ row_start,
+                                                       const float* __restrict__ pv, const int32_t* __restrict__ pi,
+                                                       int32_t* __restrict__ out_idx, float* __restrict__ out_score) {
+    const int lane = threadIdx.x & 63;
+    const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (r >= rows) return;                                // wave-uniform
+    const int t = types[r];
+    int ns = 0, L = 0, p = 0;
+    if (t >= 0 && t < n_types) {
+        rg_slice_plan(type_rowptr[t + 1] - type_rowptr[t], S, ns, L);
+        if (ns > 0) p = row_start[t] + rank[r];
+    }
+    float v[NB_MAX_N];
+    int ix[NB_MAX_N];
+#pragma unroll
+    for (int k = 0; k < NB_MAX_N; k++) { v[k] = -INFINITY; ix[k] = RG_NONE; }
+    const size_t base = (size_t)p * S * n;
+    for (int e = lane; e < ns * n; e += 64) {
+        const int xi = pi[base + e];
+        if (xi != RG_NONE) nb_insert(v, ix, n, pv[base + e], xi);
+    }
+    for (int k = 0; k < n; k++) {
+        float bv = v[0];
+        int bi = ix[0];
+#pragma unroll
+        for (int o = 32; o >= 1; o >>= 1) {
+            const float ov = __shfl_xor(bv, o, 64);
+            const int oi = __shfl_xor(bi, o, 64);
+            if (rg_better(ov, oi, bv, bi)) { bv = ov; bi = oi; }
+        }
+        if (ix[0] == bi && bi != RG_NONE) nb_pop(v, ix);
+        if (lane == 0) {
+            out_idx[(size_t)r * n + k] = bi == RG_NONE ? -1 : bi;
+            out_score[(size_t)r * n + k] = bi == RG_NONE ? -INFINITY : bv;
+        }
+    }
+}
+
+// One work item's candidate stream for a tile of NG 16-row groups (rk_stream with the biased score): accumulator register k of
+// row group g holds query row g * 16 + 4 h + k; gs / ys: the rows' target scores g = d(r, y) + bias[y] and targets.  b / pid /
+// bs: the first chunk's rows, product ids and terms, pidn: the second chunk's ids (-1: a column past the slice's end; its b is
+// product 0's row and its scores are not counted).  Leaves the wave's counts in part[wv][row].
+template <int D, int NG>
+__device__ __forceinline__ void nb_stream(const float* q, const float* gs, const int* ys, int (*part)[8192 / D],
+                                          const int32_t* __restrict__ type_col, const float* __restrict__ table,
+                                          const float* __restrict__ bias, int cb0, int ce, float4 (&b)[D / 16], int pid, int pidn,
+                                          float bs, int wv, int c, int h) {
+    float gv[NG][4];
+    int cn[NG][4];
+#pragma unroll
+    for (int g = 0; g < NG; g++) {
+        const float4 x = *reinterpret_cast<const float4*>(&gs[g * 16 + 4 * h]);
+        gv[g][0] = x.x; gv[g][1] = x.y; gv[g][2] = x.z; gv[g][3] = x.w;
+#pragma unroll
+        for (int k = 0; k < 4; k++) cn[g][k] = 0;
+    }
+    for (int cb = cb0; cb < ce; cb += RG_CHUNK) {
+        const int cc = cb + 2 * RG_CHUNK + wv * 16 + c;
+        const int pidnn = cc < ce ? type_col[cc] : -1;
+        const float4* next = reinterpret_cast<const float4*>(table + (size_t)max(pidn, 0) * D) + h;
+        f32x4 acc[NG];
+#pragma unroll
+        for (int g = 0; g < NG; g++) acc[g] = f32x4{0.f, 0.f, 0.f, 0.f};
+        rk_chain<D, NG>(q, 0, b, next, acc, c, h);
+        // s = fl(d + bias[pid]) above g is counted; equal to g: the product index decides (rare: ys is read only then)
+        if (pid >= 0) {
+            bool tie = false;
+#pragma unroll
+            for (int g = 0; g < NG; g++) {
+                acc[g] += bs;
+#pragma unroll
+                for (int k = 0; k < 4; k++) {
+                    cn[g][k] += acc[g][k] > gv[g][k] ? 1 : 0;
+                    tie |= acc[g][k] == gv[g][k];
+                }
+            }
+            if (tie) {
+#pragma unroll
+                for (int g = 0; g < NG; g++)
+#pragma unroll
+                    for (int k = 0; k < 4; k++)
+                        cn[g][k] += (acc[g][k] == gv[g][k] && pid < ys[g * 16 + 4 * h + k]) ? 1 : 0;
+            }
+        }
+        const float bsn = bias[max(pidn, 0)];             // the next chunk's term, with its product id, a chunk ahead
+        pid = pidn;
+        pidn = pidnn;
+        bs = bsn;
+    }
+    // the 16 columns of a (wave, k-lane) -> lane c == 0
+#pragma unroll
+    for (int g = 0; g < NG; g++)
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            int v = cn[g][k];
+#pragma unroll
+            for (int o = 8; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
+            if (c == 0) part[wv][g * 16 + 4 * h + k] = v;
+        }
+}
+
+// rk_rank_kernel with the biased score: rank_out[r] += #{ p of the slice : s_p > g or (s_p == g and p < y) }, one integer atomic
+// per (row, slice).
+template <int D>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(D == 128 ? 3 : 2))) void nb_rank_kernel(
+    const float* __restrict__ proj, const int32_t* __restrict__ targets, const int32_t* __restrict__ type_rowptr,
+    const int32_t* __restrict__ type_col, const float* __restrict__ table, const float* __restrict__ bias, int n_types, int S,
+    const int32_t* __restrict__ cnt, const int32_t* __restrict__ row_start, const int64_t* __restrict__ item_start,
+    const int32_t* __restrict__ order, int32_t* __restrict__ rank_out) {
+    constexpr int TM = 8192 / D;
+    constexpr int RG = TM / 16;
+    constexpr int QS = RK_QS(D);
+    constexpr int NB = D / 16;
+    __shared__ __attribute__((aligned(16))) float q[TM * QS];
+    __shared__ __attribute__((aligned(16))) float gs[TM];            // the rows' target scores
+    __shared__ __attribute__((aligned(16))) int ys[TM];              // the rows' targets
+    __shared__ int part[4][TM];                                      // the waves' counts
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, c = lane & 15, h = lane >> 4;
+    const int64_t n_items = item_start[n_types];
+    for (int64_t w = blockIdx.x; w < n_items; w += gridDim.x) {
+        const NbItem it = nb_decode<TM>(w, item_start, cnt, row_start, type_rowptr, n_types, S);
+        const int p0 = it.p0, valid = it.valid, rg = it.rg, cb0 = it.cb0, ce = it.ce;
+
+        __syncthreads();                                  // the previous item's readers of q / part are done
+        nb_load_tile<D>(q, proj, order, p0, valid, rg, tid);
+
+        auto load_pid = [&](int cb) { const int cc = cb + wv * 16 + c; return cc < ce ? type_col[cc] : -1; };
+        // (a lane without a product reads product 0's row and term: no branch, and nothing of it is used)
+        auto load_b = [&](float4* b, int pid) {
+            const float4* f = reinterpret_cast<const float4*>(table + (size_t)max(pid, 0) * D) + h;
+#pragma unroll
+            for (int k = 0; k < NB; k++) b[k] = f[4 * k];
+        };
+        float4 b[NB];
+        const int pid = load_pid(cb0);
+        load_b(b, pid);
+        const float bs = bias[max(pid, 0)];
+        const int pidn = load_pid(cb0 + RG_CHUNK);
+        // wave wv: column c = the target of query row wv * 16 + c
+        int ty = -1;
+        if (wv < rg && wv * 16 + c < valid) ty = targets[order[p0 + wv * 16 + c]];
+        __syncthreads();                                  // query tile in LDS
+        if (wv < rg) {                                    // (wave-uniform)
+            float4 bt[NB];
+            load_b(bt, ty);
+            const float by = bias[max(ty, 0)];
+            f32x4 ag[1] = {f32x4{0.f, 0.f, 0.f, 0.f}};
+            rk_chain<D, 1>(q, wv, bt, nullptr, ag, c, h);
+            const f32x4 acc = ag[0];
+            // C/D map of the 16x16 f32 MFMA: column lane & 15, row 4 (lane >> 4) + reg; the diagonal: row == column
+            if ((c >> 2) == h) {
+                const int k = c & 3;
+                gs[wv * 16 + c] = (k == 0 ? acc[0] : k == 1 ? acc[1] : k == 2 ? acc[2] : acc[3]) + by;
+                ys[wv * 16 + c] = ty;
+            }
+        }
+        __syncthreads();                                  // gs / ys in LDS
+        if (rg == 1) nb_stream<D, 1>(q, gs, ys, part, type_col, table, bias, cb0, ce, b, pid, pidn, bs, wv, c, h);
+        else if (rg == 2) nb_stream<D, 2>(q, gs, ys, part, type_col, table, bias, cb0, ce, b, pid, pidn, bs, wv, c, h);
+        else if constexpr (RG == 4) {
+            if (rg == 3) nb_stream<D, 3>(q, gs, ys, part, type_col, table, bias, cb0, ce, b, pid, pidn, bs, wv, c, h);
+            else nb_stream<D, 4>(q, gs, ys, part, type_col, table, bias, cb0, ce, b, pid, pidn, bs, wv, c, h);
+        }
+        __syncthreads();
+        if (tid < valid) {
+            const int v = part[0][tid] + part[1][tid] + part[2][tid] + part[3][tid];
+            if (v) atomicAdd(&rank_out[order[p0 + tid]], v);
+        }
+    }
+}
+
+// rk_exclude_kernel's post-pass with the biased score.  One wave per row: column 0 of the first block is the target y, then the
+// row's list ex_col[elo, ehi); g and every s_e are the bits nb_rank_kernel compared.  A list entry e with cand_type[e] ==
+// types[r] and rg_better(s_e, e, g, y) was counted there: one off.  e == y, or cand_type[y] != types[r]: rank -1.  A row the plan
+// left at -1 stays so; an id outside [0, num_products) is passed over; a key outside [-1, n_keys) is no list and is counted in
+// *bad_count.  Integer work, the row's wave the one writer.
+template <int D>
+__global__ __launch_bounds__(64) void nb_rank_exclude_kernel(const float* __restrict__ proj, const int32_t* __restrict__ types,
+                                                             const int32_t* __restrict__ targets,
+                                                             const int32_t* __restrict__ row_key,
+                                                             const int32_t* __restrict__ ex_rowptr,
+                                                             const int32_t* __restrict__ ex_col, int n_keys,
+                                                             const int32_t* __restrict__ cand_type,
+                                                             const float* __restrict__ table, const float* __restrict__ bias,
+                                                             int num_products, int32_t* __restrict__ rank_out,
+                                                             int32_t* __restrict__ bad_count) {
+    constexpr int QS = RK_QS(D), NB = D / 16;
+    __shared__ __attribute__((aligned(16))) float q[16 * QS];
+    const int lane = threadIdx.x, c = lane & 15, h = lane >> 4;
+    const int r = blockIdx.x;
+    int key = row_key[r];
+    if (key < -1 || key >= n_keys) {
+        if (lane == 0) atomicAdd(bad_count, 1);
+        key = -1;
+    }
+    const int base = rank_out[r];
+    if (base < 0) return;                                 // (wave-uniform, as every exit below) no type, or an id out of range
+    const int t = types[r], y = targets[r];               // both inside their ranges: the plan counted the row
+    if (cand_type[y] != t) {
+        if (lane == 0) rank_out[r] = -1;
+        return;
+    }
+    if (key < 0) return;
+    const int elo = ex_rowptr[key], len = ex_rowptr[key + 1] - elo;
+    if (len <= 0) return;
+    for (int e = lane; e < 16 * (QS / 4); e += 64) {
+        const int row = e / (QS / 4), d4 = e - row * (QS / 4);
+        float4 x = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (row == 0 && d4 < D / 4) x = reinterpret_cast<const float4*>(proj + (size_t)r * D)[d4];
+        *reinterpret_cast<float4*>(&q[row * QS + 4 * d4]) = x;
+    }
+    __syncthreads();
+    float g = 0.f;
+    int dec = 0;
+    bool hit = false;
+    for (int v0 = 0; v0 <= len; v0 += 16) {               // column v: the target (v == 0), list entry v - 1
+        const int v = v0 + c;
+        int id = -1;
+        if (v == 0) id = y;
+        else if (v <= len) id = ex_col[elo + v - 1];
+        if (id >= num_products) id = -1;
+        float4 b[NB];
+        const float4* f = reinterpret_cast<const float4*>(table + (size_t)max(id, 0) * D) + h;
+#pragma unroll
+        for (int k = 0; k < NB; k++) b[k] = f[4 * k];
+        const float bs = bias[max(id, 0)];
+        f32x4 acc[1] = {f32x4{0.f, 0.f, 0.f, 0.f}};
+        rk_chain<D, 1>(q, 0, b, nullptr, acc, c, h);
+        // C/D map of the 16x16 f32 MFMA: column lane & 15, row 4 (lane >> 4) + reg: row 0 is register 0 of lanes 0..15
+        const float s = acc[0][0] + bs;
+        if (v0 == 0) g = __shfl(s, 0, 64);
+        const bool mine = h == 0 && v > 0 && id >= 0;
+        hit |= __any(mine && id == y);
+        dec += __popcll(__ballot(mine && id != y && cand_type[max(id, 0)] == t && rg_better(s, id, g, y)));
+    }
+    if (lane == 0) rank_out[r] = hit ? -1 : base - dec;
+}
+
+// out[p] = -0.5f * sum_d e[p][d]^2.  ONE summation order per row, whatever the grid: a group of 16 lanes owns a row; lane l of
+// the group adds, in this order, the squares of the elements x, y, z, w of the float4s l, l + 16, .. (dimensions 4 l + 64 j + e,
+// j ascending, e ascending) into one fp32 sum by fused multiply-add, starting from zero; the 16 sums meet in a butterfly over
+// the lane distances 8, 4, 2, 1 (a + b is commutative: every lane of the group holds the same bits).  No atomics; a row's value
+// does not depend on which group, block or launch geometry computes it.
+template <int D>
+__global__ __launch_bounds__(256) void nb_half_sq_norm_kernel(const float* __restrict__ table, int rows, float* __restrict__ out) {
+    const int l = threadIdx.x & 15;
+    const int64_t stride = (int64_t)gridDim.x * 16;
+    for (int64_t p = (int64_t)blockIdx.x * 16 + (threadIdx.x >> 4); p < rows; p += stride) {
+        const float4* f = reinterpret_cast<const float4*>(table + (size_t)p * D) + l;
+        float4 x[D / 64];
+#pragma unroll
+        for (int j = 0; j < D / 64; j++) x[j] = f[16 * j];
+        float s = 0.f;
+#pragma unroll
+        for (int j = 0; j < D / 64; j++) {
+            s = __builtin_fmaf(x[j].x, x[j].x, s);
+            s = __builtin_fmaf(x[j].y, x[j].y, s);
+            s = __builtin_fmaf(x[j].z, x[j].z, s);
+            s = __builtin_fmaf(x[j].w, x[j].w, s);
+        }
+        // (a group's 16 lanes run the same number of iterations: p depends on threadIdx.x >> 4 alone)
+#pragma unroll
+        for (int o = 8; o >= 1; o >>= 1) s += __shfl_xor(s, o, 64);
+        if (l == 0) out[p] = -0.5f * s;
+    }
+}
+
+namespace {
+// (retrieve.hip's layout: the plan, then the partial lists [rows][S][n])
+struct NbWs {
+    RgPlan plan;
+    float* pv;
+    int32_t* pi;
+    size_t bytes;
+};
+NbWs nb_layout(void* ws, int rows, int n_types, int n, int S) {
+    NbWs w;
+    WsCarver cv(ws);
+    w.plan = rg_plan_carve(cv, rows, n_types);
+    w.pv = (float*)cv.bytes((size_t)rows * S * n * 4);
+    w.pi = (int32_t*)cv.bytes((size_t)rows * S * n * 4);
+    w.bytes = cv.total;
+    return w;
+}
+}  // namespace
+
+extern "C" int pc_half_sq_norm_bias(const float* table, int rows, int dim, float* out, void* stream) {
+    if (!table || !out || rows <= 0) return PC_EINVAL;
+    if (dim != 128 && dim != 256) return PC_ESHAPE;
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 grid((unsigned)min((rows + 15) / 16, RG_MAX_GRID));        // 16 rows per workgroup and pass, grid-stride
+    if (dim == 128) PC_LAUNCH(nb_half_sq_norm_kernel<128>, grid, dim3(256), 0, st, table, rows, out);
+    else PC_LAUNCH(nb_half_sq_norm_kernel<256>, grid, dim3(256), 0, st, table, rows, out);
+    return pc_launch_status();
+}
+
+extern "C" size_t pc_retrieve_topk_grouped_biased_workspace_bytes(int rows, int n_types, int n, int slices) {
+    if (rows <= 0 || n_types <= 0 || n < 1 || n > NB_MAX_N || slices < 0 || slices > RG_MAX_SLICES) return 0;
+    return nb_layout(nullptr, rows, n_types, n, rg_slices(slices)).bytes;
+}
+
+extern "C" int pc_retrieve_topk_grouped_biased(const float* proj, const int32_t* types, const int32_t* row_key, int rows,
+                                               const int32_t* type_rowptr, const int32_t* type_col, const float* table,
+                                               const float* bias, int n_types, const int32_t* ex_rowptr, const int32_t* ex_col,
+                                               int n_keys, int n, int dim, int slices, int32_t* out_idx, float* out_score,
+                                               int32_t* bad_count, void* ws, size_t ws_bytes, void* stream) {
+    if (!proj || !types || !type_rowptr || !type_col || !table || !bias || !out_idx || !out_score || !ws) return PC_EINVAL;
+    if (rows <= 0 || n_types <= 0) return PC_EINVAL;
+    if (row_key) {
+        if (!ex_rowptr || !ex_col || !bad_count || n_keys < 0) return PC_EINVAL;
+    } else if (ex_rowptr || ex_col || n_keys != 0) {
+        return PC_EINVAL;
+    }
+    if (n < 1 || n > NB_MAX_N || (dim != 128 && dim != 256) || slices < 0 || slices > RG_MAX_SLICES) return PC_ESHAPE;
+    const int S = rg_slices(slices);
+    const NbWs w = nb_layout(ws, rows, n_types, n, S);
+    if (ws_bytes < w.bytes) return PC_EWORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    const int TM = 8192 / dim;
+    const RgPlan& pl = w.plan;
+    PC_TRY(rg_plan_launch(pl, types, nullptr, rows, type_rowptr, n_types, 0, S, TM, nullptr, nullptr, st));
+    const dim3 sgrid(rg_item_grid(rows, n_types, S, TM));
+#define NB_SCORE(D, EXCL)                                                                                                       \
+    PC_LAUNCH((nb_score_kernel<D, EXCL>), sgrid, dim3(256), 0, st, proj, type_rowptr, type_col, table, bias, n_types, n, S,     \
+              pl.cnt, pl.row_start, pl.item_start, pl.order, w.pv, w.pi, row_key, rows, ex_rowptr, ex_col, n_keys, bad_count)
+    if (dim == 128) {
+        if (row_key) NB_SCORE(128, true); else NB_SCORE(128, false);
+    } else {
+        if (row_key) NB_SCORE(256, true); else NB_SCORE(256, false);
+    }
+#undef NB_SCORE
+    PC_LAUNCH(nb_merge_kernel, dim3((rows + 3) / 4), dim3(256), 0, st, types, rows, type_rowptr, n_types, n, S, pl.pos,
+              pl.row_start, w.pv, w.pi, out_idx, out_score);
+    return pc_launch_status();
+}
+
+extern "C" size_t pc_rank_grouped_biased_workspace_bytes(int rows, int n_types, int slices) {
+    if (rows <= 0 || n_types <= 0 || slices < 0 || slices > RG_MAX_SLICES) return 0;
+    WsCarver cv(nullptr);
+    rg_plan_carve(cv, rows, n_types);
+    return cv.total;
+}
+
+extern "C" int pc_rank_grouped_biased(const float* proj, const int32_t* types, const int32_t* targets, const int32_t* row_key,
+                                      int rows, const int32_t* type_rowptr, const int32_t* type_col, const float* table,
+                                      const float* bias, int n_types, int num_products, const int32_t* ex_rowptr,
+                                      const int32_t* ex_col, int n_keys, const int32_t* cand_type, int dim, int slices,
+                                      int32_t* rank_out, int32_t* bad_count, void* ws, size_t ws_bytes, void* stream) {
+    if (!proj || !types || !targets || !type_rowptr || !type_col || !table || !bias || !rank_out || !bad_count || !ws)
+        return PC_EINVAL;
+    if (rows <= 0 || n_types <= 0 || num_products <= 0) return PC_EINVAL;
+    if (row_key) {
+        if (!ex_rowptr || !ex_col || !cand_type || n_keys < 0) return PC_EINVAL;
+    } else if (ex_rowptr || ex_col || cand_type || n_keys != 0) {
+        return PC_EINVAL;
+    }
+    if ((dim != 128 && dim != 256) || slices < 0 || slices > RG_MAX_SLICES) return PC_ESHAPE;
+    const int S = rg_slices(slices);
+    WsCarver cv(ws);
+    const RgPlan w = rg_plan_carve(cv, rows, n_types);
+    if (ws_bytes < cv.total) return PC_EWORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    const int TM = 8192 / dim;
+    PC_TRY(rg_plan_launch(w, types, targets, rows, type_rowptr, n_types, num_products, S, TM, rank_out, bad_count, st));
+    const dim3 sgrid(rg_item_grid(rows, n_types, S, TM));
+    if (dim == 128)
+        PC_LAUNCH(nb_rank_kernel<128>, sgrid, dim3(256), 0, st, proj, targets, type_rowptr, type_col, table, bias, n_types, S,
+                  w.cnt, w.row_start, w.item_start, w.order, rank_out);
+    else
+        PC_LAUNCH(nb_rank_kernel<256>, sgrid, dim3(256), 0, st, proj, targets, type_rowptr, type_col, table, bias, n_types, S,
+                  w.cnt, w.row_start, w.item_start, w.order, rank_out);
+    if (row_key) {
+        if (dim == 128)
+            PC_LAUNCH(nb_rank_exclude_kernel<128>, dim3(rows), dim3(64), 0, st, proj, types, targets, row_key, ex_rowptr, ex_col,
+                      n_keys, cand_type, table, bias, num_products, rank_out, bad_count);
+        else
+            PC_LAUNCH(nb_rank_exclude_kernel<256>, dim3(rows), dim3(64), 0, st, proj, types, targets, row_key, ex_rowptr, ex_col,
+                      n_keys, cand_type, table, bias, num_products, rank_out, bad_count);
+    }
+    return pc_launch_status();
+}

@@ -15,7 +15,11 @@ selection replaced by a count) -- and fold the held-out "test" pairs into hit@k 
 set_exclusions / set_eligible keep the query, its co-viewed substitutes and unservable products out of both
 (pc_retrieve_topk_grouped_excluding / pc_rank_grouped_excluding).
 catalogue= serves the lists of up to 16 from a bf16 copy of the product table (pc_retrieve_topk_grouped_bf16): half the bytes,
-scored against the unrounded query; the scores are those of the ROUNDED table."""
+scored against the unrounded query; the scores are those of the ROUNDED table.
+
+SimilarProducts is the substitute side: the nearest products of a query under Euclidean distance over any [P, D] fp32 table
+(Product2Vec's export), the grouped retrieval and rank with the per-product term -|e_p|^2 / 2 on the score
+(pc_retrieve_topk_grouped_biased / pc_rank_grouped_biased), and hit@k / MRR over held-out similar pairs."""
 import os
 from typing import Any, Dict, List
 
@@ -28,7 +32,77 @@ from .metrics import Metrics
 from .p_companion import PCompanion
 
 
-class PCompanionInference:
+class _CandidateFilters:
+    """set_exclusions / set_eligible for a class that serves type-grouped candidates (PCompanionInference, SimilarProducts).
+    The class provides device, type_idx [P] int32, _all_products = the unfiltered (type_rowptr, type_col), and the two hooks."""
+
+    def _candidate_types(self):
+        """(cand [P] int32: the type under which each product is a candidate, the number of types)"""
+        return self.type_idx, self.bpg.n_types
+
+    def _default_exclusions(self):
+        """the device CSR set_exclusions() takes when none is given"""
+        return self._graph["cv_rowptr"], self._graph["cv_col"]
+
+    def set_exclusions(self, rowptr=None, col=None, include_self=True):
+        """Keep named products out of what is served and ranked for a query: an exclusion set keyed by the QUERY product id.
+        Default: the graph's own co-view CSR (co-viewed products are substitutes) and, with include_self, the query itself,
+        through ops.exclusion_csr; rowptr / col: any device CSR over the products instead (a basket, say).  With a set installed
+        recommend_batch, rank_targets and evaluate_catalogue go through pc_retrieve_topk_grouped_excluding /
+        pc_rank_grouped_excluding with the query id as the row key of its K slots -- an uploaded IntBPG too: its arrays are on
+        the device, and the per-row kernel has no filter.  set_exclusions(False) removes the set.  Once per catalogue, off the
+        serving path.  (SimilarProducts: the default is the EMPTY CSR -- with include_self the query alone.)"""
+        if rowptr is False:
+            self.exclusions = None
+            return self
+        if (rowptr is None) != (col is None):
+            raise ValueError("set_exclusions: pass rowptr and col together, or neither for the co-view graph")
+        if rowptr is None:
+            rowptr, col = self._default_exclusions()
+        p = int(self.type_idx.shape[0])
+        if rowptr.numel() != p + 1:
+            raise ValueError(f"set_exclusions: the set is keyed by query id: rowptr must hold {p + 1} entries, got {rowptr.numel()}")
+        self.exclusions = ops.exclusion_csr(rowptr.to(self.device), col.to(self.device), include_self=include_self, num_products=p)
+        return self
+
+    def set_eligible(self, mask=None):
+        """Serve and rank over the eligible products only (in stock, not withdrawn): mask [P] bool on the device, None = all.
+        Rebuilds type_rowptr / type_col over the eligible products (ops.type_csr on the filtered ids) and forms
+        cand_type = where(mask, type_idx, -1); a held-out target that is not eligible gets rank -1."""
+        cand, n_types = self._candidate_types()
+        if mask is None:
+            self.eligible, self.cand_type = None, cand
+            self.type_rowptr, self.type_col = self._all_products
+            return self
+        p = int(self.type_idx.shape[0])
+        if not torch.is_tensor(mask) or mask.dtype != torch.bool or tuple(mask.shape) != (p,):
+            raise ValueError(f"set_eligible: expected a bool tensor of shape ({p},)")
+        mask = mask.to(self.device)
+        ids = torch.nonzero(mask).reshape(-1).to(torch.int32)
+        rowptr, local = ops.type_csr(cand[ids.long()].contiguous(), n_types)
+        self.type_rowptr, self.type_col = rowptr, ids[local.long()].contiguous()
+        self.eligible = mask
+        self.cand_type = torch.where(mask, cand, torch.full_like(cand, -1))
+        return self
+
+    def _excluded(self, query_idx, target_idx):
+        """[B] bool: target_idx[b] is in query_idx[b]'s exclusion list (a bisection per pair, as vector operations; the lists
+        are strictly ascending)."""
+        ex_rowptr, ex_col = self.exclusions
+        q = query_idx.long()
+        lo, end = ex_rowptr[q].long(), ex_rowptr[q + 1].long()
+        hi = end.clone()
+        if ex_col.numel() == 0:
+            return torch.zeros_like(q, dtype=torch.bool)
+        y = target_idx.long()
+        for _ in range(max(int(ex_col.numel()).bit_length(), 1)):
+            mid = (lo + hi) >> 1
+            below = (lo < hi) & (ex_col[mid.clamp(max=ex_col.numel() - 1)].long() < y)
+            lo, hi = torch.where(below, mid + 1, lo), torch.where(below | (lo >= hi), hi, mid)
+        return (lo < end) & (ex_col[lo.clamp(max=ex_col.numel() - 1)].long() == y)
+
+
+class PCompanionInference(_CandidateFilters):
     catalogue = None                           # the bf16 copy that is served from (__init__: catalogue=); None: the fp32 features
 
     def __init__(self, model, config, bpg: IntBPG, product_ids: List[str] = None, catalogue=None):
@@ -100,62 +174,6 @@ class PCompanionInference:
         self.type_rowptr = torch.from_numpy(rowptr).to(self.device)
         self.type_col = torch.from_numpy(order).to(self.device)
         self._all_products = (self.type_rowptr, self.type_col)
-
-    def set_exclusions(self, rowptr=None, col=None, include_self=True):
-        """Keep named products out of what is served and ranked for a query: an exclusion set keyed by the QUERY product id.
-        Default: the graph's own co-view CSR (co-viewed products are substitutes) and, with include_self, the query itself,
-        through ops.exclusion_csr; rowptr / col: any device CSR over the products instead (a basket, say).  With a set installed
-        recommend_batch, rank_targets and evaluate_catalogue go through pc_retrieve_topk_grouped_excluding /
-        pc_rank_grouped_excluding with the query id as the row key of its K slots -- an uploaded IntBPG too: its arrays are on
-        the device, and the per-row kernel has no filter.  set_exclusions(False) removes the set.  Once per catalogue, off the
-        serving path."""
-        if rowptr is False:
-            self.exclusions = None
-            return self
-        if (rowptr is None) != (col is None):
-            raise ValueError("set_exclusions: pass rowptr and col together, or neither for the co-view graph")
-        if rowptr is None:
-            rowptr, col = self._graph["cv_rowptr"], self._graph["cv_col"]
-        p = int(self.type_idx.shape[0])
-        if rowptr.numel() != p + 1:
-            raise ValueError(f"set_exclusions: the set is keyed by query id: rowptr must hold {p + 1} entries, got {rowptr.numel()}")
-        self.exclusions = ops.exclusion_csr(rowptr.to(self.device), col.to(self.device), include_self=include_self, num_products=p)
-        return self
-
-    def set_eligible(self, mask=None):
-        """Serve and rank over the eligible products only (in stock, not withdrawn): mask [P] bool on the device, None = all.
-        Rebuilds type_rowptr / type_col over the eligible products (ops.type_csr on the filtered ids) and forms
-        cand_type = where(mask, type_idx, -1); a held-out target that is not eligible gets rank -1."""
-        if mask is None:
-            self.eligible, self.cand_type = None, self.type_idx
-            self.type_rowptr, self.type_col = self._all_products
-            return self
-        p = int(self.type_idx.shape[0])
-        if not torch.is_tensor(mask) or mask.dtype != torch.bool or tuple(mask.shape) != (p,):
-            raise ValueError(f"set_eligible: expected a bool tensor of shape ({p},)")
-        mask = mask.to(self.device)
-        ids = torch.nonzero(mask).reshape(-1).to(torch.int32)
-        rowptr, local = ops.type_csr(self.type_idx[ids.long()].contiguous(), self.bpg.n_types)
-        self.type_rowptr, self.type_col = rowptr, ids[local.long()].contiguous()
-        self.eligible = mask
-        self.cand_type = torch.where(mask, self.type_idx, torch.full_like(self.type_idx, -1))
-        return self
-
-    def _excluded(self, query_idx, target_idx):
-        """[B] bool: target_idx[b] is in query_idx[b]'s exclusion list (a bisection per pair, as vector operations; the lists
-        are strictly ascending)."""
-        ex_rowptr, ex_col = self.exclusions
-        q = query_idx.long()
-        lo, end = ex_rowptr[q].long(), ex_rowptr[q + 1].long()
-        hi = end.clone()
-        if ex_col.numel() == 0:
-            return torch.zeros_like(q, dtype=torch.bool)
-        y = target_idx.long()
-        for _ in range(max(int(ex_col.numel()).bit_length(), 1)):
-            mid = (lo + hi) >> 1
-            below = (lo < hi) & (ex_col[mid.clamp(max=ex_col.numel() - 1)].long() < y)
-            lo, hi = torch.where(below, mid + 1, lo), torch.where(below | (lo >= hi), hi, mid)
-        return (lo < end) & (ex_col[lo.clamp(max=ex_col.numel() - 1)].long() == y)
 
     def _load_model(self, model_path):
         """Load trained model weights (inference.py:28-36)"""
@@ -340,3 +358,133 @@ class PCompanionInference:
             recommendations.append([self.product_ids[i] for i in ids] if self.product_ids is not None else ids.tolist())
             scores.append(sc[j][keep])
         return {"complementary_types": types.tolist(), "recommendations": recommendations, "scores": scores}
+
+
+class SimilarProducts(_CandidateFilters):
+    """Substitutes: the nearest products of a query under Euclidean distance over an embedding table -- the order Product2Vec's
+    triplet loss trains for.  |q - e_p|^2 = |q|^2 - 2 (<q, e_p> - |e_p|^2 / 2), so the nearest product is the largest
+    <q, e_p> + b_p with b_p = -|e_p|^2 / 2: ops.retrieve_topk_grouped / ops.rank_grouped with bias = ops.half_sq_norm_bias(table),
+    formed once here.  Everything around the grouped retrieval carries over: the plan, the slices, the total order (score
+    descending, product index ascending), exclusion lists, "rank < n exactly when the list holds the target at position rank",
+    bitwise determinism.
+
+    table: a [P, D] fp32 device tensor, D 128 or 256 -- Product2Vec.generate_embedding_table's export, or the raw features.
+    bpg: an IntBPG or a world-1 DeviceBPG over the same P products (type_idx).
+    scope "type": the candidates of a query are the products of its own type (ops.type_csr); "catalogue": every product, as
+    one type (rowptr = [0, P], col = arange(P)).
+    By default the query itself is excluded (set_exclusions() over an empty CSR with include_self), so a product is never its
+    own neighbour; the co-view graph is NOT excluded -- co-viewed products are the substitutes being looked for.
+    set_exclusions(False) removes the set; set_eligible(mask) serves and ranks over the eligible products only."""
+
+    MAX_N = 16
+
+    def __init__(self, table, bpg, scope="type"):
+        if scope not in ("type", "catalogue"):
+            raise ValueError(f"SimilarProducts: scope must be 'type' or 'catalogue', got {scope!r}")
+        if not torch.is_tensor(table) or table.dtype != torch.float32:
+            raise ValueError(f"SimilarProducts: the table must be a [P, D] float32 device tensor, got "
+                             f"{table.dtype if torch.is_tensor(table) else type(table).__name__}")
+        if table.dim() != 2 or table.shape[1] not in (128, 256) or table.shape[0] < 1:
+            raise ValueError(f"SimilarProducts: the table must be [P, 128 or 256], got {tuple(table.shape)}")
+        if not table.is_cuda or not table.is_contiguous():
+            raise ValueError("SimilarProducts: the table must be a contiguous device tensor")
+        if isinstance(bpg, DeviceBPG) and bpg.world != 1:
+            raise ValueError(f"SimilarProducts: this DeviceBPG holds a cyclic 1/{bpg.world} shard (rank {bpg.rank}); serving "
+                             "needs the whole catalogue on one device -- generate it with world = 1")
+        if bpg.num_products != table.shape[0]:
+            raise ValueError(f"SimilarProducts: the table holds {table.shape[0]} rows, the graph {bpg.num_products} products")
+        self.table, self.bpg, self.scope, self.device = table, bpg, scope, table.device
+        self._graph = bpg.cuda(self.device)
+        self.type_idx = self._graph["type_idx"]
+        p = table.shape[0]
+        if scope == "type":
+            self._scope_type, self._scope_types = self.type_idx, bpg.n_types
+            self._all_products = ops.type_csr(self.type_idx, bpg.n_types)
+        else:
+            self._scope_type, self._scope_types = torch.zeros(p, dtype=torch.int32, device=self.device), 1
+            self._all_products = (torch.tensor([0, p], dtype=torch.int32, device=self.device),
+                                  torch.arange(p, dtype=torch.int32, device=self.device))
+        self.type_rowptr, self.type_col = self._all_products
+        self.cand_type, self.eligible, self.exclusions = self._scope_type, None, None
+        self.bias = ops.half_sq_norm_bias(table)          # once per catalogue
+        self.set_exclusions()                             # the query itself
+
+    def _candidate_types(self):
+        return self._scope_type, self._scope_types
+
+    def _default_exclusions(self):
+        p = int(self.type_idx.shape[0])
+        return (torch.zeros(p + 1, dtype=torch.int32, device=self.device), torch.zeros(0, dtype=torch.int32, device=self.device))
+
+    @torch.no_grad()
+    def similar_batch(self, query_idx: torch.Tensor, n: int = 10):
+        """The n nearest candidates of every query, nearest first: (idx [B, n] int32, -1 past the end; dist [B, n] fp32, +inf
+        past the end).  The order is the biased retrieval's; dist is recomputed for the returned ids as |q - e + 1e-6|_2, the
+        distance of the triplet loss (F.pairwise_distance) -- not derived from the score, whose terms cancel."""
+        n = int(n)
+        if not 1 <= n <= self.MAX_N:
+            raise ValueError(f"similar_batch: 1 to {self.MAX_N} neighbours per query, got {n}")
+        query_idx = query_idx.to(self.device).to(torch.int32).contiguous()
+        if query_idx.dim() != 1:
+            raise ValueError("similar_batch: query_idx must be 1-D")
+        b = query_idx.shape[0]
+        if b == 0:
+            return (torch.empty(0, n, dtype=torch.int32, device=self.device),
+                    torch.empty(0, n, dtype=torch.float32, device=self.device))
+        q = self.table[query_idx.long()]
+        exclude = None if self.exclusions is None else (query_idx,) + self.exclusions
+        idx, _ = ops.retrieve_topk_grouped(q, self._scope_type[query_idx.long()].contiguous(), self.type_rowptr, self.type_col,
+                                           self.table, n, exclude=exclude, bias=self.bias)
+        e = self.table[idx.clamp(min=0).long()]                                   # [B, n, D]
+        dist = (q[:, None, :] - e + 1e-6).norm(dim=2)
+        return idx, torch.where(idx >= 0, dist, torch.full_like(dist, float("inf")))
+
+    @torch.no_grad()
+    def rank_pairs(self, anchor_idx: torch.Tensor, target_idx: torch.Tensor):
+        """Where does target_idx[b] stand among the neighbours of anchor_idx[b]?  slot[b] = 0 where the target is a candidate
+        of the anchor's scope (its type under scope "type"; eligible), -1 otherwise; rank[b] = the target's position in
+        similar_batch's list, were the list the whole scope -- rank < n exactly when similar_batch(anchor, n) holds the target
+        at that position -- and -1 as ops.rank_grouped defines: no candidate of the scope, in the anchor's exclusion list (the
+        anchor itself by default), outside the catalogue.  (slot, rank) int32 [B] on the device; nothing is read back."""
+        anchor_idx = anchor_idx.to(self.device).to(torch.int32).contiguous()
+        target_idx = target_idx.to(self.device).to(torch.int32).contiguous()
+        if anchor_idx.dim() != 1 or anchor_idx.shape != target_idx.shape:
+            raise ValueError("rank_pairs: anchor_idx and target_idx must be 1-D and of equal length")
+        if anchor_idx.shape[0] == 0:
+            e = torch.empty(0, dtype=torch.int32, device=self.device)
+            return e, e.clone()
+        p = self.table.shape[0]
+        row_type = self._scope_type[anchor_idx.long()]
+        inside = (target_idx >= 0) & (target_idx < p)
+        candidate = inside & (self.cand_type[target_idx.long().clamp(0, p - 1)] == row_type)
+        slot = torch.where(candidate, 0, -1).to(torch.int32)
+        q = self.table[anchor_idx.long()]
+        if self.exclusions is not None:
+            rank, _ = ops.rank_grouped(q, row_type.contiguous(), target_idx, self.type_rowptr, self.type_col, self.table,
+                                       exclude=(anchor_idx,) + self.exclusions, cand_type=self.cand_type, bias=self.bias)
+            return slot, rank
+        # no lists: a target that is no candidate costs no search
+        row_type = torch.where(candidate, row_type, torch.full_like(row_type, -1)).contiguous()
+        rank, _ = ops.rank_grouped(q, row_type, target_idx, self.type_rowptr, self.type_col, self.table, bias=self.bias)
+        return slot, rank
+
+    def evaluate_pairs(self, pairs, ks=(1, 3, 10, 100), chunk: int = 65536) -> Dict[str, Any]:
+        """Are held-out similar pairs among the neighbours that are served?  pairs [M, 2] (anchor, target) int -- whatever the
+        caller held out, e.g. the co-view pairs of a later window of edges.  Chunks of `chunk` pairs go through rank_pairs
+        into two device vectors; Metrics.catalogue_metrics folds them and reads back once: {"pairs", "type_hit" (the share
+        whose target is a candidate of the anchor's scope), "hit@k" for k in ks, "mrr", "median_rank"}."""
+        chunk = int(chunk)
+        if chunk < 1:
+            raise ValueError("evaluate_pairs: chunk must be positive")
+        if not torch.is_tensor(pairs):
+            pairs = torch.from_numpy(np.ascontiguousarray(np.asarray(pairs), dtype=np.int32))
+        if pairs.dim() != 2 or pairs.shape[1] != 2 or pairs.shape[0] == 0:
+            raise ValueError(f"evaluate_pairs: expected a non-empty [M, 2] array of (anchor, target), got {tuple(pairs.shape)}")
+        pairs = pairs.to(self.device).to(torch.int32)
+        m = pairs.shape[0]
+        slot = torch.empty(m, dtype=torch.int32, device=self.device)
+        rank = torch.empty(m, dtype=torch.int32, device=self.device)
+        for lo in range(0, m, chunk):
+            hi = min(lo + chunk, m)
+            slot[lo:hi], rank[lo:hi] = self.rank_pairs(pairs[lo:hi, 0], pairs[lo:hi, 1])
+        return Metrics.catalogue_metrics(slot, rank, ks)

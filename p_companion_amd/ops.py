@@ -1888,7 +1888,35 @@ def _exclude_args(exclude):
     return row_key, ex_rowptr, ex_col, ex_rowptr.numel() - 1
 
 
-def retrieve_topk_grouped(proj, types, type_rowptr, type_col, table, n, slices=0, exclude=None, bad=None):
+def half_sq_norm_bias(table):
+    """pc_half_sq_norm_bias: bias[p] = -0.5 * |table[p]|^2 for a [P, D] fp32 device table -> [P] fp32, the per-product term under
+    which retrieve_topk_grouped / rank_grouped (bias=) order by Euclidean distance: |q - e|^2 = |q|^2 - 2 (<q, e> + bias).  One
+    fixed summation order per row, no atomics: the same bits on every run.  Once per catalogue."""
+    _req(table, torch.float32, "table")
+    if table.dim() != 2:
+        raise ValueError(f"table: expected [P, D], got shape {tuple(table.shape)}")
+    d = _width(table.shape[1])
+    if table.shape[0] < 1:
+        raise ValueError("table: expected at least one row")
+    out = torch.empty(table.shape[0], dtype=torch.float32, device=table.device)
+    check(_lib.lib().pc_half_sq_norm_bias(_p(table), table.shape[0], d, _p(out), _stream()), "pc_half_sq_norm_bias")
+    return out
+
+
+def _check_bias(what, bias, table):
+    """bias: a [P] fp32 tensor beside an fp32 table, checked on the host side alone (ValueError) before any launch."""
+    if not isinstance(bias, torch.Tensor):
+        raise ValueError(f"{what}: bias must be a [P] float32 device tensor, got {type(bias).__name__}")
+    if isinstance(table, torch.Tensor) and table.dtype == torch.bfloat16:
+        raise ValueError(f"{what}: bias with a bf16 table is not supported (the biased entries read the fp32 table)")
+    if bias.dtype != torch.float32:
+        raise ValueError(f"{what}: bias of dtype {bias.dtype} is not supported: it must be float32")
+    if bias.dim() != 1 or bias.shape[0] != table.shape[0]:
+        raise ValueError(f"{what}: bias of shape {tuple(bias.shape)} is not supported: it must hold one entry per product "
+                         f"({table.shape[0]})")
+
+
+def retrieve_topk_grouped(proj, types, type_rowptr, type_col, table, n, slices=0, exclude=None, bad=None, bias=None):
     """pc_retrieve_topk_grouped: retrieve_topk's contract (idx [R,n] int32, -1 = none; scores [R,n] fp32, -inf = none) for a
     catalogue of any size -- rows grouped by type on the device, each type's candidates scored as a tiled fp32 MFMA GEMM,
     large types split over up to `slices` candidate slices (0 = automatic).  Bitwise deterministic, the same bits for every
@@ -1901,7 +1929,13 @@ def retrieve_topk_grouped(proj, types, type_rowptr, type_col, table, n, slices=0
     table: [P, D] fp32, or the [P, D] torch.bfloat16 copy catalogue_bf16 makes of it: pc_retrieve_topk_grouped_bf16 -- the
     same contract, order and determinism over half the bytes, with or without exclude; the scores are the fp32-grade dot
     products of the unrounded proj with the ROUNDED table (the query is split into three bf16 pieces, the products are
-    exact), so a list can differ from the fp32 table's where two products lie within bf16 rounding of each other."""
+    exact), so a list can differ from the fp32 table's where two products lie within bf16 rounding of each other.
+    bias: a [P] fp32 device tensor (fp32 table only): pc_retrieve_topk_grouped_biased -- the same contract, order and
+    determinism under the score fl(<proj[r], table[p]> + bias[p]), one fp32 addition after the unbiased entry's own chain (a
+    zero bias gives that entry's bits), with or without exclude; half_sq_norm_bias(table) makes the order Euclidean.
+    bias=None: exactly the calls above."""
+    if bias is not None:
+        _check_bias("retrieve_topk_grouped", bias, table)
     if exclude is not None:
         exclude = _check_exclude("retrieve_topk_grouped", exclude, types.shape[0] if isinstance(types, torch.Tensor) else -1)
     elif bad is not None:
@@ -1919,6 +1953,24 @@ def retrieve_topk_grouped(proj, types, type_rowptr, type_col, table, n, slices=0
         raise ValueError(f"slices must be in [0, {RETRIEVE_MAX_SLICES}] (0 = automatic), got {slices}")
     out_idx = torch.empty(r, n, dtype=torch.int32, device=proj.device)
     out_sc = torch.empty(r, n, dtype=torch.float32, device=proj.device)
+    if bias is not None:
+        _req(bias, torch.float32, "bias", (table.shape[0],))
+        row_key = ex_rowptr = ex_col = None
+        n_keys = 0
+        if exclude is not None:
+            row_key, ex_rowptr, ex_col, n_keys = _exclude_args(exclude)
+            if bad is None:
+                bad = torch.zeros(1, dtype=torch.int32, device=proj.device)
+            else:
+                _req(bad, torch.int32, "bad", (1,))
+        nbytes = _lib.lib().pc_retrieve_topk_grouped_biased_workspace_bytes(r, t, n, slices)
+        ws = workspace(nbytes, proj.device, "retrieve_grouped")
+        # (without a triple row_key, ex_rowptr, ex_col and bad are None: null pointers, n_keys 0)
+        check(_lib.lib().pc_retrieve_topk_grouped_biased(_p(proj), _p(types), _p(row_key), r, _p(type_rowptr), _p(type_col),
+                                                         _p(table), _p(bias), t, _p(ex_rowptr), _p(ex_col), n_keys, n, d, slices,
+                                                         _p(out_idx), _p(out_sc), _p(bad), _p(ws), ws.numel(), _stream()),
+              "pc_retrieve_topk_grouped_biased")
+        return out_idx, out_sc
     if bf16:
         row_key = ex_rowptr = ex_col = None
         n_keys = 0
@@ -2004,7 +2056,8 @@ def retrieve_list_grouped(proj, types, type_rowptr, type_col, table, n, slices=0
     return out_idx, out_sc
 
 
-def rank_grouped(proj, types, targets, type_rowptr, type_col, table, slices=0, bad=None, exclude=None, cand_type=None):
+def rank_grouped(proj, types, targets, type_rowptr, type_col, table, slices=0, bad=None, exclude=None, cand_type=None,
+                 bias=None):
     """pc_rank_grouped: for row r the number of products of type types[r] that retrieve_topk_grouped orders in front of
     targets[r] under proj[r] (score descending, product index ascending) -- the position of the target in the served list,
     over the whole type, from the retrieval's own score bits: rank < n exactly when retrieve_topk_grouped(..., n) holds the
@@ -2015,7 +2068,12 @@ def rank_grouped(proj, types, targets, type_rowptr, type_col, table, slices=0, b
     p is a candidate, -1 if none; it must agree with type_rowptr / type_col): pc_rank_grouped_excluding -- the number of
     NON-excluded products of the type in front of the target, -1 where the target is in the row's list or is no candidate of
     the row's type; rank < n exactly when the filtered retrieval holds the target at position rank.  A key outside
-    [-1, n_keys) is served as -1 and counted in `bad`.  exclude=None: exactly the unfiltered call."""
+    [-1, n_keys) is served as -1 and counted in `bad`.  exclude=None: exactly the unfiltered call.
+    bias: a [P] fp32 device tensor: pc_rank_grouped_biased -- the same counts under retrieve_topk_grouped(bias=)'s score
+    fl(<proj[r], table[p]> + bias[p]), with or without exclude / cand_type: rank < n exactly when that call holds the target at
+    position rank.  bias=None: exactly the calls above."""
+    if bias is not None:
+        _check_bias("rank_grouped", bias, table)
     if exclude is not None:
         exclude = _check_exclude("rank_grouped", exclude, types.shape[0] if isinstance(types, torch.Tensor) else -1)
         if cand_type is None:
@@ -2041,6 +2099,21 @@ def rank_grouped(proj, types, targets, type_rowptr, type_col, table, slices=0, b
         bad = torch.zeros(1, dtype=torch.int32, device=proj.device)
     else:
         _req(bad, torch.int32, "bad", (1,))
+    if bias is not None:
+        _req(bias, torch.float32, "bias", (table.shape[0],))
+        row_key = ex_rowptr = ex_col = None
+        n_keys = 0
+        if exclude is not None:
+            row_key, ex_rowptr, ex_col, n_keys = _exclude_args(exclude)
+            _req(cand_type, torch.int32, "cand_type", (table.shape[0],))
+        nbytes = _lib.lib().pc_rank_grouped_biased_workspace_bytes(r, t, slices)
+        ws = workspace(nbytes, proj.device, "rank_grouped")
+        # (without a triple row_key, ex_rowptr, ex_col and cand_type are None: null pointers, n_keys 0)
+        check(_lib.lib().pc_rank_grouped_biased(_p(proj), _p(types), _p(targets), _p(row_key), r, _p(type_rowptr), _p(type_col),
+                                                _p(table), _p(bias), t, table.shape[0], _p(ex_rowptr), _p(ex_col), n_keys,
+                                                _p(cand_type), d, slices, _p(rank), _p(bad), _p(ws), ws.numel(), _stream()),
+              "pc_rank_grouped_biased")
+        return rank, bad
     nbytes = _lib.lib().pc_rank_grouped_workspace_bytes(r, t, slices)
     ws = workspace(nbytes, proj.device, "rank_grouped")
     if exclude is not None:
