@@ -1245,6 +1245,47 @@ int pc_rank_grouped_biased(const float *proj, const int32_t *types, const int32_
                            const int32_t *cand_type, int dim, int slices, int32_t *rank_out, int32_t *bad_count, void *ws,
                            size_t ws_bytes, void *stream);
 
+/* A trainable product table in the joint step (ABI 8, additive; csrc/table_train.hip; a labelled extension -- the reference's
+ * table is frozen -- for one device).  In the batch layout only the query row reaches the table (p_companion.py:51), so the
+ * rows with a gradient are query_idx and the only path is the item hinge through item_projection.
+ *
+ * pc_joint_query_grad: dq [B, dim] = d(loss)/d(E_prod[query_idx[b]]) of pc_joint_train_step's loss for the K predicted types
+ * topk [B, K] of the step that just ran (the type branch does not depend on the query row, topk carries no gradient):
+ *   pi_b = W_item q_b + b_item;  tp_bk = W_type E_c[topk[b,k]] + b_type;  x_bk = pi_b * tp_bk
+ *   np = |x_bk - pos_b|, nn = |x_bk - neg_b| (no eps), l = margin - np + nn, g = l > 0 ? alpha / (B K) : 0
+ *   dx_bk = -(x_bk - pos_b) (np > 0 ? g / np : 0) + (x_bk - neg_b) (nn > 0 ? g / nn : 0)
+ *   dq_b = W_item^T sum_k dx_bk * tp_bk
+ * -- pc_joint_loss's conventions (strict hinge, subgradient 0 at a zero norm).  p: the step's parameters with product_table
+ * [num_products, dim] set; dim 128 or 256; dq is written for every row.  A query_idx outside [0, num_products) or a topk id
+ * outside [0, T) never indexes anything: the sample's dq row is zero and every such id adds one to *bad (int32 [1], added to).
+ * Six launches on `stream` (id check, the two projections, W_item^T, the row-wise pass, the product with W_item^T), no host
+ * readback; ws: pc_joint_query_grad_workspace_bytes(B, K, dim) (0 for arguments out of range).  PC_EINVAL: null pointer,
+ * B, T or num_products <= 0; PC_ESHAPE: K outside [1, 8] or > T, dim not 128 / 256, pos_items / neg_items / dq / ws not
+ * 16-byte aligned; PC_EWORKSPACE: ws_bytes too small -- each checked before anything is launched.
+ *
+ * pc_sparse_adam_rows: torch.optim.SparseAdam (no weight decay) over table [P, dim] with moments exp_avg / exp_avg_sq [P, dim]:
+ * moments and parameter of a row move only in a step that names it.  idx [R] int32 (duplicates expected), grad [R, dim],
+ * step number t >= 1 owned by the host.  For every distinct id u in [0, P), with every fl one fp32 rounding (no contraction,
+ * division and square root correctly rounded):
+ *   g_u = grad[r1] + grad[r2] + ...   over all r with idx[r] = u, sequential fp32 adds in ascending r
+ *   m_u += fl(fl(g_u - m_u) fl32(1 - beta1));  v_u += fl(fl(fl(g_u g_u) - v_u) fl32(1 - beta2))
+ *   p_u += fl(fl32(-s) fl(m_u / fl(sqrt(v_u) + fl32(eps)))),  s = lr sqrt(1 - beta2^t) / (1 - beta1^t) in fp64
+ * An id of -1 is skipped (padding); any other id outside [0, P) is skipped, never indexes anything and adds one to *bad
+ * (int32 [1], added to).  Rows not named keep their bits.  The sources of a row are brought together by a stable LSD radix
+ * sort of (id, r) (8-bit digits over bit_length(P) bits; one launch up to R = 8192, three per digit above) and one wave per
+ * distinct row applies the update: no float atomics, the result is a function of the inputs alone.  1 <= R <= 2^20; ws:
+ * pc_sparse_adam_rows_workspace_bytes(R) (0 for R out of range).  PC_EINVAL: null pointer, P < 1 or >= 2^31, R out of
+ * range, t < 1; PC_ESHAPE: dim not 128 / 256, table / exp_avg / exp_avg_sq / grad / ws not 16-byte aligned, idx / bad not
+ * 4-byte aligned; PC_EWORKSPACE: ws_bytes too small -- each checked before anything is launched. */
+size_t pc_joint_query_grad_workspace_bytes(int batch, int k, int dim);
+int pc_joint_query_grad(const pc_joint_tensors *p, const int32_t *query_idx, const int32_t *topk, const float *pos_items,
+                        const float *neg_items, int batch, int64_t num_products, int num_types, int k, int dim, float margin,
+                        float alpha, float *dq, int32_t *bad, void *ws, size_t ws_bytes, void *stream);
+size_t pc_sparse_adam_rows_workspace_bytes(int rows);
+int pc_sparse_adam_rows(float *table, float *exp_avg, float *exp_avg_sq, int64_t num_products, int dim, const int32_t *idx,
+                        const float *grad, int rows, int64_t t, double lr, double beta1, double beta2, double eps,
+                        int32_t *bad, void *ws, size_t ws_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -226,6 +226,11 @@ SIGNATURES = {
     "pc_rank_grouped_biased_workspace_bytes": (_sz, [_i, _i, _i]),
     "pc_rank_grouped_biased": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _vp, _i, _i, _vp, _vp, _vp,
                                     _sz, _vp]),
+    # a trainable product table (csrc/table_train.hip; ABI 8, additive)
+    "pc_joint_query_grad_workspace_bytes": (_sz, [_i, _i, _i]),
+    "pc_joint_query_grad": (_i, [_P(JointTensors), _vp, _vp, _vp, _vp, _i, _i64, _i, _i, _i, _f, _f, _vp, _vp, _vp, _sz, _vp]),
+    "pc_sparse_adam_rows_workspace_bytes": (_sz, [_i]),
+    "pc_sparse_adam_rows": (_i, [_vp, _vp, _vp, _i64, _i, _vp, _vp, _i, _i64, _d, _d, _d, _d, _vp, _vp, _sz, _vp]),
     "pc_hadamard_forward":(_i, [_vp, _vp, _i, _i, _vp, _vp]),
     "pc_hadamard_forward_dim": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
     "pc_hadamard_backward": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp]),

@@ -1023,6 +1023,76 @@ def joint_train_step(params, grads, query_idx, query_types, pos_types, neg_types
     return losses, topk
 
 
+def _bad_counter(bad, device):
+    if bad is None:
+        return torch.zeros(1, dtype=torch.int32, device=device)
+    return _req(bad, torch.int32, "bad", (1,))
+
+
+def joint_query_grad(params, query_idx, topk, pos_items, neg_items, margin, alpha, bad=None):
+    """pc_joint_query_grad: dq [B, D] = d(loss)/d(product_embeddings.weight[query_idx[b]]) of the joint step's loss for the
+    predicted types topk [B, K] of the step that just ran -- the only rows of the product table the batch reaches, through the
+    item hinge alone.  params: the step's tensor dict with "product_embeddings.weight" [P, D], D = 128 or 256.  A query_idx
+    outside the table or a topk id outside the type table gives a zero row and one count in `bad` (int32 [1], added to)."""
+    table = params.get("product_embeddings.weight")
+    _req(table, torch.float32, "product_embeddings.weight")
+    if table.dim() != 2:
+        raise ValueError(f"product_embeddings.weight: expected [P, D], got shape {tuple(table.shape)}")
+    d = _width(table.shape[1])
+    _req(query_idx, torch.int32, "query_idx")
+    if query_idx.dim() != 1 or query_idx.numel() < 1:
+        raise ValueError(f"query_idx: expected [B], got shape {tuple(query_idx.shape)}")
+    b = query_idx.numel()
+    _req(topk, torch.int32, "topk")
+    if topk.dim() != 2 or topk.shape[0] != b:
+        raise ValueError(f"topk: expected [B, K] with B = {b}, got shape {tuple(topk.shape)}")
+    k = topk.shape[1]
+    t = params["complementary_type_embeddings.weight"].shape[0]
+    if not 1 <= k <= min(8, t):
+        raise ValueError(f"topk: K = {k} outside [1, min(8, NUM_TYPES = {t})]")
+    _req(pos_items, torch.float32, "positive_items", (b, d)); _req(neg_items, torch.float32, "negative_items", (b, d))
+    st, dev = joint_struct(params)
+    if tuple(params["item_prediction.item_projection.weight"].shape) != (d, d) or \
+            tuple(params["item_prediction.type_projection.weight"].shape) != (d, L):
+        raise ValueError(f"the projections do not match the table's width {d}")
+    bad = _bad_counter(bad, dev)
+    dq = torch.empty(b, d, dtype=torch.float32, device=dev)
+    nbytes = _lib.lib().pc_joint_query_grad_workspace_bytes(b, k, d)
+    ws = workspace(nbytes, dev, "query_grad")
+    check(_lib.lib().pc_joint_query_grad(ctypes.byref(st), _p(query_idx), _p(topk), _p(pos_items), _p(neg_items), b,
+                                         table.shape[0], t, k, d, float(margin), float(alpha), _p(dq), _p(bad), _p(ws), nbytes,
+                                         _stream()), "pc_joint_query_grad")
+    return dq
+
+
+SPARSE_ADAM_MAX_ROWS = 1 << 20
+
+
+def sparse_adam_rows(table, exp_avg, exp_avg_sq, idx, grad, t, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, bad=None):
+    """pc_sparse_adam_rows: torch.optim.SparseAdam's step number t (>= 1, owned by the caller) over the rows idx [R] of table
+    [P, D] (in place, with its moments): duplicates are summed in ascending position, -1 is skipped, any other id outside
+    [0, P) is skipped and counted in `bad` (int32 [1], added to); rows not named keep their bits.  No float atomics: the same
+    bits on every run."""
+    _req(table, torch.float32, "table")
+    if table.dim() != 2 or table.shape[0] < 1:
+        raise ValueError(f"table: expected [P, D], got shape {tuple(table.shape)}")
+    p, d = table.shape[0], _width(table.shape[1])
+    _req(exp_avg, torch.float32, "exp_avg", (p, d)); _req(exp_avg_sq, torch.float32, "exp_avg_sq", (p, d))
+    _req(idx, torch.int32, "idx")
+    if idx.dim() != 1 or not 1 <= idx.numel() <= SPARSE_ADAM_MAX_ROWS:
+        raise ValueError(f"idx: expected [R] with 1 <= R <= {SPARSE_ADAM_MAX_ROWS}, got shape {tuple(idx.shape)}")
+    r = idx.numel()
+    _req(grad, torch.float32, "grad", (r, d))
+    if int(t) < 1:
+        raise ValueError(f"t = {t}: the step number starts at 1")
+    bad = _bad_counter(bad, table.device)
+    nbytes = _lib.lib().pc_sparse_adam_rows_workspace_bytes(r)
+    ws = workspace(nbytes, table.device, "sparse_adam")
+    check(_lib.lib().pc_sparse_adam_rows(_p(table), _p(exp_avg), _p(exp_avg_sq), p, d, _p(idx), _p(grad), r, int(t), float(lr),
+                                         float(betas[0]), float(betas[1]), float(eps), _p(bad), _p(ws), nbytes, _stream()),
+          "pc_sparse_adam_rows")
+
+
 def joint_fused_supported(num_types, k, dropout_p=0.0):
     return bool(_lib.lib().pc_joint_fused_supported(int(num_types), int(k), float(dropout_p)))
 

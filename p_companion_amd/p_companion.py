@@ -277,13 +277,17 @@ class PCompanion(nn.Module, _FlatParamsMixin):
                                 negative_items.float().contiguous(), float(self.config.MARGIN), 1.0, 2)
 
     # ------------------------------------------------------------------ fused loop body
-    def train_step(self, batch, optimizer=None):
+    def train_step(self, batch, optimizer=None, table_optimizer=None):
         """train.py:42-46 (forward, compute_loss, zero_grad, backward) as one C-ABI call; with `optimizer` (a FusedAdam
         over this module) also train.py:48 optimizer.step(), applied by the step's last kernel.
         Returns (losses[3] = total/type/item on the device, complementary_types[B,K]).
         The fused form (pc_joint_fused_step: two launches at T <= 128) serves K <= 4 (T > 512 with dropout: the similarity row
         per sample instead of per distinct query type); anything else takes the launch-per-op sequence pc_joint_train_step
-        (self.use_fused_joint = False forces it)."""
+        (self.use_fused_joint = False forces it).
+        table_optimizer (a table_optim.ProductTableAdam over this module; not in the reference, whose table is frozen): the
+        product table is trained as well -- see _train_step_with_table.  None: the table is not touched."""
+        if table_optimizer is not None:
+            return self._train_step_with_table(batch, optimizer, table_optimizer)
         if self.dim != ops.D:
             # PRODUCT_EMB_DIM = 256: the reference's loop body through the per-op path (train.py:42-48)
             self.flatten_parameters()
@@ -326,6 +330,28 @@ class PCompanion(nn.Module, _FlatParamsMixin):
         if optimizer is not None:
             optimizer.step()
         return out
+
+    def _train_step_with_table(self, batch, optimizer, table_optimizer):
+        """The step with a trainable product table (one device): the step as it is without its Adam (gradients only, the
+        parameters stay), the gradient of the batch's query rows from those unchanged parameters and the step's
+        complementary_types (ops.joint_query_grad: the only rows of the table a batch reaches, p_companion.py:51), then
+        optimizer.step() and the row-sparse Adam over the table.  The table stays requires_grad=False."""
+        from .table_optim import ProductTableAdam
+        if not isinstance(table_optimizer, ProductTableAdam) or table_optimizer.model is not self:
+            raise TypeError("train_step(table_optimizer=...) takes the ProductTableAdam built over this module")
+        losses, topk = self.train_step(batch)
+        dev = self.query_type_embeddings.weight.device
+        params = self._tensor_dict()
+        params["product_embeddings.weight"] = self.product_embeddings.weight
+        qi = self._query_indices(batch, dev)
+        bad = self._bad_counter()              # (an id outside the table is counted by every stage that refuses it)
+        dq = ops.joint_query_grad(params, qi, topk.contiguous(), batch["positive_items"].to(dev).float().contiguous(),
+                                  batch["negative_items"].to(dev).float().contiguous(), float(self.config.MARGIN),
+                                  float(self.config.ALPHA), bad=bad)
+        if optimizer is not None:
+            optimizer.step()
+        table_optimizer.step(qi, dq, bad=bad)
+        return losses, topk
 
     def _named_flat(self):
         sd = dict(self.named_parameters())

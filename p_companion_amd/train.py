@@ -68,11 +68,32 @@ def train(config, train_loader, val_loader, pretrained_embeddings, fused=True):
     hit@10 checkpoint.  fused=True runs the loop body as pc_joint_train_step + one Adam launch;
     fused=False runs model(batch) / compute_loss / backward / torch Adam like the reference.
     Returns the model (the reference returns None); model.step_losses [steps] holds every step's total loss (what the
-    reference's progress bar averages, :50-51) and model.epoch_metrics the metrics dict of every epoch (:54)."""
+    reference's progress bar averages, :50-51) and model.epoch_metrics the metrics dict of every epoch (:54).
+    config.TRAIN_PRODUCT_EMBEDDINGS (not in the reference, default False): the product table is trained too, by a row-sparse
+    Adam (table_optim.ProductTableAdam, lr = config.PRODUCT_EMBEDDING_LR or LEARNING_RATE) over the query rows of every batch;
+    one device, fused=True, the plain loop; the checkpoint gains 'table_optimizer_state_dict'."""
     logger = logging.getLogger(__name__)
+    train_table = bool(getattr(config, "TRAIN_PRODUCT_EMBEDDINGS", False))
+    if train_table:
+        if not fused:
+            raise ValueError("TRAIN_PRODUCT_EMBEDDINGS trains the table by the row-sparse step of PCompanion.train_step; "
+                             "fused=False (autograd with a dense [P, D] gradient) is not what the flag means")
+        for ld in (train_loader, val_loader):
+            bpg = getattr(getattr(ld, "dataset", None), "bpg", None)
+            if isinstance(bpg, DeviceBPG) and int(getattr(bpg, "world", 1)) != 1:
+                raise ValueError("TRAIN_PRODUCT_EMBEDDINGS: a row-sharded product table (DeviceBPG world = "
+                                 f"{bpg.world}) is not trainable; world must be 1")
     model = PCompanion(config, pretrained_embeddings).to(config.DEVICE)
     optimizer = FusedAdam(model, lr=config.LEARNING_RATE) if fused else \
         torch.optim.Adam(model.parameters(), lr=config.LEARNING_RATE)
+    table_optimizer = None
+    if train_table:
+        from .table_optim import ProductTableAdam
+        src = pretrained_embeddings.table if isinstance(pretrained_embeddings, EmbeddingMapping) else pretrained_embeddings
+        weight = model.product_embeddings.weight
+        if isinstance(src, torch.Tensor) and src.data_ptr() == weight.data_ptr():
+            weight.data = weight.data.clone()          # (a device table is taken without a copy: the caller's stays pretrained)
+        table_optimizer = ProductTableAdam(model, lr=getattr(config, "PRODUCT_EMBEDDING_LR", config.LEARNING_RATE))
     for ld in (train_loader, val_loader):
         _check_ranges(config, ld, model)
     best_hit10 = 0.0
@@ -82,7 +103,7 @@ def train(config, train_loader, val_loader, pretrained_embeddings, fused=True):
     epoch_runner = None
     loader_out = (train_loader.out, getattr(train_loader, "_prepared", None)) if isinstance(train_loader, ComplementaryIndexLoader) else None
     # (PRODUCT_EMB_DIM = 256: no fused / fixed-buffer forms -- the loop below steps the per-op path, PCompanion.train_step)
-    if fused and isinstance(train_loader, ComplementaryIndexLoader) and torch.device(config.DEVICE).type == "cuda" and \
+    if fused and not train_table and isinstance(train_loader, ComplementaryIndexLoader) and torch.device(config.DEVICE).type == "cuda" and \
             train_loader.out is None and len(train_loader.dataset) >= train_loader.batch_size and model.dim == ops.D:
         from .p_companion import GraphedJointStep
         step = GraphedJointStep(model, optimizer, train_loader.batch_size, warmup=0, mode="auto")
@@ -100,7 +121,10 @@ def train(config, train_loader, val_loader, pretrained_embeddings, fused=True):
         for batch in (train_loader if epoch_runner is None else ()):
             batch = {k: v.to(config.DEVICE) if isinstance(v, torch.Tensor) else v for k, v in batch.items()}
             if fused:
-                losses, _ = model.train_step(batch, optimizer=optimizer)      # Adam applied by the step's last kernel
+                if table_optimizer is not None:
+                    losses, _ = model.train_step(batch, optimizer=optimizer, table_optimizer=table_optimizer)
+                else:
+                    losses, _ = model.train_step(batch, optimizer=optimizer)      # Adam applied by the step's last kernel
                 loss = losses[0:1]
             else:
                 outputs = model(batch)
@@ -122,10 +146,13 @@ def train(config, train_loader, val_loader, pretrained_embeddings, fused=True):
         if metrics["hit@10"] > best_hit10:
             best_hit10 = metrics["hit@10"]
             os.makedirs(config.MODEL_DIR, exist_ok=True)
-            torch.save({"epoch": epoch,
-                        "model_state_dict": {k: v.detach().cpu() for k, v in model.state_dict().items()},
-                        "optimizer_state_dict": _cpu_state(optimizer.state_dict()),      # torch.optim.Adam's layout in both modes
-                        "metrics": metrics}, os.path.join(config.MODEL_DIR, "best_model.pth"))
+            checkpoint = {"epoch": epoch,
+                          "model_state_dict": {k: v.detach().cpu() for k, v in model.state_dict().items()},
+                          "optimizer_state_dict": _cpu_state(optimizer.state_dict()),      # torch.optim.Adam's layout in both modes
+                          "metrics": metrics}
+            if table_optimizer is not None:          # (the table itself is in model_state_dict; torch.optim.SparseAdam's layout)
+                checkpoint["table_optimizer_state_dict"] = _cpu_state(table_optimizer.state_dict())
+            torch.save(checkpoint, os.path.join(config.MODEL_DIR, "best_model.pth"))
         logger.info(f"Best Hit@10: {best_hit10:.4f}")
     if epoch_runner is not None:                     # the caller's loader leaves as it came (its batches no longer alias the step's buffers)
         train_loader.out, train_loader._prepared = loader_out
