@@ -1,4 +1,5 @@
-// The planning launches of the type-grouped catalogue kernels (grouped_plan.h; retrieve.hip and rank.hip call them):
+// The planning launches of the type-grouped catalogue kernels (grouped_plan.h; every entry of the family calls them) and the
+// host plumbing of the entries:
 //   count   pos[r] = atomic position of row r among the rows of its type, cnt[t] = rows of type t
 //   scan    (one workgroup) row_start[t] = exclusive sum of cnt, item_start[t] = exclusive sum of tiles(t) * slices(t)
 //   place   order[row_start[t] + pos[r]] = r
@@ -89,4 +90,28 @@ int rg_plan_launch(const RgPlan& w, const int32_t* types, const int32_t* targets
 unsigned rg_item_grid(int rows, int n_types, int S, int TM) {
     const int64_t cap = ((int64_t)(rows + TM - 1) / TM + (int64_t)(rows < n_types ? rows : n_types)) * S;
     return (unsigned)(cap < RG_MAX_GRID ? cap : RG_MAX_GRID);
+}
+
+RgWs rg_ws_carve(void* ws, int rows, int n_types, int n, int S) {
+    RgWs w;
+    WsCarver cv(ws);
+    w.plan = rg_plan_carve(cv, rows, n_types);
+    w.pv = (float*)cv.bytes((size_t)rows * S * n * 4);
+    w.pi = (int32_t*)cv.bytes((size_t)rows * S * n * 4);
+    w.bytes = cv.total;
+    return w;
+}
+
+size_t rg_topn_workspace_bytes(int rows, int n_types, int n, int max_n, int slices) {
+    if (rows <= 0 || n_types <= 0 || n < 1 || n > max_n || slices < 0 || slices > RG_MAX_SLICES) return 0;
+    return rg_ws_carve(nullptr, rows, n_types, n, rg_slices(slices)).bytes;
+}
+
+int rg_begin(RgWs& w, unsigned& grid, void* ws, size_t ws_bytes, const int32_t* types, const int32_t* targets, int rows,
+             const int32_t* type_rowptr, int n_types, int num_products, int n, int S, int TM, int32_t* rank_out,
+             int32_t* bad_count, hipStream_t st) {
+    w = rg_ws_carve(ws, rows, n_types, n, S);
+    if (ws_bytes < w.bytes) return PC_EWORKSPACE;
+    grid = rg_item_grid(rows, n_types, S, TM);
+    return rg_plan_launch(w.plan, types, targets, rows, type_rowptr, n_types, num_products, S, TM, rank_out, bad_count, st);
 }

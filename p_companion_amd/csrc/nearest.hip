@@ -6,16 +6,16 @@
 //   s(r, p) = fl(d(r, p) + bias[p]),   d(r, p) = rk_chain (rank_chain.h) over the fp32 table,
 // ONE fp32 addition in the epilogue, after the chain -- the accumulator starts at zero, never at the bias -- so d is bit for bit
 // what pc_retrieve_topk_grouped orders by and a zero bias gives that entry's output.  A unit of its own: inside retrieve.hip or
-// rank.hip the new kernels move the register allocation of the existing ones, and those keep their instruction text; what
-// cannot be shared through a header (the list helpers, the item decode, the merge) is restated here.
+// rank.hip the new kernels move the register allocation of the existing ones.  The list helpers, the item decode, the tile
+// load, the selection and the partial-list write are the family's (grouped_select.h), the merge is retrieve.hip's.
 //
 //   plan     grouped_plan.hip as it is (tiles of TM = 8192 / D rows)
 //   score    nb_score_kernel: work item (type, slice, tile); query tile -> LDS in RK_QS rows; candidates in chunks of 64, one
 //            16-candidate column group per wave; a lane holds ONE set of row registers, which rk_chain refills with the next
 //            chunk's rows step by step (a tile of more than two 16-row groups in two passes of two accumulators); bias[pid] is
 //            a 4-byte gather per column, issued with the column's product id a chunk ahead; biased scores -> LDS, then
-//            rg_score_kernel's threshold test, per-thread lists of 16, exclusion lists
-//   merge    nb_merge_kernel: rg_merge_kernel's body
+//            rg_select_chunk (the threshold test, per-thread lists of 16, exclusion lists) and rg_write_partial
+//   merge    rg_merge_kernel (retrieve.hip) through rg_merge_launch
 //   rank     nb_rank_kernel: rk_rank_kernel with g = d(r, y) + bias[y] and every candidate compared as d + bias[pid] against g;
 //            nb_rank_exclude_kernel: rk_exclude_kernel's post-pass with the same biased scores
 //   bias     nb_half_sq_norm_kernel: out[p] = -0.5f * sum_d e[p][d]^2
@@ -26,87 +26,9 @@
 // total order (score descending, product index ascending), so the output does not depend on the slices, on the order of the
 // rows in a tile (the one thing the planning atomics decide) or on the order of type_col inside a type.  Counts are sums of
 // integers, one integer atomic per (row, slice).  No float atomics.
-#include <type_traits>
 #include "common.h"
-#include "grouped_plan.h"
+#include "grouped_select.h"        // the item decode, the tile load, the dispatch on a tile's row groups, the selection, the write
 #include "rank_chain.h"
-
-#define NB_MAX_N 16                // (RG_MAX_N of retrieve.hip)
-
-// (retrieve.hip's rg_insert / rg_nth / rg_pop)
-__device__ __forceinline__ void nb_insert(float* v, int* ix, int n, float x, int xi) {
-#pragma unroll
-    for (int j = 0; j < NB_MAX_N; j++) {
-        if (j < n && rg_better(x, xi, v[j], ix[j])) {
-            const float tv = v[j]; const int ti = ix[j];
-            v[j] = x; ix[j] = xi; x = tv; xi = ti;
-        }
-    }
-}
-__device__ __forceinline__ void nb_nth(const float* v, const int* ix, int n, float& tv, int& ti) {
-#pragma unroll
-    for (int j = 0; j < NB_MAX_N; j++)
-        if (j == n - 1) { tv = v[j]; ti = ix[j]; }
-}
-__device__ __forceinline__ void nb_pop(float* v, int* ix) {
-#pragma unroll
-    for (int j = 0; j < NB_MAX_N - 1; j++) { v[j] = v[j + 1]; ix[j] = ix[j + 1]; }
-    v[NB_MAX_N - 1] = -INFINITY; ix[NB_MAX_N - 1] = RG_NONE;
-}
-
-// f(integral_constant<R>) for the R in [1, RMAX] that equals rg: rk_chain's group count is a template argument, so the chain is
-// straight-line code for every number of 16-row groups a tile can hold.
-template <int RMAX, class F>
-__device__ __forceinline__ void nb_dispatch_groups(int rg, F& f) {
-    if (rg == RMAX) f(std::integral_constant<int, RMAX>{});
-    else if constexpr (RMAX > 1) nb_dispatch_groups<RMAX - 1>(rg, f);
-}
-
-// Work item w = (type t, slice s, tile j) -> the tile's rows and the slice's candidates (rg_score_kernel's decode).
-struct NbItem { int s, p0, valid, rg, cb0, ce; };
-template <int TM>
-__device__ __forceinline__ NbItem nb_decode(int64_t w, const int64_t* __restrict__ item_start, const int32_t* __restrict__ cnt,
-                                            const int32_t* __restrict__ row_start, const int32_t* __restrict__ type_rowptr,
-                                            int n_types, int S) {
-    int lo = 0, hi = n_types - 1;                         // the largest t with item_start[t] <= w (< n_types: w < n_items)
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (item_start[mid] <= w) lo = mid; else hi = mid - 1;
-    }
-    const int t = lo;
-    const int rows_t = cnt[t];
-    const int tiles = (rows_t + TM - 1) / TM;
-    const int local = (int)(w - item_start[t]);
-    NbItem it;
-    it.s = local / tiles;
-    const int j = local - it.s * tiles;
-    it.p0 = row_start[t] + j * TM;
-    it.valid = min(TM, rows_t - j * TM);
-    it.rg = (it.valid + 15) >> 4;
-    const int c0 = type_rowptr[t], C = type_rowptr[t + 1] - c0;
-    int ns, L;
-    rg_slice_plan(C, S, ns, L);
-    it.cb0 = c0 + it.s * L;
-    it.ce = c0 + min(C, (it.s + 1) * L);
-    return it;
-}
-
-// the rows order[p0 .. p0 + valid) of proj as the query tile rk_chain reads (rows of RK_QS floats; rows past `valid` of the last
-// 16-row group are zero, rows past that group are never read)
-template <int D>
-__device__ __forceinline__ void nb_load_tile(float* q, const float* __restrict__ proj, const int32_t* __restrict__ order, int p0,
-                                             int valid, int rg, int tid) {
-    constexpr int QS = RK_QS(D);
-    // (opaque to the optimiser: the addresses below are formed per work item and die with the load; hoisted out of the item loop
-    // they live through the chunk loop, and the D = 128 kernels then keep three of them in scratch)
-    asm volatile("" : "+v"(tid));
-    for (int e = tid; e < rg * 16 * (D / 4); e += 256) {
-        const int row = e / (D / 4), d4 = e - row * (D / 4);
-        float4 x = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (row < valid) x = reinterpret_cast<const float4*>(proj + (size_t)order[p0 + row] * D)[d4];
-        *reinterpret_cast<float4*>(&q[row * QS + 4 * d4]) = x;
-    }
-}
 
 // Lane l of wave wv: column c = l & 15 (candidate wv * 16 + c of the chunk, query row g * 16 + c of the A operand), k-lane
 // h = l >> 4.  Partial lists: pv / pi [rows][S][n] at the row's grouped position.  EXCL: rg_score_excl_kernel's exclusion lists
@@ -124,7 +46,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(D == 128 ? 
     constexpr int RG = TM / 16;              // 16-row groups
     constexpr int QS = RK_QS(D);             // padded LDS row
     constexpr int TPR = 256 / TM;            // threads per row in the selection phase
-    constexpr int CPT = RG_CHUNK / TPR;      // candidates per thread per chunk
     constexpr int NB = D / 16;               // float4 operands per lane per candidate
     __shared__ __attribute__((aligned(16))) float q[TM * QS];
     __shared__ float sc[TM][RG_CHUNK + 1];
@@ -139,17 +60,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(D == 128 ? 
         }
     }
     for (int64_t w = blockIdx.x; w < n_items; w += gridDim.x) {
-        const NbItem it = nb_decode<TM>(w, item_start, cnt, row_start, type_rowptr, n_types, S);
+        const RgItem it = rg_decode<TM>(w, item_start, cnt, row_start, type_rowptr, n_types, S);
         const int p0 = it.p0, valid = it.valid, rg = it.rg, cb0 = it.cb0, ce = it.ce;
 
         __syncthreads();                                  // the previous item's readers of q are done
-        nb_load_tile<D>(q, proj, order, p0, valid, rg, tid);
-        float v[NB_MAX_N];
-        int ix[NB_MAX_N];
+        rg_load_tile<D, QS>(q, proj, order, p0, valid, rg, tid);
+        float v[RG_MAX_N];
+        int ix[RG_MAX_N];
 #pragma unroll
-        for (int k = 0; k < NB_MAX_N; k++) { v[k] = -INFINITY; ix[k] = RG_NONE; }
-        float tv = -INFINITY, hv = -INFINITY;             // this thread's n-th entry; the row's threshold
-        int ti = RG_NONE, hix = RG_NONE;
+        for (int k = 0; k < RG_MAX_N; k++) { v[k] = -INFINITY; ix[k] = RG_NONE; }
+        float hv = -INFINITY;                             // the row's threshold
+        int hix = RG_NONE;
         int elo = 0, ehi = 0;                             // this thread's row's list: ex_col[elo, ehi)
         if constexpr (EXCL) {
             if (rr < valid) {
@@ -206,110 +127,18 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(D == 128 ? 
                     }
                 }
             };
-            nb_dispatch_groups<RG>(rg, score);
+            rg_dispatch_groups<RG>(rg, score);
             // the next chunk's term, with its product id, a chunk ahead: in flight through this chunk's selection (issued
             // behind the chain, where a register is free for it)
             const float bsn = bias[max(pidn, 0)];
             __syncthreads();
-            // (rg_score_kernel's selection: the threshold test, then a loop over each lane's own survivors)
-            unsigned keep = 0;
-            if (rr < valid) {
-#pragma unroll
-                for (int k = 0; k < CPT; k++) {
-                    const int col = qq + TPR * k;
-                    const int xi = cid[col];
-                    keep |= (xi != RG_NONE && rg_better(sc[rr][col], xi, hv, hix) ? 1u : 0u) << k;
-                }
-            }
-            while (keep) {
-                const int k = __builtin_ctz(keep);
-                keep &= keep - 1;
-                const int col = qq + TPR * k;
-                const int xi = cid[col];
-                const float x = sc[rr][col];
-                if (rg_better(x, xi, hv, hix)) {
-                    if constexpr (EXCL) {
-                        int a = elo, b2 = ehi;            // the first list entry >= xi
-                        while (a < b2) {
-                            const int mid = (a + b2) >> 1;
-                            if (ex_col[mid] < xi) a = mid + 1; else b2 = mid;
-                        }
-                        if (a < ehi && ex_col[a] == xi) continue;     // excluded: never inserted, the threshold stays
-                    }
-                    nb_insert(v, ix, n, x, xi);
-                    nb_nth(v, ix, n, tv, ti);
-                    if (rg_better(tv, ti, hv, hix)) { hv = tv; hix = ti; }
-                }
-            }
-#pragma unroll
-            for (int o = TPR / 2; o >= 1; o >>= 1) {
-                const float ov = __shfl_xor(hv, o, 64);
-                const int oi = __shfl_xor(hix, o, 64);
-                if (rg_better(ov, oi, hv, hix)) { hv = ov; hix = oi; }
-            }
+            rg_select_chunk<TM, EXCL>(sc, cid, rr, qq, valid, n, v, ix, hv, hix, elo, ehi, ex_col);
             __syncthreads();
             pid = pidn;
             pidn = pidnn;
             bs = bsn;
         }
-        // the TPR lists of a row (adjacent lanes) -> the slice's top n of the row
-        for (int k = 0; k < n; k++) {
-            float bv = v[0];
-            int bi = ix[0];
-#pragma unroll
-            for (int o = TPR / 2; o >= 1; o >>= 1) {
-                const float ov = __shfl_xor(bv, o, 64);
-                const int oi = __shfl_xor(bi, o, 64);
-                if (rg_better(ov, oi, bv, bi)) { bv = ov; bi = oi; }
-            }
-            if (ix[0] == bi && bi != RG_NONE) nb_pop(v, ix);
-            if (qq == 0 && rr < valid) {
-                const size_t o = ((size_t)(p0 + rr) * S + it.s) * n + k;
-                pv[o] = bv;
-                pi[o] = bi;
-            }
-        }
-    }
-}
-
-// One wave per row: the top n of its slices' partial lists (rg_merge_kernel's contract and body).
-__global__ __launch_bounds__(256) void nb_merge_kernel(const int32_t* __restrict__ types, int rows,
-                                                       const int32_t* __restrict__ type_rowptr, int n_types, int n, int S,
-                                                       const int32_t* __restrict__ rank, const int32_t* __restrict__ row_start,
-                                                       const float* __restrict__ pv, const int32_t* __restrict__ pi,
-                                                       int32_t* __restrict__ out_idx, float* __restrict__ out_score) {
-    const int lane = threadIdx.x & 63;
-    const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (r >= rows) return;                                // wave-uniform
-    const int t = types[r];
-    int ns = 0, L = 0, p = 0;
-    if (t >= 0 && t < n_types) {
-        rg_slice_plan(type_rowptr[t + 1] - type_rowptr[t], S, ns, L);
-        if (ns > 0) p = row_start[t] + rank[r];
-    }
-    float v[NB_MAX_N];
-    int ix[NB_MAX_N];
-#pragma unroll
-    for (int k = 0; k < NB_MAX_N; k++) { v[k] = -INFINITY; ix[k] = RG_NONE; }
-    const size_t base = (size_t)p * S * n;
-    for (int e = lane; e < ns * n; e += 64) {
-        const int xi = pi[base + e];
-        if (xi != RG_NONE) nb_insert(v, ix, n, pv[base + e], xi);
-    }
-    for (int k = 0; k < n; k++) {
-        float bv = v[0];
-        int bi = ix[0];
-#pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) {
-            const float ov = __shfl_xor(bv, o, 64);
-            const int oi = __shfl_xor(bi, o, 64);
-            if (rg_better(ov, oi, bv, bi)) { bv = ov; bi = oi; }
-        }
-        if (ix[0] == bi && bi != RG_NONE) nb_pop(v, ix);
-        if (lane == 0) {
-            out_idx[(size_t)r * n + k] = bi == RG_NONE ? -1 : bi;
-            out_score[(size_t)r * n + k] = bi == RG_NONE ? -INFINITY : bv;
-        }
+        rg_write_partial<TM>(v, ix, n, qq == 0 && rr < valid, ((size_t)(p0 + rr) * S + it.s) * n, pv, pi);
     }
 }
 
@@ -395,11 +224,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(D == 128 ? 
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, c = lane & 15, h = lane >> 4;
     const int64_t n_items = item_start[n_types];
     for (int64_t w = blockIdx.x; w < n_items; w += gridDim.x) {
-        const NbItem it = nb_decode<TM>(w, item_start, cnt, row_start, type_rowptr, n_types, S);
+        const RgItem it = rg_decode<TM>(w, item_start, cnt, row_start, type_rowptr, n_types, S);
         const int p0 = it.p0, valid = it.valid, rg = it.rg, cb0 = it.cb0, ce = it.ce;
 
         __syncthreads();                                  // the previous item's readers of q / part are done
-        nb_load_tile<D>(q, proj, order, p0, valid, rg, tid);
+        rg_load_tile<D, QS>(q, proj, order, p0, valid, rg, tid);
 
         auto load_pid = [&](int cb) { const int cc = cb + wv * 16 + c; return cc < ce ? type_col[cc] : -1; };
         // (a lane without a product reads product 0's row and term: no branch, and nothing of it is used)
@@ -542,25 +371,6 @@ __global__ __launch_bounds__(256) void nb_half_sq_norm_kernel(const float* __res
     }
 }
 
-namespace {
-// (retrieve.hip's layout: the plan, then the partial lists [rows][S][n])
-struct NbWs {
-    RgPlan plan;
-    float* pv;
-    int32_t* pi;
-    size_t bytes;
-};
-NbWs nb_layout(void* ws, int rows, int n_types, int n, int S) {
-    NbWs w;
-    WsCarver cv(ws);
-    w.plan = rg_plan_carve(cv, rows, n_types);
-    w.pv = (float*)cv.bytes((size_t)rows * S * n * 4);
-    w.pi = (int32_t*)cv.bytes((size_t)rows * S * n * 4);
-    w.bytes = cv.total;
-    return w;
-}
-}  // namespace
-
 extern "C" int pc_half_sq_norm_bias(const float* table, int rows, int dim, float* out, void* stream) {
     if (!table || !out || rows <= 0) return PC_EINVAL;
     if (dim != 128 && dim != 256) return PC_ESHAPE;
@@ -572,8 +382,7 @@ extern "C" int pc_half_sq_norm_bias(const float* table, int rows, int dim, float
 }
 
 extern "C" size_t pc_retrieve_topk_grouped_biased_workspace_bytes(int rows, int n_types, int n, int slices) {
-    if (rows <= 0 || n_types <= 0 || n < 1 || n > NB_MAX_N || slices < 0 || slices > RG_MAX_SLICES) return 0;
-    return nb_layout(nullptr, rows, n_types, n, rg_slices(slices)).bytes;
+    return rg_topn_workspace_bytes(rows, n_types, n, RG_MAX_N, slices);
 }
 
 extern "C" int pc_retrieve_topk_grouped_biased(const float* proj, const int32_t* types, const int32_t* row_key, int rows,
@@ -581,24 +390,16 @@ extern "C" int pc_retrieve_topk_grouped_biased(const float* proj, const int32_t*
                                                const float* bias, int n_types, const int32_t* ex_rowptr, const int32_t* ex_col,
                                                int n_keys, int n, int dim, int slices, int32_t* out_idx, float* out_score,
                                                int32_t* bad_count, void* ws, size_t ws_bytes, void* stream) {
-    if (!proj || !types || !type_rowptr || !type_col || !table || !bias || !out_idx || !out_score || !ws) return PC_EINVAL;
-    if (rows <= 0 || n_types <= 0) return PC_EINVAL;
-    if (row_key) {
-        if (!ex_rowptr || !ex_col || !bad_count || n_keys < 0) return PC_EINVAL;
-    } else if (ex_rowptr || ex_col || n_keys != 0) {
-        return PC_EINVAL;
-    }
-    if (n < 1 || n > NB_MAX_N || (dim != 128 && dim != 256) || slices < 0 || slices > RG_MAX_SLICES) return PC_ESHAPE;
+    PC_TRY(rg_topn_check(proj && types && type_rowptr && type_col && table && bias && out_idx && out_score && ws, rows, n_types,
+                         rg_lists_ok(row_key, ex_rowptr, ex_col, bad_count, n_keys), n, RG_MAX_N, dim, slices));
     const int S = rg_slices(slices);
-    const NbWs w = nb_layout(ws, rows, n_types, n, S);
-    if (ws_bytes < w.bytes) return PC_EWORKSPACE;
     hipStream_t st = (hipStream_t)stream;
-    const int TM = 8192 / dim;
+    RgWs w;
+    unsigned grid;
+    PC_TRY(rg_begin(w, grid, ws, ws_bytes, types, nullptr, rows, type_rowptr, n_types, 0, n, S, 8192 / dim, nullptr, nullptr, st));
     const RgPlan& pl = w.plan;
-    PC_TRY(rg_plan_launch(pl, types, nullptr, rows, type_rowptr, n_types, 0, S, TM, nullptr, nullptr, st));
-    const dim3 sgrid(rg_item_grid(rows, n_types, S, TM));
 #define NB_SCORE(D, EXCL)                                                                                                       \
-    PC_LAUNCH((nb_score_kernel<D, EXCL>), sgrid, dim3(256), 0, st, proj, type_rowptr, type_col, table, bias, n_types, n, S,     \
+    PC_LAUNCH((nb_score_kernel<D, EXCL>), dim3(grid), dim3(256), 0, st, proj, type_rowptr, type_col, table, bias, n_types, n, S, \
               pl.cnt, pl.row_start, pl.item_start, pl.order, w.pv, w.pi, row_key, rows, ex_rowptr, ex_col, n_keys, bad_count)
     if (dim == 128) {
         if (row_key) NB_SCORE(128, true); else NB_SCORE(128, false);
@@ -606,16 +407,12 @@ extern "C" int pc_retrieve_topk_grouped_biased(const float* proj, const int32_t*
         if (row_key) NB_SCORE(256, true); else NB_SCORE(256, false);
     }
 #undef NB_SCORE
-    PC_LAUNCH(nb_merge_kernel, dim3((rows + 3) / 4), dim3(256), 0, st, types, rows, type_rowptr, n_types, n, S, pl.pos,
-              pl.row_start, w.pv, w.pi, out_idx, out_score);
+    rg_merge_launch(w, types, rows, type_rowptr, n_types, n, S, out_idx, out_score, st);
     return pc_launch_status();
 }
 
 extern "C" size_t pc_rank_grouped_biased_workspace_bytes(int rows, int n_types, int slices) {
-    if (rows <= 0 || n_types <= 0 || slices < 0 || slices > RG_MAX_SLICES) return 0;
-    WsCarver cv(nullptr);
-    rg_plan_carve(cv, rows, n_types);
-    return cv.total;
+    return pc_rank_grouped_workspace_bytes(rows, n_types, slices);
 }
 
 extern "C" int pc_rank_grouped_biased(const float* proj, const int32_t* types, const int32_t* targets, const int32_t* row_key,
@@ -626,26 +423,22 @@ extern "C" int pc_rank_grouped_biased(const float* proj, const int32_t* types, c
     if (!proj || !types || !targets || !type_rowptr || !type_col || !table || !bias || !rank_out || !bad_count || !ws)
         return PC_EINVAL;
     if (rows <= 0 || n_types <= 0 || num_products <= 0) return PC_EINVAL;
-    if (row_key) {
-        if (!ex_rowptr || !ex_col || !cand_type || n_keys < 0) return PC_EINVAL;
-    } else if (ex_rowptr || ex_col || cand_type || n_keys != 0) {
-        return PC_EINVAL;
-    }
+    // the lists and the products' types: all or none
+    if (!rg_lists_ok(row_key, ex_rowptr, ex_col, bad_count, n_keys) || !row_key != !cand_type) return PC_EINVAL;
     if ((dim != 128 && dim != 256) || slices < 0 || slices > RG_MAX_SLICES) return PC_ESHAPE;
     const int S = rg_slices(slices);
-    WsCarver cv(ws);
-    const RgPlan w = rg_plan_carve(cv, rows, n_types);
-    if (ws_bytes < cv.total) return PC_EWORKSPACE;
     hipStream_t st = (hipStream_t)stream;
-    const int TM = 8192 / dim;
-    PC_TRY(rg_plan_launch(w, types, targets, rows, type_rowptr, n_types, num_products, S, TM, rank_out, bad_count, st));
-    const dim3 sgrid(rg_item_grid(rows, n_types, S, TM));
+    RgWs w;
+    unsigned grid;
+    PC_TRY(rg_begin(w, grid, ws, ws_bytes, types, targets, rows, type_rowptr, n_types, num_products, 0, S, 8192 / dim, rank_out,
+                    bad_count, st));
+    const RgPlan& pl = w.plan;
     if (dim == 128)
-        PC_LAUNCH(nb_rank_kernel<128>, sgrid, dim3(256), 0, st, proj, targets, type_rowptr, type_col, table, bias, n_types, S,
-                  w.cnt, w.row_start, w.item_start, w.order, rank_out);
+        PC_LAUNCH(nb_rank_kernel<128>, dim3(grid), dim3(256), 0, st, proj, targets, type_rowptr, type_col, table, bias, n_types, S,
+                  pl.cnt, pl.row_start, pl.item_start, pl.order, rank_out);
     else
-        PC_LAUNCH(nb_rank_kernel<256>, sgrid, dim3(256), 0, st, proj, targets, type_rowptr, type_col, table, bias, n_types, S,
-                  w.cnt, w.row_start, w.item_start, w.order, rank_out);
+        PC_LAUNCH(nb_rank_kernel<256>, dim3(grid), dim3(256), 0, st, proj, targets, type_rowptr, type_col, table, bias, n_types, S,
+                  pl.cnt, pl.row_start, pl.item_start, pl.order, rank_out);
     if (row_key) {
         if (dim == 128)
             PC_LAUNCH(nb_rank_exclude_kernel<128>, dim3(rows), dim3(64), 0, st, proj, types, targets, row_key, ex_rowptr, ex_col,
@@ -656,3 +449,4 @@ extern "C" int pc_rank_grouped_biased(const float* proj, const int32_t* types, c
     }
     return pc_launch_status();
 }
+

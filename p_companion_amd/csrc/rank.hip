@@ -16,9 +16,10 @@
 // dimension 16 j + 4 h + e; the chain's order depends on the dimension index alone), so s_y and g are the same bits and a
 // (row, product) score is bit for bit the one the retrieval orders by.  The count is a sum of integers: it does not depend
 // on the slices, on the order of the rows in a tile, or on the order of type_col inside a type.  No float atomics.
-// The plan (count, scan, place), the slice plan and the order predicate are retrieve.hip's (grouped_plan.h).
+// The plan (count, scan, place), the slice plan and the order predicate are the family's (grouped_plan.h), the work-item
+// decode and the query-tile load too (grouped_select.h).
 #include "common.h"
-#include "grouped_plan.h"
+#include "grouped_select.h"        // the item decode, the tile load
 
 #include "rank_chain.h"           // RK_QS, rk_chain: THE k-chain (rank_exclude.hip scores through it too)
 
@@ -103,32 +104,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(D == 128 ? 
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, c = lane & 15, h = lane >> 4;
     const int64_t n_items = item_start[n_types];
     for (int64_t w = blockIdx.x; w < n_items; w += gridDim.x) {
-        // (this decode and the tile load below are retrieve.hip's rg_score_kernel; as a shared function they move both kernels' code)
-        int lo = 0, hi = n_types - 1;                     // the largest t with item_start[t] <= w (< n_types: w < n_items)
-        while (lo < hi) {
-            const int mid = (lo + hi + 1) >> 1;
-            if (item_start[mid] <= w) lo = mid; else hi = mid - 1;
-        }
-        const int t = lo;
-        const int rows_t = cnt[t];
-        const int tiles = (rows_t + TM - 1) / TM;
-        const int local = (int)(w - item_start[t]);
-        const int s = local / tiles, j = local - s * tiles;
-        const int p0 = row_start[t] + j * TM;
-        const int valid = min(TM, rows_t - j * TM);
-        const int rg = (valid + 15) >> 4;
-        const int c0 = type_rowptr[t], C = type_rowptr[t + 1] - c0;
-        int ns, L;
-        rg_slice_plan(C, S, ns, L);
-        const int cb0 = c0 + s * L, ce = c0 + min(C, (s + 1) * L);
+        const RgItem it = rg_decode<TM>(w, item_start, cnt, row_start, type_rowptr, n_types, S);
+        const int p0 = it.p0, valid = it.valid, rg = it.rg, cb0 = it.cb0, ce = it.ce;
 
         __syncthreads();                                  // the previous item's readers of q / part are done
-        for (int e = tid; e < rg * 16 * (D / 4); e += 256) {          // (rows past the last 16-row group are never read)
-            const int row = e / (D / 4), d4 = e - row * (D / 4);
-            float4 x = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (row < valid) x = reinterpret_cast<const float4*>(proj + (size_t)order[p0 + row] * D)[d4];
-            *reinterpret_cast<float4*>(&q[row * QS + 4 * d4]) = x;
-        }
+        rg_load_tile<D, QS>(q, proj, order, p0, valid, rg, tid);
 
         auto load_pid = [&](int cb) { const int cc = cb + wv * 16 + c; return cc < ce ? type_col[cc] : -1; };
         // (a lane without a product reads product 0's row: no branch, and nothing of it is used)
@@ -176,9 +156,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(D == 128 ? 
 
 extern "C" size_t pc_rank_grouped_workspace_bytes(int rows, int n_types, int slices) {
     if (rows <= 0 || n_types <= 0 || slices < 0 || slices > RG_MAX_SLICES) return 0;
-    WsCarver cv(nullptr);
-    rg_plan_carve(cv, rows, n_types);
-    return cv.total;
+    return rg_ws_carve(nullptr, rows, n_types, 0, rg_slices(slices)).bytes;
 }
 
 extern "C" int pc_rank_grouped(const float* proj, const int32_t* types, const int32_t* targets, int rows,
@@ -189,18 +167,17 @@ extern "C" int pc_rank_grouped(const float* proj, const int32_t* types, const in
     if (rows <= 0 || n_types <= 0 || num_products <= 0) return PC_EINVAL;
     if ((dim != 128 && dim != 256) || slices < 0 || slices > RG_MAX_SLICES) return PC_ESHAPE;
     const int S = rg_slices(slices);
-    WsCarver cv(ws);
-    const RgPlan w = rg_plan_carve(cv, rows, n_types);
-    if (ws_bytes < cv.total) return PC_EWORKSPACE;
     hipStream_t st = (hipStream_t)stream;
-    const int TM = 8192 / dim;
-    PC_TRY(rg_plan_launch(w, types, targets, rows, type_rowptr, n_types, num_products, S, TM, rank_out, bad_count, st));
-    const dim3 sgrid(rg_item_grid(rows, n_types, S, TM));
+    RgWs w;
+    unsigned grid;
+    PC_TRY(rg_begin(w, grid, ws, ws_bytes, types, targets, rows, type_rowptr, n_types, num_products, 0, S, 8192 / dim, rank_out,
+                    bad_count, st));
+    const RgPlan& pl = w.plan;
     if (dim == 128)
-        PC_LAUNCH(rk_rank_kernel<128>, sgrid, dim3(256), 0, st, proj, targets, type_rowptr, type_col, table, n_types, S, w.cnt,
-                  w.row_start, w.item_start, w.order, rank_out);
+        PC_LAUNCH(rk_rank_kernel<128>, dim3(grid), dim3(256), 0, st, proj, targets, type_rowptr, type_col, table, n_types, S,
+                  pl.cnt, pl.row_start, pl.item_start, pl.order, rank_out);
     else
-        PC_LAUNCH(rk_rank_kernel<256>, sgrid, dim3(256), 0, st, proj, targets, type_rowptr, type_col, table, n_types, S, w.cnt,
-                  w.row_start, w.item_start, w.order, rank_out);
+        PC_LAUNCH(rk_rank_kernel<256>, dim3(grid), dim3(256), 0, st, proj, targets, type_rowptr, type_col, table, n_types, S,
+                  pl.cnt, pl.row_start, pl.item_start, pl.order, rank_out);
     return pc_launch_status();
 }

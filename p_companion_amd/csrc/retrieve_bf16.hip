@@ -11,8 +11,9 @@
 //           a split per chunk would make the VALU, not the matrix pipe, the bound); candidates in chunks of 64, one
 //           16-candidate column group per wave: lane (c = lane & 15, h = lane >> 4) holds the 8 dimensions 32 k + 8 h .. + 7
 //           of candidate c for every k-block k -- D / 32 loads of 16 B, the next chunk's in flight while this one is scored;
-//           scores -> LDS, then rg_score_kernel's threshold test, per-thread lists of 16 and (EXCL) exclusion lists
-//   merge   rg_merge_kernel's, restated here (rb_merge_kernel) so that retrieve.hip's kernels keep their instruction text
+//           scores -> LDS, then the family's selection (grouped_select.h: rg_select_chunk, the threshold test, per-thread lists of
+//           16 and (EXCL) exclusion lists) and partial-list write
+//   merge   rg_merge_kernel (retrieve.hip) through rg_merge_launch: the one merge of the entries with lists of up to 16
 //
 // Determinism: the chain of a (row, product) pair is k-block 0 .. D / 32 - 1, inside a k-block the pieces p0, p1, p2, one
 // MFMA each into ONE accumulator, inside an MFMA k-lane h and element e cover dimension 32 k + 8 h + e: its order depends on
@@ -20,44 +21,12 @@
 // has the same bits wherever it is scored.  Every selection is under the total order (score descending, product index
 // ascending), so the top n of the union does not depend on how the candidates were split, on the order of the rows in a tile
 // (the one thing the planning atomics decide), or on the order of type_col inside a type.  No float atomics.
-#include <type_traits>
 #include "common.h"
-#include "grouped_plan.h"
+#include "grouped_select.h"        // the item decode, the dispatch on a tile's row groups, the selection, the partial-list write
 
-#define RB_MAX_N 16                // (RG_MAX_N of retrieve.hip)
-
-// (retrieve.hip's rg_insert / rg_nth / rg_pop)
-__device__ __forceinline__ void rb_insert(float* v, int* ix, int n, float x, int xi) {
-#pragma unroll
-    for (int j = 0; j < RB_MAX_N; j++) {
-        if (j < n && rg_better(x, xi, v[j], ix[j])) {
-            const float tv = v[j]; const int ti = ix[j];
-            v[j] = x; ix[j] = xi; x = tv; xi = ti;
-        }
-    }
-}
-__device__ __forceinline__ void rb_nth(const float* v, const int* ix, int n, float& tv, int& ti) {
-#pragma unroll
-    for (int j = 0; j < RB_MAX_N; j++)
-        if (j == n - 1) { tv = v[j]; ti = ix[j]; }
-}
-__device__ __forceinline__ void rb_pop(float* v, int* ix) {
-#pragma unroll
-    for (int j = 0; j < RB_MAX_N - 1; j++) { v[j] = v[j + 1]; ix[j] = ix[j + 1]; }
-    v[RB_MAX_N - 1] = -INFINITY; ix[RB_MAX_N - 1] = RG_NONE;
-}
-
-// f(integral_constant<R>) for the R in [1, RMAX] that equals rg: the MFMA section is written once per group count, so that
-// inside it every loop bound is a constant -- no branch between an LDS read and its MFMA, and the reads can be issued ahead.
-template <int RMAX, class F>
-__device__ __forceinline__ void rb_dispatch_groups(int rg, F& f) {
-    if (rg == RMAX) f(std::integral_constant<int, RMAX>{});
-    else if constexpr (RMAX > 1) rb_dispatch_groups<RMAX - 1>(rg, f);
-}
-
-// Work item w = (type t, slice s, tile j) as in rg_score_kernel.  Lane l of wave wv: column c = l & 15 (candidate
+// Work item w = (type t, slice s, tile j) (rg_decode).  Lane l of wave wv: column c = l & 15 (candidate
 // wv * 16 + c of the chunk, query row g * 16 + c of the A operand), k-lane h = l >> 4.  The C/D map of the 16x16x32 bf16
-// MFMA is the 16x16x4 f32 one's (column lane & 15, row 4 (lane >> 4) + reg), so the selection is rg_score_kernel's.
+// MFMA is the 16x16x4 f32 one's (column lane & 15, row 4 (lane >> 4) + reg), so the selection is rg_select_chunk as it is.
 // EXCL: rg_score_excl_kernel's exclusion lists and key count.
 // Two workgroups per CU: the three query images and the score tile take 66 KB (D = 128) / 58 KB (D = 256) of the 160 KB.
 template <int D, bool EXCL>
@@ -70,7 +39,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void r
     constexpr int TM = 8192 / D;             // rows per tile: 64 (D = 128) or 32 (D = 256)
     constexpr int RG = TM / 16;              // 16-row groups
     constexpr int TPR = 256 / TM;            // threads per row in the selection phase
-    constexpr int CPT = RG_CHUNK / TPR;      // candidates per thread per chunk
     constexpr int NB = D / 32;               // k-blocks: 16-byte operands per lane per candidate
     // the pieces p0, p1, p2 of the query tile, each as [D / 8][TM] operands of 16 bytes: operand (d8, row) = the dimensions
     // 8 d8 .. 8 d8 + 7 of a row.  The 16 lanes of one LDS cycle of a ds_read_b128 (16 distinct columns c at one or two h) then
@@ -88,24 +56,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void r
         }
     }
     for (int64_t w = blockIdx.x; w < n_items; w += gridDim.x) {
-        // (rg_score_kernel's decode)
-        int lo = 0, hi = n_types - 1;                     // the largest t with item_start[t] <= w (< n_types: w < n_items)
-        while (lo < hi) {
-            const int mid = (lo + hi + 1) >> 1;
-            if (item_start[mid] <= w) lo = mid; else hi = mid - 1;
-        }
-        const int t = lo;
-        const int rows_t = cnt[t];
-        const int tiles = (rows_t + TM - 1) / TM;
-        const int local = (int)(w - item_start[t]);
-        const int s = local / tiles, j = local - s * tiles;
-        const int p0 = row_start[t] + j * TM;
-        const int valid = min(TM, rows_t - j * TM);
-        const int rg = (valid + 15) >> 4;
-        const int c0 = type_rowptr[t], C = type_rowptr[t + 1] - c0;
-        int ns, L;
-        rg_slice_plan(C, S, ns, L);
-        const int cb0 = c0 + s * L, ce = c0 + min(C, (s + 1) * L);
+        const RgItem it = rg_decode<TM>(w, item_start, cnt, row_start, type_rowptr, n_types, S);
+        const int p0 = it.p0, valid = it.valid, rg = it.rg, cb0 = it.cb0, ce = it.ce;
 
         __syncthreads();                                  // the previous item's readers of q are done
         for (int e = tid; e < rg * 16 * (D / 8); e += 256) {          // (rows past the last 16-row group are never read)
@@ -121,12 +73,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void r
             q[1][d8 * TM + row] = sp.p1;
             q[2][d8 * TM + row] = sp.p2;
         }
-        float v[RB_MAX_N];
-        int ix[RB_MAX_N];
+        float v[RG_MAX_N];
+        int ix[RG_MAX_N];
 #pragma unroll
-        for (int k = 0; k < RB_MAX_N; k++) { v[k] = -INFINITY; ix[k] = RG_NONE; }
-        float tv = -INFINITY, hv = -INFINITY;             // this thread's n-th entry; the row's threshold
-        int ti = RG_NONE, hix = RG_NONE;
+        for (int k = 0; k < RG_MAX_N; k++) { v[k] = -INFINITY; ix[k] = RG_NONE; }
+        float hv = -INFINITY;                             // the row's threshold
+        int hix = RG_NONE;
         int elo = 0, ehi = 0;                             // this thread's row's list: ex_col[elo, ehi)
         if constexpr (EXCL) {
             if (rr < valid) {
@@ -181,130 +133,18 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void r
                     for (int k = 0; k < 4; k++) sc[g * 16 + 4 * h + k][wv * 16 + c] = acc[g][k];
                 }
             };
-            rb_dispatch_groups<RG>(rg, score);
+            rg_dispatch_groups<RG>(rg, score);
             if (h == 0) cid[wv * 16 + c] = pid < 0 ? RG_NONE : pid;
             __syncthreads();
-            // (rg_score_kernel's selection: the threshold test, then a loop over each lane's own survivors)
-            unsigned keep = 0;
-            if (rr < valid) {
-#pragma unroll
-                for (int k = 0; k < CPT; k++) {
-                    const int col = qq + TPR * k;
-                    const int xi = cid[col];
-                    if (xi != RG_NONE && rg_better(sc[rr][col], xi, hv, hix)) keep |= 1u << k;
-                }
-            }
-            while (keep) {
-                const int k = __builtin_ctz(keep);
-                keep &= keep - 1;
-                const int col = qq + TPR * k;
-                const int xi = cid[col];
-                const float x = sc[rr][col];
-                if (rg_better(x, xi, hv, hix)) {
-                    if constexpr (EXCL) {
-                        int a = elo, b2 = ehi;            // the first list entry >= xi
-                        while (a < b2) {
-                            const int mid = (a + b2) >> 1;
-                            if (ex_col[mid] < xi) a = mid + 1; else b2 = mid;
-                        }
-                        if (a < ehi && ex_col[a] == xi) continue;     // excluded: never inserted, the threshold stays
-                    }
-                    rb_insert(v, ix, n, x, xi);
-                    rb_nth(v, ix, n, tv, ti);
-                    if (rg_better(tv, ti, hv, hix)) { hv = tv; hix = ti; }
-                }
-            }
-#pragma unroll
-            for (int o = TPR / 2; o >= 1; o >>= 1) {
-                const float ov = __shfl_xor(hv, o, 64);
-                const int oi = __shfl_xor(hix, o, 64);
-                if (rg_better(ov, oi, hv, hix)) { hv = ov; hix = oi; }
-            }
+            rg_select_chunk<TM, EXCL>(sc, cid, rr, qq, valid, n, v, ix, hv, hix, elo, ehi, ex_col);
             __syncthreads();
         }
-        // the TPR lists of a row (adjacent lanes) -> the slice's top n of the row
-        for (int k = 0; k < n; k++) {
-            float bv = v[0];
-            int bi = ix[0];
-#pragma unroll
-            for (int o = TPR / 2; o >= 1; o >>= 1) {
-                const float ov = __shfl_xor(bv, o, 64);
-                const int oi = __shfl_xor(bi, o, 64);
-                if (rg_better(ov, oi, bv, bi)) { bv = ov; bi = oi; }
-            }
-            if (ix[0] == bi && bi != RG_NONE) rb_pop(v, ix);
-            if (qq == 0 && rr < valid) {
-                const size_t o = ((size_t)(p0 + rr) * S + s) * n + k;
-                pv[o] = bv;
-                pi[o] = bi;
-            }
-        }
+        rg_write_partial<TM>(v, ix, n, qq == 0 && rr < valid, ((size_t)(p0 + rr) * S + it.s) * n, pv, pi);
     }
 }
-
-// One wave per row: the top n of its slices' partial lists (rg_merge_kernel's contract and body).
-__global__ __launch_bounds__(256) void rb_merge_kernel(const int32_t* __restrict__ types, int rows,
-                                                       const int32_t* __restrict__ type_rowptr, int n_types, int n, int S,
-                                                       const int32_t* __restrict__ rank, const int32_t* __restrict__ row_start,
-                                                       const float* __restrict__ pv, const int32_t* __restrict__ pi,
-                                                       int32_t* __restrict__ out_idx, float* __restrict__ out_score) {
-    const int lane = threadIdx.x & 63;
-    const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (r >= rows) return;                                // wave-uniform
-    const int t = types[r];
-    int ns = 0, L = 0, p = 0;
-    if (t >= 0 && t < n_types) {
-        rg_slice_plan(type_rowptr[t + 1] - type_rowptr[t], S, ns, L);
-        if (ns > 0) p = row_start[t] + rank[r];
-    }
-    float v[RB_MAX_N];
-    int ix[RB_MAX_N];
-#pragma unroll
-    for (int k = 0; k < RB_MAX_N; k++) { v[k] = -INFINITY; ix[k] = RG_NONE; }
-    const size_t base = (size_t)p * S * n;
-    for (int e = lane; e < ns * n; e += 64) {
-        const int xi = pi[base + e];
-        if (xi != RG_NONE) rb_insert(v, ix, n, pv[base + e], xi);
-    }
-    for (int k = 0; k < n; k++) {
-        float bv = v[0];
-        int bi = ix[0];
-#pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) {
-            const float ov = __shfl_xor(bv, o, 64);
-            const int oi = __shfl_xor(bi, o, 64);
-            if (rg_better(ov, oi, bv, bi)) { bv = ov; bi = oi; }
-        }
-        if (ix[0] == bi && bi != RG_NONE) rb_pop(v, ix);
-        if (lane == 0) {
-            out_idx[(size_t)r * n + k] = bi == RG_NONE ? -1 : bi;
-            out_score[(size_t)r * n + k] = bi == RG_NONE ? -INFINITY : bv;
-        }
-    }
-}
-
-namespace {
-// (retrieve.hip's layout: the plan, then the partial lists [rows][S][n])
-struct RbWs {
-    RgPlan plan;
-    float* pv;
-    int32_t* pi;
-    size_t bytes;
-};
-RbWs rb_layout(void* ws, int rows, int n_types, int n, int S) {
-    RbWs w;
-    WsCarver cv(ws);
-    w.plan = rg_plan_carve(cv, rows, n_types);
-    w.pv = (float*)cv.bytes((size_t)rows * S * n * 4);
-    w.pi = (int32_t*)cv.bytes((size_t)rows * S * n * 4);
-    w.bytes = cv.total;
-    return w;
-}
-}  // namespace
 
 extern "C" size_t pc_retrieve_topk_grouped_bf16_workspace_bytes(int rows, int n_types, int n, int slices) {
-    if (rows <= 0 || n_types <= 0 || n < 1 || n > RB_MAX_N || slices < 0 || slices > RG_MAX_SLICES) return 0;
-    return rb_layout(nullptr, rows, n_types, n, rg_slices(slices)).bytes;
+    return rg_topn_workspace_bytes(rows, n_types, n, RG_MAX_N, slices);
 }
 
 extern "C" int pc_retrieve_topk_grouped_bf16(const float* proj, const int32_t* types, const int32_t* row_key, int rows,
@@ -312,33 +152,25 @@ extern "C" int pc_retrieve_topk_grouped_bf16(const float* proj, const int32_t* t
                                              int n_types, const int32_t* ex_rowptr, const int32_t* ex_col, int n_keys, int n,
                                              int dim, int slices, int32_t* out_idx, float* out_score, int32_t* bad_count,
                                              void* ws, size_t ws_bytes, void* stream) {
-    if (!proj || !types || !type_rowptr || !type_col || !table_bf16 || !out_idx || !out_score || !ws) return PC_EINVAL;
-    if (rows <= 0 || n_types <= 0) return PC_EINVAL;
-    if (row_key) {
-        if (!ex_rowptr || !ex_col || !bad_count || n_keys < 0) return PC_EINVAL;
-    } else if (ex_rowptr || ex_col || n_keys != 0) {
-        return PC_EINVAL;
-    }
-    if (n < 1 || n > RB_MAX_N || (dim != 128 && dim != 256) || slices < 0 || slices > RG_MAX_SLICES) return PC_ESHAPE;
+    PC_TRY(rg_topn_check(proj && types && type_rowptr && type_col && table_bf16 && out_idx && out_score && ws, rows, n_types,
+                         rg_lists_ok(row_key, ex_rowptr, ex_col, bad_count, n_keys), n, RG_MAX_N, dim, slices));
     if ((uintptr_t)table_bf16 & 15) return PC_ESHAPE;     // a lane reads 16 bytes of a row at once
     const int S = rg_slices(slices);
-    const RbWs w = rb_layout(ws, rows, n_types, n, S);
-    if (ws_bytes < w.bytes) return PC_EWORKSPACE;
     hipStream_t st = (hipStream_t)stream;
-    const int TM = 8192 / dim;
+    RgWs w;
+    unsigned grid;
+    PC_TRY(rg_begin(w, grid, ws, ws_bytes, types, nullptr, rows, type_rowptr, n_types, 0, n, S, 8192 / dim, nullptr, nullptr, st));
     const RgPlan& pl = w.plan;
-    PC_TRY(rg_plan_launch(pl, types, nullptr, rows, type_rowptr, n_types, 0, S, TM, nullptr, nullptr, st));
-    const dim3 sgrid(rg_item_grid(rows, n_types, S, TM));
 #define RB_SCORE(D, EXCL)                                                                                                   \
-    PC_LAUNCH((rg_score_bf16_kernel<D, EXCL>), sgrid, dim3(256), 0, st, proj, type_rowptr, type_col, table_bf16, n_types, n, S, \
-              pl.cnt, pl.row_start, pl.item_start, pl.order, w.pv, w.pi, row_key, rows, ex_rowptr, ex_col, n_keys, bad_count)
+    PC_LAUNCH((rg_score_bf16_kernel<D, EXCL>), dim3(grid), dim3(256), 0, st, proj, type_rowptr, type_col, table_bf16, n_types, n, \
+              S, pl.cnt, pl.row_start, pl.item_start, pl.order, w.pv, w.pi, row_key, rows, ex_rowptr, ex_col, n_keys, bad_count)
     if (dim == 128) {
         if (row_key) RB_SCORE(128, true); else RB_SCORE(128, false);
     } else {
         if (row_key) RB_SCORE(256, true); else RB_SCORE(256, false);
     }
 #undef RB_SCORE
-    PC_LAUNCH(rb_merge_kernel, dim3((rows + 3) / 4), dim3(256), 0, st, types, rows, type_rowptr, n_types, n, S, pl.pos,
-              pl.row_start, w.pv, w.pi, out_idx, out_score);
+    rg_merge_launch(w, types, rows, type_rowptr, n_types, n, S, out_idx, out_score, st);
     return pc_launch_status();
 }
+

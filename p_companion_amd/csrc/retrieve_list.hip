@@ -23,7 +23,7 @@
 // it never moves a threshold.  Hence the output does not depend on the slices, the rows' places, the order of type_col, or
 // the arrival order; for n <= 16 it is pc_retrieve_topk_grouped[_excluding]'s bit for bit.  No float atomics, no readback.
 #include "common.h"
-#include "grouped_plan.h"
+#include "grouped_select.h"        // the item decode
 #include "wave_sort.h"                 // rl_sort: the bitonic network (shared with ingest.hip)
 
 #define RL_MAX_N 256
@@ -74,22 +74,8 @@ __global__ __launch_bounds__(256) void rl_score_kernel(const float* __restrict__
         }
     }
     for (int64_t w = blockIdx.x; w < n_items; w += gridDim.x) {
-        int lo = 0, hi = n_types - 1;                     // the largest t with item_start[t] <= w (< n_types: w < n_items)
-        while (lo < hi) {
-            const int mid = (lo + hi + 1) >> 1;
-            if (item_start[mid] <= w) lo = mid; else hi = mid - 1;
-        }
-        const int t = lo;
-        const int rows_t = cnt[t];
-        const int tiles = (rows_t + TM - 1) / TM;
-        const int local = (int)(w - item_start[t]);
-        const int s = local / tiles, j = local - s * tiles;
-        const int p0 = row_start[t] + j * TM;
-        const int valid = min(TM, rows_t - j * TM);
-        const int c0 = type_rowptr[t], C = type_rowptr[t + 1] - c0;
-        int ns, L;
-        rg_slice_plan(C, S, ns, L);
-        const int cb0 = c0 + s * L, ce = c0 + min(C, (s + 1) * L);
+        const RgItem it = rg_decode<TM>(w, item_start, cnt, row_start, type_rowptr, n_types, S);
+        const int s = it.s, p0 = it.p0, valid = it.valid, cb0 = it.cb0, ce = it.ce;
 
         __syncthreads();                                  // the previous item's readers of q and of the buffers are done
         for (int e = tid; e < TM * (D / 4); e += 256) {
@@ -273,25 +259,9 @@ __global__ __launch_bounds__(256) void rl_merge_kernel(const int32_t* __restrict
 }
 
 namespace {
-struct RlWs {
-    RgPlan plan;
-    float* pv;                             // the partial lists [rows][S][n], sorted
-    int32_t* pi;
-    size_t bytes;
-};
-RlWs rl_layout(void* ws, int rows, int n_types, int n, int S) {
-    RlWs w;
-    WsCarver cv(ws);
-    w.plan = rg_plan_carve(cv, rows, n_types);
-    w.pv = (float*)cv.bytes((size_t)rows * S * n * 4);
-    w.pi = (int32_t*)cv.bytes((size_t)rows * S * n * 4);
-    w.bytes = cv.total;
-    return w;
-}
-
 template <int D, int NE>
 void rl_launch_score(dim3 grid, hipStream_t st, const float* proj, const int32_t* type_rowptr, const int32_t* type_col,
-                     const float* table, int n_types, int n, int S, const RlWs& w, const int32_t* row_key, int rows,
+                     const float* table, int n_types, int n, int S, const RgWs& w, const int32_t* row_key, int rows,
                      const int32_t* ex_rowptr, const int32_t* ex_col, int n_keys, int32_t* bad_count) {
     const RgPlan& pl = w.plan;
     if (row_key)
@@ -304,8 +274,7 @@ void rl_launch_score(dim3 grid, hipStream_t st, const float* proj, const int32_t
 }  // namespace
 
 extern "C" size_t pc_retrieve_list_grouped_workspace_bytes(int rows, int n_types, int n, int slices) {
-    if (rows <= 0 || n_types <= 0 || n < 1 || n > RL_MAX_N || slices < 0 || slices > RG_MAX_SLICES) return 0;
-    return rl_layout(nullptr, rows, n_types, n, rg_slices(slices)).bytes;
+    return rg_topn_workspace_bytes(rows, n_types, n, RL_MAX_N, slices);
 }
 
 extern "C" int pc_retrieve_list_grouped(const float* proj, const int32_t* types, const int32_t* row_key, int rows,
@@ -313,20 +282,18 @@ extern "C" int pc_retrieve_list_grouped(const float* proj, const int32_t* types,
                                         const int32_t* ex_rowptr, const int32_t* ex_col, int n_keys, int n, int dim, int slices,
                                         int32_t* out_idx, float* out_score, int32_t* bad_count, void* ws, size_t ws_bytes,
                                         void* stream) {
-    if (!proj || !types || !type_rowptr || !type_col || !table || !out_idx || !out_score || !ws) return PC_EINVAL;
-    if (row_key && (!ex_rowptr || !ex_col || !bad_count || n_keys < 0)) return PC_EINVAL;
-    if (!row_key && (ex_rowptr || ex_col || n_keys != 0)) return PC_EINVAL;          // a list without keys: a caller's slip
-    if (rows <= 0 || n_types <= 0) return PC_EINVAL;
-    if (n < 1 || n > RL_MAX_N || (dim != 128 && dim != 256) || slices < 0 || slices > RG_MAX_SLICES) return PC_ESHAPE;
+    // (this entry looks at its lists before its counts: a list without keys is a caller's slip)
+    PC_TRY(rg_topn_check(proj && types && type_rowptr && type_col && table && out_idx && out_score && ws &&
+                             rg_lists_ok(row_key, ex_rowptr, ex_col, bad_count, n_keys),
+                         rows, n_types, true, n, RL_MAX_N, dim, slices));
     const int S = rg_slices(slices);
-    const RlWs w = rl_layout(ws, rows, n_types, n, S);
-    if (ws_bytes < w.bytes) return PC_EWORKSPACE;
     hipStream_t st = (hipStream_t)stream;
+    RgWs w;
+    unsigned grid;
+    PC_TRY(rg_begin(w, grid, ws, ws_bytes, types, nullptr, rows, type_rowptr, n_types, 0, n, S, RL_TM, nullptr, nullptr, st));
     const RgPlan& pl = w.plan;
-    PC_TRY(rg_plan_launch(pl, types, nullptr, rows, type_rowptr, n_types, 0, S, RL_TM, nullptr, nullptr, st));
-    const dim3 sgrid(rg_item_grid(rows, n_types, S, RL_TM));
 #define RL_SCORE(D, NE) \
-    rl_launch_score<D, NE>(sgrid, st, proj, type_rowptr, type_col, table, n_types, n, S, w, row_key, rows, ex_rowptr, ex_col, n_keys, bad_count)
+    rl_launch_score<D, NE>(dim3(grid), st, proj, type_rowptr, type_col, table, n_types, n, S, w, row_key, rows, ex_rowptr, ex_col, n_keys, bad_count)
     if (dim == 128) {
         if (n <= RL_N2) RL_SCORE(128, 2);
         else if (n <= RL_N4) RL_SCORE(128, 4);
@@ -341,3 +308,4 @@ extern "C" int pc_retrieve_list_grouped(const float* proj, const int32_t* types,
               pl.row_start, w.pv, w.pi, out_idx, out_score);
     return pc_launch_status();
 }
+
