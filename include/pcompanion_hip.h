@@ -1286,6 +1286,33 @@ int pc_sparse_adam_rows(float *table, float *exp_avg, float *exp_avg_sq, int64_t
                         const float *grad, int rows, int64_t t, double lr, double beta1, double beta2, double eps,
                         int32_t *bad, void *ws, size_t ws_bytes, void *stream);
 
+/* A k-means cell index over the product table (ABI 8, additive; csrc/cells.hip; ops.build_cell_index,
+ * inference.IndexedSimilarProducts).  The assignment of a Lloyd iteration and the search inside the probed cells are
+ * pc_retrieve_topk_grouped_biased with a cell in the place of a type; these two entries are what it does not provide.
+ *
+ * pc_cell_means: the centroid update.  cell_rowptr [n_cells + 1] / cell_col: a CSR of product ids per cell (ops.type_csr of the
+ * assignment); centroids [n_cells, dim] fp32, read and written:
+ *   centroids[c] = (sum of table[cell_col[i]], i in [cell_rowptr[c], cell_rowptr[c + 1])) / m_c   in fp32,
+ * m_c the number of those ids inside [0, num_products).  A cell with m_c == 0 keeps the centroid it had.  An id outside
+ * [0, num_products) is passed over: never read, not summed and not counted in m_c -- the mean is over the rows that were
+ * summed.  Passed-over ids are NOT reported (no bad_count argument): the CSR is the project's own (type_csr yields ids in
+ * range by construction), so an id out of range is a caller's slip that must do no harm, not a served condition to count.
+ * One workgroup per cell; 1024 / dim thread groups take the members g, g + G, .. of the cell in turn (16-byte loads of the
+ * rows, sequential fp32 additions from zero), the groups' sums meet in a fixed tree in LDS, one correctly rounded division by
+ * (float) m_c.  The summation order is a function of the member's position in the cell and of the dimension alone: the same
+ * bits on every run and for every grid; no atomics.  m_c above 2^24 is rounded to fp32 before the division.
+ * PC_EINVAL: null pointer, n_cells or num_products <= 0; PC_ESHAPE: dim not 128 / 256, table / centroids not 16-byte aligned.
+ *
+ * pc_merge_lists: idx / score [rows, L, n]: L lists per row, each sorted under (score descending, product index ascending)
+ * with -1 / -inf behind its last entry (the output format of the grouped retrievals); the lists of one row hold disjoint
+ * products.  out_idx / out_score [rows, n] = the first n of their union under the same total order, the scores copied bit
+ * for bit, -1 / -inf past the end.  One wave per row, lane l a cursor into list l, n rounds of a wave-wide best head.
+ * PC_EINVAL: null pointer, rows <= 0; PC_ESHAPE: L outside [1, 64], n outside [1, 256]. */
+int pc_cell_means(const float *table, const int32_t *cell_rowptr, const int32_t *cell_col, int n_cells, int num_products,
+                  int dim, float *centroids, void *stream);
+int pc_merge_lists(const int32_t *idx, const float *score, int rows, int L, int n, int32_t *out_idx, float *out_score,
+                   void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -231,6 +231,9 @@ SIGNATURES = {
     "pc_joint_query_grad": (_i, [_P(JointTensors), _vp, _vp, _vp, _vp, _i, _i64, _i, _i, _i, _f, _f, _vp, _vp, _vp, _sz, _vp]),
     "pc_sparse_adam_rows_workspace_bytes": (_sz, [_i]),
     "pc_sparse_adam_rows": (_i, [_vp, _vp, _vp, _i64, _i, _vp, _vp, _i, _i64, _d, _d, _d, _d, _vp, _vp, _sz, _vp]),
+    # the k-means cell index (csrc/cells.hip; ABI 8, additive)
+    "pc_cell_means": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
+    "pc_merge_lists": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
     "pc_hadamard_forward":(_i, [_vp, _vp, _i, _i, _vp, _vp]),
     "pc_hadamard_forward_dim": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
     "pc_hadamard_backward": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp]),

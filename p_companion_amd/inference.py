@@ -19,7 +19,9 @@ scored against the unrounded query; the scores are those of the ROUNDED table.
 
 SimilarProducts is the substitute side: the nearest products of a query under Euclidean distance over any [P, D] fp32 table
 (Product2Vec's export), the grouped retrieval and rank with the per-product term -|e_p|^2 / 2 on the score
-(pc_retrieve_topk_grouped_biased / pc_rank_grouped_biased), and hit@k / MRR over held-out similar pairs."""
+(pc_retrieve_topk_grouped_biased / pc_rank_grouped_biased), and hit@k / MRR over held-out similar pairs.
+IndexedSimilarProducts serves its whole-catalogue scope through a k-means cell index (ops.build_cell_index): the same retrieval
+over the products of a query's nearest cells, the probe lists of a query merged by pc_merge_lists."""
 import os
 from typing import Any, Dict, List
 
@@ -488,3 +490,118 @@ class SimilarProducts(_CandidateFilters):
             hi = min(lo + chunk, m)
             slot[lo:hi], rank[lo:hi] = self.rank_pairs(pairs[lo:hi, 0], pairs[lo:hi, 1])
         return Metrics.catalogue_metrics(slot, rank, ks)
+
+
+class IndexedSimilarProducts(SimilarProducts):
+    """SimilarProducts(scope="catalogue") served through a k-means cell index (ops.build_cell_index): a query is scored against
+    the products of its nprobe nearest cells, not against the catalogue.  similar_batch is APPROXIMATE in one way only: a
+    neighbour outside the probed cells is missed.  Inside them everything is the parent's -- the score bits, the total order
+    (score descending, product index ascending), exclusions, eligibility -- so the list is exactly the parent's order
+    restricted to the probed cells' products, and with nprobe == n_cells it is the parent's list bit for bit.
+    rank_pairs / evaluate_pairs are the parent's exact whole-catalogue code: an approximate rank has no meaning.
+
+    index: a CellIndex over this table; or n_cells (with iters, seed) to build one here.  nprobe: the default number of cells
+    a query probes, 1 .. min(16, n_cells)."""
+
+    MAX_NPROBE = 16
+
+    def __init__(self, table, bpg, index=None, n_cells=None, nprobe=8, iters=10, seed=0):
+        if (index is None) == (n_cells is None):
+            raise ValueError("IndexedSimilarProducts: pass an index, or n_cells to build one (not both)")
+        if index is not None and torch.is_tensor(table) and table.dim() == 2 \
+                and (index.num_products, index.dim) != tuple(table.shape):
+            raise ValueError(f"IndexedSimilarProducts: the index is over [{index.num_products}, {index.dim}], the table is "
+                             f"{tuple(table.shape)}")
+        cells = int(n_cells) if index is None else int(index.n_cells)
+        self._check_nprobe("IndexedSimilarProducts", nprobe, cells)
+        super().__init__(table, bpg, scope="catalogue")
+        if index is None:
+            index = ops.build_cell_index(table, cells, iters=iters, seed=seed)
+        self.index, self.n_cells, self.nprobe = index, cells, int(nprobe)
+        self.cell_rowptr, self.cell_col = index.cell_rowptr, index.cell_col
+        self._one_cell_type = (torch.tensor([0, cells], dtype=torch.int32, device=self.device),
+                               torch.arange(cells, dtype=torch.int32, device=self.device))
+
+    @classmethod
+    def _check_nprobe(cls, what, nprobe, n_cells):
+        top = min(cls.MAX_NPROBE, n_cells)
+        if not 1 <= int(nprobe) <= top:
+            raise ValueError(f"{what}: nprobe must be in [1, min({cls.MAX_NPROBE}, n_cells) = {top}], got {nprobe}")
+        return int(nprobe)
+
+    def set_eligible(self, mask=None):
+        """The parent's filter for the exact paths (the one-type CSR and cand_type), and the cell CSR filtered the same way:
+        type_csr of the eligible products' cells."""
+        super().set_eligible(mask)
+        if self.eligible is None:
+            self.cell_rowptr, self.cell_col = self.index.cell_rowptr, self.index.cell_col
+            return self
+        ids = torch.nonzero(self.eligible).reshape(-1).to(torch.int32)
+        rowptr, local = ops.type_csr(self.index.cell_of[ids.long()].contiguous(), self.n_cells)
+        self.cell_rowptr, self.cell_col = rowptr, ids[local.long()].contiguous()
+        return self
+
+    def _queries(self, what, query_idx):
+        query_idx = query_idx.to(self.device).to(torch.int32).contiguous()
+        if query_idx.dim() != 1:
+            raise ValueError(f"{what}: query_idx must be 1-D")
+        return query_idx
+
+    def _probe(self, q, nprobe):
+        rowptr, col = self._one_cell_type
+        zeros = torch.zeros(q.shape[0], dtype=torch.int32, device=self.device)
+        cells, _ = ops.retrieve_topk_grouped(q, zeros, rowptr, col, self.index.centroids, nprobe, bias=self.index.centroid_bias)
+        return cells
+
+    def _search(self, query_idx, q, n, nprobe):
+        """(idx [B, n] int32, score [B, n] fp32 = the biased retrieval's own score bits; -1 / -inf past the end) of the checked
+        queries query_idx [B] int32 with rows q [B, D]: steps 1 to 3 of similar_batch."""
+        b = q.shape[0]
+        cells = self._probe(q, nprobe)                                            # [B, nprobe]
+        rows = q.repeat_interleave(nprobe, dim=0)                                 # [B nprobe, D]
+        exclude = None if self.exclusions is None else (query_idx.repeat_interleave(nprobe),) + self.exclusions
+        idx, score = ops.retrieve_topk_grouped(rows, cells.reshape(-1), self.cell_rowptr, self.cell_col, self.table, n,
+                                               exclude=exclude, bias=self.bias)
+        return ops.merge_lists(idx.view(b, nprobe, n), score.view(b, nprobe, n))
+
+    @torch.no_grad()
+    def probe_cells(self, query_idx: torch.Tensor, nprobe: int = None):
+        """[B, nprobe] int32: the nprobe nearest cells of every query, nearest first (the biased 16-entry retrieval over the
+        centroids; ties to the lower cell)."""
+        nprobe = self._check_nprobe("probe_cells", self.nprobe if nprobe is None else nprobe, self.n_cells)
+        query_idx = self._queries("probe_cells", query_idx)
+        if query_idx.shape[0] == 0:
+            return torch.empty(0, nprobe, dtype=torch.int32, device=self.device)
+        return self._probe(self.table[query_idx.long()], nprobe)
+
+    @torch.no_grad()
+    def similar_batch(self, query_idx: torch.Tensor, n: int = 10, nprobe: int = None):
+        """The parent's contract over the non-excluded, eligible products of each query's nprobe nearest cells (None: the
+        constructor's): (idx [B, n] int32, -1 past the end; dist [B, n] fp32, +inf past the end).  Four steps: probe the
+        centroids; one grouped retrieval over B nprobe rows (row type = the probed cell, row key = the query); merge_lists of a
+        query's nprobe lists; the distances recomputed as the parent does."""
+        n = int(n)
+        if not 1 <= n <= self.MAX_N:
+            raise ValueError(f"similar_batch: 1 to {self.MAX_N} neighbours per query, got {n}")
+        nprobe = self._check_nprobe("similar_batch", self.nprobe if nprobe is None else nprobe, self.n_cells)
+        query_idx = self._queries("similar_batch", query_idx)
+        b = query_idx.shape[0]
+        if b == 0:
+            return (torch.empty(0, n, dtype=torch.int32, device=self.device),
+                    torch.empty(0, n, dtype=torch.float32, device=self.device))
+        q = self.table[query_idx.long()]
+        idx, _ = self._search(query_idx, q, n, nprobe)
+        e = self.table[idx.clamp(min=0).long()]                                   # [B, n, D]
+        dist = (q[:, None, :] - e + 1e-6).norm(dim=2)
+        return idx, torch.where(idx >= 0, dist, torch.full_like(dist, float("inf")))
+
+    @torch.no_grad()
+    def recall(self, query_idx: torch.Tensor, n: int = 10, nprobe: int = None):
+        """A device scalar (fp32): the share of the ids of the exact lists (SimilarProducts.similar_batch on this object) that
+        the indexed lists of the same queries hold; 1 where the exact lists are empty."""
+        nprobe = self._check_nprobe("recall", self.nprobe if nprobe is None else nprobe, self.n_cells)
+        exact, _ = SimilarProducts.similar_batch(self, query_idx, n)
+        got, _ = self.similar_batch(query_idx, n, nprobe)
+        held = ((exact[:, :, None] == got[:, None, :]) & (exact[:, :, None] >= 0)).any(dim=2).sum()
+        total = (exact >= 0).sum()
+        return torch.where(total > 0, held.float() / total.clamp(min=1).float(), torch.ones((), device=self.device))

@@ -2254,3 +2254,128 @@ def exclusion_csr(rowptr, col, include_self=True, num_products=None):
     if n_keys:
         ex_rowptr[1:] = torch.cumsum(torch.bincount(row, minlength=n_keys), 0).to(torch.int32)
     return ex_rowptr, ids.to(torch.int32).contiguous()
+
+
+MERGE_MAX_LISTS, MERGE_MAX_N = 64, 256
+
+
+def cell_means(table, cell_rowptr, cell_col, centroids):
+    """pc_cell_means: the centroid update of a Lloyd iteration, in place: centroids[c] = the fp32 mean of the rows
+    table[cell_col[i]], i in [cell_rowptr[c], cell_rowptr[c + 1]); a cell without members keeps the centroid it had.  table
+    [P, D] fp32, D 128 or 256; cell_rowptr [C + 1] / cell_col int32 as type_csr makes them of an assignment; centroids [C, D]
+    fp32.  One fixed summation order per cell, no atomics: the same bits on every run.  An id outside [0, P) is passed over
+    (not summed, not counted in the divisor, not reported).  Returns centroids."""
+    _req(table, torch.float32, "table")
+    if table.dim() != 2:
+        raise ValueError(f"table: expected [P, D], got shape {tuple(table.shape)}")
+    d = _width(table.shape[1])
+    if table.shape[0] < 1:
+        raise ValueError("table: expected at least one row")
+    _req(centroids, torch.float32, "centroids")
+    if centroids.dim() != 2 or centroids.shape[1] != d or centroids.shape[0] < 1:
+        raise ValueError(f"centroids: expected [C, {d}] with C >= 1, got shape {tuple(centroids.shape)}")
+    c = centroids.shape[0]
+    _req(cell_rowptr, torch.int32, "cell_rowptr", (c + 1,))
+    _req(cell_col, torch.int32, "cell_col")
+    if cell_col.dim() != 1:
+        raise ValueError(f"cell_col: expected a 1-D tensor, got shape {tuple(cell_col.shape)}")
+    if cell_col.numel() == 0:                             # (every cell empty: one unread entry)
+        cell_col = torch.zeros(1, dtype=torch.int32, device=table.device)
+    check(_lib.lib().pc_cell_means(_p(table), _p(cell_rowptr), _p(cell_col), c, table.shape[0], d, _p(centroids), _stream()),
+          "pc_cell_means")
+    return centroids
+
+
+def merge_lists(idx, score):
+    """pc_merge_lists: idx [R, L, n] int32 / score [R, L, n] fp32, L lists per row as the grouped retrievals return them (sorted
+    under (score descending, product index ascending), -1 / -inf behind the last entry), the lists of a row over disjoint
+    products -> (idx [R, n] int32, score [R, n] fp32): the first n of the row's union under the same total order, the scores'
+    bits unchanged, -1 / -inf past the end.  1 <= L <= 64, 1 <= n <= 256."""
+    _req(idx, torch.int32, "idx")
+    _req(score, torch.float32, "score")
+    if idx.dim() != 3 or tuple(score.shape) != tuple(idx.shape):
+        raise ValueError(f"merge_lists: expected idx and score of one shape [R, L, n], got {tuple(idx.shape)} and "
+                         f"{tuple(score.shape)}")
+    r, l, n = idx.shape
+    if not 1 <= l <= MERGE_MAX_LISTS:
+        raise ValueError(f"merge_lists: L must be in [1, {MERGE_MAX_LISTS}], got {l}")
+    if not 1 <= n <= MERGE_MAX_N:
+        raise ValueError(f"merge_lists: n must be in [1, {MERGE_MAX_N}], got {n}")
+    out_idx = torch.empty(r, n, dtype=torch.int32, device=idx.device)
+    out_sc = torch.empty(r, n, dtype=torch.float32, device=idx.device)
+    if r == 0:
+        return out_idx, out_sc
+    check(_lib.lib().pc_merge_lists(_p(idx), _p(score), r, l, n, _p(out_idx), _p(out_sc), _stream()), "pc_merge_lists")
+    return out_idx, out_sc
+
+
+class CellIndex:
+    """A k-means cell index over a [P, D] table (build_cell_index): centroids [C, D] fp32, centroid_bias [C] fp32 =
+    half_sq_norm_bias(centroids), cell_of [P] int32 = the assignment under THESE centroids, cell_rowptr [C + 1] / cell_col [P]
+    int32 = type_csr(cell_of, C), and the integers n_cells, dim, num_products."""
+
+    def __init__(self, centroids, centroid_bias, cell_of, cell_rowptr, cell_col):
+        self.centroids, self.centroid_bias, self.cell_of = centroids, centroid_bias, cell_of
+        self.cell_rowptr, self.cell_col = cell_rowptr, cell_col
+        self.n_cells, self.dim = int(centroids.shape[0]), int(centroids.shape[1])
+        self.num_products = int(cell_of.shape[0])
+
+
+def _assign_cells(table, centroids, centroid_bias=None, chunk_rows=1 << 20):
+    """cell_of [P] int32: the nearest centroid of every row of table under Euclidean distance -- the biased grouped retrieval
+    with the centroids as the candidates of one type and n = 1, in chunks of chunk_rows rows; the total order (score
+    descending, index ascending) gives a tie to the lowest cell."""
+    p, c = table.shape[0], centroids.shape[0]
+    dev = table.device
+    if centroid_bias is None:
+        centroid_bias = half_sq_norm_bias(centroids)
+    chunk_rows = min(int(chunk_rows), p)
+    zeros = torch.zeros(chunk_rows, dtype=torch.int32, device=dev)
+    rowptr = torch.tensor([0, c], dtype=torch.int32, device=dev)
+    col = torch.arange(c, dtype=torch.int32, device=dev)
+    cell_of = torch.empty(p, dtype=torch.int32, device=dev)
+    for lo in range(0, p, chunk_rows):
+        hi = min(lo + chunk_rows, p)
+        idx, _ = retrieve_topk_grouped(table[lo:hi], zeros[:hi - lo], rowptr, col, centroids, 1, bias=centroid_bias)
+        cell_of[lo:hi] = idx[:, 0]
+    return cell_of
+
+
+def build_cell_index(table, n_cells, iters=10, seed=0, init=None, chunk_rows=1 << 20):
+    """Lloyd's k-means over table [P, D] fp32 (D 128 or 256) on the device -> CellIndex with 1 <= n_cells <= P cells.
+    init: [n_cells, D] fp32 device tensor of starting centroids; None: the rows at the first n_cells entries of
+    torch.randperm(P) drawn from a CPU torch.Generator seeded with `seed`.  An iteration is one assignment (_assign_cells: the
+    biased grouped retrieval over the centroids, chunk_rows rows at a time) and one update (type_csr of the assignment, then
+    cell_means; an empty cell keeps its centroid); the final centroids get one more assignment, so cell_of is always the
+    assignment under the stored centroids.  Every step is bitwise deterministic, so equal arguments give equal bits in every
+    field.  Nothing is read back to the host but type_csr's range check of the assignment."""
+    _req(table, torch.float32, "table")
+    if table.dim() != 2:
+        raise ValueError(f"table: expected [P, D], got shape {tuple(table.shape)}")
+    d = _width(table.shape[1])
+    p = table.shape[0]
+    n_cells, iters, chunk_rows = int(n_cells), int(iters), int(chunk_rows)
+    if not 1 <= n_cells <= p:
+        raise ValueError(f"build_cell_index: n_cells must be in [1, P = {p}], got {n_cells}")
+    if iters < 0:
+        raise ValueError(f"build_cell_index: iters must not be negative, got {iters}")
+    if chunk_rows < 1:
+        raise ValueError(f"build_cell_index: chunk_rows must be positive, got {chunk_rows}")
+    if init is not None:
+        _req(init, torch.float32, "init")
+        if tuple(init.shape) != (n_cells, d):
+            raise ValueError(f"build_cell_index: init must be [{n_cells}, {d}], got shape {tuple(init.shape)}")
+        centroids = init.clone()
+    else:
+        gen = torch.Generator(device="cpu")
+        gen.manual_seed(int(seed))
+        first = torch.randperm(p, generator=gen)[:n_cells].to(table.device)
+        centroids = table[first].contiguous()
+    for _ in range(iters):
+        cell_of = _assign_cells(table, centroids, None, chunk_rows)
+        rowptr, col = type_csr(cell_of, n_cells)
+        cell_means(table, rowptr, col, centroids)
+    bias = half_sq_norm_bias(centroids)
+    cell_of = _assign_cells(table, centroids, bias, chunk_rows)
+    rowptr, col = type_csr(cell_of, n_cells)
+    return CellIndex(centroids, bias, cell_of, rowptr, col)
