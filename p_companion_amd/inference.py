@@ -87,6 +87,15 @@ class _CandidateFilters:
         self.cand_type = torch.where(mask, cand, torch.full_like(cand, -1))
         return self
 
+    def _exclude_rows(self, query_idx, repeat=None):
+        """The `exclude` triple of the grouped entries for rows keyed by their query's id -- `repeat` consecutive rows per query
+        (its K slots, its probed cells), one if None; None when no set is installed."""
+        if self.exclusions is None:
+            return None
+        if repeat is not None:
+            query_idx = query_idx.repeat_interleave(repeat).contiguous()
+        return (query_idx,) + self.exclusions
+
     def _excluded(self, query_idx, target_idx):
         """[B] bool: target_idx[b] is in query_idx[b]'s exclusion list (a bisection per pair, as vector operations; the lists
         are strictly ascending)."""
@@ -225,26 +234,17 @@ class PCompanionInference(_CandidateFilters):
         b, k = types.shape
         proj = out["projected_embeddings"].contiguous().reshape(b * k, -1)
         row_types = types.to(torch.int32).reshape(-1).contiguous()
+        exclude = self._exclude_rows(query_idx, k)
+        rows = (proj, row_types, self.type_rowptr, self.type_col)
         if self.catalogue is not None:                    # (n <= 16) the bf16 entry, whatever the graph's kind
-            exclude = None
-            if self.exclusions is not None:
-                exclude = (query_idx.repeat_interleave(k).contiguous(),) + self.exclusions
-            idx, sc = ops.retrieve_topk_grouped(proj, row_types, self.type_rowptr, self.type_col, self.catalogue, n,
-                                                exclude=exclude)
+            idx, sc = ops.retrieve_topk_grouped(*rows, self.catalogue, n, exclude=exclude)
         elif n > 16:                                      # (RG_MAX_N / RMAX_N: the entries below refuse 17)
-            exclude = None
-            if self.exclusions is not None:
-                exclude = (query_idx.repeat_interleave(k).contiguous(),) + self.exclusions
-            idx, sc = ops.retrieve_list_grouped(proj, row_types, self.type_rowptr, self.type_col, self.features, n,
-                                                exclude=exclude)
-        elif self.exclusions is not None:
-            # the per-row kernel has no filter: the grouped search, whatever the graph's kind
-            exclude = (query_idx.repeat_interleave(k).contiguous(),) + self.exclusions
-            idx, sc = ops.retrieve_topk_grouped(proj, row_types, self.type_rowptr, self.type_col, self.features,
-                                                int(num_recommendations), exclude=exclude)
+            idx, sc = ops.retrieve_list_grouped(*rows, self.features, n, exclude=exclude)
+        elif exclude is not None or self.grouped:
+            # (the per-row kernel has no filter: with a set the grouped search, whatever the graph's kind)
+            idx, sc = ops.retrieve_topk_grouped(*rows, self.features, n, exclude=exclude)
         else:
-            retrieve = ops.retrieve_topk_grouped if self.grouped else ops.retrieve_topk
-            idx, sc = retrieve(proj, row_types, self.type_rowptr, self.type_col, self.features, int(num_recommendations))
+            idx, sc = ops.retrieve_topk(*rows, self.features, n)
         return types, idx.reshape(b, k, -1), sc.reshape(b, k, -1)
 
     @torch.no_grad()
@@ -280,10 +280,11 @@ class PCompanionInference(_CandidateFilters):
         slot = torch.where(found, k, torch.full_like(k, -1)).to(torch.int32)
         proj = out["projected_embeddings"][torch.arange(b, device=self.device), k].contiguous()      # [B, D]
         row_type = torch.where(found, target_type, torch.full_like(target_type, -1)).to(torch.int32)
-        if self.exclusions is not None:
+        exclude = self._exclude_rows(query_idx)
+        if exclude is not None:
             # a target in the query's list, or not eligible: -1 from the entry itself
             rank, _ = ops.rank_grouped(proj, row_type, target_idx, self.type_rowptr, self.type_col, self.features,
-                                       exclude=(query_idx,) + self.exclusions, cand_type=self.cand_type)
+                                       exclude=exclude, cand_type=self.cand_type)
             return slot, rank
         rank, _ = ops.rank_grouped(proj, row_type, target_idx, self.type_rowptr, self.type_col, self.features)
         if self.eligible is not None:
@@ -423,23 +424,37 @@ class SimilarProducts(_CandidateFilters):
         """The n nearest candidates of every query, nearest first: (idx [B, n] int32, -1 past the end; dist [B, n] fp32, +inf
         past the end).  The order is the biased retrieval's; dist is recomputed for the returned ids as |q - e + 1e-6|_2, the
         distance of the triplet loss (F.pairwise_distance) -- not derived from the score, whose terms cancel."""
+        n = self._neighbours(n)
+        query_idx = self._queries("similar_batch", query_idx)
+        if query_idx.shape[0] == 0:
+            return self._no_neighbours(n)
+        q = self.table[query_idx.long()]
+        idx, _ = ops.retrieve_topk_grouped(q, self._scope_type[query_idx.long()].contiguous(), self.type_rowptr, self.type_col,
+                                           self.table, n, exclude=self._exclude_rows(query_idx), bias=self.bias)
+        return idx, self._distances(q, idx)
+
+    def _neighbours(self, n):
+        """n of similar_batch as an int; outside 1 .. MAX_N: ValueError, before anything of the object is read."""
         n = int(n)
         if not 1 <= n <= self.MAX_N:
             raise ValueError(f"similar_batch: 1 to {self.MAX_N} neighbours per query, got {n}")
+        return n
+
+    def _queries(self, what, query_idx):
         query_idx = query_idx.to(self.device).to(torch.int32).contiguous()
         if query_idx.dim() != 1:
-            raise ValueError("similar_batch: query_idx must be 1-D")
-        b = query_idx.shape[0]
-        if b == 0:
-            return (torch.empty(0, n, dtype=torch.int32, device=self.device),
-                    torch.empty(0, n, dtype=torch.float32, device=self.device))
-        q = self.table[query_idx.long()]
-        exclude = None if self.exclusions is None else (query_idx,) + self.exclusions
-        idx, _ = ops.retrieve_topk_grouped(q, self._scope_type[query_idx.long()].contiguous(), self.type_rowptr, self.type_col,
-                                           self.table, n, exclude=exclude, bias=self.bias)
+            raise ValueError(f"{what}: query_idx must be 1-D")
+        return query_idx
+
+    def _no_neighbours(self, n):
+        """similar_batch of no query"""
+        return (torch.empty(0, n, dtype=torch.int32, device=self.device), torch.empty(0, n, dtype=torch.float32, device=self.device))
+
+    def _distances(self, q, idx):
+        """[B, n] fp32: |q[b] - table[idx[b, j]] + 1e-6|_2, +inf where idx is -1"""
         e = self.table[idx.clamp(min=0).long()]                                   # [B, n, D]
         dist = (q[:, None, :] - e + 1e-6).norm(dim=2)
-        return idx, torch.where(idx >= 0, dist, torch.full_like(dist, float("inf")))
+        return torch.where(idx >= 0, dist, torch.full_like(dist, float("inf")))
 
     @torch.no_grad()
     def rank_pairs(self, anchor_idx: torch.Tensor, target_idx: torch.Tensor):
@@ -461,9 +476,10 @@ class SimilarProducts(_CandidateFilters):
         candidate = inside & (self.cand_type[target_idx.long().clamp(0, p - 1)] == row_type)
         slot = torch.where(candidate, 0, -1).to(torch.int32)
         q = self.table[anchor_idx.long()]
-        if self.exclusions is not None:
+        exclude = self._exclude_rows(anchor_idx)
+        if exclude is not None:
             rank, _ = ops.rank_grouped(q, row_type.contiguous(), target_idx, self.type_rowptr, self.type_col, self.table,
-                                       exclude=(anchor_idx,) + self.exclusions, cand_type=self.cand_type, bias=self.bias)
+                                       exclude=exclude, cand_type=self.cand_type, bias=self.bias)
             return slot, rank
         # no lists: a target that is no candidate costs no search
         row_type = torch.where(candidate, row_type, torch.full_like(row_type, -1)).contiguous()
@@ -541,12 +557,6 @@ class IndexedSimilarProducts(SimilarProducts):
         self.cell_rowptr, self.cell_col = rowptr, ids[local.long()].contiguous()
         return self
 
-    def _queries(self, what, query_idx):
-        query_idx = query_idx.to(self.device).to(torch.int32).contiguous()
-        if query_idx.dim() != 1:
-            raise ValueError(f"{what}: query_idx must be 1-D")
-        return query_idx
-
     def _probe(self, q, nprobe):
         rowptr, col = self._one_cell_type
         zeros = torch.zeros(q.shape[0], dtype=torch.int32, device=self.device)
@@ -559,9 +569,8 @@ class IndexedSimilarProducts(SimilarProducts):
         b = q.shape[0]
         cells = self._probe(q, nprobe)                                            # [B, nprobe]
         rows = q.repeat_interleave(nprobe, dim=0)                                 # [B nprobe, D]
-        exclude = None if self.exclusions is None else (query_idx.repeat_interleave(nprobe),) + self.exclusions
         idx, score = ops.retrieve_topk_grouped(rows, cells.reshape(-1), self.cell_rowptr, self.cell_col, self.table, n,
-                                               exclude=exclude, bias=self.bias)
+                                               exclude=self._exclude_rows(query_idx, nprobe), bias=self.bias)
         return ops.merge_lists(idx.view(b, nprobe, n), score.view(b, nprobe, n))
 
     @torch.no_grad()
@@ -580,20 +589,14 @@ class IndexedSimilarProducts(SimilarProducts):
         constructor's): (idx [B, n] int32, -1 past the end; dist [B, n] fp32, +inf past the end).  Four steps: probe the
         centroids; one grouped retrieval over B nprobe rows (row type = the probed cell, row key = the query); merge_lists of a
         query's nprobe lists; the distances recomputed as the parent does."""
-        n = int(n)
-        if not 1 <= n <= self.MAX_N:
-            raise ValueError(f"similar_batch: 1 to {self.MAX_N} neighbours per query, got {n}")
+        n = self._neighbours(n)
         nprobe = self._check_nprobe("similar_batch", self.nprobe if nprobe is None else nprobe, self.n_cells)
         query_idx = self._queries("similar_batch", query_idx)
-        b = query_idx.shape[0]
-        if b == 0:
-            return (torch.empty(0, n, dtype=torch.int32, device=self.device),
-                    torch.empty(0, n, dtype=torch.float32, device=self.device))
+        if query_idx.shape[0] == 0:
+            return self._no_neighbours(n)
         q = self.table[query_idx.long()]
         idx, _ = self._search(query_idx, q, n, nprobe)
-        e = self.table[idx.clamp(min=0).long()]                                   # [B, n, D]
-        dist = (q[:, None, :] - e + 1e-6).norm(dim=2)
-        return idx, torch.where(idx >= 0, dist, torch.full_like(dist, float("inf")))
+        return idx, self._distances(q, idx)
 
     @torch.no_grad()
     def recall(self, query_idx: torch.Tensor, n: int = 10, nprobe: int = None):

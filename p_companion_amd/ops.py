@@ -1919,13 +1919,21 @@ def retrieve_topk(proj, types, type_rowptr, type_col, table, n):
 RETRIEVE_MAX_SLICES = 64
 
 
+def _table_width(table, name="table", rows=False):
+    """D of a [P, D] fp32 device table, D 128 or 256 (rows: P >= 1 too)."""
+    _req(table, torch.float32, name)
+    if table.dim() != 2:
+        raise ValueError(f"{name}: expected [P, D], got shape {tuple(table.shape)}")
+    d = _width(table.shape[1])
+    if rows and table.shape[0] < 1:
+        raise ValueError(f"{name}: expected at least one row")
+    return d
+
+
 def catalogue_bf16(features):
     """The bf16 copy of a catalogue that retrieve_topk_grouped serves from: [P, D] fp32 on the device -> [P, D] torch.bfloat16,
     rounded to nearest even, half the bytes.  Once per catalogue, off the serving path: no kernel of its own."""
-    _req(features, torch.float32, "features")
-    if features.dim() != 2:
-        raise ValueError(f"features: expected [P, D], got shape {tuple(features.shape)}")
-    _width(features.shape[1])
+    _table_width(features, "features")
     return features.to(torch.bfloat16)
 
 
@@ -1947,27 +1955,26 @@ def _check_exclude(what, exclude, rows):
     return row_key, ex_rowptr, ex_col
 
 
-def _exclude_args(exclude):
-    """The triple as device arguments: (row_key, ex_rowptr, ex_col -- one unread entry where every list is empty --, n_keys)."""
+def _filter_args(exclude, bad, device, counted=False):
+    """A checked triple and the caller's counter as device arguments: (row_key, ex_rowptr, ex_col -- one unread entry where
+    every list is empty --, n_keys, bad -- a fresh zero where the caller gave none).  Without a triple: (None, None, None, 0,
+    None) -- null pointers -- and, for an entry that counts other things too (counted), the counter."""
+    if exclude is None:
+        return None, None, None, 0, _bad_counter(bad, device) if counted else None
     row_key, ex_rowptr, ex_col = exclude
     _req(row_key, torch.int32, "exclude row_key")
     _req(ex_rowptr, torch.int32, "exclude ex_rowptr")
     if ex_col.numel() == 0:
         ex_col = torch.zeros(1, dtype=torch.int32, device=ex_rowptr.device)
     _req(ex_col, torch.int32, "exclude ex_col")
-    return row_key, ex_rowptr, ex_col, ex_rowptr.numel() - 1
+    return row_key, ex_rowptr, ex_col, ex_rowptr.numel() - 1, _bad_counter(bad, device)
 
 
 def half_sq_norm_bias(table):
     """pc_half_sq_norm_bias: bias[p] = -0.5 * |table[p]|^2 for a [P, D] fp32 device table -> [P] fp32, the per-product term under
     which retrieve_topk_grouped / rank_grouped (bias=) order by Euclidean distance: |q - e|^2 = |q|^2 - 2 (<q, e> + bias).  One
     fixed summation order per row, no atomics: the same bits on every run.  Once per catalogue."""
-    _req(table, torch.float32, "table")
-    if table.dim() != 2:
-        raise ValueError(f"table: expected [P, D], got shape {tuple(table.shape)}")
-    d = _width(table.shape[1])
-    if table.shape[0] < 1:
-        raise ValueError("table: expected at least one row")
+    d = _table_width(table, rows=True)
     out = torch.empty(table.shape[0], dtype=torch.float32, device=table.device)
     check(_lib.lib().pc_half_sq_norm_bias(_p(table), table.shape[0], d, _p(out), _stream()), "pc_half_sq_norm_bias")
     return out
@@ -1984,6 +1991,56 @@ def _check_bias(what, bias, table):
     if bias.dim() != 1 or bias.shape[0] != table.shape[0]:
         raise ValueError(f"{what}: bias of shape {tuple(bias.shape)} is not supported: it must hold one entry per product "
                          f"({table.shape[0]})")
+
+
+def _grouped_rows(proj, types, type_rowptr, type_col, table, table_dtype, slices):
+    """The rows of a grouped call, checked: (proj as [R, D], R, the number of types, D, slices)."""
+    slices = int(slices)
+    if not 0 <= slices <= RETRIEVE_MAX_SLICES:
+        raise ValueError(f"slices must be in [0, {RETRIEVE_MAX_SLICES}] (0 = automatic), got {slices}")
+    d = _width(table.shape[1])
+    proj = _req(proj.reshape(-1, d), torch.float32, "proj")
+    r = proj.shape[0]
+    _req(types, torch.int32, "types", (r,))
+    _req(type_rowptr, torch.int32, "type_rowptr")
+    _req(type_col, torch.int32, "type_col")
+    _req(table, table_dtype, "table")
+    return proj, r, type_rowptr.numel() - 1, d, slices
+
+
+def _grouped_call(name, tag, device, sizes, args, sized_as=None):
+    """Entry `name` of the grouped family with `args`, its arguments in the header's order up to the workspace; behind them
+    go the workspace that NAME_workspace_bytes(*sizes) asks for (sized_as: another entry's query), its byte count and the
+    stream.  In the lists of this family a tensor that is always there travels as its data_ptr() -- the address that _p wraps,
+    without a call and an object per pointer -- and one that may be absent through _p (None: a null pointer)."""
+    lib = _lib.lib()
+    ws = workspace(getattr(lib, (sized_as or name) + "_workspace_bytes")(*sizes), device, tag)
+    check(getattr(lib, name)(*args, ws.data_ptr(), ws.numel(), _stream()), name)
+
+
+def _retrieve_grouped(name, proj, types, type_rowptr, type_col, table, n, slices, exclude, bad, *, bias=None,
+                      what="retrieve_topk_grouped", tag="retrieve_grouped", table_dtype=torch.float32):
+    """retrieve_topk_grouped / retrieve_list_grouped behind the choice of the entry."""
+    if exclude is not None:
+        exclude = _check_exclude(what, exclude, types.shape[0] if isinstance(types, torch.Tensor) else -1)
+    elif bad is not None:
+        raise ValueError(f"{what}: bad counts keys out of range and is read with an exclude triple only")
+    proj, r, t, d, slices = _grouped_rows(proj, types, type_rowptr, type_col, table, table_dtype, slices)
+    device = proj.device
+    out_idx = torch.empty(r, n, dtype=torch.int32, device=device)
+    out_sc = torch.empty(r, n, dtype=torch.float32, device=device)
+    if name == "pc_retrieve_topk_grouped":
+        args = (proj.data_ptr(), types.data_ptr(), r, type_rowptr.data_ptr(), type_col.data_ptr(), table.data_ptr(), t, n, d,
+                slices, out_idx.data_ptr(), out_sc.data_ptr())
+    else:
+        # (the filtered entries' list, bias behind table where the entry has it; without a triple row_key, ex_rowptr, ex_col
+        # and bad are None: null pointers, n_keys 0)
+        row_key, ex_rowptr, ex_col, n_keys, bad = _filter_args(exclude, bad, device)
+        bias = () if bias is None else (_req(bias, torch.float32, "bias", (table.shape[0],)).data_ptr(),)
+        args = (proj.data_ptr(), types.data_ptr(), _p(row_key), r, type_rowptr.data_ptr(), type_col.data_ptr(), table.data_ptr(),
+                *bias, t, _p(ex_rowptr), _p(ex_col), n_keys, n, d, slices, out_idx.data_ptr(), out_sc.data_ptr(), _p(bad))
+    _grouped_call(name, tag, device, (r, t, n, slices), args)
+    return out_idx, out_sc
 
 
 def retrieve_topk_grouped(proj, types, type_rowptr, type_col, table, n, slices=0, exclude=None, bad=None, bias=None):
@@ -2004,79 +2061,16 @@ def retrieve_topk_grouped(proj, types, type_rowptr, type_col, table, n, slices=0
     determinism under the score fl(<proj[r], table[p]> + bias[p]), one fp32 addition after the unbiased entry's own chain (a
     zero bias gives that entry's bits), with or without exclude; half_sq_norm_bias(table) makes the order Euclidean.
     bias=None: exactly the calls above."""
+    bf16 = isinstance(table, torch.Tensor) and table.dtype == torch.bfloat16
     if bias is not None:
         _check_bias("retrieve_topk_grouped", bias, table)
-    if exclude is not None:
-        exclude = _check_exclude("retrieve_topk_grouped", exclude, types.shape[0] if isinstance(types, torch.Tensor) else -1)
-    elif bad is not None:
-        raise ValueError("retrieve_topk_grouped: bad counts keys out of range and is read with an exclude triple only")
-    d = _width(table.shape[1])
-    proj = _req(proj.reshape(-1, d), torch.float32, "proj")
-    r = proj.shape[0]
-    _req(types, torch.int32, "types", (r,))
-    _req(type_rowptr, torch.int32, "type_rowptr")
-    _req(type_col, torch.int32, "type_col")
-    bf16 = isinstance(table, torch.Tensor) and table.dtype == torch.bfloat16
-    _req(table, torch.bfloat16 if bf16 else torch.float32, "table")
-    n, slices, t = int(n), int(slices), type_rowptr.numel() - 1
-    if not 0 <= slices <= RETRIEVE_MAX_SLICES:
-        raise ValueError(f"slices must be in [0, {RETRIEVE_MAX_SLICES}] (0 = automatic), got {slices}")
-    out_idx = torch.empty(r, n, dtype=torch.int32, device=proj.device)
-    out_sc = torch.empty(r, n, dtype=torch.float32, device=proj.device)
-    if bias is not None:
-        _req(bias, torch.float32, "bias", (table.shape[0],))
-        row_key = ex_rowptr = ex_col = None
-        n_keys = 0
-        if exclude is not None:
-            row_key, ex_rowptr, ex_col, n_keys = _exclude_args(exclude)
-            if bad is None:
-                bad = torch.zeros(1, dtype=torch.int32, device=proj.device)
-            else:
-                _req(bad, torch.int32, "bad", (1,))
-        nbytes = _lib.lib().pc_retrieve_topk_grouped_biased_workspace_bytes(r, t, n, slices)
-        ws = workspace(nbytes, proj.device, "retrieve_grouped")
-        # (without a triple row_key, ex_rowptr, ex_col and bad are None: null pointers, n_keys 0)
-        check(_lib.lib().pc_retrieve_topk_grouped_biased(_p(proj), _p(types), _p(row_key), r, _p(type_rowptr), _p(type_col),
-                                                         _p(table), _p(bias), t, _p(ex_rowptr), _p(ex_col), n_keys, n, d, slices,
-                                                         _p(out_idx), _p(out_sc), _p(bad), _p(ws), ws.numel(), _stream()),
-              "pc_retrieve_topk_grouped_biased")
-        return out_idx, out_sc
-    if bf16:
-        row_key = ex_rowptr = ex_col = None
-        n_keys = 0
-        if exclude is not None:
-            row_key, ex_rowptr, ex_col, n_keys = _exclude_args(exclude)
-            if bad is None:
-                bad = torch.zeros(1, dtype=torch.int32, device=proj.device)
-            else:
-                _req(bad, torch.int32, "bad", (1,))
-        nbytes = _lib.lib().pc_retrieve_topk_grouped_bf16_workspace_bytes(r, t, n, slices)
-        ws = workspace(nbytes, proj.device, "retrieve_grouped")
-        # (without a triple row_key, ex_rowptr, ex_col and bad are None: null pointers, n_keys 0)
-        check(_lib.lib().pc_retrieve_topk_grouped_bf16(_p(proj), _p(types), _p(row_key), r, _p(type_rowptr), _p(type_col),
-                                                       _p(table), t, _p(ex_rowptr), _p(ex_col), n_keys, n, d, slices,
-                                                       _p(out_idx), _p(out_sc), _p(bad), _p(ws), ws.numel(), _stream()),
-              "pc_retrieve_topk_grouped_bf16")
-        return out_idx, out_sc
-    if exclude is not None:
-        row_key, ex_rowptr, ex_col, n_keys = _exclude_args(exclude)
-        if bad is None:
-            bad = torch.zeros(1, dtype=torch.int32, device=proj.device)
-        else:
-            _req(bad, torch.int32, "bad", (1,))
-        nbytes = _lib.lib().pc_retrieve_topk_grouped_excluding_workspace_bytes(r, t, n, slices)
-        ws = workspace(nbytes, proj.device, "retrieve_grouped")
-        check(_lib.lib().pc_retrieve_topk_grouped_excluding(_p(proj), _p(types), _p(row_key), r, _p(type_rowptr), _p(type_col),
-                                                            _p(table), t, _p(ex_rowptr), _p(ex_col), n_keys, n, d, slices,
-                                                            _p(out_idx), _p(out_sc), _p(bad), _p(ws), ws.numel(), _stream()),
-              "pc_retrieve_topk_grouped_excluding")
-        return out_idx, out_sc
-    nbytes = _lib.lib().pc_retrieve_topk_grouped_workspace_bytes(r, t, n, slices)
-    ws = workspace(nbytes, proj.device, "retrieve_grouped")
-    check(_lib.lib().pc_retrieve_topk_grouped(_p(proj), _p(types), r, _p(type_rowptr), _p(type_col), _p(table), t, n, d,
-                                              slices, _p(out_idx), _p(out_sc), _p(ws), ws.numel(), _stream()),
-          "pc_retrieve_topk_grouped")
-    return out_idx, out_sc
+        name = "pc_retrieve_topk_grouped_biased"
+    elif bf16:
+        name = "pc_retrieve_topk_grouped_bf16"
+    else:
+        name = "pc_retrieve_topk_grouped" if exclude is None else "pc_retrieve_topk_grouped_excluding"
+    return _retrieve_grouped(name, proj, types, type_rowptr, type_col, table, int(n), slices, exclude, bad, bias=bias,
+                             table_dtype=torch.bfloat16 if bf16 else torch.float32)
 
 
 RETRIEVE_LIST_MAX_N = 256
@@ -2089,41 +2083,11 @@ def retrieve_list_grouped(proj, types, type_rowptr, type_col, table, n, slices=0
     bits for every `slices`, and for n <= 16 retrieve_topk_grouped's own bits.  Nothing is read back to the host.
     exclude = (row_key [R] int32, ex_rowptr [n_keys + 1] int32, ex_col [E] int32) and `bad` as in retrieve_topk_grouped: the
     first n products of the type that are NOT in the list of row_key[r].  exclude=None: the unfiltered list."""
-    n, slices = int(n), int(slices)
+    n = int(n)
     if not 1 <= n <= RETRIEVE_LIST_MAX_N:
         raise ValueError(f"retrieve_list_grouped: n must be in [1, {RETRIEVE_LIST_MAX_N}], got {n}")
-    if not 0 <= slices <= RETRIEVE_MAX_SLICES:
-        raise ValueError(f"slices must be in [0, {RETRIEVE_MAX_SLICES}] (0 = automatic), got {slices}")
-    if exclude is not None:
-        exclude = _check_exclude("retrieve_list_grouped", exclude, types.shape[0] if isinstance(types, torch.Tensor) else -1)
-    elif bad is not None:
-        raise ValueError("retrieve_list_grouped: bad counts keys out of range and is read with an exclude triple only")
-    d = _width(table.shape[1])
-    proj = _req(proj.reshape(-1, d), torch.float32, "proj")
-    r = proj.shape[0]
-    _req(types, torch.int32, "types", (r,))
-    _req(type_rowptr, torch.int32, "type_rowptr")
-    _req(type_col, torch.int32, "type_col")
-    _req(table, torch.float32, "table")
-    t = type_rowptr.numel() - 1
-    out_idx = torch.empty(r, n, dtype=torch.int32, device=proj.device)
-    out_sc = torch.empty(r, n, dtype=torch.float32, device=proj.device)
-    row_key = ex_rowptr = ex_col = None
-    n_keys = 0
-    if exclude is not None:
-        row_key, ex_rowptr, ex_col, n_keys = _exclude_args(exclude)
-        if bad is None:
-            bad = torch.zeros(1, dtype=torch.int32, device=proj.device)
-        else:
-            _req(bad, torch.int32, "bad", (1,))
-    nbytes = _lib.lib().pc_retrieve_list_grouped_workspace_bytes(r, t, n, slices)
-    ws = workspace(nbytes, proj.device, "retrieve_list")
-    # (without a triple row_key, ex_rowptr, ex_col and bad are None: null pointers, n_keys 0)
-    check(_lib.lib().pc_retrieve_list_grouped(_p(proj), _p(types), _p(row_key), r, _p(type_rowptr), _p(type_col), _p(table), t,
-                                              _p(ex_rowptr), _p(ex_col), n_keys, n, d, slices, _p(out_idx), _p(out_sc),
-                                              _p(bad), _p(ws), ws.numel(), _stream()),
-          "pc_retrieve_list_grouped")
-    return out_idx, out_sc
+    return _retrieve_grouped("pc_retrieve_list_grouped", proj, types, type_rowptr, type_col, table, n, slices, exclude, bad,
+                             what="retrieve_list_grouped", tag="retrieve_list")
 
 
 def rank_grouped(proj, types, targets, type_rowptr, type_col, table, slices=0, bad=None, exclude=None, cand_type=None,
@@ -2153,50 +2117,28 @@ def rank_grouped(proj, types, targets, type_rowptr, type_col, table, slices=0, b
             raise ValueError("rank_grouped: cand_type must be an int32 tensor of one entry per product")
     elif cand_type is not None:
         raise ValueError("rank_grouped: cand_type is read with an exclude triple only")
-    d = _width(table.shape[1])
-    proj = _req(proj.reshape(-1, d), torch.float32, "proj")
-    r = proj.shape[0]
-    _req(types, torch.int32, "types", (r,))
+    proj, r, t, d, slices = _grouped_rows(proj, types, type_rowptr, type_col, table, torch.float32, slices)
     _req(targets, torch.int32, "targets", (r,))
-    _req(type_rowptr, torch.int32, "type_rowptr")
-    _req(type_col, torch.int32, "type_col")
-    _req(table, torch.float32, "table")
-    slices, t = int(slices), type_rowptr.numel() - 1
-    if not 0 <= slices <= RETRIEVE_MAX_SLICES:
-        raise ValueError(f"slices must be in [0, {RETRIEVE_MAX_SLICES}] (0 = automatic), got {slices}")
-    rank = torch.empty(r, dtype=torch.int32, device=proj.device)
-    if bad is None:
-        bad = torch.zeros(1, dtype=torch.int32, device=proj.device)
+    p, device = table.shape[0], proj.device
+    rank = torch.empty(r, dtype=torch.int32, device=device)
+    row_key, ex_rowptr, ex_col, n_keys, bad = _filter_args(exclude, bad, device, counted=True)
+    if bias is None and exclude is None:
+        name, sized_as = "pc_rank_grouped", None
+        args = (proj.data_ptr(), types.data_ptr(), targets.data_ptr(), r, type_rowptr.data_ptr(), type_col.data_ptr(),
+                table.data_ptr(), t, p, d, slices, rank.data_ptr(), bad.data_ptr())
     else:
-        _req(bad, torch.int32, "bad", (1,))
-    if bias is not None:
-        _req(bias, torch.float32, "bias", (table.shape[0],))
-        row_key = ex_rowptr = ex_col = None
-        n_keys = 0
+        # (the filtered entries' list, bias behind table where the entry has it; without a triple row_key, ex_rowptr, ex_col
+        # and cand_type are None: null pointers, n_keys 0)
         if exclude is not None:
-            row_key, ex_rowptr, ex_col, n_keys = _exclude_args(exclude)
-            _req(cand_type, torch.int32, "cand_type", (table.shape[0],))
-        nbytes = _lib.lib().pc_rank_grouped_biased_workspace_bytes(r, t, slices)
-        ws = workspace(nbytes, proj.device, "rank_grouped")
-        # (without a triple row_key, ex_rowptr, ex_col and cand_type are None: null pointers, n_keys 0)
-        check(_lib.lib().pc_rank_grouped_biased(_p(proj), _p(types), _p(targets), _p(row_key), r, _p(type_rowptr), _p(type_col),
-                                                _p(table), _p(bias), t, table.shape[0], _p(ex_rowptr), _p(ex_col), n_keys,
-                                                _p(cand_type), d, slices, _p(rank), _p(bad), _p(ws), ws.numel(), _stream()),
-              "pc_rank_grouped_biased")
-        return rank, bad
-    nbytes = _lib.lib().pc_rank_grouped_workspace_bytes(r, t, slices)
-    ws = workspace(nbytes, proj.device, "rank_grouped")
-    if exclude is not None:
-        row_key, ex_rowptr, ex_col, n_keys = _exclude_args(exclude)
-        _req(cand_type, torch.int32, "cand_type", (table.shape[0],))
-        check(_lib.lib().pc_rank_grouped_excluding(_p(proj), _p(types), _p(targets), _p(row_key), r, _p(type_rowptr), _p(type_col),
-                                                   _p(table), t, table.shape[0], _p(ex_rowptr), _p(ex_col), n_keys,
-                                                   _p(cand_type), d, slices, _p(rank), _p(bad), _p(ws), ws.numel(), _stream()),
-              "pc_rank_grouped_excluding")
-        return rank, bad
-    check(_lib.lib().pc_rank_grouped(_p(proj), _p(types), _p(targets), r, _p(type_rowptr), _p(type_col), _p(table), t,
-                                     table.shape[0], d, slices, _p(rank), _p(bad), _p(ws), ws.numel(), _stream()),
-          "pc_rank_grouped")
+            _req(cand_type, torch.int32, "cand_type", (p,))
+        if bias is None:
+            name, sized_as, bias = "pc_rank_grouped_excluding", "pc_rank_grouped", ()
+        else:
+            name, sized_as, bias = "pc_rank_grouped_biased", None, (_req(bias, torch.float32, "bias", (p,)).data_ptr(),)
+        args = (proj.data_ptr(), types.data_ptr(), targets.data_ptr(), _p(row_key), r, type_rowptr.data_ptr(),
+                type_col.data_ptr(), table.data_ptr(), *bias, t, p, _p(ex_rowptr), _p(ex_col), n_keys, _p(cand_type), d, slices,
+                rank.data_ptr(), bad.data_ptr())
+    _grouped_call(name, "rank_grouped", device, (r, t, slices), args, sized_as)
     return rank, bad
 
 
@@ -2265,12 +2207,7 @@ def cell_means(table, cell_rowptr, cell_col, centroids):
     [P, D] fp32, D 128 or 256; cell_rowptr [C + 1] / cell_col int32 as type_csr makes them of an assignment; centroids [C, D]
     fp32.  One fixed summation order per cell, no atomics: the same bits on every run.  An id outside [0, P) is passed over
     (not summed, not counted in the divisor, not reported).  Returns centroids."""
-    _req(table, torch.float32, "table")
-    if table.dim() != 2:
-        raise ValueError(f"table: expected [P, D], got shape {tuple(table.shape)}")
-    d = _width(table.shape[1])
-    if table.shape[0] < 1:
-        raise ValueError("table: expected at least one row")
+    d = _table_width(table, rows=True)
     _req(centroids, torch.float32, "centroids")
     if centroids.dim() != 2 or centroids.shape[1] != d or centroids.shape[0] < 1:
         raise ValueError(f"centroids: expected [C, {d}] with C >= 1, got shape {tuple(centroids.shape)}")
@@ -2349,10 +2286,7 @@ def build_cell_index(table, n_cells, iters=10, seed=0, init=None, chunk_rows=1 <
     cell_means; an empty cell keeps its centroid); the final centroids get one more assignment, so cell_of is always the
     assignment under the stored centroids.  Every step is bitwise deterministic, so equal arguments give equal bits in every
     field.  Nothing is read back to the host but type_csr's range check of the assignment."""
-    _req(table, torch.float32, "table")
-    if table.dim() != 2:
-        raise ValueError(f"table: expected [P, D], got shape {tuple(table.shape)}")
-    d = _width(table.shape[1])
+    d = _table_width(table)
     p = table.shape[0]
     n_cells, iters, chunk_rows = int(n_cells), int(iters), int(chunk_rows)
     if not 1 <= n_cells <= p:
