@@ -1313,6 +1313,41 @@ int pc_cell_means(const float *table, const int32_t *cell_rowptr, const int32_t 
 int pc_merge_lists(const int32_t *idx, const float *score, int rows, int L, int n, int32_t *out_idx, float *out_score,
                    void *stream);
 
+/* Diversified lists (ABI 8, additive; csrc/diversify.hip; ops.diversify_lists, ops.inv_norm,
+ * PCompanionInference.recommend_diverse_batch): a greedy maximal-marginal-relevance re-rank of a served pool, on the device.
+ *
+ * pc_diversify_lists: idx / score [rows, m], 1 <= m <= 256: a pool of candidates per row as pc_retrieve_list_grouped and
+ * pc_retrieve_topk_grouped return it, in any order.  A slot is no candidate if its id is -1 or its score is not finite,
+ * wherever it stands; a slot whose id lies outside [-1, num_products) is no candidate either, is never dereferenced and adds
+ * one to *bad_count (int32 [1], optional, added to).  table [num_products, dim] fp32, 16-byte aligned, dim 128 or 256; scale
+ * [num_products] fp32 or NULL.  The similarity of two products is
+ *   sim(a, b) = fl(d(a, b) * fl(scale[a] * scale[b]))    (scale == NULL: d(a, b)),
+ * d the fp32 dot product of table[a] and table[b] from zero: four fused-multiply-add chains per 128 dimensions (chain e over
+ * the dimensions 128 h + 4 k + e, k ascending) joined as (c0 + c2) + (c1 + c3), the two halves of a 256-dimension row added
+ * last.  It is symmetric bit for bit, and its order depends on the dimension index alone.  With mu = fl(1 - lam) in fp32, the
+ * rounds t = 0 .. n - 1 give every remaining candidate the value
+ *   v_j = fl(lam * score_j)                               (t = 0),
+ *   v_j = fl(fl(lam * score_j) - fl(mu * pen_j))          (t > 0), pen_j = max of sim(j, i) over the products i picked so far,
+ * three separately rounded operations, and pick the best under (value descending, product index ascending).  out_idx
+ * [rows, n]: the picks in pick order; out_score [rows, n]: each pick's INPUT score; -1 / -inf past the end of a pool with fewer
+ * than n candidates.  Distinct ids within a row are the caller's contract: duplicates are served as separate candidates, and
+ * which of two slots equal in (value, id) is picked is unspecified.  lam = 1 returns the first n of the pool under the total
+ * order -- of a grouped entry's list its own first n, bit for bit --, n = m returns every candidate once, and a permutation of
+ * a row's slots changes no output bit.  One workgroup per row holds the pool's table rows in registers, gathered once;
+ * 64 slots per workgroup for m <= 64, 256 above, the same bits from both.  No workspace, no float atomics, no host readback.
+ * PC_ESHAPE: rows < 0, m outside [1, 256], n outside [1, m], dim not 128 / 256, num_products < 1, lam outside [0, 1] or NaN, a
+ * null idx / score / table / out_idx / out_score, table not 16-byte aligned -- each checked before anything is launched;
+ * rows == 0 succeeds without a launch.
+ *
+ * pc_inv_norm: out[p] = 1 / |table[p]|_2 for p < rows, the scale under which sim is the cosine: the sum of squares in
+ * pc_half_sq_norm_bias's fixed order (16 partial sums over the dimensions 4 l + 64 j + e, met in a butterfly), one correctly
+ * rounded square root, one correctly rounded division; an all-zero row gives 0.  The same bits for every launch geometry and
+ * run.  PC_EINVAL: null pointer, rows <= 0; PC_ESHAPE: dim not 128 / 256, table not 16-byte aligned. */
+int pc_diversify_lists(const int32_t *idx, const float *score, int rows, int m, const float *table, const float *scale,
+                       int num_products, int dim, int n, float lam, int32_t *out_idx, float *out_score, int32_t *bad_count,
+                       void *stream);
+int pc_inv_norm(const float *table, int rows, int dim, float *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -234,6 +234,9 @@ SIGNATURES = {
     # the k-means cell index (csrc/cells.hip; ABI 8, additive)
     "pc_cell_means": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
     "pc_merge_lists": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
+    # diversified lists (csrc/diversify.hip; ABI 8, additive)
+    "pc_diversify_lists": (_i, [_vp, _vp, _i, _i, _vp, _vp, _i, _i, _i, _f, _vp, _vp, _vp, _vp]),
+    "pc_inv_norm": (_i, [_vp, _i, _i, _vp, _vp]),
     "pc_hadamard_forward":(_i, [_vp, _vp, _i, _i, _vp, _vp]),
     "pc_hadamard_forward_dim": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
     "pc_hadamard_backward": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp]),

@@ -16,6 +16,8 @@ set_exclusions / set_eligible keep the query, its co-viewed substitutes and unse
 (pc_retrieve_topk_grouped_excluding / pc_rank_grouped_excluding).
 catalogue= serves the lists of up to 16 from a bf16 copy of the product table (pc_retrieve_topk_grouped_bf16): half the bytes,
 scored against the unrounded query; the scores are those of the ROUNDED table.
+recommend_diverse_batch re-ranks recommend_batch's long list for diversity inside a type, on the device: a greedy maximal-
+marginal-relevance pick of the products to show (pc_diversify_lists over the fp32 features, pc_inv_norm for the cosine).
 
 SimilarProducts is the substitute side: the nearest products of a query under Euclidean distance over any [P, D] fp32 table
 (Product2Vec's export), the grouped retrieval and rank with the per-product term -|e_p|^2 / 2 on the score
@@ -246,6 +248,46 @@ class PCompanionInference(_CandidateFilters):
         else:
             idx, sc = ops.retrieve_topk(*rows, self.features, n)
         return types, idx.reshape(b, k, -1), sc.reshape(b, k, -1)
+
+    _inv_norm = None                           # ops.inv_norm of the fp32 features: recommend_diverse_batch, formed on first use
+
+    @torch.no_grad()
+    def recommend_diverse_batch(self, query_idx: torch.Tensor, num_recommendations: int = 10, pool: int = 64,
+                                diversity: float = 0.3, similarity: str = "cosine"):
+        """recommend_batch's lists re-ranked for diversity inside a type: the pool is recommend_batch(query_idx, pool) itself --
+        its exclusions, eligibility, catalogue and choice of retrieval entry --, and ops.diversify_lists picks the
+        num_recommendations products to show from it by greedy maximal marginal relevance with lam = 1 - diversity: every pick
+        is the best of relevance weighed against its largest similarity to the products already picked.  similarity: "cosine"
+        (the dot product of the fp32 features' rows times ops.inv_norm of both, formed once on first use) or "dot" (no scale).
+        diversity = 0 is recommend_batch(query_idx, num_recommendations), bit for bit, wherever both go through the grouped
+        entries (an uploaded IntBPG without exclusions serves up to 16 through the per-row kernel, whose sums run in another
+        order: there it is the same list up to that kernel's last bits).  Returns recommend_batch's triple
+        (types [B, K], idx [B, K, n], score [B, K, n]): the scores are the pool's relevance scores, in pick order.
+        1 <= num_recommendations <= pool <= ops.DIVERSIFY_MAX_POOL and 0 <= diversity <= 1, checked before the model runs; the
+        similarity reads the fp32 features, so a bf16 catalogue needs a graph that still holds them and bounds the pool at
+        what it serves (16)."""
+        n, pool = int(num_recommendations), int(pool)
+        if not 1 <= n <= pool <= ops.DIVERSIFY_MAX_POOL:
+            raise ValueError(f"recommend_diverse_batch: need 1 <= num_recommendations <= pool <= {ops.DIVERSIFY_MAX_POOL}, got "
+                             f"num_recommendations {n} and pool {pool}")
+        diversity = float(diversity)
+        if not 0.0 <= diversity <= 1.0:
+            raise ValueError(f"recommend_diverse_batch: diversity must be in [0, 1], got {diversity}")
+        if similarity not in ("cosine", "dot"):
+            raise ValueError(f"recommend_diverse_batch: similarity must be 'cosine' or 'dot', got {similarity!r}")
+        table = self.features if self.features is not None else self._graph.get("features")
+        if table is None:
+            raise ValueError("recommend_diverse_batch: the similarity is taken over the fp32 features, and this graph was "
+                             "generated without them (the bf16 catalogue alone cannot serve diversified lists)")
+        types, idx, sc = self.recommend_batch(query_idx, pool)
+        b, k, m = idx.shape
+        scale = None
+        if similarity == "cosine":
+            if self._inv_norm is None:
+                self._inv_norm = ops.inv_norm(table)          # once per catalogue
+            scale = self._inv_norm
+        idx, sc = ops.diversify_lists(idx.reshape(b * k, m), sc.reshape(b * k, m), table, n, 1.0 - diversity, scale=scale)
+        return types, idx.reshape(b, k, n), sc.reshape(b, k, n)
 
     @torch.no_grad()
     def rank_targets(self, query_idx: torch.Tensor, target_idx: torch.Tensor, take: torch.Tensor = None):

@@ -83,6 +83,33 @@ class Metrics:
         return res
 
     @staticmethod
+    def intra_list_similarity(idx: torch.Tensor, table: torch.Tensor, scale: torch.Tensor = None, chunk: int = 4096) -> torch.Tensor:
+        """How alike the products inside a served list are: idx [..., n] product ids (-1: none) as recommend_batch /
+        recommend_diverse_batch / ops.diversify_lists return them, table [P, D], scale [P] or None -> the mean over the lists with
+        at least two products of the list's mean pairwise similarity <table[a], table[b]> scale[a] scale[b] over its distinct
+        pairs (scale = ops.inv_norm(table): the cosine).  A 0-dim float64 tensor where the tensors live (0 when no list holds
+        two products); nothing is read back.  Plain torch in float64, `chunk` lists at a time: a reporting figure, not a
+        serving path."""
+        idx = idx.reshape(-1, idx.shape[-1]).long()
+        total = torch.zeros((), dtype=torch.float64, device=table.device)
+        lists = torch.zeros((), dtype=torch.float64, device=table.device)
+        for lo in range(0, idx.shape[0], int(chunk)):
+            ids = idx[lo:lo + int(chunk)]
+            live = ids >= 0
+            rows = table[ids.clamp(min=0)].double()
+            if scale is not None:
+                rows = rows * scale[ids.clamp(min=0)].double()[..., None]
+            rows = rows * live[..., None]
+            gram = rows @ rows.transpose(1, 2)                                  # [lists, n, n]
+            pair_sum = (gram.sum((1, 2)) - gram.diagonal(dim1=1, dim2=2).sum(1)) / 2
+            k = live.sum(1).double()
+            pairs = k * (k - 1) / 2
+            has = pairs > 0
+            total += torch.where(has, pair_sum / pairs.clamp(min=1), torch.zeros_like(pair_sum)).sum()
+            lists += has.sum()
+        return total / lists.clamp(min=1)
+
+    @staticmethod
     def _fused_refusal(model, data_loader):
         """Why the one-call evaluation (pc_joint_eval_epoch) does not serve (model, data_loader); None: it does."""
         from .data import ComplementaryIndexLoader

@@ -2246,6 +2246,60 @@ def merge_lists(idx, score):
     return out_idx, out_sc
 
 
+DIVERSIFY_MAX_POOL = 256
+
+
+def inv_norm(table):
+    """pc_inv_norm: scale[p] = 1 / |table[p]|_2 for a [P, D] fp32 device table -> [P] fp32, the per-product factor under which
+    diversify_lists' similarity is the cosine; 0 for an all-zero row.  half_sq_norm_bias's fixed summation order, one correctly
+    rounded square root and one correctly rounded division: the same bits on every run.  Once per catalogue."""
+    d = _table_width(table, rows=True)
+    out = torch.empty(table.shape[0], dtype=torch.float32, device=table.device)
+    check(_lib.lib().pc_inv_norm(_p(table), table.shape[0], d, _p(out), _stream()), "pc_inv_norm")
+    return out
+
+
+def diversify_lists(idx, score, table, n, lam, scale=None, bad=None):
+    """pc_diversify_lists: a greedy maximal-marginal-relevance re-rank of a served pool.  idx [R, m] int32 / score [R, m] fp32,
+    1 <= m <= DIVERSIFY_MAX_POOL, as retrieve_list_grouped / retrieve_topk_grouped return them (any order; a slot with id -1 or a
+    score that is not finite is no candidate) -> (idx [R, n] int32, score [R, n] fp32): the n products to show in pick order,
+    each with its INPUT score, -1 / -inf past the end of a pool with fewer than n candidates.  Round 0 picks the best
+    fl(lam * score); every later round the best fl(fl(lam * score_j) - fl((1 - lam) * pen_j)), pen_j the largest similarity of j
+    to a product picked so far, under (value descending, product index ascending).  The similarity is the fp32 dot product of
+    the two rows of table [P, D] (D 128 or 256) in one fixed order, times fl(scale[a] * scale[b]) with scale [P] fp32
+    (inv_norm(table): the cosine); scale=None: the dot product.  lam in [0, 1]: 1 is the pool's own first n, bit for bit.
+    An id outside [-1, P) is no candidate, is never read and is counted in `bad` (a [1] int32 device counter the caller passes to
+    see the count; added to).  Bitwise deterministic; a permutation of a row's slots changes nothing.  Nothing is read back."""
+    _req(idx, torch.int32, "idx")
+    _req(score, torch.float32, "score")
+    if idx.dim() != 2 or tuple(score.shape) != tuple(idx.shape):
+        raise ValueError(f"diversify_lists: expected idx and score of one shape [R, m], got {tuple(idx.shape)} and "
+                         f"{tuple(score.shape)}")
+    r, m = idx.shape
+    if not 1 <= m <= DIVERSIFY_MAX_POOL:
+        raise ValueError(f"diversify_lists: the pool m must be in [1, {DIVERSIFY_MAX_POOL}], got {m}")
+    n = int(n)
+    if not 1 <= n <= m:
+        raise ValueError(f"diversify_lists: n must be in [1, m = {m}], got {n}")
+    lam = float(lam)
+    if not 0.0 <= lam <= 1.0:                             # (a NaN fails the comparison)
+        raise ValueError(f"diversify_lists: lam must be in [0, 1], got {lam}")
+    d = _table_width(table, rows=True)
+    if scale is not None:
+        if not isinstance(scale, torch.Tensor):
+            raise ValueError(f"diversify_lists: scale must be a [P] float32 device tensor, got {type(scale).__name__}")
+        _req(scale, torch.float32, "scale", (table.shape[0],))
+    if bad is not None:
+        _req(bad, torch.int32, "bad", (1,))
+    out_idx = torch.empty(r, n, dtype=torch.int32, device=idx.device)
+    out_sc = torch.empty(r, n, dtype=torch.float32, device=idx.device)
+    if r == 0:
+        return out_idx, out_sc
+    check(_lib.lib().pc_diversify_lists(_p(idx), _p(score), r, m, _p(table), _p(scale), table.shape[0], d, n, lam, _p(out_idx),
+                                        _p(out_sc), _p(bad), _stream()), "pc_diversify_lists")
+    return out_idx, out_sc
+
+
 class CellIndex:
     """A k-means cell index over a [P, D] table (build_cell_index): centroids [C, D] fp32, centroid_bias [C] fp32 =
     half_sq_norm_bias(centroids), cell_of [P] int32 = the assignment under THESE centroids, cell_rowptr [C + 1] / cell_col [P]
