@@ -1348,6 +1348,42 @@ int pc_diversify_lists(const int32_t *idx, const float *score, int rows, int m, 
                        void *stream);
 int pc_inv_norm(const float *table, int rows, int dim, float *out, void *stream);
 
+/* Long and diversified lists from the bf16 copy alone (ABI 8, additive; csrc/retrieve_list_bf16.hip, csrc/diversify.hip;
+ * ops.CompactCatalogue, PCompanionInference(..., catalogue=ops.CompactCatalogue(...))): a server that shows a page of 50 to 200
+ * products per type, or a diversified row, without the fp32 table in HBM.  table_bf16 [num_products, dim] everywhere: bf16 bit
+ * patterns, row-major, 16-byte aligned, dim 128 or 256 (pc_retrieve_topk_grouped_bf16's table).
+ *
+ * pc_retrieve_list_grouped_bf16: pc_retrieve_list_grouped's contract and argument list for 1 <= n <= 256 -- out_idx / out_score
+ * [rows, n] = the first n products of type types[r] that are not in the list of row_key[r] (row_key == NULL: no lists), -1 /
+ * -inf past the end -- over table_bf16.  The score of a (row, product) pair is formed through pc_retrieve_topk_grouped_bf16's
+ * own chain (the unrounded fp32 query split into three bf16 pieces, k-block by k-block on v_mfma_f32_16x16x32_bf16 into one
+ * accumulator) and has that entry's bits; the selection is pc_retrieve_list_grouped's (a row's unsorted candidate buffer and
+ * threshold on chip, compacted by a sorting network, the slices' sorted partial lists merged by one wave per row), every step
+ * under the total order (score descending, product index ascending).  For n <= 16 the output is
+ * pc_retrieve_topk_grouped_bf16's bit for bit; for every n it does not depend on `slices`, on the placement of the rows or on
+ * the order of type_col inside a type.  A key outside [-1, n_keys) is served as -1, never indexes memory and is counted in
+ * *bad_count (required with row_key; added to).  No float atomics, no host readback; the workspace
+ * (pc_retrieve_list_grouped_bf16_workspace_bytes, 0 for arguments out of range) is pc_retrieve_list_grouped's size.
+ * PC_EINVAL: null pointer, rows or n_types <= 0; with row_key a null ex_rowptr / ex_col / bad_count or n_keys < 0; without it a
+ * list or n_keys != 0; PC_ESHAPE: n outside [1, 256], dim not 128 / 256, slices outside [0, 64], table_bf16 not 16-byte
+ * aligned; PC_EWORKSPACE: ws_bytes too small -- each checked before anything is launched.
+ *
+ * pc_diversify_lists_bf16 / pc_inv_norm_bf16: pc_diversify_lists' / pc_inv_norm's contracts and return codes over table_bf16.
+ * The result is, bit for bit, what the fp32 entry returns on the widened table (every bf16 value is an fp32 value): the rows
+ * are widened as they are gathered, and the dot product's chains, the similarity, the rounds' values, the pick rule and the
+ * norm's summation order are the fp32 entries' own code.  scale is fp32 [num_products] or NULL as there (pc_inv_norm_bf16 of
+ * the same table: the cosine between the rows that are stored). */
+size_t pc_retrieve_list_grouped_bf16_workspace_bytes(int rows, int n_types, int n, int slices);
+int pc_retrieve_list_grouped_bf16(const float *proj, const int32_t *types, const int32_t *row_key, int rows,
+                                  const int32_t *type_rowptr, const int32_t *type_col, const uint16_t *table_bf16,
+                                  int n_types, const int32_t *ex_rowptr, const int32_t *ex_col, int n_keys, int n, int dim,
+                                  int slices, int32_t *out_idx, float *out_score, int32_t *bad_count, void *ws,
+                                  size_t ws_bytes, void *stream);
+int pc_diversify_lists_bf16(const int32_t *idx, const float *score, int rows, int m, const uint16_t *table_bf16,
+                            const float *scale, int num_products, int dim, int n, float lam, int32_t *out_idx,
+                            float *out_score, int32_t *bad_count, void *stream);
+int pc_inv_norm_bf16(const uint16_t *table_bf16, int rows, int dim, float *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

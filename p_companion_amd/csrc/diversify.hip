@@ -28,6 +28,14 @@
 //                takes a second lane per slot rather than 256 registers per lane (which leaves no register for anything else
 //                without the accumulation file) or a re-read of the pool's rows through L2 in every round (n times the
 //                gather's bytes): a lane's registers and code are those of D = 128.
+//   bf16 table   pc_diversify_lists_bf16 / pc_inv_norm_bf16 read the [P, D] bf16 copy of the catalogue (ops.CompactCatalogue)
+//                and return, bit for bit, what the fp32 entries return on the widened table: widening bf16 -> fp32 is exact,
+//                and everything after the gather -- dv_dot, dv_sim, dv_value, the pick rule, the norm's summation order -- is
+//                the same code on the same fp32 registers.  The kernels are templated on the table's element type; only the
+//                gather differs.  A lane's part is 256 bytes: 16 lanes fetch it together (16-byte loads, FOUR whole parts per
+//                wave instruction), the bf16 patterns are staged in the same per-wave LDS rows -- two parts side by side in a
+//                row, so 32 lanes' parts per pass and as many loads in flight as the fp32 gather has -- and widened at the
+//                read-back.
 // No workspace, no float atomics (one integer atomic per id out of range), nothing read back.
 #include "common.h"
 #include "grouped_select.h"        // rg_better, RG_NONE, RG_MAX_GRID
@@ -38,6 +46,12 @@
 #define DV_ST (DV_PART + 4)        // a staging row in LDS, padded: 16 lanes read 16 rows without a bank conflict
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+
+// bf16 -> fp32, exact: the pattern is the upper half of the fp32 pattern.  Two packed elements: the lower address in the low half.
+__device__ __forceinline__ float dv_widen_lo(unsigned w) { return __builtin_bit_cast(float, w << 16); }
+__device__ __forceinline__ float dv_widen_hi(unsigned w) { return __builtin_bit_cast(float, w & 0xffff0000u); }
 
 // The dot product of a lane's part x of its slot's row with the same part of the picked row (LDS, every lane of a part reads
 // the same address), then the parts' sums.  LPS = D / 128 lanes per slot, adjacent.  The four chains are written as two
@@ -78,11 +92,12 @@ __device__ __forceinline__ float dv_value(float ls, float mu, float pen, bool fi
     return v == v ? v : -INFINITY;                        // (a NaN -- a non-finite table row -- ranks last, not nowhere)
 }
 
-// CAP slots, LPS lanes per slot: CAP * LPS threads.  mu = fl(1 - lam), formed on the host.
-template <int D, int CAP>
+// CAP slots, LPS lanes per slot: CAP * LPS threads.  mu = fl(1 - lam), formed on the host.  T: the table's element type, float
+// or uint16_t (bf16 patterns).
+template <int D, int CAP, typename T>
 __global__ __launch_bounds__(CAP * (D / DV_PART)) void dv_mmr_kernel(const int32_t* __restrict__ idx,
                                                                      const float* __restrict__ score, int rows, int m,
-                                                                     const float* __restrict__ table,
+                                                                     const T* __restrict__ table,
                                                                      const float* __restrict__ scale, int num_products, int n,
                                                                      float lam, float mu, int32_t* __restrict__ out_idx,
                                                                      float* __restrict__ out_score,
@@ -121,7 +136,7 @@ __global__ __launch_bounds__(CAP * (D / DV_PART)) void dv_mmr_kernel(const int32
         // reads two whole parts, 1 KB, not 16 bytes of 64 different rows), 16 lanes' parts per pass, and come back from LDS
         // one row per lane.  Same-wave LDS instructions execute in order: no barrier between the store and the read-back.
         f32x4 x[DV_NB];
-        {
+        if constexpr (std::is_same<T, float>::value) {
             float(*st)[DV_ST] = stage[wave];
             const int half = lane >> 5, chunk = lane & 31;
 #pragma unroll
@@ -141,6 +156,38 @@ __global__ __launch_bounds__(CAP * (D / DV_PART)) void dv_mmr_kernel(const int32
                 for (int k = 0; k < DV_NB; k++) {
                     const f32x4 z = *reinterpret_cast<const f32x4*>(&st[lane & 15][4 * k]);
                     x[k] = (mine || p == 0) ? z : x[k];
+                }
+                __builtin_amdgcn_wave_barrier();
+            }
+        } else {
+            // bf16: a part is 256 bytes, fetched by 16 lanes at once (a wave instruction reads four whole parts); staging row
+            // o & 15 holds the parts of the pass's owners o and o + 16 side by side (2 x 256 of its 528 bytes), so a pass
+            // serves 32 lanes.  A lane reads its part back as 16 operands of 8 bf16 and widens them: x[k] holds the dimensions
+            // 4 k .. 4 k + 3 of the part, as from the fp32 table.
+            float(*st)[DV_ST] = stage[wave];
+            const int quarter = lane >> 4, chunk = lane & 15;
+#pragma unroll
+            for (int p = 0; p < 2; p++) {
+                u32x4 y[8];
+#pragma unroll
+                for (int i = 0; i < 8; i++) {
+                    const int owner = 32 * p + 4 * i + quarter;                 // the lane whose part this is (64 % LPS == 0)
+                    const int orow = __shfl(row, owner, 64);
+                    y[i] = *reinterpret_cast<const u32x4*>(table + (size_t)orow * D + (owner % LPS) * DV_PART + 8 * chunk);
+                }
+#pragma unroll
+                for (int i = 0; i < 8; i++) {
+                    const int o = 4 * i + quarter;                              // the owner within the pass: row o & 15, half o >> 4
+                    *reinterpret_cast<u32x4*>(&st[o & 15][64 * (o >> 4) + 4 * chunk]) = y[i];
+                }
+                __builtin_amdgcn_wave_barrier();
+                if ((lane >> 5) == p) {                   // (every lane belongs to exactly one pass: x is written once)
+#pragma unroll
+                    for (int k = 0; k < DV_NB / 2; k++) {
+                        const u32x4 z = *reinterpret_cast<const u32x4*>(&st[lane & 15][64 * ((lane >> 4) & 1) + 4 * k]);
+                        x[2 * k] = f32x4{dv_widen_lo(z.x), dv_widen_hi(z.x), dv_widen_lo(z.y), dv_widen_hi(z.y)};
+                        x[2 * k + 1] = f32x4{dv_widen_lo(z.z), dv_widen_hi(z.z), dv_widen_lo(z.w), dv_widen_hi(z.w)};
+                    }
                 }
                 __builtin_amdgcn_wave_barrier();
             }
@@ -205,15 +252,25 @@ __global__ __launch_bounds__(CAP * (D / DV_PART)) void dv_mmr_kernel(const int32
 // .. (dimensions 4 l + 64 j + e, j ascending, e ascending) into one fp32 sum by fused multiply-add, starting from zero; the 16
 // sums meet in a butterfly over the lane distances 8, 4, 2, 1 (every lane of the group holds the same bits).  Then one
 // correctly rounded square root and one correctly rounded division.  No atomics; a row's value does not depend on the grid.
-template <int D>
-__global__ __launch_bounds__(256) void dv_inv_norm_kernel(const float* __restrict__ table, int rows, float* __restrict__ out) {
+// T = uint16_t: the same four dimensions are 8 bytes of bf16 patterns, widened (exactly) before the sum.
+template <int D, typename T>
+__global__ __launch_bounds__(256) void dv_inv_norm_kernel(const T* __restrict__ table, int rows, float* __restrict__ out) {
     const int l = threadIdx.x & 15;
     const int64_t stride = (int64_t)gridDim.x * 16;
     for (int64_t p = (int64_t)blockIdx.x * 16 + (threadIdx.x >> 4); p < rows; p += stride) {
-        const float4* f = reinterpret_cast<const float4*>(table + (size_t)p * D) + l;
         float4 x[D / 64];
+        if constexpr (std::is_same<T, float>::value) {
+            const float4* f = reinterpret_cast<const float4*>(table + (size_t)p * D) + l;
 #pragma unroll
-        for (int j = 0; j < D / 64; j++) x[j] = f[16 * j];
+            for (int j = 0; j < D / 64; j++) x[j] = f[16 * j];
+        } else {
+            const u32x2* f = reinterpret_cast<const u32x2*>(table + (size_t)p * D) + l;
+#pragma unroll
+            for (int j = 0; j < D / 64; j++) {
+                const u32x2 z = f[16 * j];
+                x[j] = make_float4(dv_widen_lo(z.x), dv_widen_hi(z.x), dv_widen_lo(z.y), dv_widen_hi(z.y));
+            }
+        }
         float s = 0.f;
 #pragma unroll
         for (int j = 0; j < D / 64; j++) {
@@ -229,19 +286,21 @@ __global__ __launch_bounds__(256) void dv_inv_norm_kernel(const float* __restric
     }
 }
 
-extern "C" int pc_inv_norm(const float* table, int rows, int dim, float* out, void* stream) {
+namespace {
+template <typename T>
+int dv_inv_norm(const T* table, int rows, int dim, float* out, void* stream) {
     if (!table || !out || rows <= 0) return PC_EINVAL;
     if ((dim != 128 && dim != 256) || ((uintptr_t)table & 15)) return PC_ESHAPE;
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid((unsigned)min((rows + 15) / 16, RG_MAX_GRID));        // 16 rows per workgroup and pass, grid-stride
-    if (dim == 128) PC_LAUNCH(dv_inv_norm_kernel<128>, grid, dim3(256), 0, st, table, rows, out);
-    else PC_LAUNCH(dv_inv_norm_kernel<256>, grid, dim3(256), 0, st, table, rows, out);
+    if (dim == 128) PC_LAUNCH((dv_inv_norm_kernel<128, T>), grid, dim3(256), 0, st, table, rows, out);
+    else PC_LAUNCH((dv_inv_norm_kernel<256, T>), grid, dim3(256), 0, st, table, rows, out);
     return pc_launch_status();
 }
 
-extern "C" int pc_diversify_lists(const int32_t* idx, const float* score, int rows, int m, const float* table, const float* scale,
-                                  int num_products, int dim, int n, float lam, int32_t* out_idx, float* out_score,
-                                  int32_t* bad_count, void* stream) {
+template <typename T>
+int dv_diversify(const int32_t* idx, const float* score, int rows, int m, const T* table, const float* scale, int num_products,
+                 int dim, int n, float lam, int32_t* out_idx, float* out_score, int32_t* bad_count, void* stream) {
     if (rows < 0 || m < 1 || m > DV_MAX_POOL || n < 1 || n > m || (dim != 128 && dim != 256) || num_products < 1) return PC_ESHAPE;
     if (!(lam >= 0.f && lam <= 1.f)) return PC_ESHAPE;                     // (a NaN fails both comparisons)
     if (rows == 0) return PC_OK;                                          // nothing to serve: no launch, no pointer is read
@@ -250,8 +309,8 @@ extern "C" int pc_diversify_lists(const int32_t* idx, const float* score, int ro
     const float mu = 1.0f - lam;                                          // fl(1 - lam)
     const dim3 grid((unsigned)min(rows, RG_MAX_GRID));                    // one row per workgroup and pass: never more than rows
 #define DV_MMR(D, CAP)                                                                                                          \
-    PC_LAUNCH((dv_mmr_kernel<D, CAP>), grid, dim3(CAP * (D / DV_PART)), 0, st, idx, score, rows, m, table, scale, num_products, \
-              n, lam, mu, out_idx, out_score, bad_count)
+    PC_LAUNCH((dv_mmr_kernel<D, CAP, T>), grid, dim3(CAP * (D / DV_PART)), 0, st, idx, score, rows, m, table, scale,            \
+              num_products, n, lam, mu, out_idx, out_score, bad_count)
     if (dim == 128) {
         if (m <= 64) DV_MMR(128, 64); else DV_MMR(128, 256);
     } else {
@@ -259,4 +318,25 @@ extern "C" int pc_diversify_lists(const int32_t* idx, const float* score, int ro
     }
 #undef DV_MMR
     return pc_launch_status();
+}
+}  // namespace
+
+extern "C" int pc_inv_norm(const float* table, int rows, int dim, float* out, void* stream) {
+    return dv_inv_norm(table, rows, dim, out, stream);
+}
+
+extern "C" int pc_inv_norm_bf16(const uint16_t* table_bf16, int rows, int dim, float* out, void* stream) {
+    return dv_inv_norm(table_bf16, rows, dim, out, stream);
+}
+
+extern "C" int pc_diversify_lists(const int32_t* idx, const float* score, int rows, int m, const float* table, const float* scale,
+                                  int num_products, int dim, int n, float lam, int32_t* out_idx, float* out_score,
+                                  int32_t* bad_count, void* stream) {
+    return dv_diversify(idx, score, rows, m, table, scale, num_products, dim, n, lam, out_idx, out_score, bad_count, stream);
+}
+
+extern "C" int pc_diversify_lists_bf16(const int32_t* idx, const float* score, int rows, int m, const uint16_t* table_bf16,
+                                       const float* scale, int num_products, int dim, int n, float lam, int32_t* out_idx,
+                                       float* out_score, int32_t* bad_count, void* stream) {
+    return dv_diversify(idx, score, rows, m, table_bf16, scale, num_products, dim, n, lam, out_idx, out_score, bad_count, stream);
 }

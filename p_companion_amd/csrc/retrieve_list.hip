@@ -25,12 +25,7 @@
 #include "common.h"
 #include "grouped_select.h"        // the item decode
 #include "wave_sort.h"                 // rl_sort: the bitonic network (shared with ingest.hip)
-
-#define RL_MAX_N 256
-#define RL_N2 32                   // n up to here: 128 buffer entries per row (NE = 2); a compacted row has 32 entries of slack
-#define RL_N4 96                   // n up to here: 256 entries (NE = 4), 96 of slack; above: RL_CAP (NE = 8), 128 at n = 256
-#define RL_TM 16                   // rows per tile
-#define RL_CAP 448                 // buffer entries per row of the long variant: n + three chunks at n = 256
+#include "grouped_list.h"              // the RL_* sizes, rl_merge_launch (shared with retrieve_list_bf16.hip)
 
 // Work item w = (type t, slice s, tile j) as in rg_score_kernel.  Lane l of wave wv: column c = l & 15 (candidate
 // wv * 16 + c of the chunk, query row c of the A operand), k-lane h = l >> 4.  In the selection thread tid serves row
@@ -258,6 +253,12 @@ __global__ __launch_bounds__(256) void rl_merge_kernel(const int32_t* __restrict
     }
 }
 
+void rl_merge_launch(const RgWs& w, const int32_t* types, int rows, const int32_t* type_rowptr, int n_types, int n, int S,
+                     int32_t* out_idx, float* out_score, hipStream_t st) {
+    PC_LAUNCH(rl_merge_kernel, dim3((rows + 3) / 4), dim3(256), 0, st, types, rows, type_rowptr, n_types, n, S, w.plan.pos,
+              w.plan.row_start, w.pv, w.pi, out_idx, out_score);
+}
+
 namespace {
 template <int D, int NE>
 void rl_launch_score(dim3 grid, hipStream_t st, const float* proj, const int32_t* type_rowptr, const int32_t* type_col,
@@ -291,7 +292,6 @@ extern "C" int pc_retrieve_list_grouped(const float* proj, const int32_t* types,
     RgWs w;
     unsigned grid;
     PC_TRY(rg_begin(w, grid, ws, ws_bytes, types, nullptr, rows, type_rowptr, n_types, 0, n, S, RL_TM, nullptr, nullptr, st));
-    const RgPlan& pl = w.plan;
 #define RL_SCORE(D, NE) \
     rl_launch_score<D, NE>(dim3(grid), st, proj, type_rowptr, type_col, table, n_types, n, S, w, row_key, rows, ex_rowptr, ex_col, n_keys, bad_count)
     if (dim == 128) {
@@ -304,8 +304,7 @@ extern "C" int pc_retrieve_list_grouped(const float* proj, const int32_t* types,
         else RL_SCORE(256, 8);
     }
 #undef RL_SCORE
-    PC_LAUNCH(rl_merge_kernel, dim3((rows + 3) / 4), dim3(256), 0, st, types, rows, type_rowptr, n_types, n, S, pl.pos,
-              pl.row_start, w.pv, w.pi, out_idx, out_score);
+    rl_merge_launch(w, types, rows, type_rowptr, n_types, n, S, out_idx, out_score, st);
     return pc_launch_status();
 }
 

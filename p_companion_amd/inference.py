@@ -18,6 +18,8 @@ catalogue= serves the lists of up to 16 from a bf16 copy of the product table (p
 scored against the unrounded query; the scores are those of the ROUNDED table.
 recommend_diverse_batch re-ranks recommend_batch's long list for diversity inside a type, on the device: a greedy maximal-
 marginal-relevance pick of the products to show (pc_diversify_lists over the fp32 features, pc_inv_norm for the cosine).
+catalogue=ops.CompactCatalogue(...) serves both from the bf16 copy alone -- lists of up to 256 (pc_retrieve_list_grouped_bf16)
+and diversified lists (pc_diversify_lists_bf16, pc_inv_norm_bf16); ranks still need the fp32 catalogue.
 
 SimilarProducts is the substitute side: the nearest products of a query under Euclidean distance over any [P, D] fp32 table
 (Product2Vec's export), the grouped retrieval and rank with the per-product term -|e_p|^2 / 2 on the score
@@ -117,6 +119,8 @@ class _CandidateFilters:
 
 class PCompanionInference(_CandidateFilters):
     catalogue = None                           # the bf16 copy that is served from (__init__: catalogue=); None: the fp32 features
+    compact = None                             # the ops.CompactCatalogue behind `catalogue`, where one was given: long and
+    #                                            diversified lists from the bf16 copy (None: today's bf16 / fp32 branches)
 
     def __init__(self, model, config, bpg: IntBPG, product_ids: List[str] = None, catalogue=None):
         """model: a trained PCompanion, or the path of a best_model.pth written by train.train
@@ -133,11 +137,19 @@ class PCompanionInference(_CandidateFilters):
         With a bf16 catalogue recommend_batch (up to 16 per type) and recommend go through pc_retrieve_topk_grouped_bf16 for
         every kind of graph: the unrounded projected query against the ROUNDED table, so a list can differ from the fp32
         catalogue's where two products lie within bf16 rounding of each other.  set_exclusions / set_eligible work unchanged;
-        lists above 16, rank_targets and evaluate_catalogue need the fp32 catalogue and raise ValueError."""
+        lists above 16, rank_targets and evaluate_catalogue need the fp32 catalogue and raise ValueError.
+          an ops.CompactCatalogue: its .table is the catalogue, checked and accepted as a given tensor is (a DeviceBPG
+                          without features too), and the bf16 copy is then all this object needs for what it SERVES:
+                          recommend_batch up to 16 as above (the same bits), from 17 to 256 through
+                          pc_retrieve_list_grouped_bf16, and recommend_diverse_batch with its similarity over the bf16 rows
+                          (pc_diversify_lists_bf16; the cosine from the object's .inv_norm) -- no fp32 features are read.
+                          rank_targets and evaluate_catalogue still need the fp32 catalogue and raise ValueError."""
         self.config = config
         self.device = config.DEVICE
         self.bpg = bpg
         self.grouped = isinstance(bpg, DeviceBPG)
+        if isinstance(catalogue, ops.CompactCatalogue):
+            self.compact, catalogue = catalogue, catalogue.table
         given = torch.is_tensor(catalogue)
         if catalogue is not None and catalogue is not torch.bfloat16 and not given:
             raise ValueError(f"PCompanionInference: catalogue must be None (the fp32 features), torch.bfloat16 or a [P, D] "
@@ -224,9 +236,10 @@ class PCompanionInference(_CandidateFilters):
         """All queries at once.  Returns complementary_types [B,K] int64, product indices [B,K,n] int32
         (-1 past the end of a short type) and scores [B,K,n].  Up to 16 recommendations: the entries with a sorted list per
         thread; from 17 to ops.RETRIEVE_LIST_MAX_N (256): pc_retrieve_list_grouped, whatever the graph's kind -- an uploaded
-        IntBPG's arrays are on the device, and the per-row kernel stops at 16."""
+        IntBPG's arrays are on the device, and the per-row kernel stops at 16.  A bf16 catalogue serves up to 16
+        (pc_retrieve_topk_grouped_bf16); given as an ops.CompactCatalogue also 17 to 256 (pc_retrieve_list_grouped_bf16)."""
         n = self._list_length(num_recommendations)
-        if self.catalogue is not None and n > 16:
+        if self.catalogue is not None and n > 16 and self.compact is None:
             raise ValueError(f"recommend_batch: a bf16 catalogue serves at most 16 recommendations per (query, type), got {n}; "
                              "longer lists need the fp32 catalogue (catalogue=None)")
         query_idx = query_idx.to(self.device).to(torch.int32).contiguous()
@@ -238,7 +251,9 @@ class PCompanionInference(_CandidateFilters):
         row_types = types.to(torch.int32).reshape(-1).contiguous()
         exclude = self._exclude_rows(query_idx, k)
         rows = (proj, row_types, self.type_rowptr, self.type_col)
-        if self.catalogue is not None:                    # (n <= 16) the bf16 entry, whatever the graph's kind
+        if self.catalogue is not None and n > 16:         # (a CompactCatalogue) the bf16 list entry
+            idx, sc = ops.retrieve_list_grouped(*rows, self.catalogue, n, exclude=exclude)
+        elif self.catalogue is not None:                  # (n <= 16) the bf16 entry, whatever the graph's kind
             idx, sc = ops.retrieve_topk_grouped(*rows, self.catalogue, n, exclude=exclude)
         elif n > 16:                                      # (RG_MAX_N / RMAX_N: the entries below refuse 17)
             idx, sc = ops.retrieve_list_grouped(*rows, self.features, n, exclude=exclude)
@@ -265,7 +280,9 @@ class PCompanionInference(_CandidateFilters):
         (types [B, K], idx [B, K, n], score [B, K, n]): the scores are the pool's relevance scores, in pick order.
         1 <= num_recommendations <= pool <= ops.DIVERSIFY_MAX_POOL and 0 <= diversity <= 1, checked before the model runs; the
         similarity reads the fp32 features, so a bf16 catalogue needs a graph that still holds them and bounds the pool at
-        what it serves (16)."""
+        what it serves (16).  With an ops.CompactCatalogue neither holds: the pool (up to 256) and the similarity both come from
+        the bf16 rows (ops.diversify_lists_bf16; "cosine": the catalogue's .inv_norm, the factors of the rounded rows), and the
+        result is bit for bit ops.diversify_lists over the widened table."""
         n, pool = int(num_recommendations), int(pool)
         if not 1 <= n <= pool <= ops.DIVERSIFY_MAX_POOL:
             raise ValueError(f"recommend_diverse_batch: need 1 <= num_recommendations <= pool <= {ops.DIVERSIFY_MAX_POOL}, got "
@@ -275,6 +292,12 @@ class PCompanionInference(_CandidateFilters):
             raise ValueError(f"recommend_diverse_batch: diversity must be in [0, 1], got {diversity}")
         if similarity not in ("cosine", "dot"):
             raise ValueError(f"recommend_diverse_batch: similarity must be 'cosine' or 'dot', got {similarity!r}")
+        if self.compact is not None:                      # pool and similarity from the bf16 copy alone
+            types, idx, sc = self.recommend_batch(query_idx, pool)
+            b, k, m = idx.shape
+            idx, sc = ops.diversify_lists_bf16(idx.reshape(b * k, m), sc.reshape(b * k, m), self.catalogue, n, 1.0 - diversity,
+                                               scale=self.compact.inv_norm if similarity == "cosine" else None)
+            return types, idx.reshape(b, k, n), sc.reshape(b, k, n)
         table = self.features if self.features is not None else self._graph.get("features")
         if table is None:
             raise ValueError("recommend_diverse_batch: the similarity is taken over the fp32 features, and this graph was "

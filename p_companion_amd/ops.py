@@ -1919,9 +1919,9 @@ def retrieve_topk(proj, types, type_rowptr, type_col, table, n):
 RETRIEVE_MAX_SLICES = 64
 
 
-def _table_width(table, name="table", rows=False):
-    """D of a [P, D] fp32 device table, D 128 or 256 (rows: P >= 1 too)."""
-    _req(table, torch.float32, name)
+def _table_width(table, name="table", rows=False, dtype=torch.float32):
+    """D of a [P, D] fp32 device table (dtype: of another element type), D 128 or 256 (rows: P >= 1 too)."""
+    _req(table, dtype, name)
     if table.dim() != 2:
         raise ValueError(f"{name}: expected [P, D], got shape {tuple(table.shape)}")
     d = _width(table.shape[1])
@@ -2082,12 +2082,17 @@ def retrieve_list_grouped(proj, types, type_rowptr, type_col, table, n, slices=0
     unsorted candidate buffer and a threshold on chip in place of the per-thread lists of 16.  Bitwise deterministic, the same
     bits for every `slices`, and for n <= 16 retrieve_topk_grouped's own bits.  Nothing is read back to the host.
     exclude = (row_key [R] int32, ex_rowptr [n_keys + 1] int32, ex_col [E] int32) and `bad` as in retrieve_topk_grouped: the
-    first n products of the type that are NOT in the list of row_key[r].  exclude=None: the unfiltered list."""
+    first n products of the type that are NOT in the list of row_key[r].  exclude=None: the unfiltered list.
+    table: [P, D] fp32, or the [P, D] torch.bfloat16 copy catalogue_bf16 makes of it: pc_retrieve_list_grouped_bf16 -- the same
+    contract, selection and determinism over half the bytes, the scores formed through retrieve_topk_grouped's bf16 chain (the
+    unrounded proj against the ROUNDED table): for n <= 16 that call's own bits."""
     n = int(n)
     if not 1 <= n <= RETRIEVE_LIST_MAX_N:
         raise ValueError(f"retrieve_list_grouped: n must be in [1, {RETRIEVE_LIST_MAX_N}], got {n}")
-    return _retrieve_grouped("pc_retrieve_list_grouped", proj, types, type_rowptr, type_col, table, n, slices, exclude, bad,
-                             what="retrieve_list_grouped", tag="retrieve_list")
+    bf16 = isinstance(table, torch.Tensor) and table.dtype == torch.bfloat16
+    return _retrieve_grouped("pc_retrieve_list_grouped_bf16" if bf16 else "pc_retrieve_list_grouped", proj, types, type_rowptr,
+                             type_col, table, n, slices, exclude, bad, what="retrieve_list_grouped", tag="retrieve_list",
+                             table_dtype=torch.bfloat16 if bf16 else torch.float32)
 
 
 def rank_grouped(proj, types, targets, type_rowptr, type_col, table, slices=0, bad=None, exclude=None, cand_type=None,
@@ -2253,9 +2258,19 @@ def inv_norm(table):
     """pc_inv_norm: scale[p] = 1 / |table[p]|_2 for a [P, D] fp32 device table -> [P] fp32, the per-product factor under which
     diversify_lists' similarity is the cosine; 0 for an all-zero row.  half_sq_norm_bias's fixed summation order, one correctly
     rounded square root and one correctly rounded division: the same bits on every run.  Once per catalogue."""
-    d = _table_width(table, rows=True)
+    return _inv_norm("pc_inv_norm", table, torch.float32)
+
+
+def inv_norm_bf16(table):
+    """pc_inv_norm_bf16: inv_norm for the [P, D] torch.bfloat16 copy of a catalogue (catalogue_bf16) -> [P] fp32: the factors
+    of the ROUNDED rows, bit for bit inv_norm(table.float()), without the fp32 table ever being formed."""
+    return _inv_norm("pc_inv_norm_bf16", table, torch.bfloat16)
+
+
+def _inv_norm(name, table, dtype):
+    d = _table_width(table, rows=True, dtype=dtype)
     out = torch.empty(table.shape[0], dtype=torch.float32, device=table.device)
-    check(_lib.lib().pc_inv_norm(_p(table), table.shape[0], d, _p(out), _stream()), "pc_inv_norm")
+    check(getattr(_lib.lib(), name)(_p(table), table.shape[0], d, _p(out), _stream()), name)
     return out
 
 
@@ -2270,24 +2285,38 @@ def diversify_lists(idx, score, table, n, lam, scale=None, bad=None):
     (inv_norm(table): the cosine); scale=None: the dot product.  lam in [0, 1]: 1 is the pool's own first n, bit for bit.
     An id outside [-1, P) is no candidate, is never read and is counted in `bad` (a [1] int32 device counter the caller passes to
     see the count; added to).  Bitwise deterministic; a permutation of a row's slots changes nothing.  Nothing is read back."""
+    return _diversify("diversify_lists", "pc_diversify_lists", torch.float32, idx, score, table, n, lam, scale, bad)
+
+
+def diversify_lists_bf16(idx, score, table, n, lam, scale=None, bad=None):
+    """pc_diversify_lists_bf16: diversify_lists over the [P, D] torch.bfloat16 copy of a catalogue (catalogue_bf16; a
+    CompactCatalogue's .table).  The similarity is taken between the ROUNDED rows, and the result is bit for bit
+    diversify_lists(idx, score, table.float(), ...): the rows are widened (exactly) as they are gathered and everything behind
+    the gather is the same code.  scale [P] fp32 as there (inv_norm_bf16(table): the cosine) or None.  A function of its own:
+    diversify_lists refuses a bf16 table."""
+    return _diversify("diversify_lists_bf16", "pc_diversify_lists_bf16", torch.bfloat16, idx, score, table, n, lam, scale, bad)
+
+
+def _diversify(what, name, dtype, idx, score, table, n, lam, scale, bad):
+    """diversify_lists / diversify_lists_bf16 behind the choice of the entry: the checks (host side alone), then the call."""
     _req(idx, torch.int32, "idx")
     _req(score, torch.float32, "score")
     if idx.dim() != 2 or tuple(score.shape) != tuple(idx.shape):
-        raise ValueError(f"diversify_lists: expected idx and score of one shape [R, m], got {tuple(idx.shape)} and "
+        raise ValueError(f"{what}: expected idx and score of one shape [R, m], got {tuple(idx.shape)} and "
                          f"{tuple(score.shape)}")
     r, m = idx.shape
     if not 1 <= m <= DIVERSIFY_MAX_POOL:
-        raise ValueError(f"diversify_lists: the pool m must be in [1, {DIVERSIFY_MAX_POOL}], got {m}")
+        raise ValueError(f"{what}: the pool m must be in [1, {DIVERSIFY_MAX_POOL}], got {m}")
     n = int(n)
     if not 1 <= n <= m:
-        raise ValueError(f"diversify_lists: n must be in [1, m = {m}], got {n}")
+        raise ValueError(f"{what}: n must be in [1, m = {m}], got {n}")
     lam = float(lam)
     if not 0.0 <= lam <= 1.0:                             # (a NaN fails the comparison)
-        raise ValueError(f"diversify_lists: lam must be in [0, 1], got {lam}")
-    d = _table_width(table, rows=True)
+        raise ValueError(f"{what}: lam must be in [0, 1], got {lam}")
+    d = _table_width(table, rows=True, dtype=dtype)
     if scale is not None:
         if not isinstance(scale, torch.Tensor):
-            raise ValueError(f"diversify_lists: scale must be a [P] float32 device tensor, got {type(scale).__name__}")
+            raise ValueError(f"{what}: scale must be a [P] float32 device tensor, got {type(scale).__name__}")
         _req(scale, torch.float32, "scale", (table.shape[0],))
     if bad is not None:
         _req(bad, torch.int32, "bad", (1,))
@@ -2295,9 +2324,37 @@ def diversify_lists(idx, score, table, n, lam, scale=None, bad=None):
     out_sc = torch.empty(r, n, dtype=torch.float32, device=idx.device)
     if r == 0:
         return out_idx, out_sc
-    check(_lib.lib().pc_diversify_lists(_p(idx), _p(score), r, m, _p(table), _p(scale), table.shape[0], d, n, lam, _p(out_idx),
-                                        _p(out_sc), _p(bad), _stream()), "pc_diversify_lists")
+    check(getattr(_lib.lib(), name)(_p(idx), _p(score), r, m, _p(table), _p(scale), table.shape[0], d, n, lam, _p(out_idx),
+                                    _p(out_sc), _p(bad), _stream()), name)
     return out_idx, out_sc
+
+
+class CompactCatalogue:
+    """The bf16 copy of a catalogue as a serving table of its own: everything PCompanionInference needs to serve lists of up
+    to RETRIEVE_LIST_MAX_N products per type and diversified lists without the fp32 features (catalogue=CompactCatalogue(...)).
+    table: a [P, D] device tensor, D 128 or 256 -- fp32: rounded once here (catalogue_bf16); torch.bfloat16: taken as it is.
+      .table     [P, D] torch.bfloat16, contiguous, on the device
+      .inv_norm  [P] fp32 = inv_norm_bf16(.table), formed on first use: the cosine's factors
+    Both describe the ROUNDED rows: the cosine is between the rows that are actually stored.  Ranks (rank_grouped), a bias and
+    SimilarProducts still need the fp32 table."""
+
+    _inv_norm = None
+
+    def __init__(self, table):
+        if not isinstance(table, torch.Tensor) or table.dtype not in (torch.float32, torch.bfloat16):
+            raise ValueError(f"CompactCatalogue: the table must be a [P, D] float32 or bfloat16 device tensor, got "
+                             f"{table.dtype if isinstance(table, torch.Tensor) else type(table).__name__}")
+        if table.dim() != 2 or table.shape[0] < 1 or table.shape[1] not in (128, 256):
+            raise ValueError(f"CompactCatalogue: the table must be [P >= 1, 128 or 256], got {tuple(table.shape)}")
+        if not table.is_cuda or not table.is_contiguous():
+            raise ValueError("CompactCatalogue: the table must be a contiguous device tensor")
+        self.table = table if table.dtype == torch.bfloat16 else catalogue_bf16(table)
+
+    @property
+    def inv_norm(self):
+        if self._inv_norm is None:
+            self._inv_norm = inv_norm_bf16(self.table)        # once per catalogue
+        return self._inv_norm
 
 
 class CellIndex:
