@@ -1384,6 +1384,33 @@ int pc_diversify_lists_bf16(const int32_t *idx, const float *score, int rows, in
                             float *out_score, int32_t *bad_count, void *stream);
 int pc_inv_norm_bf16(const uint16_t *table_bf16, int rows, int dim, float *out, void *stream);
 
+/* Group caps and the merged page (ABI 8, additive; csrc/cap_lists.hip; ops.cap_lists,
+ * PCompanionInference.recommend_capped_batch / recommend_page_batch, SimilarProducts.similar_capped_batch): at most `cap`
+ * products of one product group (a parent item, a brand, a seller) in a served row, as a post-pass over a pool, on the device.
+ *
+ * pc_cap_lists: idx / score [rows, m], 1 <= m <= 256: a pool of candidates per row as the grouped retrievals return it -- or
+ * several of their lists side by side --, in any order.  A slot is a candidate iff its id lies in [0, num_products) and its
+ * score is finite; a slot with id -1 or a score that is not finite (+-inf, NaN) is none, wherever it stands; a slot whose id
+ * lies outside [-1, num_products) is none either, is never used as an index and adds one to *bad_count (int32 [1], optional,
+ * added to).  group [num_products] int32 or NULL: group[p] < 0 says that product p is ungrouped and never capped; group ids are
+ * only compared, so every non-negative int32 is one; NULL: no product is grouped.  row_ban [rows] int32 or NULL: with
+ * row_ban[r] = b >= 0 a candidate whose group is b is no candidate of row r ("never a variant of the query itself"); a negative
+ * entry or NULL bans nothing; row_ban needs group.  The candidates of a row are walked under the total order of the grouped
+ * retrievals (score descending, product index ascending): a grouped candidate is kept iff fewer than `cap` candidates of its
+ * group stand in front of it -- the greedy "keep while the group has room": the first `cap` of a group and none after them --,
+ * an ungrouped candidate always.  out_idx / out_score [rows, n]: the first n kept candidates in that order, each with its INPUT
+ * score bits (a -0.0 stays -0.0); -1 / -inf past the end.  Distinct ids within a row are the caller's contract: duplicates are
+ * separate candidates, and two slots equal in (score, id) are interchangeable.  Consequences: cap >= m or group == NULL returns
+ * the pool's first n under the total order -- of a grouped entry's list its own first n, bit for bit: the sort / merge alone --;
+ * a permutation of a row's slots changes no output bit; n = m returns every kept candidate; the result is the same for every
+ * launch geometry and run.  One wave per row sorts the row in registers (64 lanes x 2 slots for m <= 128, x 4 above, the same
+ * bits from both), counts for every slot the earlier slots of its group, and compacts.  Integer and float compares only: no
+ * workspace, no float atomics, no host readback.
+ * PC_ESHAPE: rows < 0, m outside [1, 256], n outside [1, m], cap < 1, num_products < 1, row_ban without group, a null idx /
+ * score / out_idx / out_score -- each checked before anything is launched; rows == 0 succeeds without a launch. */
+int pc_cap_lists(const int32_t *idx, const float *score, int rows, int m, const int32_t *group, const int32_t *row_ban,
+                 int num_products, int n, int cap, int32_t *out_idx, float *out_score, int32_t *bad_count, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

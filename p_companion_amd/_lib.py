@@ -243,6 +243,8 @@ SIGNATURES = {
                                            _sz, _vp]),
     "pc_diversify_lists_bf16": (_i, [_vp, _vp, _i, _i, _vp, _vp, _i, _i, _i, _f, _vp, _vp, _vp, _vp]),
     "pc_inv_norm_bf16": (_i, [_vp, _i, _i, _vp, _vp]),
+    # group caps and the merged page (csrc/cap_lists.hip; ABI 8, additive)
+    "pc_cap_lists": (_i, [_vp, _vp, _i, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "pc_hadamard_forward":(_i, [_vp, _vp, _i, _i, _vp, _vp]),
     "pc_hadamard_forward_dim": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
     "pc_hadamard_backward": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp]),

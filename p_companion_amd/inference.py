@@ -20,6 +20,9 @@ recommend_diverse_batch re-ranks recommend_batch's long list for diversity insid
 marginal-relevance pick of the products to show (pc_diversify_lists over the fp32 features, pc_inv_norm for the cosine).
 catalogue=ops.CompactCatalogue(...) serves both from the bf16 copy alone -- lists of up to 256 (pc_retrieve_list_grouped_bf16)
 and diversified lists (pc_diversify_lists_bf16, pc_inv_norm_bf16); ranks still need the fp32 catalogue.
+recommend_capped_batch keeps at most `cap` products of one product group (a parent item, a brand, a seller) in a list, and
+recommend_page_batch merges a query's K lists into one row under a per-type quota and that cap: one pc_cap_lists pass over
+recommend_batch's own pool.  SimilarProducts.similar_capped_batch does the same for substitutes, without the query's variants.
 
 SimilarProducts is the substitute side: the nearest products of a query under Euclidean distance over any [P, D] fp32 table
 (Product2Vec's export), the grouped retrieval and rank with the per-product term -|e_p|^2 / 2 on the score
@@ -36,6 +39,19 @@ from . import ops
 from .data import ComplementaryIndexDataset, DeviceBPG, IntBPG
 from .metrics import Metrics
 from .p_companion import PCompanion
+
+
+def _check_group(what, group, cap):
+    """cap as an int, and the shape of a product-group array (ops.cap_lists): cap >= 1, group None or a 1-D int32 tensor --
+    ValueError before anything of the serving object is read."""
+    cap = int(cap)
+    if cap < 1:
+        raise ValueError(f"{what}: cap must be at least 1, got {cap}")
+    if group is not None and (not torch.is_tensor(group) or group.dtype != torch.int32 or group.dim() != 1):
+        raise ValueError(f"{what}: group must be None or a [P] int32 device tensor (the product's group, negative = ungrouped), "
+                         f"got {tuple(group.shape) if torch.is_tensor(group) else type(group).__name__}"
+                         f"{' ' + str(group.dtype) if torch.is_tensor(group) else ''}")
+    return cap
 
 
 class _CandidateFilters:
@@ -90,6 +106,14 @@ class _CandidateFilters:
         self.eligible = mask
         self.cand_type = torch.where(mask, cand, torch.full_like(cand, -1))
         return self
+
+    def _group_covers(self, what, group):
+        """a product-group array names every product of the catalogue (a shorter one would turn served ids into bad ids)"""
+        if group is None:
+            return
+        p = int(self.type_idx.shape[0])
+        if group.shape[0] != p:
+            raise ValueError(f"{what}: group must hold one entry per product ({p}), got {group.shape[0]}")
 
     def _exclude_rows(self, query_idx, repeat=None):
         """The `exclude` triple of the grouped entries for rows keyed by their query's id -- `repeat` consecutive rows per query
@@ -292,25 +316,102 @@ class PCompanionInference(_CandidateFilters):
             raise ValueError(f"recommend_diverse_batch: diversity must be in [0, 1], got {diversity}")
         if similarity not in ("cosine", "dot"):
             raise ValueError(f"recommend_diverse_batch: similarity must be 'cosine' or 'dot', got {similarity!r}")
-        if self.compact is not None:                      # pool and similarity from the bf16 copy alone
-            types, idx, sc = self.recommend_batch(query_idx, pool)
-            b, k, m = idx.shape
-            idx, sc = ops.diversify_lists_bf16(idx.reshape(b * k, m), sc.reshape(b * k, m), self.catalogue, n, 1.0 - diversity,
-                                               scale=self.compact.inv_norm if similarity == "cosine" else None)
-            return types, idx.reshape(b, k, n), sc.reshape(b, k, n)
-        table = self.features if self.features is not None else self._graph.get("features")
-        if table is None:
-            raise ValueError("recommend_diverse_batch: the similarity is taken over the fp32 features, and this graph was "
-                             "generated without them (the bf16 catalogue alone cannot serve diversified lists)")
+        table = self._similarity_table("recommend_diverse_batch")
         types, idx, sc = self.recommend_batch(query_idx, pool)
         b, k, m = idx.shape
+        idx, sc = self._rerank(idx.reshape(b * k, m), sc.reshape(b * k, m), table, n, diversity, similarity)
+        return types, idx.reshape(b, k, n), sc.reshape(b, k, n)
+
+    def _similarity_table(self, what):
+        """The fp32 table the re-rank's similarity reads -- None with an ops.CompactCatalogue, whose bf16 rows serve it; a
+        graph without fp32 features and without one: ValueError, before the model runs."""
+        if self.compact is not None:
+            return None
+        table = self.features if self.features is not None else self._graph.get("features")
+        if table is None:
+            raise ValueError(f"{what}: the similarity is taken over the fp32 features, and this graph was "
+                             "generated without them (the bf16 catalogue alone cannot serve diversified lists)")
+        return table
+
+    def _rerank(self, idx, sc, table, n, diversity, similarity):
+        """The greedy MMR pick of n from the pools idx / sc [R, m] (recommend_diverse_batch, recommend_capped_batch): the choice
+        between ops.diversify_lists_bf16 over a CompactCatalogue's rows and ops.diversify_lists over `table`
+        (_similarity_table), and the cosine's scale."""
+        if self.compact is not None:                      # the similarity from the bf16 copy alone
+            return ops.diversify_lists_bf16(idx, sc, self.catalogue, n, 1.0 - diversity,
+                                            scale=self.compact.inv_norm if similarity == "cosine" else None)
         scale = None
         if similarity == "cosine":
             if self._inv_norm is None:
                 self._inv_norm = ops.inv_norm(table)          # once per catalogue
             scale = self._inv_norm
-        idx, sc = ops.diversify_lists(idx.reshape(b * k, m), sc.reshape(b * k, m), table, n, 1.0 - diversity, scale=scale)
+        return ops.diversify_lists(idx, sc, table, n, 1.0 - diversity, scale=scale)
+
+    @torch.no_grad()
+    def recommend_capped_batch(self, query_idx: torch.Tensor, num_recommendations: int = 10, group: torch.Tensor = None,
+                               cap: int = 1, pool: int = 64, diversity: float = None, similarity: str = "cosine"):
+        """recommend_batch's lists with at most `cap` products of one product group (a parent item, a brand, a seller) per
+        list.  group [P] int32 on the device: the product's group, negative = ungrouped and never capped.  The pool is
+        recommend_batch(query_idx, pool) itself -- its exclusions, eligibility, catalogue and choice of retrieval entry --, and
+        ops.cap_lists walks it in serving order and keeps a product while its group has room.  diversity=None: the first
+        num_recommendations kept products.  A diversity in [0, 1]: every kept product of the pool (ops.cap_lists with n = pool),
+        then exactly recommend_diverse_batch's re-rank of that pool -- the same entry, similarity and scale; the cap is
+        enforced on the pool, the re-rank then orders what is left.  Returns recommend_batch's triple (types [B, K], idx
+        [B, K, n], score [B, K, n]), the scores the pool's own bits, -1 / -inf where the capped pool holds fewer than
+        num_recommendations products: the cap is on a POOL, and a pool that is mostly one group gives a short list -- take a
+        longer pool.  1 <= num_recommendations <= pool <= ops.CAP_LISTS_MAX_POOL and cap >= 1, checked before the model runs.
+        group=None and diversity=None is recommend_batch(query_idx, num_recommendations), bit for bit, wherever the pool comes
+        through a grouped entry."""
+        n, pool = int(num_recommendations), int(pool)
+        if not 1 <= n <= pool <= ops.CAP_LISTS_MAX_POOL:
+            raise ValueError(f"recommend_capped_batch: need 1 <= num_recommendations <= pool <= {ops.CAP_LISTS_MAX_POOL}, got "
+                             f"num_recommendations {n} and pool {pool}")
+        cap = _check_group("recommend_capped_batch", group, cap)
+        table = None
+        if diversity is not None:
+            diversity = float(diversity)
+            if not 0.0 <= diversity <= 1.0:
+                raise ValueError(f"recommend_capped_batch: diversity must be None or in [0, 1], got {diversity}")
+            if similarity not in ("cosine", "dot"):
+                raise ValueError(f"recommend_capped_batch: similarity must be 'cosine' or 'dot', got {similarity!r}")
+            table = self._similarity_table("recommend_capped_batch")
+        self._group_covers("recommend_capped_batch", group)
+        types, idx, sc = self.recommend_batch(query_idx, pool)
+        b, k, m = idx.shape
+        idx, sc = idx.reshape(b * k, m), sc.reshape(b * k, m)
+        if diversity is None:
+            idx, sc = ops.cap_lists(idx, sc, n, group, cap)
+        else:
+            idx, sc = ops.cap_lists(idx, sc, m, group, cap)                       # every kept product; -1 slots are no candidates
+            idx, sc = self._rerank(idx, sc, table, n, diversity, similarity)
         return types, idx.reshape(b, k, n), sc.reshape(b, k, n)
+
+    @torch.no_grad()
+    def recommend_page_batch(self, query_idx: torch.Tensor, num_recommendations: int = 10, per_type: int = 4,
+                             group: torch.Tensor = None, cap: int = 1):
+        """One row per query across its K predicted complementary types -- what a widget shows: (idx [B, n] int32, score
+        [B, n] fp32, types [B, n] int64 = the product's type, -1 where idx is -1).  The K lists of
+        recommend_batch(query_idx, per_type) side by side are one pool of K per_type products, and ONE ops.cap_lists call
+        merges it under the serving order (score descending, product index ascending): the per-type quota is the pool's own
+        length -- no type can place more than per_type products --, and the group cap (group [P] int32, negative = ungrouped;
+        None: no cap) holds across the whole page.  The scores of different types are compared AS THEY ARE: each is the dot
+        product of that type's projected query with the product's features, and nothing normalises one type against another --
+        a type whose projections score higher takes the head of the page.  Needs K per_type <= ops.CAP_LISTS_MAX_POOL and
+        1 <= num_recommendations <= K per_type (and cap >= 1), checked before the model runs; -1 / -inf where fewer products
+        are kept."""
+        n, per_type, k = int(num_recommendations), int(per_type), int(self.config.NUM_COMP_TYPES)
+        if per_type < 1 or k * per_type > ops.CAP_LISTS_MAX_POOL:
+            raise ValueError(f"recommend_page_batch: need 1 <= per_type and K * per_type <= {ops.CAP_LISTS_MAX_POOL}, got K = {k} "
+                             f"and per_type {per_type}")
+        if not 1 <= n <= k * per_type:
+            raise ValueError(f"recommend_page_batch: need 1 <= num_recommendations <= K * per_type = {k * per_type}, got {n}")
+        cap = _check_group("recommend_page_batch", group, cap)
+        self._group_covers("recommend_page_batch", group)
+        _, idx, sc = self.recommend_batch(query_idx, per_type)
+        b = idx.shape[0]
+        idx, sc = ops.cap_lists(idx.reshape(b, -1), sc.reshape(b, -1), n, group, cap)
+        types = torch.where(idx >= 0, self.type_idx[idx.clamp(min=0).long()].long(), -1)
+        return idx, sc, types
 
     @torch.no_grad()
     def rank_targets(self, query_idx: torch.Tensor, target_idx: torch.Tensor, take: torch.Tensor = None):
@@ -497,6 +598,32 @@ class SimilarProducts(_CandidateFilters):
         idx, _ = ops.retrieve_topk_grouped(q, self._scope_type[query_idx.long()].contiguous(), self.type_rowptr, self.type_col,
                                            self.table, n, exclude=self._exclude_rows(query_idx), bias=self.bias)
         return idx, self._distances(q, idx)
+
+    @torch.no_grad()
+    def similar_capped_batch(self, query_idx: torch.Tensor, n: int = 10, group: torch.Tensor = None, cap: int = 1,
+                             own_group: bool = False):
+        """similar_batch with at most `cap` products of one product group per list, and -- unless own_group -- none of the
+        query's own group: a product's nearest neighbours are its own variants, and they are not its substitutes.  group [P]
+        int32 on the device, negative = ungrouped (never capped, never banned); None: nothing is grouped.  The pool is this
+        object's similar_batch(query_idx, MAX_N): its 16 nearest candidates with their reported distances.  ops.cap_lists runs on
+        the NEGATED distances, so nearer is better and equal distances go to the lower product index, with
+        row_ban = group[query_idx] unless own_group.  Returns (idx [B, n] int32, dist [B, n] fp32), the distances those
+        similar_batch reported for the same ids, -1 / +inf past the end.  1 <= n <= 16.
+        THE LIMIT: the pool is 16 products, because the biased retrieval entries serve at most 16.  In a heavily varianted
+        neighbourhood most of the 16 are the query's own variants or share a few groups, and the list comes back SHORT (even
+        empty) although the catalogue holds further neighbours; a longer substitute pool needs a biased long-list entry."""
+        n = int(n)
+        if not 1 <= n <= self.MAX_N:
+            raise ValueError(f"similar_capped_batch: 1 to {self.MAX_N} neighbours per query, got {n}")
+        cap = _check_group("similar_capped_batch", group, cap)
+        self._group_covers("similar_capped_batch", group)
+        query_idx = self._queries("similar_capped_batch", query_idx)
+        if query_idx.shape[0] == 0:
+            return self._no_neighbours(n)
+        idx, dist = self.similar_batch(query_idx, self.MAX_N)
+        ban = group[query_idx.long()].contiguous() if group is not None and not own_group else None
+        idx, near = ops.cap_lists(idx, -dist, n, group, cap, row_ban=ban)
+        return idx, -near
 
     def _neighbours(self, n):
         """n of similar_batch as an int; outside 1 .. MAX_N: ValueError, before anything of the object is read."""

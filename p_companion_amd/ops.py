@@ -2329,6 +2329,61 @@ def _diversify(what, name, dtype, idx, score, table, n, lam, scale, bad):
     return out_idx, out_sc
 
 
+CAP_LISTS_MAX_POOL = 256
+
+
+def cap_lists(idx, score, n, group=None, cap=1, row_ban=None, bad=None):
+    """pc_cap_lists: at most `cap` products of one product group in a served row, as a post-pass over a pool.  idx [R, m] int32
+    / score [R, m] fp32, 1 <= m <= CAP_LISTS_MAX_POOL, as the grouped retrievals return them -- or several of their lists side
+    by side -- in any order (a slot with id -1 or a score that is not finite is no candidate) -> (idx [R, n] int32, score [R, n]
+    fp32): the first n candidates under (score descending, product index ascending) that the rule keeps, each with its INPUT
+    score bits, -1 / -inf past the end.  group [P] int32: the product's group, negative = ungrouped and never capped (ids are
+    only compared: any non-negative int32); None: nothing is grouped, and the call is the sort / merge alone.  A grouped
+    candidate is kept iff fewer than cap candidates of its group stand in front of it.  row_ban [R] int32 (needs group): a
+    non-negative entry names a group none of whose products is a candidate of that row.  An id outside [-1, P) -- without a
+    group: a negative id below -1 -- is no candidate, is never used as an index and is counted in `bad` (a [1] int32 device
+    counter the caller passes to see the count; added to).  cap >= m or group=None returns the pool's first n: of a grouped
+    entry's list its own first n, bit for bit.  Bitwise deterministic; a permutation of a row's slots changes nothing.  Nothing
+    is read back."""
+    _req(idx, torch.int32, "idx")
+    _req(score, torch.float32, "score")
+    if idx.dim() != 2 or tuple(score.shape) != tuple(idx.shape):
+        raise ValueError(f"cap_lists: expected idx and score of one shape [R, m], got {tuple(idx.shape)} and "
+                         f"{tuple(score.shape)}")
+    r, m = idx.shape
+    if not 1 <= m <= CAP_LISTS_MAX_POOL:
+        raise ValueError(f"cap_lists: the pool m must be in [1, {CAP_LISTS_MAX_POOL}], got {m}")
+    n, cap = int(n), int(cap)
+    if not 1 <= n <= m:
+        raise ValueError(f"cap_lists: n must be in [1, m = {m}], got {n}")
+    if cap < 1:
+        raise ValueError(f"cap_lists: cap must be at least 1, got {cap}")
+    num_products = 2 ** 31 - 1                            # without groups every non-negative id is a candidate
+    if group is not None:
+        if not isinstance(group, torch.Tensor):
+            raise ValueError(f"cap_lists: group must be a [P] int32 device tensor, got {type(group).__name__}")
+        _req(group, torch.int32, "group")
+        if group.dim() != 1 or group.shape[0] < 1:
+            raise ValueError(f"cap_lists: group must be [P] with at least one product, got {tuple(group.shape)}")
+        num_products = group.shape[0]
+    if row_ban is not None:
+        if group is None:
+            raise ValueError("cap_lists: row_ban names a group per row and needs group")
+        if not isinstance(row_ban, torch.Tensor):
+            raise ValueError(f"cap_lists: row_ban must be a [R] int32 device tensor, got {type(row_ban).__name__}")
+        _req(row_ban, torch.int32, "row_ban", (r,))
+    if bad is not None:
+        _req(bad, torch.int32, "bad", (1,))
+    out_idx = torch.empty(r, n, dtype=torch.int32, device=idx.device)
+    out_sc = torch.empty(r, n, dtype=torch.float32, device=idx.device)
+    if r == 0:
+        return out_idx, out_sc
+    # (a group holds at most m of a row's slots: every cap >= m is the cap m, whatever fits a C int)
+    check(_lib.lib().pc_cap_lists(_p(idx), _p(score), r, m, _p(group), _p(row_ban), num_products, n, min(cap, m), _p(out_idx),
+                                  _p(out_sc), _p(bad), _stream()), "pc_cap_lists")
+    return out_idx, out_sc
+
+
 class CompactCatalogue:
     """The bf16 copy of a catalogue as a serving table of its own: everything PCompanionInference needs to serve lists of up
     to RETRIEVE_LIST_MAX_N products per type and diversified lists without the fp32 features (catalogue=CompactCatalogue(...)).
