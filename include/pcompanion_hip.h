@@ -1357,8 +1357,9 @@ int pc_inv_norm(const float *table, int rows, int dim, float *out, void *stream)
  * [rows, n] = the first n products of type types[r] that are not in the list of row_key[r] (row_key == NULL: no lists), -1 /
  * -inf past the end -- over table_bf16.  The score of a (row, product) pair is formed through pc_retrieve_topk_grouped_bf16's
  * own chain (the unrounded fp32 query split into three bf16 pieces, k-block by k-block on v_mfma_f32_16x16x32_bf16 into one
- * accumulator) and has that entry's bits; the selection is pc_retrieve_list_grouped's (a row's unsorted candidate buffer and
- * threshold on chip, compacted by a sorting network, the slices' sorted partial lists merged by one wave per row), every step
+ * accumulator) and has that entry's bits; everything else is pc_retrieve_list_grouped's own code -- one kernel body and one host
+ * path for the two tables (csrc/grouped_list.h), the score chain its only parameter: a row's unsorted candidate buffer and
+ * threshold on chip, compacted by a sorting network, the slices' sorted partial lists merged by one wave per row, every step
  * under the total order (score descending, product index ascending).  For n <= 16 the output is
  * pc_retrieve_topk_grouped_bf16's bit for bit; for every n it does not depend on `slices`, on the placement of the rows or on
  * the order of type_col inside a type.  A key outside [-1, n_keys) is served as -1, never indexes memory and is counted in

@@ -237,7 +237,8 @@ SIGNATURES = {
     # diversified lists (csrc/diversify.hip; ABI 8, additive)
     "pc_diversify_lists": (_i, [_vp, _vp, _i, _i, _vp, _vp, _i, _i, _i, _f, _vp, _vp, _vp, _vp]),
     "pc_inv_norm": (_i, [_vp, _i, _i, _vp, _vp]),
-    # long and diversified lists from the bf16 copy (csrc/retrieve_list_bf16.hip, csrc/diversify.hip; ABI 8, additive)
+    # long and diversified lists from the bf16 copy (csrc/retrieve_list_bf16.hip -- the kernel body and the host path are
+    # pc_retrieve_list_grouped's, csrc/grouped_list.h -- and csrc/diversify.hip; ABI 8, additive)
     "pc_retrieve_list_grouped_bf16_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "pc_retrieve_list_grouped_bf16": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp,
                                            _sz, _vp]),

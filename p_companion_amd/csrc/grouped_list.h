@@ -1,7 +1,26 @@
-// What the long-list entries share (retrieve_list.hip: the fp32 table; retrieve_list_bf16.hip: the bf16 copy): the list and
-// buffer sizes of the per-row selection, and on the host the merge of the slices' sorted partial lists (retrieve_list.hip).
+// The long-list family's header (retrieve_list.hip: the fp32 table; retrieve_list_bf16.hip: the bf16 copy), the way
+// grouped_select.h is the 16-entry kernels': the list and buffer sizes, the score kernel's body and the host path, one text
+// each.  A unit supplies its score chain (a policy, below), its kernels as one-line wrappers of rl_score_body and its entries.
+//
+// The kernel.  The contract, the plan, the work items and the chunks are retrieve.hip's; what differs is the selection.  There
+// every thread keeps a sorted list of 16 in registers; a list of 256 per thread is out of reach of the register file, and
+// indexed at run time it would live in scratch.  Here a ROW keeps an unsorted candidate buffer in LDS and a threshold:
+//
+//   plan    grouped_plan.hip as it is, with tiles of RL_TM = 16 rows (the buffers take the LDS the wider tile had)
+//   score   work item (type, slice, tile): query tile -> LDS (the chain's image), candidates in chunks of 64 (one 16-candidate
+//           column group per wave, the next chunk's rows in flight in registers), the chain's scores -> LDS.  The 16 threads of
+//           a row test 4 candidates each against the row's threshold ((-inf, none) until the row has been compacted once); a
+//           survivor is looked up in the row's exclusion list (when there is one) and appended to the row's buffer through an
+//           integer LDS counter.  A row whose buffer could overflow on the next chunk (more than CAP - 64 entries) is
+//           compacted, and every row once more at the end of the item: one wave sorts the buffer under rg_better (a bitonic
+//           network over 64 NE slots, slot i = NE lane + e: strides below NE between a lane's own registers, the others
+//           between lanes, all register indices static), keeps the first n and sets the threshold to the n-th.  The partial
+//           lists [rows][S][n] are written sorted.
+//   merge   rl_merge_kernel (retrieve_list.hip), one wave per row
 #pragma once
-#include "grouped_plan.h"
+#include <type_traits>
+#include "grouped_select.h"        // the item decode
+#include "wave_sort.h"             // rl_sort: the bitonic network (shared with ingest.hip)
 
 #define RL_MAX_N 256
 #define RL_N2 32                   // n up to here: 128 buffer entries per row (NE = 2); a compacted row has 32 entries of slack
@@ -13,3 +32,216 @@
 // w.pv / w.pi [rows][S][n] -> out_idx / out_score [rows][n] (-1 / -inf past the end of a short list).
 void rl_merge_launch(const RgWs& w, const int32_t* types, int rows, const int32_t* type_rowptr, int n_types, int n, int S,
                      int32_t* out_idx, float* out_score, hipStream_t st);
+
+// A score kernel's arguments, the table's element type T apart the same for both tables.
+#define RL_SCORE_PARAMS(T)                                                                                                       \
+    const float* __restrict__ proj, const int32_t* __restrict__ type_rowptr, const int32_t* __restrict__ type_col,               \
+        const T* __restrict__ table, int n_types, int n, int S, const int32_t* __restrict__ cnt,                                 \
+        const int32_t* __restrict__ row_start, const int64_t* __restrict__ item_start, const int32_t* __restrict__ order,        \
+        float* __restrict__ pv, int32_t* __restrict__ pi, const int32_t* __restrict__ row_key, int rows,                         \
+        const int32_t* __restrict__ ex_rowptr, const int32_t* __restrict__ ex_col, int n_keys, int32_t* __restrict__ bad_count
+#define RL_SCORE_ARGS                                                                                                            \
+    proj, type_rowptr, type_col, table, n_types, n, S, cnt, row_start, item_start, order, pv, pi, row_key, rows, ex_rowptr,      \
+        ex_col, n_keys, bad_count
+
+// Work item w = (type t, slice s, tile j) (rg_decode).  Lane l of wave wv: column c = l & 15 (candidate wv * 16 + c of the
+// chunk, query row c of the A operand), k-lane h = l >> 4.  In the selection thread tid serves row rr = tid / 16 with
+// candidates qq + 16 k, so the rows 4 wv .. 4 wv + 3 are appended to AND compacted by wave wv.
+// NE = 2 / 4 / 8: 128 / 256 / RL_CAP buffer entries per row for n <= RL_N2 / RL_N4 / RL_MAX_N; the slack between n and
+// CAP - 64 is what a compacted row can take before it is sorted again.  EX: with exclusion lists.
+// Chain, the score chain of a table type at width D:
+//   Q                                       the query tile's image in LDS (16-byte aligned)
+//   load_tile(q, proj, order, p0, valid, tid)   the rows order[p0 .. p0 + valid) of proj -> q, rows past `valid` zero
+//   B, NB, zero()                           a lane's operand of 16 bytes and how many a candidate row gives it: operand k
+//                                           of lane (c, h) is the row's 16-byte piece h + 4 k; zero() where there is no row
+//                                           (written out per type: B{} costs rl_score_kernel<128, 2, EX> a wave per SIMD)
+//   score(q, b, c, h)                       the lane's part of the 16 x 16 scores of the tile against the wave's column
+//                                           group in the C/D map of the 16-row MFMAs: column lane & 15 (the candidate), row
+//                                           4 (lane >> 4) + reg (the query row)
+template <class Chain, int NE, bool EX>
+__device__ __forceinline__ void rl_score_body(RL_SCORE_PARAMS(typename Chain::Table)) {
+    using B = typename Chain::B;
+    constexpr int D = Chain::D, NB = Chain::NB;
+    constexpr int TM = RL_TM;
+    constexpr int TPR = 256 / TM;            // threads per row in the selection phase
+    constexpr int CPT = RG_CHUNK / TPR;      // candidates per thread per chunk
+    constexpr int CAP = NE == 8 ? RL_CAP : 64 * NE;
+    constexpr int BS = CAP + 4;              // buffer row stride: a lane's NE slots stay 16-byte aligned
+    static_assert(CAP <= 64 * NE && CAP % NE == 0 && TM == 16 && TPR == 16, "buffer within the sort's slots; one MFMA row group");
+    static_assert(sizeof(B) == 16 && NB * 64 == D * (int)sizeof(typename Chain::Table), "four k-lanes of NB 16-byte operands are a row");
+    __shared__ __attribute__((aligned(16))) typename Chain::Q q;
+    __shared__ float sc[TM][RG_CHUNK + 1];
+    __shared__ int cid[RG_CHUNK];
+    __shared__ __attribute__((aligned(16))) float bv[TM][BS];        // the rows' candidate buffers, unsorted between compactions
+    __shared__ __attribute__((aligned(16))) int bi[TM][BS];
+    __shared__ int bcnt[TM];                 // entries in a row's buffer
+    __shared__ float thv[TM];                // the row's threshold: its n-th entry at the last compaction
+    __shared__ int thi[TM];
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, c = lane & 15, h = lane >> 4;
+    const int rr = tid / TPR, qq = tid % TPR;
+    const int64_t n_items = item_start[n_types];
+    if (EX) {
+        for (int r = blockIdx.x * 256 + tid; r < rows; r += gridDim.x * 256) {
+            const int key = row_key[r];
+            if (key < -1 || key >= n_keys) atomicAdd(bad_count, 1);
+        }
+    }
+    for (int64_t w = blockIdx.x; w < n_items; w += gridDim.x) {
+        const RgItem it = rg_decode<TM>(w, item_start, cnt, row_start, type_rowptr, n_types, S);
+        const int s = it.s, p0 = it.p0, valid = it.valid, cb0 = it.cb0, ce = it.ce;
+
+        __syncthreads();                                  // the previous item's readers of q and of the buffers are done
+        Chain::load_tile(q, proj, order, p0, valid, tid);
+        if (tid < TM) { bcnt[tid] = 0; thv[tid] = -INFINITY; thi[tid] = RG_NONE; }
+        int elo = 0, ehi = 0;                             // this thread's row's list: ex_col[elo, ehi)
+        if (EX && rr < valid) {
+            const int key = row_key[order[p0 + rr]];
+            if (key >= 0 && key < n_keys) { elo = ex_rowptr[key]; ehi = ex_rowptr[key + 1]; }
+        }
+
+        auto load_pid = [&](int cb) { const int cc = cb + wv * 16 + c; return cc < ce ? type_col[cc] : -1; };
+        auto load_b = [&](B* b, int pid) {
+            if (pid >= 0) {
+                const B* f = reinterpret_cast<const B*>(table + (size_t)pid * D) + h;
+#pragma unroll
+                for (int k = 0; k < NB; k++) b[k] = f[4 * k];
+            } else {
+#pragma unroll
+                for (int k = 0; k < NB; k++) b[k] = Chain::zero();
+            }
+        };
+        B bn[NB];
+        int pidn = load_pid(cb0);
+        load_b(bn, pidn);
+        int pidnn = load_pid(cb0 + RG_CHUNK);
+        __syncthreads();                                  // query image, counters and thresholds in LDS
+
+        for (int cb = cb0;; cb += RG_CHUNK) {
+            const bool fin = cb >= ce;                    // past the last chunk: the closing compaction only
+            if (!fin) {
+                B b[NB];
+#pragma unroll
+                for (int k = 0; k < NB; k++) b[k] = bn[k];
+                const int pid = pidn;
+                pidn = pidnn;
+                if (cb + RG_CHUNK < ce) load_b(bn, pidn); // the next chunk's rows in flight while this one is scored
+                pidnn = load_pid(cb + 2 * RG_CHUNK);
+                const f32x4 acc = Chain::score(q, b, c, h);
+#pragma unroll
+                for (int k = 0; k < 4; k++) sc[4 * h + k][wv * 16 + c] = acc[k];
+                if (h == 0) cid[wv * 16 + c] = pid < 0 ? RG_NONE : pid;
+                __syncthreads();                          // (also: the last compaction's threshold and count are visible)
+                if (rr < valid) {
+                    const float hv = thv[rr];
+                    const int hix = thi[rr];
+#pragma unroll
+                    for (int k = 0; k < CPT; k++) {
+                        const int col = qq + TPR * k;
+                        const int xi = cid[col];
+                        const float x = sc[rr][col];
+                        if (xi == RG_NONE || !rg_better(x, xi, hv, hix)) continue;
+                        if (EX) {
+                            int a = elo, e = ehi;         // the first list entry >= xi
+                            while (a < e) {
+                                const int mid = (a + e) >> 1;
+                                if (ex_col[mid] < xi) a = mid + 1; else e = mid;
+                            }
+                            if (a < ehi && ex_col[a] == xi) continue;     // excluded: never buffered, the threshold stays
+                        }
+                        // at most CAP - 64 entries before the chunk (or the row was compacted to n <= CAP - 64) and at
+                        // most 64 candidates of the row in a chunk: slot < CAP
+                        const int slot = atomicAdd(&bcnt[rr], 1);
+                        bv[rr][slot] = x;
+                        bi[rr][slot] = xi;
+                    }
+                }
+                __syncthreads();                          // the chunk's scores are read; the appends are visible
+            }
+            for (int k = 0; k < TM / 4; k++) {
+                const int row = wv * (TM / 4) + k;
+                const int cn = __builtin_amdgcn_readfirstlane(bcnt[row]);
+                if (fin ? row >= valid : cn <= CAP - RG_CHUNK) continue;          // (wave-uniform)
+                float v[NE];
+                int ix[NE];
+#pragma unroll
+                for (int e = 0; e < NE; e++) { v[e] = -INFINITY; ix[e] = RG_NONE; }
+                if (NE * lane < cn) {                     // (cn <= CAP, a multiple of NE: the lane's NE slots are inside the row)
+#pragma unroll
+                    for (int e = 0; e < NE; e++) {
+                        const float x = bv[row][NE * lane + e];
+                        const int xi = bi[row][NE * lane + e];
+                        if (NE * lane + e < cn) { v[e] = x; ix[e] = xi; }
+                    }
+                }
+                rl_sort<NE>(v, ix, lane);
+                if (fin) {
+                    const size_t o = ((size_t)(p0 + row) * S + s) * n;
+#pragma unroll
+                    for (int e = 0; e < NE; e++) {
+                        const int slot = NE * lane + e;
+                        if (slot < n) { pv[o + slot] = v[e]; pi[o + slot] = ix[e]; }
+                    }
+                } else {
+                    float tv = -INFINITY;                 // slot n - 1: the n-th entry ((-inf, none) while the row holds fewer)
+                    int ti = RG_NONE;
+#pragma unroll
+                    for (int e = 0; e < NE; e++) {
+                        const int slot = NE * lane + e;
+                        if (slot < n && slot < cn) { bv[row][slot] = v[e]; bi[row][slot] = ix[e]; }
+                        if (e == (n - 1) % NE) { tv = v[e]; ti = ix[e]; }
+                    }
+                    tv = __shfl(tv, (n - 1) / NE, 64);
+                    ti = __shfl(ti, (n - 1) / NE, 64);
+                    if (lane == 0) { bcnt[row] = min(cn, n); thv[row] = tv; thi[row] = ti; }
+                }
+            }
+            if (fin) break;
+        }
+    }
+}
+
+// The host path of an entry.  K names the unit's kernels: K::kernel<D, NE, EX>() is the score kernel over a table of T.
+// The entry looks at its lists before its counts (a list without keys is a caller's slip), then -- the bf16 entry's refusal
+// alone -- at the alignment a lane's 16-byte reads of a row need, then plans.
+template <class K, int D, int NE, class T>
+void rl_launch_score(dim3 grid, hipStream_t st, const float* proj, const int32_t* type_rowptr, const int32_t* type_col,
+                     const T* table, int n_types, int n, int S, const RgWs& w, const int32_t* row_key, int rows,
+                     const int32_t* ex_rowptr, const int32_t* ex_col, int n_keys, int32_t* bad_count) {
+    const RgPlan& pl = w.plan;
+    if (row_key)
+        PC_LAUNCH((K::template kernel<D, NE, true>()), grid, dim3(256), 0, st, proj, type_rowptr, type_col, table, n_types, n, S,
+                  pl.cnt, pl.row_start, pl.item_start, pl.order, w.pv, w.pi, row_key, rows, ex_rowptr, ex_col, n_keys, bad_count);
+    else
+        PC_LAUNCH((K::template kernel<D, NE, false>()), grid, dim3(256), 0, st, proj, type_rowptr, type_col, table, n_types, n, S,
+                  pl.cnt, pl.row_start, pl.item_start, pl.order, w.pv, w.pi, row_key, rows, ex_rowptr, ex_col, n_keys, bad_count);
+}
+
+template <class K, class T>
+int rl_list_entry(const float* proj, const int32_t* types, const int32_t* row_key, int rows, const int32_t* type_rowptr,
+                  const int32_t* type_col, const T* table, int n_types, const int32_t* ex_rowptr, const int32_t* ex_col, int n_keys,
+                  int n, int dim, int slices, int32_t* out_idx, float* out_score, int32_t* bad_count, void* ws, size_t ws_bytes,
+                  void* stream) {
+    PC_TRY(rg_topn_check(proj && types && type_rowptr && type_col && table && out_idx && out_score && ws &&
+                             rg_lists_ok(row_key, ex_rowptr, ex_col, bad_count, n_keys),
+                         rows, n_types, true, n, RL_MAX_N, dim, slices));
+    if (std::is_same<T, uint16_t>::value && ((uintptr_t)table & 15)) return PC_ESHAPE;
+    const int S = rg_slices(slices);
+    hipStream_t st = (hipStream_t)stream;
+    RgWs w;
+    unsigned grid;
+    PC_TRY(rg_begin(w, grid, ws, ws_bytes, types, nullptr, rows, type_rowptr, n_types, 0, n, S, RL_TM, nullptr, nullptr, st));
+#define RL_SCORE(D, NE) \
+    rl_launch_score<K, D, NE>(dim3(grid), st, proj, type_rowptr, type_col, table, n_types, n, S, w, row_key, rows, ex_rowptr, ex_col, n_keys, bad_count)
+    if (dim == 128) {
+        if (n <= RL_N2) RL_SCORE(128, 2);
+        else if (n <= RL_N4) RL_SCORE(128, 4);
+        else RL_SCORE(128, 8);
+    } else {
+        if (n <= RL_N2) RL_SCORE(256, 2);
+        else if (n <= RL_N4) RL_SCORE(256, 4);
+        else RL_SCORE(256, 8);
+    }
+#undef RL_SCORE
+    rl_merge_launch(w, types, rows, type_rowptr, n_types, n, S, out_idx, out_score, st);
+    return pc_launch_status();
+}

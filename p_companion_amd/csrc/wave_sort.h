@@ -1,5 +1,5 @@
 // One wave's bitonic network over 64 NE register slots under the total order of grouped_plan.h (rg_better: value descending,
-// index ascending).  retrieve_list.hip compacts a row's candidate buffer with it; ingest.hip sorts a short neighbour bucket
+// index ascending).  The long-list kernels (grouped_list.h) compact a row's candidate buffer with it; ingest.hip sorts a short neighbour bucket
 // (all values equal: the order is the ascending index).
 #pragma once
 #include "grouped_plan.h"

@@ -2,7 +2,7 @@
 """Two builds of libpcompanion_hip.so side by side, no device involved: every workspace query of the type-grouped catalogue
 entries over a grid of (rows, n_types, n, slices) with each bound and one step past it, and the return code of refused calls
 of those entries -- the cases of the family's error-code tests (tests/test_gpu_retrieval_grouped.py, test_gpu_exclusions.py,
-test_gpu_retrieval_list.py, test_gpu_retrieval_bf16.py, test_gpu_nearest.py, test_gpu_rank_grouped.py and the *_host.py ones)
+test_gpu_retrieval_list.py, test_gpu_retrieval_bf16.py, test_gpu_compact_catalogue.py, test_gpu_nearest.py, test_gpu_rank_grouped.py and the *_host.py ones)
 and around them every single null pointer, every pair of two changed arguments out of the edge values below, and every
 combination of present / absent exclusion arguments.  No call here can launch: the workspace handed in is one byte short at
 the most, and the pointers are never dereferenced before that check.
@@ -25,7 +25,7 @@ TYPES = (-1, 0, 1, 2, 100, 1024, 1025, 34_800)
 NS = (-1, 0, 1, 2, 15, 16, 17, 32, 33, 96, 97, 255, 256, 257)
 SLICES = (-1, 0, 1, 15, 16, 17, 63, 64, 65)
 TOPN = ("pc_retrieve_topk_grouped", "pc_retrieve_topk_grouped_excluding", "pc_retrieve_list_grouped",
-        "pc_retrieve_topk_grouped_bf16", "pc_retrieve_topk_grouped_biased")
+        "pc_retrieve_topk_grouped_bf16", "pc_retrieve_list_grouped_bf16", "pc_retrieve_topk_grouped_biased")
 RANK = ("pc_rank_grouped", "pc_rank_grouped_biased")
 
 # the entries' arguments in the order of the C ABI (include/pcompanion_hip.h)
@@ -36,6 +36,8 @@ ARGS = {
     "pc_retrieve_list_grouped": "proj types row_key rows type_rowptr type_col table n_types ex_rowptr ex_col n_keys n dim slices "
                                 "out_idx out_score bad_count ws ws_bytes stream",
     "pc_retrieve_topk_grouped_bf16": "proj types row_key rows type_rowptr type_col table n_types ex_rowptr ex_col n_keys n dim slices "
+                                     "out_idx out_score bad_count ws ws_bytes stream",
+    "pc_retrieve_list_grouped_bf16": "proj types row_key rows type_rowptr type_col table n_types ex_rowptr ex_col n_keys n dim slices "
                                      "out_idx out_score bad_count ws ws_bytes stream",
     "pc_retrieve_topk_grouped_biased": "proj types row_key rows type_rowptr type_col table bias n_types ex_rowptr ex_col n_keys n dim "
                                        "slices out_idx out_score bad_count ws ws_bytes stream",
