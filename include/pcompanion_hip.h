@@ -1412,6 +1412,31 @@ int pc_inv_norm_bf16(const uint16_t *table_bf16, int rows, int dim, float *out, 
 int pc_cap_lists(const int32_t *idx, const float *score, int rows, int m, const int32_t *group, const int32_t *row_ban,
                  int num_products, int n, int cap, int32_t *out_idx, float *out_score, int32_t *bad_count, void *stream);
 
+/* Long substitute lists (ABI 8, additive; csrc/nearest_list.hip; SimilarProducts.similar_list_batch and
+ * similar_capped_list_batch: a product's nearest neighbours are its own variants, so a group cap over a pool of 16 leaves the
+ * served list short).  pc_retrieve_list_grouped_biased is pc_retrieve_list_grouped's contract and argument list, bias
+ * [num_products] fp32 directly behind the table, for 1 <= n <= 256 under the biased score
+ *   s(r, p) = fl(d(r, p) + bias[p]),  d(r, p) = pc_retrieve_list_grouped's own fp32 MFMA chain over table [num_products, dim],
+ * one fp32 addition after the chain (the accumulator starts at zero): out_idx / out_score [rows, n] = the first n products of
+ * type types[r] that are not in the list of row_key[r] under (s descending, product index ascending), out_score = s, -1 / -inf
+ * past the end of a short type and for a type outside [0, n_types).  row_key == NULL: no lists (ex_rowptr, ex_col NULL, n_keys
+ * 0; bad_count may be NULL); with row_key a key outside [-1, n_keys) is served as -1, never indexes memory and is counted in
+ * *bad_count (required then; added to).  A (row, product) score has pc_retrieve_topk_grouped_biased's and
+ * pc_rank_grouped_biased's bits: for n <= 16 the output is pc_retrieve_topk_grouped_biased's bit for bit, with a zero bias it is
+ * pc_retrieve_list_grouped's, and pc_rank_grouped_biased is < n exactly when the list holds the target at that position.  The
+ * kernel body, the merge and the host path are pc_retrieve_list_grouped's own code: bitwise deterministic and independent of
+ * `slices`, of the placement of the rows and of the order of type_col inside a type; no float atomics, no host readback.  The
+ * workspace (pc_retrieve_list_grouped_biased_workspace_bytes, 0 for arguments out of range) is pc_retrieve_list_grouped's size.
+ * PC_EINVAL: null pointer (bias among them), rows or n_types <= 0; with row_key a null ex_rowptr / ex_col / bad_count or
+ * n_keys < 0; without it a list or n_keys != 0; PC_ESHAPE: n outside [1, 256], dim not 128 / 256, slices outside [0, 64];
+ * PC_EWORKSPACE: ws_bytes too small -- each checked before anything is launched. */
+size_t pc_retrieve_list_grouped_biased_workspace_bytes(int rows, int n_types, int n, int slices);
+int pc_retrieve_list_grouped_biased(const float *proj, const int32_t *types, const int32_t *row_key, int rows,
+                                    const int32_t *type_rowptr, const int32_t *type_col, const float *table,
+                                    const float *bias, int n_types, const int32_t *ex_rowptr, const int32_t *ex_col,
+                                    int n_keys, int n, int dim, int slices, int32_t *out_idx, float *out_score,
+                                    int32_t *bad_count, void *ws, size_t ws_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

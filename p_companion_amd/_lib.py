@@ -246,6 +246,11 @@ SIGNATURES = {
     "pc_inv_norm_bf16": (_i, [_vp, _i, _i, _vp, _vp]),
     # group caps and the merged page (csrc/cap_lists.hip; ABI 8, additive)
     "pc_cap_lists": (_i, [_vp, _vp, _i, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    # long substitute lists (csrc/nearest_list.hip -- grouped_list.h's kernel body and host path under nearest.hip's biased
+    # score; pc_retrieve_list_grouped's list with the bias behind the table; ABI 8, additive)
+    "pc_retrieve_list_grouped_biased_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "pc_retrieve_list_grouped_biased": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp,
+                                             _vp, _sz, _vp]),
     "pc_hadamard_forward":(_i, [_vp, _vp, _i, _i, _vp, _vp]),
     "pc_hadamard_forward_dim": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
     "pc_hadamard_backward": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp]),

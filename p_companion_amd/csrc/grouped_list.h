@@ -1,6 +1,7 @@
-// The long-list family's header (retrieve_list.hip: the fp32 table; retrieve_list_bf16.hip: the bf16 copy), the way
-// grouped_select.h is the 16-entry kernels': the list and buffer sizes, the score kernel's body and the host path, one text
-// each.  A unit supplies its score chain (a policy, below), its kernels as one-line wrappers of rl_score_body and its entries.
+// The long-list family's header (retrieve_list.hip: the fp32 table; retrieve_list_bf16.hip: the bf16 copy; nearest_list.hip:
+// the fp32 table under a per-product bias), the way grouped_select.h is the 16-entry kernels': the list and buffer sizes, the
+// score kernel's body and the host path, one text each.  A unit supplies its score chain (a policy, below), its kernels as
+// one-line wrappers of rl_score_body and its entries.
 //
 // The kernel.  The contract, the plan, the work items and the chunks are retrieve.hip's; what differs is the selection.  There
 // every thread keeps a sorted list of 16 in registers; a list of 256 per thread is out of reach of the register file, and
@@ -58,8 +59,12 @@ void rl_merge_launch(const RgWs& w, const int32_t* types, int rows, const int32_
 //   score(q, b, c, h)                       the lane's part of the 16 x 16 scores of the tile against the wave's column
 //                                           group in the C/D map of the 16-row MFMAs: column lane & 15 (the candidate), row
 //                                           4 (lane >> 4) + reg (the query row)
-template <class Chain, int NE, bool EX>
-__device__ __forceinline__ void rl_score_body(RL_SCORE_PARAMS(typename Chain::Table)) {
+// BIAS: the score is fl(chain + bias[pid]), ONE fp32 addition behind the chain (the accumulator starts at zero, as without):
+// bias[pid] is a 4-byte gather per column, issued with the column's product id a chunk ahead (nb_score_kernel's scheme).  A
+// column past the slice's end (pid -1) reads bias[0]; nothing of it is used: its id in LDS is RG_NONE.  Without BIAS the
+// pointer is not read and the body is the text it was.
+template <class Chain, int NE, bool EX, bool BIAS = false>
+__device__ __forceinline__ void rl_score_body(RL_SCORE_PARAMS(typename Chain::Table), const float* __restrict__ bias = nullptr) {
     using B = typename Chain::B;
     constexpr int D = Chain::D, NB = Chain::NB;
     constexpr int TM = RL_TM;
@@ -114,6 +119,8 @@ __device__ __forceinline__ void rl_score_body(RL_SCORE_PARAMS(typename Chain::Ta
         int pidn = load_pid(cb0);
         load_b(bn, pidn);
         int pidnn = load_pid(cb0 + RG_CHUNK);
+        float bsn = 0.f;                                  // (BIAS) the term of the chunk in bn
+        if constexpr (BIAS) bsn = bias[max(pidn, 0)];
         __syncthreads();                                  // query image, counters and thresholds in LDS
 
         for (int cb = cb0;; cb += RG_CHUNK) {
@@ -123,10 +130,16 @@ __device__ __forceinline__ void rl_score_body(RL_SCORE_PARAMS(typename Chain::Ta
 #pragma unroll
                 for (int k = 0; k < NB; k++) b[k] = bn[k];
                 const int pid = pidn;
+                const float bs = bsn;
                 pidn = pidnn;
                 if (cb + RG_CHUNK < ce) load_b(bn, pidn); // the next chunk's rows in flight while this one is scored
                 pidnn = load_pid(cb + 2 * RG_CHUNK);
-                const f32x4 acc = Chain::score(q, b, c, h);
+                f32x4 acc = Chain::score(q, b, c, h);
+                if constexpr (BIAS) {
+#pragma unroll
+                    for (int k = 0; k < 4; k++) acc[k] = acc[k] + bs;     // the one addition: s = fl(d + bias[pid])
+                    bsn = bias[max(pidn, 0)];             // the next chunk's term: in flight through this chunk's selection
+                }
 #pragma unroll
                 for (int k = 0; k < 4; k++) sc[4 * h + k][wv * 16 + c] = acc[k];
                 if (h == 0) cid[wv * 16 + c] = pid < 0 ? RG_NONE : pid;
@@ -202,26 +215,27 @@ __device__ __forceinline__ void rl_score_body(RL_SCORE_PARAMS(typename Chain::Ta
 
 // The host path of an entry.  K names the unit's kernels: K::kernel<D, NE, EX>() is the score kernel over a table of T.
 // The entry looks at its lists before its counts (a list without keys is a caller's slip), then -- the bf16 entry's refusal
-// alone -- at the alignment a lane's 16-byte reads of a row need, then plans.
-template <class K, int D, int NE, class T>
+// alone -- at the alignment a lane's 16-byte reads of a row need, then plans.  more: what the unit's kernels take behind
+// bad_count (the biased unit's bias), required pointers of the entry like the table.
+template <class K, int D, int NE, class T, class... More>
 void rl_launch_score(dim3 grid, hipStream_t st, const float* proj, const int32_t* type_rowptr, const int32_t* type_col,
                      const T* table, int n_types, int n, int S, const RgWs& w, const int32_t* row_key, int rows,
-                     const int32_t* ex_rowptr, const int32_t* ex_col, int n_keys, int32_t* bad_count) {
+                     const int32_t* ex_rowptr, const int32_t* ex_col, int n_keys, int32_t* bad_count, More... more) {
     const RgPlan& pl = w.plan;
     if (row_key)
         PC_LAUNCH((K::template kernel<D, NE, true>()), grid, dim3(256), 0, st, proj, type_rowptr, type_col, table, n_types, n, S,
-                  pl.cnt, pl.row_start, pl.item_start, pl.order, w.pv, w.pi, row_key, rows, ex_rowptr, ex_col, n_keys, bad_count);
+                  pl.cnt, pl.row_start, pl.item_start, pl.order, w.pv, w.pi, row_key, rows, ex_rowptr, ex_col, n_keys, bad_count, more...);
     else
         PC_LAUNCH((K::template kernel<D, NE, false>()), grid, dim3(256), 0, st, proj, type_rowptr, type_col, table, n_types, n, S,
-                  pl.cnt, pl.row_start, pl.item_start, pl.order, w.pv, w.pi, row_key, rows, ex_rowptr, ex_col, n_keys, bad_count);
+                  pl.cnt, pl.row_start, pl.item_start, pl.order, w.pv, w.pi, row_key, rows, ex_rowptr, ex_col, n_keys, bad_count, more...);
 }
 
-template <class K, class T>
+template <class K, class T, class... More>
 int rl_list_entry(const float* proj, const int32_t* types, const int32_t* row_key, int rows, const int32_t* type_rowptr,
                   const int32_t* type_col, const T* table, int n_types, const int32_t* ex_rowptr, const int32_t* ex_col, int n_keys,
                   int n, int dim, int slices, int32_t* out_idx, float* out_score, int32_t* bad_count, void* ws, size_t ws_bytes,
-                  void* stream) {
-    PC_TRY(rg_topn_check(proj && types && type_rowptr && type_col && table && out_idx && out_score && ws &&
+                  void* stream, More... more) {
+    PC_TRY(rg_topn_check(proj && types && type_rowptr && type_col && table && (true && ... && more) && out_idx && out_score && ws &&
                              rg_lists_ok(row_key, ex_rowptr, ex_col, bad_count, n_keys),
                          rows, n_types, true, n, RL_MAX_N, dim, slices));
     if (std::is_same<T, uint16_t>::value && ((uintptr_t)table & 15)) return PC_ESHAPE;
@@ -231,7 +245,7 @@ int rl_list_entry(const float* proj, const int32_t* types, const int32_t* row_ke
     unsigned grid;
     PC_TRY(rg_begin(w, grid, ws, ws_bytes, types, nullptr, rows, type_rowptr, n_types, 0, n, S, RL_TM, nullptr, nullptr, st));
 #define RL_SCORE(D, NE) \
-    rl_launch_score<K, D, NE>(dim3(grid), st, proj, type_rowptr, type_col, table, n_types, n, S, w, row_key, rows, ex_rowptr, ex_col, n_keys, bad_count)
+    rl_launch_score<K, D, NE>(dim3(grid), st, proj, type_rowptr, type_col, table, n_types, n, S, w, row_key, rows, ex_rowptr, ex_col, n_keys, bad_count, more...)
     if (dim == 128) {
         if (n <= RL_N2) RL_SCORE(128, 2);
         else if (n <= RL_N4) RL_SCORE(128, 4);

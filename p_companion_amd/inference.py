@@ -26,7 +26,8 @@ recommend_batch's own pool.  SimilarProducts.similar_capped_batch does the same 
 
 SimilarProducts is the substitute side: the nearest products of a query under Euclidean distance over any [P, D] fp32 table
 (Product2Vec's export), the grouped retrieval and rank with the per-product term -|e_p|^2 / 2 on the score
-(pc_retrieve_topk_grouped_biased / pc_rank_grouped_biased), and hit@k / MRR over held-out similar pairs.
+(pc_retrieve_topk_grouped_biased / pc_rank_grouped_biased), and hit@k / MRR over held-out similar pairs.  similar_list_batch
+serves up to 256 neighbours (pc_retrieve_list_grouped_biased) and similar_capped_list_batch caps groups over such a pool.
 IndexedSimilarProducts serves its whole-catalogue scope through a k-means cell index (ops.build_cell_index): the same retrieval
 over the products of a query's nearest cells, the probe lists of a query merged by pc_merge_lists."""
 import os
@@ -543,7 +544,9 @@ class SimilarProducts(_CandidateFilters):
     one type (rowptr = [0, P], col = arange(P)).
     By default the query itself is excluded (set_exclusions() over an empty CSR with include_self), so a product is never its
     own neighbour; the co-view graph is NOT excluded -- co-viewed products are the substitutes being looked for.
-    set_exclusions(False) removes the set; set_eligible(mask) serves and ranks over the eligible products only."""
+    set_exclusions(False) removes the set; set_eligible(mask) serves and ranks over the eligible products only.
+    similar_batch / similar_capped_batch serve up to MAX_N = 16 (the 16-entry biased retrieval), similar_list_batch /
+    similar_capped_list_batch up to MAX_LIST = 256 (ops.retrieve_list_grouped_biased): the same score bits and order."""
 
     MAX_N = 16
 
@@ -609,21 +612,73 @@ class SimilarProducts(_CandidateFilters):
         the NEGATED distances, so nearer is better and equal distances go to the lower product index, with
         row_ban = group[query_idx] unless own_group.  Returns (idx [B, n] int32, dist [B, n] fp32), the distances those
         similar_batch reported for the same ids, -1 / +inf past the end.  1 <= n <= 16.
-        THE LIMIT: the pool is 16 products, because the biased retrieval entries serve at most 16.  In a heavily varianted
-        neighbourhood most of the 16 are the query's own variants or share a few groups, and the list comes back SHORT (even
-        empty) although the catalogue holds further neighbours; a longer substitute pool needs a biased long-list entry."""
+        THE LIMIT: the pool is 16 products, because this method's pool is the 16-entry biased retrieval's.  In a heavily
+        varianted neighbourhood most of the 16 are the query's own variants or share a few groups, and the list comes back SHORT
+        (even empty) although the catalogue holds further neighbours.  similar_capped_list_batch is the same rule over a pool of
+        up to MAX_LIST = 256 candidates (the biased long-list entry, ops.retrieve_list_grouped_biased): use it where the
+        neighbourhoods are varianted."""
         n = int(n)
         if not 1 <= n <= self.MAX_N:
             raise ValueError(f"similar_capped_batch: 1 to {self.MAX_N} neighbours per query, got {n}")
-        cap = _check_group("similar_capped_batch", group, cap)
-        self._group_covers("similar_capped_batch", group)
-        query_idx = self._queries("similar_capped_batch", query_idx)
+        return self._capped("similar_capped_batch", self.similar_batch, query_idx, n, group, cap, own_group, self.MAX_N)
+
+    def _capped(self, what, pool_of, query_idx, n, group, cap, own_group, pool):
+        """The group cap's rule on the `pool` nearest candidates that pool_of(query_idx, pool) serves (similar_capped_batch)."""
+        cap = _check_group(what, group, cap)
+        self._group_covers(what, group)
+        query_idx = self._queries(what, query_idx)
         if query_idx.shape[0] == 0:
             return self._no_neighbours(n)
-        idx, dist = self.similar_batch(query_idx, self.MAX_N)
+        idx, dist = pool_of(query_idx, pool)
         ban = group[query_idx.long()].contiguous() if group is not None and not own_group else None
         idx, near = ops.cap_lists(idx, -dist, n, group, cap, row_ban=ban)
         return idx, -near
+
+    MAX_LIST = 256                    # ops.RETRIEVE_LIST_MAX_N: what the biased long-list entry serves
+    DIST_BYTES = 64 << 20             # similar_list_batch: the bytes of ONE [queries, n, D] fp32 temporary of the distances
+
+    @torch.no_grad()
+    def similar_list_batch(self, query_idx: torch.Tensor, n: int = 64):
+        """similar_batch's contract for 1 <= n <= MAX_LIST = 256: (idx [B, n] int32, -1 past the end; dist [B, n] fp32, +inf
+        past the end), nearest first, through ops.retrieve_list_grouped_biased -- the same score bits and total order, so for
+        n <= 16 ids and distances are similar_batch's bit for bit.  The distances are recomputed as there, over chunks of
+        DIST_BYTES / (4 n D) queries: the gathered rows [B, n, D] and their differences are 0.5 GB each at B = 4096, n = 256,
+        D = 128 unchunked, and at most DIST_BYTES = 64 MiB each here; a row's distance does not depend on its chunk."""
+        n = self._list_length("similar_list_batch", n)
+        query_idx = self._queries("similar_list_batch", query_idx)
+        if query_idx.shape[0] == 0:
+            return self._no_neighbours(n)
+        q = self.table[query_idx.long()]
+        idx, _ = ops.retrieve_list_grouped_biased(q, self._scope_type[query_idx.long()].contiguous(), self.type_rowptr,
+                                                  self.type_col, self.table, self.bias, n, exclude=self._exclude_rows(query_idx))
+        return idx, self._list_distances(q, idx)
+
+    @torch.no_grad()
+    def similar_capped_list_batch(self, query_idx: torch.Tensor, n: int = 10, group: torch.Tensor = None, cap: int = 1,
+                                  own_group: bool = False, pool: int = 64):
+        """similar_capped_batch's rule over a longer pool: ops.cap_lists on the negated reported distances of this object's
+        similar_list_batch(query_idx, pool), row_ban = group[query_idx] unless own_group.  1 <= n <= pool <= MAX_LIST = 256.
+        Returns (idx [B, n] int32, dist [B, n] fp32), -1 / +inf past the end: a list is short only where the pool itself holds
+        fewer than n products that the cap lets through."""
+        n, pool = int(n), int(pool)
+        if not 1 <= n <= pool <= self.MAX_LIST:
+            raise ValueError(f"similar_capped_list_batch: 1 <= n <= pool <= {self.MAX_LIST} neighbours per query, got n = {n}, "
+                             f"pool = {pool}")
+        return self._capped("similar_capped_list_batch", self.similar_list_batch, query_idx, n, group, cap, own_group, pool)
+
+    def _list_length(self, what, n):
+        """n of similar_list_batch as an int; outside 1 .. MAX_LIST: ValueError, before anything of the object is read."""
+        n = int(n)
+        if not 1 <= n <= self.MAX_LIST:
+            raise ValueError(f"{what}: 1 to {self.MAX_LIST} neighbours per query, got {n}")
+        return n
+
+    def _list_distances(self, q, idx):
+        """_distances over chunks of queries whose [rows, n, D] fp32 temporaries hold at most DIST_BYTES each."""
+        rows = max(1, self.DIST_BYTES // (4 * idx.shape[1] * q.shape[1]))
+        if q.shape[0] <= rows:
+            return self._distances(q, idx)
+        return torch.cat([self._distances(q[lo:lo + rows], idx[lo:lo + rows]) for lo in range(0, q.shape[0], rows)])
 
     def _neighbours(self, n):
         """n of similar_batch as an int; outside 1 .. MAX_N: ValueError, before anything of the object is read."""
@@ -755,14 +810,20 @@ class IndexedSimilarProducts(SimilarProducts):
         cells, _ = ops.retrieve_topk_grouped(q, zeros, rowptr, col, self.index.centroids, nprobe, bias=self.index.centroid_bias)
         return cells
 
-    def _search(self, query_idx, q, n, nprobe):
+    def _search(self, query_idx, q, n, nprobe, long=False):
         """(idx [B, n] int32, score [B, n] fp32 = the biased retrieval's own score bits; -1 / -inf past the end) of the checked
-        queries query_idx [B] int32 with rows q [B, D]: steps 1 to 3 of similar_batch."""
+        queries query_idx [B] int32 with rows q [B, D]: steps 1 to 3 of similar_batch; long: of similar_list_batch (step 2
+        through the biased long-list entry, n up to MAX_LIST)."""
         b = q.shape[0]
         cells = self._probe(q, nprobe)                                            # [B, nprobe]
         rows = q.repeat_interleave(nprobe, dim=0)                                 # [B nprobe, D]
-        idx, score = ops.retrieve_topk_grouped(rows, cells.reshape(-1), self.cell_rowptr, self.cell_col, self.table, n,
-                                               exclude=self._exclude_rows(query_idx, nprobe), bias=self.bias)
+        exclude = self._exclude_rows(query_idx, nprobe)
+        if long:
+            idx, score = ops.retrieve_list_grouped_biased(rows, cells.reshape(-1), self.cell_rowptr, self.cell_col, self.table,
+                                                          self.bias, n, exclude=exclude)
+        else:
+            idx, score = ops.retrieve_topk_grouped(rows, cells.reshape(-1), self.cell_rowptr, self.cell_col, self.table, n,
+                                                   exclude=exclude, bias=self.bias)
         return ops.merge_lists(idx.view(b, nprobe, n), score.view(b, nprobe, n))
 
     @torch.no_grad()
@@ -789,6 +850,20 @@ class IndexedSimilarProducts(SimilarProducts):
         q = self.table[query_idx.long()]
         idx, _ = self._search(query_idx, q, n, nprobe)
         return idx, self._distances(q, idx)
+
+    @torch.no_grad()
+    def similar_list_batch(self, query_idx: torch.Tensor, n: int = 64, nprobe: int = None):
+        """similar_batch's four steps for 1 <= n <= MAX_LIST = 256, the grouped retrieval over the B nprobe rows through the
+        biased long-list entry (ops.merge_lists takes lists of up to 256): the parent's similar_list_batch restricted to the
+        probed cells' products, and with nprobe == n_cells that list bit for bit.  The distances are the parent's, chunked."""
+        n = self._list_length("similar_list_batch", n)
+        nprobe = self._check_nprobe("similar_list_batch", self.nprobe if nprobe is None else nprobe, self.n_cells)
+        query_idx = self._queries("similar_list_batch", query_idx)
+        if query_idx.shape[0] == 0:
+            return self._no_neighbours(n)
+        q = self.table[query_idx.long()]
+        idx, _ = self._search(query_idx, q, n, nprobe, long=True)
+        return idx, self._list_distances(q, idx)
 
     @torch.no_grad()
     def recall(self, query_idx: torch.Tensor, n: int = 10, nprobe: int = None):

@@ -2095,6 +2095,22 @@ def retrieve_list_grouped(proj, types, type_rowptr, type_col, table, n, slices=0
                              table_dtype=torch.bfloat16 if bf16 else torch.float32)
 
 
+def retrieve_list_grouped_biased(proj, types, type_rowptr, type_col, table, bias, n, slices=0, exclude=None, bad=None):
+    """pc_retrieve_list_grouped_biased: retrieve_list_grouped's contract (idx [R,n] int32, -1 = none; scores [R,n] fp32, -inf =
+    none; 1 <= n <= RETRIEVE_LIST_MAX_N; exclude and `bad` as there) under retrieve_topk_grouped(bias=)'s score
+    fl(<proj[r], table[p]> + bias[p]) -- one fp32 addition after retrieve_list_grouped's own chain.  bias: a [P] fp32 device
+    tensor beside an fp32 table; half_sq_norm_bias(table) makes the order Euclidean.  The same kernel body, merge and
+    determinism: the same bits for every `slices`; for n <= 16 retrieve_topk_grouped(bias=)'s own bits, with a zero bias
+    retrieve_list_grouped's, and rank_grouped(bias=) < n exactly when the list holds the target at that position.  Nothing is
+    read back to the host."""
+    n = int(n)
+    if not 1 <= n <= RETRIEVE_LIST_MAX_N:
+        raise ValueError(f"retrieve_list_grouped_biased: n must be in [1, {RETRIEVE_LIST_MAX_N}], got {n}")
+    _check_bias("retrieve_list_grouped_biased", bias, table)
+    return _retrieve_grouped("pc_retrieve_list_grouped_biased", proj, types, type_rowptr, type_col, table, n, slices, exclude, bad,
+                             bias=bias, what="retrieve_list_grouped_biased", tag="retrieve_list")
+
+
 def rank_grouped(proj, types, targets, type_rowptr, type_col, table, slices=0, bad=None, exclude=None, cand_type=None,
                  bias=None):
     """pc_rank_grouped: for row r the number of products of type types[r] that retrieve_topk_grouped orders in front of
