@@ -1437,6 +1437,52 @@ int pc_retrieve_list_grouped_biased(const float *proj, const int32_t *types, con
                                     int n_keys, int n, int dim, int slices, int32_t *out_idx, float *out_score,
                                     int32_t *bad_count, void *ws, size_t ws_bytes, void *stream);
 
+/* Ranks and substitutes from the bf16 copy alone (ABI 8, additive; csrc/rank_bf16.hip, csrc/nearest_list_bf16.hip;
+ * ops.rank_grouped_bf16, ops.retrieve_list_grouped_bf16_biased, ops.half_sq_norm_bias_bf16; inference.CompactInference and
+ * inference.CompactSimilarProducts): a deployment that gave the fp32 table back measures hit@k / MRR of what it serves and
+ * serves Euclidean neighbours, over the stored (rounded) rows.  table_bf16 [num_products, dim] everywhere: bf16 bit patterns,
+ * row-major, 16-byte aligned, dim 128 or 256 (pc_retrieve_topk_grouped_bf16's table).  The score of row r and product p is
+ *   s(r, p) = fl(d(r, p) + bias[p]),  d(r, p) = pc_retrieve_topk_grouped_bf16's own chain (the unrounded fp32 query split into
+ * three bf16 pieces, k-block by k-block on v_mfma_f32_16x16x32_bf16 into one accumulator), one fp32 addition after the chain
+ * (the accumulator starts at zero); bias [num_products] fp32.
+ *
+ * pc_half_sq_norm_bias_bf16: out[p] = -0.5f * sum_d e[p][d]^2 over the stored rows, in pc_half_sq_norm_bias's summation order
+ * (16 partial sums over the dimensions 4 l + 64 j + e, met in a butterfly over the lane distances 8, 4, 2, 1): bit for bit
+ * pc_half_sq_norm_bias on the widened table, which is never formed.  PC_EINVAL: null pointer, rows <= 0; PC_ESHAPE: dim not
+ * 128 / 256, table_bf16 not 8-byte aligned.
+ *
+ * pc_retrieve_list_grouped_bf16_biased: pc_retrieve_list_grouped_biased's contract and argument list over table_bf16, for
+ * 1 <= n <= 256 (it serves n <= 16 too: there is no 16-entry biased bf16 entry).  pc_retrieve_list_grouped_bf16's kernel body,
+ * merge and host path with the body's bias hook: with a zero bias the output is pc_retrieve_list_grouped_bf16's bit for bit;
+ * out_score = fl(that entry's score + bias[p]); the same bits for every `slices`, placement of the rows and order of type_col
+ * inside a type.  Error codes as pc_retrieve_list_grouped_biased, and PC_ESHAPE for a table_bf16 that is not 16-byte aligned.
+ * Workspace: pc_retrieve_list_grouped_bf16_biased_workspace_bytes (pc_retrieve_list_grouped's size).
+ *
+ * pc_rank_grouped_bf16: pc_rank_grouped_biased's contract and argument list over table_bf16, with a bias that may be NULL
+ * (then s = d): rank_out[r] = #{ p of type types[r], not in the row's list : s_p > g or (s_p == g and p < y) }, g = s(r, y),
+ * y = targets[r]; row_key, ex_rowptr, ex_col and cand_type all four or none; with them rank_out[r] = -1 where the target is in
+ * the row's list or cand_type[y] != types[r]; -1 and *bad_count for rows without a type or with an id out of range as
+ * pc_rank_grouped.  A (row, product) score has the bits pc_retrieve_topk_grouped_bf16, pc_retrieve_list_grouped_bf16 and, with
+ * a bias, pc_retrieve_list_grouped_bf16_biased give it: rank_out[r] < n exactly when that list (same bias, same lists) holds
+ * the target at that position.  pc_rank_grouped's plan, work items and count (integer atomics, one per (row, slice)); the same
+ * result for every `slices`; no float atomics, no host readback.  Workspace: pc_rank_grouped_bf16_workspace_bytes
+ * (pc_rank_grouped's size).  PC_EINVAL: null pointer (bias apart), rows, n_types or num_products <= 0, n_keys < 0, half-given
+ * exclusion arguments; PC_ESHAPE: dim not 128 / 256, slices outside [0, 64], table_bf16 not 16-byte aligned; PC_EWORKSPACE:
+ * ws_bytes too small -- each checked before anything is launched. */
+int pc_half_sq_norm_bias_bf16(const uint16_t *table_bf16, int rows, int dim, float *out, void *stream);
+size_t pc_retrieve_list_grouped_bf16_biased_workspace_bytes(int rows, int n_types, int n, int slices);
+int pc_retrieve_list_grouped_bf16_biased(const float *proj, const int32_t *types, const int32_t *row_key, int rows,
+                                         const int32_t *type_rowptr, const int32_t *type_col, const uint16_t *table_bf16,
+                                         const float *bias, int n_types, const int32_t *ex_rowptr, const int32_t *ex_col,
+                                         int n_keys, int n, int dim, int slices, int32_t *out_idx, float *out_score,
+                                         int32_t *bad_count, void *ws, size_t ws_bytes, void *stream);
+size_t pc_rank_grouped_bf16_workspace_bytes(int rows, int n_types, int slices);
+int pc_rank_grouped_bf16(const float *proj, const int32_t *types, const int32_t *targets, const int32_t *row_key, int rows,
+                         const int32_t *type_rowptr, const int32_t *type_col, const uint16_t *table_bf16, const float *bias,
+                         int n_types, int num_products, const int32_t *ex_rowptr, const int32_t *ex_col, int n_keys,
+                         const int32_t *cand_type, int dim, int slices, int32_t *rank_out, int32_t *bad_count, void *ws,
+                         size_t ws_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -251,6 +251,16 @@ SIGNATURES = {
     "pc_retrieve_list_grouped_biased_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "pc_retrieve_list_grouped_biased": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp,
                                              _vp, _sz, _vp]),
+    # ranks and substitutes from the bf16 copy alone (csrc/rank_bf16.hip: rank.hip's schedule and count under
+    # retrieve_bf16.hip's chain; csrc/nearest_list_bf16.hip: grouped_list.h's body over the bf16 chain with its bias hook; the
+    # biased fp32 entries' lists with the bf16 table; ABI 8, additive)
+    "pc_half_sq_norm_bias_bf16": (_i, [_vp, _i, _i, _vp, _vp]),
+    "pc_retrieve_list_grouped_bf16_biased_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "pc_retrieve_list_grouped_bf16_biased": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _vp, _vp,
+                                                  _vp, _vp, _sz, _vp]),
+    "pc_rank_grouped_bf16_workspace_bytes": (_sz, [_i, _i, _i]),
+    "pc_rank_grouped_bf16": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _vp, _i, _i, _vp, _vp, _vp,
+                                  _sz, _vp]),
     "pc_hadamard_forward":(_i, [_vp, _vp, _i, _i, _vp, _vp]),
     "pc_hadamard_forward_dim": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
     "pc_hadamard_backward": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp]),

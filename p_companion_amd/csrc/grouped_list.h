@@ -1,7 +1,7 @@
 // The long-list family's header (retrieve_list.hip: the fp32 table; retrieve_list_bf16.hip: the bf16 copy; nearest_list.hip:
-// the fp32 table under a per-product bias), the way grouped_select.h is the 16-entry kernels': the list and buffer sizes, the
-// score kernel's body and the host path, one text each.  A unit supplies its score chain (a policy, below), its kernels as
-// one-line wrappers of rl_score_body and its entries.
+// the fp32 table under a per-product bias; nearest_list_bf16.hip: the bf16 copy under one), the way grouped_select.h is the
+// 16-entry kernels': the list and buffer sizes, the score kernel's body and the host path, one text each.  A unit supplies its
+// score chain (a policy, below), its kernels as one-line wrappers of rl_score_body and its entries.
 //
 // The kernel.  The contract, the plan, the work items and the chunks are retrieve.hip's; what differs is the selection.  There
 // every thread keeps a sorted list of 16 in registers; a list of 256 per thread is out of reach of the register file, and

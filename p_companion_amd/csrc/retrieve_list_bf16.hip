@@ -1,7 +1,7 @@
 // Long complement lists from the bf16 copy of the catalogue: the first n <= 256 products of a type per (query, type) row over
 // a [P, D] bf16 table (pc_retrieve_list_grouped_bf16; PCompanionInference with an ops.CompactCatalogue, recommend_batch above
 // 16).  The kernel's body and the host path are grouped_list.h's, the merge is rl_merge_kernel (retrieve_list.hip) through
-// rl_merge_launch; here are the bf16 score chain, the kernels under their names and the entries.
+// rl_merge_launch, the bf16 score chain grouped_list_bf16.h's; here are the kernels under their names and the entries.
 //
 // Determinism: the chain of a (row, product) pair is k-block 0 .. D / 32 - 1, inside a k-block the pieces p0, p1, p2, one
 // v_mfma_f32_16x16x32_bf16 each into ONE accumulator, inside an MFMA k-lane h and element e cover dimension 32 k + 8 h + e: its
@@ -12,47 +12,7 @@
 // so it never moves a threshold.  Hence the output does not depend on the slices, the rows' places, the order of type_col or
 // the arrival order; for n <= 16 it is pc_retrieve_topk_grouped_bf16's bit for bit.  No float atomics, nothing read back.
 #include "common.h"
-#include "grouped_list.h"
-
-// retrieve_bf16.hip's chain (rg_score_bf16_kernel) at one 16-row group: the fp32 query tile is split ONCE per work item by
-// split3 into the pieces p0, p1, p2, each an image of [D / 8][16] operands of 16 bytes (12 KB at D = 128, 24 KB at D = 256; with
-// 16 rows the sixteen lanes c at one k-lane h read sixteen consecutive operands, so there is no padding); lane (c, h) holds the
-// 8 dimensions 32 k + 8 h .. + 7 of candidate c for every k-block k.  LDS at NE = 8: 58 KB of buffers, 12 / 24 KB of images,
-// 4 KB of scores.
-template <int D_>
-struct RlChainBf16 {
-    static constexpr int D = D_, NB = D / 32;
-    using Table = uint16_t;
-    using B = bf16x8;
-    using Q = bf16x8[3][(D / 8) * RL_TM];
-    static __device__ __forceinline__ void load_tile(Q& q, const float* __restrict__ proj, const int32_t* __restrict__ order,
-                                                     int p0, int valid, int tid) {
-        for (int e = tid; e < RL_TM * (D / 8); e += 256) {
-            const int d8 = e / RL_TM, row = e - d8 * RL_TM;           // (row fastest: a wave's 16-byte stores are contiguous)
-            float4 x0 = make_float4(0.f, 0.f, 0.f, 0.f), x1 = x0;
-            if (row < valid) {
-                const float4* f = reinterpret_cast<const float4*>(proj + (size_t)order[p0 + row] * D) + 2 * d8;
-                x0 = f[0];
-                x1 = f[1];
-            }
-            const Split3 sp = split3(x0, x1);
-            q[0][d8 * RL_TM + row] = sp.p0;
-            q[1][d8 * RL_TM + row] = sp.p1;
-            q[2][d8 * RL_TM + row] = sp.p2;
-        }
-    }
-    static __device__ __forceinline__ B zero() { return bf16x8{0, 0, 0, 0, 0, 0, 0, 0}; }
-    static __device__ __forceinline__ f32x4 score(const Q& q, const B* b, int c, int h) {
-        f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int k = 0; k < NB; k++) {
-#pragma unroll
-            for (int p = 0; p < 3; p++)
-                acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(q[p][(4 * k + h) * RL_TM + c], b[k], acc, 0, 0, 0);
-        }
-        return acc;
-    }
-};
+#include "grouped_list_bf16.h"     // RlChainBf16: the bf16 score chain (nearest_list_bf16.hip scores through it too)
 
 template <int D, int NE, bool EX>
 __global__ __launch_bounds__(256) void rl_score_bf16_kernel(RL_SCORE_PARAMS(uint16_t)) {

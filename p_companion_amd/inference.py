@@ -19,7 +19,10 @@ scored against the unrounded query; the scores are those of the ROUNDED table.
 recommend_diverse_batch re-ranks recommend_batch's long list for diversity inside a type, on the device: a greedy maximal-
 marginal-relevance pick of the products to show (pc_diversify_lists over the fp32 features, pc_inv_norm for the cosine).
 catalogue=ops.CompactCatalogue(...) serves both from the bf16 copy alone -- lists of up to 256 (pc_retrieve_list_grouped_bf16)
-and diversified lists (pc_diversify_lists_bf16, pc_inv_norm_bf16); ranks still need the fp32 catalogue.
+and diversified lists (pc_diversify_lists_bf16, pc_inv_norm_bf16); on this class ranks still need the fp32 catalogue.
+CompactInference is the same object with rank_targets / evaluate_catalogue over the bf16 copy (pc_rank_grouped_bf16): it measures
+what it serves, over the rounded table; rank_targets reads no fp32 features (evaluate_catalogue's dataset still wants a graph
+that holds them: see the class).
 recommend_capped_batch keeps at most `cap` products of one product group (a parent item, a brand, a seller) in a list, and
 recommend_page_batch merges a query's K lists into one row under a per-type quota and that cap: one pc_cap_lists pass over
 recommend_batch's own pool.  SimilarProducts.similar_capped_batch does the same for substitutes, without the query's variants.
@@ -28,6 +31,8 @@ SimilarProducts is the substitute side: the nearest products of a query under Eu
 (Product2Vec's export), the grouped retrieval and rank with the per-product term -|e_p|^2 / 2 on the score
 (pc_retrieve_topk_grouped_biased / pc_rank_grouped_biased), and hit@k / MRR over held-out similar pairs.  similar_list_batch
 serves up to 256 neighbours (pc_retrieve_list_grouped_biased) and similar_capped_list_batch caps groups over such a pool.
+CompactSimilarProducts is SimilarProducts over the bf16 copy of the table alone (pc_retrieve_list_grouped_bf16_biased,
+pc_rank_grouped_bf16, pc_half_sq_norm_bias_bf16): distances to the stored rows, no fp32 table.
 IndexedSimilarProducts serves its whole-catalogue scope through a k-means cell index (ops.build_cell_index): the same retrieval
 over the products of a query's nearest cells, the probe lists of a query merged by pc_merge_lists."""
 import os
@@ -414,6 +419,17 @@ class PCompanionInference(_CandidateFilters):
         types = torch.where(idx >= 0, self.type_idx[idx.clamp(min=0).long()].long(), -1)
         return idx, sc, types
 
+    def _rank_guard(self, what):
+        """rank_targets and evaluate_catalogue ask here first: a bf16 catalogue is refused, before the model runs or the
+        dataset is looked at (CompactInference, which ranks over the bf16 table, lets it pass)."""
+        if self.catalogue is not None:
+            raise ValueError(f"{what}: the rank kernels read the fp32 catalogue (catalogue=None); a bf16 catalogue serves "
+                             "recommend_batch / recommend up to 16 per type")
+
+    def _rank_entry(self):
+        """(the ops function the ranks go through, the table it reads)"""
+        return ops.rank_grouped, self.features
+
     @torch.no_grad()
     def rank_targets(self, query_idx: torch.Tensor, target_idx: torch.Tensor, take: torch.Tensor = None):
         """Where does target_idx[b] stand in what is served for query_idx[b]?  The model runs in eval mode on the queries;
@@ -424,9 +440,8 @@ class PCompanionInference(_CandidateFilters):
         they keep out are not counted, and a target they keep out has rank -1 (its slot stays).  A target outside the catalogue has no type:
         slot -1, rank -1.  `take` [B] bool (optional): rows that are False get slot -1 / rank -1 and cost no search.
         Returns (slot int32 [B], rank int32 [B]) on the device; nothing is read back."""
-        if self.catalogue is not None:
-            raise ValueError("rank_targets: the rank kernels read the fp32 catalogue (catalogue=None); a bf16 catalogue serves "
-                             "recommend_batch / recommend up to 16 per type")
+        self._rank_guard("rank_targets")
+        rank_grouped, table = self._rank_entry()
         query_idx = query_idx.to(self.device).to(torch.int32).contiguous()
         target_idx = target_idx.to(self.device).to(torch.int32).contiguous()
         if query_idx.dim() != 1 or query_idx.shape != target_idx.shape:
@@ -437,8 +452,8 @@ class PCompanionInference(_CandidateFilters):
             return e, e.clone()
         out = self.model({"query_idx": query_idx, "query_types": self.type_idx[query_idx.long()]})
         types = out["complementary_types"]                                        # [B, K], distinct in a row
-        inside = (target_idx >= 0) & (target_idx < self.features.shape[0])
-        target_type = self.type_idx[target_idx.long().clamp(0, self.features.shape[0] - 1)].long()
+        inside = (target_idx >= 0) & (target_idx < table.shape[0])
+        target_type = self.type_idx[target_idx.long().clamp(0, table.shape[0] - 1)].long()
         match = (types == target_type[:, None]) & inside[:, None]
         if take is not None:
             match &= take.to(self.device).bool()[:, None]
@@ -450,12 +465,12 @@ class PCompanionInference(_CandidateFilters):
         exclude = self._exclude_rows(query_idx)
         if exclude is not None:
             # a target in the query's list, or not eligible: -1 from the entry itself
-            rank, _ = ops.rank_grouped(proj, row_type, target_idx, self.type_rowptr, self.type_col, self.features,
-                                       exclude=exclude, cand_type=self.cand_type)
+            rank, _ = rank_grouped(proj, row_type, target_idx, self.type_rowptr, self.type_col, table, exclude=exclude,
+                                   cand_type=self.cand_type)
             return slot, rank
-        rank, _ = ops.rank_grouped(proj, row_type, target_idx, self.type_rowptr, self.type_col, self.features)
+        rank, _ = rank_grouped(proj, row_type, target_idx, self.type_rowptr, self.type_col, table)
         if self.eligible is not None:
-            kept = self.eligible[target_idx.long().clamp(0, self.features.shape[0] - 1)]
+            kept = self.eligible[target_idx.long().clamp(0, table.shape[0] - 1)]
             rank = torch.where(kept, rank, torch.full_like(rank, -1))
         return slot, rank
 
@@ -472,9 +487,7 @@ class PCompanionInference(_CandidateFilters):
         served; a pair whose target the filters keep out (it is in its query's list, or not eligible) is a miss -- it keeps its
         slot, its rank is -1 -- and the dict gains "filtered_targets", the number of such pairs."""
         bpg = self.bpg
-        if self.catalogue is not None:
-            raise ValueError("evaluate_catalogue: the rank kernels read the fp32 catalogue (catalogue=None); a bf16 catalogue "
-                             "serves recommend_batch / recommend up to 16 per type")
+        self._rank_guard("evaluate_catalogue")
         if isinstance(bpg, DeviceBPG) and bpg.world != 1:
             raise ValueError(f"evaluate_catalogue: this DeviceBPG holds a cyclic 1/{bpg.world} shard of the features")
         if not isinstance(dataset, ComplementaryIndexDataset) or dataset.bpg is not bpg:
@@ -530,6 +543,31 @@ class PCompanionInference(_CandidateFilters):
         return {"complementary_types": types.tolist(), "recommendations": recommendations, "scores": scores}
 
 
+class CompactInference(PCompanionInference):
+    """PCompanionInference over an ops.CompactCatalogue that also RANKS from the bf16 copy: rank_targets and evaluate_catalogue
+    go through ops.rank_grouped_bf16 (pc_rank_grouped_bf16), whose (row, product) scores are the bits recommend_batch's
+    entries order by -- pc_retrieve_topk_grouped_bf16 up to 16, pc_retrieve_list_grouped_bf16 up to 256.  So rank < n exactly
+    when recommend_batch(q, n) of this object holds the target at that position, evaluate_catalogue's hit@k for k <= 256
+    describes recommend_batch(q, k) exactly, and both are measured over the ROUNDED table that is served.  No fp32 features are read by this object, and a DeviceBPG generated
+    without them is accepted: recommend_batch and rank_targets (folded by Metrics.catalogue_metrics over the caller's own pairs)
+    run on such a graph.  evaluate_catalogue takes a ComplementaryIndexDataset over the SAME graph object, and that dataset
+    refuses a DeviceBPG without features: over a device graph it runs only while the graph still holds them.
+    set_exclusions / set_eligible work as in the parent.
+    A class of its own: PCompanionInference keeps refusing ranks with any bf16 catalogue."""
+
+    def __init__(self, model, config, bpg, product_ids=None, catalogue=None):
+        if not isinstance(catalogue, ops.CompactCatalogue):
+            raise ValueError(f"CompactInference: catalogue must be an ops.CompactCatalogue, got "
+                             f"{type(catalogue).__name__}; PCompanionInference serves the other catalogues")
+        super().__init__(model, config, bpg, product_ids, catalogue=catalogue)
+
+    def _rank_guard(self, what):
+        pass
+
+    def _rank_entry(self):
+        return ops.rank_grouped_bf16, self.catalogue
+
+
 class SimilarProducts(_CandidateFilters):
     """Substitutes: the nearest products of a query under Euclidean distance over an embedding table -- the order Product2Vec's
     triplet loss trains for.  |q - e_p|^2 = |q|^2 - 2 (<q, e_p> - |e_p|^2 / 2), so the nearest product is the largest
@@ -553,13 +591,7 @@ class SimilarProducts(_CandidateFilters):
     def __init__(self, table, bpg, scope="type"):
         if scope not in ("type", "catalogue"):
             raise ValueError(f"SimilarProducts: scope must be 'type' or 'catalogue', got {scope!r}")
-        if not torch.is_tensor(table) or table.dtype != torch.float32:
-            raise ValueError(f"SimilarProducts: the table must be a [P, D] float32 device tensor, got "
-                             f"{table.dtype if torch.is_tensor(table) else type(table).__name__}")
-        if table.dim() != 2 or table.shape[1] not in (128, 256) or table.shape[0] < 1:
-            raise ValueError(f"SimilarProducts: the table must be [P, 128 or 256], got {tuple(table.shape)}")
-        if not table.is_cuda or not table.is_contiguous():
-            raise ValueError("SimilarProducts: the table must be a contiguous device tensor")
+        table = self._check_table(table)
         if isinstance(bpg, DeviceBPG) and bpg.world != 1:
             raise ValueError(f"SimilarProducts: this DeviceBPG holds a cyclic 1/{bpg.world} shard (rank {bpg.rank}); serving "
                              "needs the whole catalogue on one device -- generate it with world = 1")
@@ -578,8 +610,38 @@ class SimilarProducts(_CandidateFilters):
                                   torch.arange(p, dtype=torch.int32, device=self.device))
         self.type_rowptr, self.type_col = self._all_products
         self.cand_type, self.eligible, self.exclusions = self._scope_type, None, None
-        self.bias = ops.half_sq_norm_bias(table)          # once per catalogue
+        self.bias = self._half_sq_norm()                  # once per catalogue
         self.set_exclusions()                             # the query itself
+
+    # What differs between the tables (CompactSimilarProducts: the bf16 copy) is behind these hooks: the check of the table,
+    # the bias, the three device calls (retrieval up to 16, list, rank) and the gather of fp32 rows.
+    def _check_table(self, table):
+        if not torch.is_tensor(table) or table.dtype != torch.float32:
+            raise ValueError(f"SimilarProducts: the table must be a [P, D] float32 device tensor, got "
+                             f"{table.dtype if torch.is_tensor(table) else type(table).__name__}")
+        if table.dim() != 2 or table.shape[1] not in (128, 256) or table.shape[0] < 1:
+            raise ValueError(f"SimilarProducts: the table must be [P, 128 or 256], got {tuple(table.shape)}")
+        if not table.is_cuda or not table.is_contiguous():
+            raise ValueError("SimilarProducts: the table must be a contiguous device tensor")
+        return table
+
+    def _half_sq_norm(self):
+        return ops.half_sq_norm_bias(self.table)
+
+    def _retrieve(self, q, row_type, n, exclude):
+        return ops.retrieve_topk_grouped(q, row_type, self.type_rowptr, self.type_col, self.table, n, exclude=exclude,
+                                         bias=self.bias)
+
+    def _retrieve_list(self, q, row_type, n, exclude):
+        return ops.retrieve_list_grouped_biased(q, row_type, self.type_rowptr, self.type_col, self.table, self.bias, n,
+                                                exclude=exclude)
+
+    def _rank(self, q, row_type, target_idx, **lists):
+        return ops.rank_grouped(q, row_type, target_idx, self.type_rowptr, self.type_col, self.table, bias=self.bias, **lists)
+
+    def _rows(self, ids):
+        """[..., D] fp32: the rows `ids` (int64) of the table"""
+        return self.table[ids]
 
     def _candidate_types(self):
         return self._scope_type, self._scope_types
@@ -597,9 +659,8 @@ class SimilarProducts(_CandidateFilters):
         query_idx = self._queries("similar_batch", query_idx)
         if query_idx.shape[0] == 0:
             return self._no_neighbours(n)
-        q = self.table[query_idx.long()]
-        idx, _ = ops.retrieve_topk_grouped(q, self._scope_type[query_idx.long()].contiguous(), self.type_rowptr, self.type_col,
-                                           self.table, n, exclude=self._exclude_rows(query_idx), bias=self.bias)
+        q = self._rows(query_idx.long())
+        idx, _ = self._retrieve(q, self._scope_type[query_idx.long()].contiguous(), n, self._exclude_rows(query_idx))
         return idx, self._distances(q, idx)
 
     @torch.no_grad()
@@ -648,9 +709,8 @@ class SimilarProducts(_CandidateFilters):
         query_idx = self._queries("similar_list_batch", query_idx)
         if query_idx.shape[0] == 0:
             return self._no_neighbours(n)
-        q = self.table[query_idx.long()]
-        idx, _ = ops.retrieve_list_grouped_biased(q, self._scope_type[query_idx.long()].contiguous(), self.type_rowptr,
-                                                  self.type_col, self.table, self.bias, n, exclude=self._exclude_rows(query_idx))
+        q = self._rows(query_idx.long())
+        idx, _ = self._retrieve_list(q, self._scope_type[query_idx.long()].contiguous(), n, self._exclude_rows(query_idx))
         return idx, self._list_distances(q, idx)
 
     @torch.no_grad()
@@ -699,7 +759,7 @@ class SimilarProducts(_CandidateFilters):
 
     def _distances(self, q, idx):
         """[B, n] fp32: |q[b] - table[idx[b, j]] + 1e-6|_2, +inf where idx is -1"""
-        e = self.table[idx.clamp(min=0).long()]                                   # [B, n, D]
+        e = self._rows(idx.clamp(min=0).long())                                   # [B, n, D]
         dist = (q[:, None, :] - e + 1e-6).norm(dim=2)
         return torch.where(idx >= 0, dist, torch.full_like(dist, float("inf")))
 
@@ -722,15 +782,14 @@ class SimilarProducts(_CandidateFilters):
         inside = (target_idx >= 0) & (target_idx < p)
         candidate = inside & (self.cand_type[target_idx.long().clamp(0, p - 1)] == row_type)
         slot = torch.where(candidate, 0, -1).to(torch.int32)
-        q = self.table[anchor_idx.long()]
+        q = self._rows(anchor_idx.long())
         exclude = self._exclude_rows(anchor_idx)
         if exclude is not None:
-            rank, _ = ops.rank_grouped(q, row_type.contiguous(), target_idx, self.type_rowptr, self.type_col, self.table,
-                                       exclude=exclude, cand_type=self.cand_type, bias=self.bias)
+            rank, _ = self._rank(q, row_type.contiguous(), target_idx, exclude=exclude, cand_type=self.cand_type)
             return slot, rank
         # no lists: a target that is no candidate costs no search
         row_type = torch.where(candidate, row_type, torch.full_like(row_type, -1)).contiguous()
-        rank, _ = ops.rank_grouped(q, row_type, target_idx, self.type_rowptr, self.type_col, self.table, bias=self.bias)
+        rank, _ = self._rank(q, row_type, target_idx)
         return slot, rank
 
     def evaluate_pairs(self, pairs, ks=(1, 3, 10, 100), chunk: int = 65536) -> Dict[str, Any]:
@@ -753,6 +812,51 @@ class SimilarProducts(_CandidateFilters):
             hi = min(lo + chunk, m)
             slot[lo:hi], rank[lo:hi] = self.rank_pairs(pairs[lo:hi, 0], pairs[lo:hi, 1])
         return Metrics.catalogue_metrics(slot, rank, ks)
+
+
+class CompactSimilarProducts(SimilarProducts):
+    """SimilarProducts over the bf16 copy of the table alone: substitutes by Euclidean distance to the STORED (rounded) rows,
+    for a deployment that gave the fp32 table back.  catalogue: an ops.CompactCatalogue, or a contiguous [P, 128 | 256]
+    torch.bfloat16 device tensor (wrapped in one).  The same scopes, default self-exclusion, set_exclusions / set_eligible,
+    MAX_N and MAX_LIST, and the same methods:
+      similar_batch, similar_list_batch, similar_capped_batch, similar_capped_list_batch  all through the biased bf16 list
+                  entry (ops.retrieve_list_grouped_bf16_biased), at n <= 16 too, with bias = the catalogue's .half_sq_norm;
+      rank_pairs / evaluate_pairs  through ops.rank_grouped_bf16(bias=): rank < n exactly when similar_list_batch(anchor, n)
+                  holds the target at that position.
+    The query row is the stored row widened (exactly) to fp32; the reported distances are |q - e + 1e-6|_2 over widened
+    gathered rows, in chunks of DIST_BYTES.  An fp32 table is never materialised: the widened rows are the [B, D] queries and
+    the [rows, n, D] chunks of the distances alone.  On a table that bf16 represents exactly AND whose partial sums are exact in
+    both score chains (small integers) every method returns what SimilarProducts(table.float()) returns, bit for bit; on merely
+    representable data the two chains' different summation orders may order a near-tie differently."""
+
+    def _check_table(self, catalogue):
+        if torch.is_tensor(catalogue):
+            if catalogue.dtype != torch.bfloat16:
+                raise ValueError(f"CompactSimilarProducts: a table tensor must be torch.bfloat16 (ops.catalogue_bf16), got "
+                                 f"{catalogue.dtype}; SimilarProducts serves the float32 table")
+            catalogue = ops.CompactCatalogue(catalogue)   # (its shape, device and layout checks)
+        if not isinstance(catalogue, ops.CompactCatalogue):
+            raise ValueError(f"CompactSimilarProducts: the catalogue must be an ops.CompactCatalogue or a [P, 128 or 256] "
+                             f"bfloat16 device tensor, got {type(catalogue).__name__}")
+        self.compact = catalogue
+        return catalogue.table
+
+    def _half_sq_norm(self):
+        return self.compact.half_sq_norm
+
+    def _retrieve(self, q, row_type, n, exclude):
+        return self._retrieve_list(q, row_type, n, exclude)
+
+    def _retrieve_list(self, q, row_type, n, exclude):
+        return ops.retrieve_list_grouped_bf16_biased(q, row_type, self.type_rowptr, self.type_col, self.table, self.bias, n,
+                                                     exclude=exclude)
+
+    def _rank(self, q, row_type, target_idx, **lists):
+        return ops.rank_grouped_bf16(q, row_type, target_idx, self.type_rowptr, self.type_col, self.table, bias=self.bias,
+                                     **lists)
+
+    def _rows(self, ids):
+        return self.table[ids].float()                    # (the gathered rows alone are widened)
 
 
 class IndexedSimilarProducts(SimilarProducts):

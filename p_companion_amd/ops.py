@@ -2163,6 +2163,102 @@ def rank_grouped(proj, types, targets, type_rowptr, type_col, table, slices=0, b
     return rank, bad
 
 
+def half_sq_norm_bias_bf16(table):
+    """pc_half_sq_norm_bias_bf16: half_sq_norm_bias for the [P, D] torch.bfloat16 copy of a catalogue (catalogue_bf16; a
+    CompactCatalogue's .table) -> [P] fp32: the terms of the ROUNDED rows, bit for bit half_sq_norm_bias(table.float()),
+    without the fp32 table ever being formed.  Under it retrieve_list_grouped_bf16_biased / rank_grouped_bf16 order by Euclidean
+    distance to the stored rows."""
+    if isinstance(table, torch.Tensor) and table.dtype == torch.float32:
+        raise ValueError("half_sq_norm_bias_bf16: an fp32 table is half_sq_norm_bias's; this function reads the bf16 copy")
+    d = _table_width(table, rows=True, dtype=torch.bfloat16)
+    out = torch.empty(table.shape[0], dtype=torch.float32, device=table.device)
+    check(_lib.lib().pc_half_sq_norm_bias_bf16(_p(table), table.shape[0], d, _p(out), _stream()), "pc_half_sq_norm_bias_bf16")
+    return out
+
+
+def _check_bf16_table(what, table, fp32_name):
+    """table: a [P, D] torch.bfloat16 tensor, checked on the host side alone (ValueError) before any launch; an fp32 table
+    is pointed at the fp32 function."""
+    if not isinstance(table, torch.Tensor):
+        raise ValueError(f"{what}: table must be a [P, D] bfloat16 device tensor, got {type(table).__name__}")
+    if table.dtype == torch.float32:
+        raise ValueError(f"{what}: an fp32 table is {fp32_name}'s; this function reads the bf16 copy (catalogue_bf16)")
+    if table.dtype != torch.bfloat16:
+        raise ValueError(f"{what}: table of dtype {table.dtype} is not supported: it must be bfloat16")
+    if table.dim() != 2:
+        raise ValueError(f"{what}: table must be [P, D], got shape {tuple(table.shape)}")
+
+
+def _check_bias_bf16(what, bias, table):
+    """bias: a [P] fp32 tensor beside a bf16 table, checked on the host side alone (ValueError) before any launch."""
+    if not isinstance(bias, torch.Tensor):
+        raise ValueError(f"{what}: bias must be a [P] float32 device tensor, got {type(bias).__name__}")
+    if bias.dtype != torch.float32:
+        raise ValueError(f"{what}: bias of dtype {bias.dtype} is not supported: it must be float32")
+    if bias.dim() != 1 or bias.shape[0] != table.shape[0]:
+        raise ValueError(f"{what}: bias of shape {tuple(bias.shape)} is not supported: it must hold one entry per product "
+                         f"({table.shape[0]})")
+
+
+def retrieve_list_grouped_bf16_biased(proj, types, type_rowptr, type_col, table, bias, n, slices=0, exclude=None, bad=None):
+    """pc_retrieve_list_grouped_bf16_biased: retrieve_list_grouped_biased's contract (idx [R,n] int32, -1 = none; scores [R,n]
+    fp32, -inf = none; 1 <= n <= RETRIEVE_LIST_MAX_N; exclude and `bad` as there) over the [P, D] torch.bfloat16 copy of a
+    catalogue, under the score fl(s + bias[p]) with s retrieve_list_grouped's own bf16 score of the pair -- one fp32 addition
+    after that chain.  bias: a [P] fp32 device tensor; half_sq_norm_bias_bf16(table) makes the order Euclidean over the stored
+    rows.  The same kernel body, merge and determinism: the same bits for every `slices`; with a zero bias
+    retrieve_list_grouped(table)'s bit for bit; rank_grouped_bf16(bias=) < n exactly when the list holds the target at that
+    position.  It serves n <= 16 too (there is no 16-entry biased bf16 kernel).  A function of its own:
+    retrieve_list_grouped_biased refuses a bf16 table.  Nothing is read back to the host."""
+    what = "retrieve_list_grouped_bf16_biased"
+    n = int(n)
+    if not 1 <= n <= RETRIEVE_LIST_MAX_N:
+        raise ValueError(f"{what}: n must be in [1, {RETRIEVE_LIST_MAX_N}], got {n}")
+    _check_bf16_table(what, table, "retrieve_list_grouped_biased")
+    _check_bias_bf16(what, bias, table)
+    return _retrieve_grouped("pc_retrieve_list_grouped_bf16_biased", proj, types, type_rowptr, type_col, table, n, slices, exclude,
+                             bad, bias=bias, what=what, tag="retrieve_list", table_dtype=torch.bfloat16)
+
+
+def rank_grouped_bf16(proj, types, targets, type_rowptr, type_col, table, slices=0, bad=None, exclude=None, cand_type=None,
+                      bias=None):
+    """pc_rank_grouped_bf16: rank_grouped's contract over the [P, D] torch.bfloat16 copy of a catalogue -- for row r the number
+    of products of type types[r] that retrieve_list_grouped(table) (bias: retrieve_list_grouped_bf16_biased) orders in front
+    of targets[r], from that call's own score bits: rank < n exactly when the list holds the target at position rank.  Returns
+    (rank [R] int32, bad [1] int32) with rank_grouped's -1 rows and `bad` count; exclude = (row_key, ex_rowptr, ex_col) with
+    cand_type [P] int32, and bias [P] fp32, as there.  Bitwise deterministic, the same for every `slices`; it reads half the
+    candidate bytes of rank_grouped and no fp32 table.  A function of its own: rank_grouped refuses a bf16 table.  Nothing is
+    read back to the host."""
+    what = "rank_grouped_bf16"
+    _check_bf16_table(what, table, "rank_grouped")
+    if bias is not None:
+        _check_bias_bf16(what, bias, table)
+    if exclude is not None:
+        exclude = _check_exclude(what, exclude, types.shape[0] if isinstance(types, torch.Tensor) else -1)
+        if cand_type is None:
+            raise ValueError(f"{what}: exclude needs cand_type (the type under which each product is a candidate)")
+        if not isinstance(cand_type, torch.Tensor) or cand_type.dtype != torch.int32 or cand_type.dim() != 1 \
+                or cand_type.shape[0] != table.shape[0]:
+            raise ValueError(f"{what}: cand_type must be an int32 tensor of one entry per product")
+    elif cand_type is not None:
+        raise ValueError(f"{what}: cand_type is read with an exclude triple only")
+    proj, r, t, d, slices = _grouped_rows(proj, types, type_rowptr, type_col, table, torch.bfloat16, slices)
+    _req(targets, torch.int32, "targets", (r,))
+    p, device = table.shape[0], proj.device
+    rank = torch.empty(r, dtype=torch.int32, device=device)
+    row_key, ex_rowptr, ex_col, n_keys, bad = _filter_args(exclude, bad, device, counted=True)
+    if exclude is not None:
+        _req(cand_type, torch.int32, "cand_type", (p,))
+    if bias is not None:
+        _req(bias, torch.float32, "bias", (p,))
+    # (the biased entry's list; without a triple row_key, ex_rowptr, ex_col and cand_type are None, without a bias it too:
+    # null pointers, n_keys 0)
+    args = (proj.data_ptr(), types.data_ptr(), targets.data_ptr(), _p(row_key), r, type_rowptr.data_ptr(), type_col.data_ptr(),
+            table.data_ptr(), _p(bias), t, p, _p(ex_rowptr), _p(ex_col), n_keys, _p(cand_type), d, slices, rank.data_ptr(),
+            bad.data_ptr())
+    _grouped_call("pc_rank_grouped_bf16", "rank_grouped", device, (r, t, slices), args)
+    return rank, bad
+
+
 def type_csr(type_idx, n_types):
     """The type-grouped product CSR of PCompanionInference (bpg.get_products_by_type, bpg.py:40-43), built on the device from
     an int32 CUDA type_idx [P]: rowptr [T+1] int32, col [P] int32 = the products of each type in ascending node order (the
@@ -2406,10 +2502,14 @@ class CompactCatalogue:
     table: a [P, D] device tensor, D 128 or 256 -- fp32: rounded once here (catalogue_bf16); torch.bfloat16: taken as it is.
       .table     [P, D] torch.bfloat16, contiguous, on the device
       .inv_norm  [P] fp32 = inv_norm_bf16(.table), formed on first use: the cosine's factors
-    Both describe the ROUNDED rows: the cosine is between the rows that are actually stored.  Ranks (rank_grouped), a bias and
-    SimilarProducts still need the fp32 table."""
+      .half_sq_norm  [P] fp32 = half_sq_norm_bias_bf16(.table), formed on first use: the Euclidean order's terms
+    All describe the ROUNDED rows: the cosine and the distance are between the rows that are actually stored.  Ranks
+    (rank_grouped_bf16), a bias (retrieve_list_grouped_bf16_biased) and substitutes (inference.CompactSimilarProducts) are
+    served from it too, through functions and classes of their own: rank_grouped, the bias= arguments and SimilarProducts
+    still take the fp32 table alone."""
 
     _inv_norm = None
+    _half_sq_norm = None
 
     def __init__(self, table):
         if not isinstance(table, torch.Tensor) or table.dtype not in (torch.float32, torch.bfloat16):
@@ -2426,6 +2526,12 @@ class CompactCatalogue:
         if self._inv_norm is None:
             self._inv_norm = inv_norm_bf16(self.table)        # once per catalogue
         return self._inv_norm
+
+    @property
+    def half_sq_norm(self):
+        if self._half_sq_norm is None:
+            self._half_sq_norm = half_sq_norm_bias_bf16(self.table)   # once per catalogue
+        return self._half_sq_norm
 
 
 class CellIndex:
