@@ -1483,6 +1483,39 @@ int pc_rank_grouped_bf16(const float *proj, const int32_t *types, const int32_t 
                          const int32_t *cand_type, int dim, int slices, int32_t *rank_out, int32_t *bad_count, void *ws,
                          size_t ws_bytes, void *stream);
 
+/* Basket recommendations (ABI 8, additive; csrc/fuse_lists.hip; ops.fuse_lists, PCompanionInference.recommend_basket_batch):
+ * the lists served for the items of a basket fused into one list, on the device.
+ *
+ * pc_fuse_lists: idx / score [baskets, sources, w], 1 <= sources * w <= 1024: `sources` rows of w slots per basket, each row
+ * what a grouped retrieval returned for one basket item -- its K type lists side by side --, the slots in any order.  source
+ * [baskets, sources] int32 or NULL: the product id of the item behind each row, -1 = no item here (padding); NULL: every row
+ * counts and nothing is banned.  ex_rowptr [num_products + 1] / ex_col: an exclusion CSR keyed by product id with strictly
+ * ascending rows (ops.exclusion_csr), both or neither, and only with source.
+ *   candidate  a slot whose row's source is not -1, whose id lies in [0, num_products) and whose score is finite.  An id
+ *              outside [-1, num_products) is never used as an index and adds one to *bad_count (int32 [1], optional, added to),
+ *              whatever its row; a source outside [-1, num_products) does the same, once, and its row is dropped.
+ *   ban set    the basket's own source ids and, with the CSR, every id in the exclusion rows of those sources.  A banned
+ *              product is no candidate, whichever row offered it: a substitute of item A is not served through item B, and
+ *              nothing already in the basket is served.
+ *   fusion     all candidate slots of a basket that hold one product id are one product.  With its slot scores in descending
+ *              order s1 >= s2 >= ... (+0.0 before -0.0) -- combine 0 (sum): f = s1, then f = fl(f + s2), and so on:
+ *              sequential fp32, the largest first; this order is part of the contract and makes the bits independent of the
+ *              order of the slots.  combine 1 (max): f = s1.  support = the number of slots fused.  A sum that overflows is
+ *              served as the infinity it became, where the order below puts it.
+ *   order      out_idx / out_score / out_support [baskets, n], 1 <= n <= min(sources * w, 256): the first n products under
+ *              (fused score descending, product index ascending); -1 / -inf / 0 past the end.
+ * One wave per basket sorts the slots in registers (64 lanes x 2, 4, 8 or 16 slots for pools up to 128, 256, 512, 1024, the
+ * same bits from all four), compares them with the ban ids streamed through LDS, fuses equal ids by a walk over the sorted
+ * row, sorts the products again under their sums and compacts.  Integer compares, float compares and the fp32 additions above
+ * only: no workspace, no float atomics, no host readback; the result is the same for every launch geometry and run and under
+ * a permutation of a basket's rows (with their sources) or of the slots inside rows.
+ * PC_ESHAPE: baskets < 0, sources < 1, w < 1, sources * w > 1024, n outside [1, min(sources * w, 256)], num_products < 1,
+ * combine not 0 / 1, one of ex_rowptr / ex_col without the other or without source, a null idx / score / out_idx / out_score /
+ * out_support -- each checked before anything is launched; baskets == 0 succeeds without a launch. */
+int pc_fuse_lists(const int32_t *idx, const float *score, const int32_t *source, int baskets, int sources, int w,
+                  const int32_t *ex_rowptr, const int32_t *ex_col, int num_products, int n, int combine, int32_t *out_idx,
+                  float *out_score, int32_t *out_support, int32_t *bad_count, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

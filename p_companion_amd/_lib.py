@@ -261,6 +261,8 @@ SIGNATURES = {
     "pc_rank_grouped_bf16_workspace_bytes": (_sz, [_i, _i, _i]),
     "pc_rank_grouped_bf16": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _vp, _i, _i, _vp, _vp, _vp,
                                   _sz, _vp]),
+    # basket recommendations (csrc/fuse_lists.hip; ABI 8, additive)
+    "pc_fuse_lists": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "pc_hadamard_forward":(_i, [_vp, _vp, _i, _i, _vp, _vp]),
     "pc_hadamard_forward_dim": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
     "pc_hadamard_backward": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp]),

@@ -26,6 +26,8 @@ that holds them: see the class).
 recommend_capped_batch keeps at most `cap` products of one product group (a parent item, a brand, a seller) in a list, and
 recommend_page_batch merges a query's K lists into one row under a per-type quota and that cap: one pc_cap_lists pass over
 recommend_batch's own pool.  SimilarProducts.similar_capped_batch does the same for substitutes, without the query's variants.
+recommend_basket_batch answers for a whole basket: the items' lists fused into one on the device (pc_fuse_lists), without the
+basket's own products and the substitutes of any of them.
 
 SimilarProducts is the substitute side: the nearest products of a query under Euclidean distance over any [P, D] fp32 table
 (Product2Vec's export), the grouped retrieval and rank with the per-product term -|e_p|^2 / 2 on the score
@@ -418,6 +420,46 @@ class PCompanionInference(_CandidateFilters):
         idx, sc = ops.cap_lists(idx.reshape(b, -1), sc.reshape(b, -1), n, group, cap)
         types = torch.where(idx >= 0, self.type_idx[idx.clamp(min=0).long()].long(), -1)
         return idx, sc, types
+
+    @torch.no_grad()
+    def recommend_basket_batch(self, basket: torch.Tensor, num_recommendations: int = 10, per_item: int = 8,
+                               combine: str = "sum"):
+        """What goes with ALL the products of a basket: (idx [B, n] int32, score [B, n] fp32, types [B, n] int64 = the
+        product's type, -1 where idx is -1, support [B, n] int32).  basket [B, I] int32: the product ids of each basket's items,
+        -1 = no item (padding).  Every item is served as a query of its own -- recommend_batch(items, per_item): its catalogue,
+        its per-item exclusions and eligibility, its choice of retrieval entry and its refusals (a bare bf16 catalogue stops at
+        per_item 16) --, the I rows of K per_item slots are one pool, and ONE ops.fuse_lists call fuses it: a product that
+        several items (or several types of one item) suggested is one product, its scores met under `combine` ("sum": added,
+        the largest first, sequential fp32 -- a product many items agree on rises; "max": its best score, a dedupe), support =
+        the number of lists that offered it; the basket's own items are never served, and with an exclusion set installed
+        (set_exclusions) neither is a product in the set of ANY item, whichever item's list offered it.  Served under
+        (fused score descending, product index ascending), -1 / -inf / -1 / 0 where fewer products are left.  Needs
+        I K per_item <= ops.FUSE_LISTS_MAX_POOL and 1 <= num_recommendations <= min(I K per_item, ops.FUSE_LISTS_MAX_N), checked
+        before the model runs.  A padding slot still costs a retrieval row (it is served for product 0 and dropped by the
+        fusion), so bucket baskets by length.  Nothing is read back."""
+        n, per_item, k = int(num_recommendations), int(per_item), int(self.config.NUM_COMP_TYPES)
+        if not torch.is_tensor(basket) or basket.dim() != 2 or basket.dtype != torch.int32 or basket.shape[1] < 1:
+            raise ValueError(f"recommend_basket_batch: basket must be a [B, I] int32 tensor with I >= 1 (-1 = no item), got "
+                             f"{tuple(basket.shape) if torch.is_tensor(basket) else type(basket).__name__}"
+                             f"{' ' + str(basket.dtype) if torch.is_tensor(basket) else ''}")
+        b, items = basket.shape
+        if per_item < 1 or items * k * per_item > ops.FUSE_LISTS_MAX_POOL:
+            raise ValueError(f"recommend_basket_batch: need 1 <= per_item and I * K * per_item <= {ops.FUSE_LISTS_MAX_POOL}, got "
+                             f"I = {items}, K = {k} and per_item {per_item}")
+        most = min(items * k * per_item, ops.FUSE_LISTS_MAX_N)
+        if not 1 <= n <= most:
+            raise ValueError(f"recommend_basket_batch: need 1 <= num_recommendations <= min(I * K * per_item, "
+                             f"{ops.FUSE_LISTS_MAX_N}) = {most}, got {n}")
+        if combine not in ("sum", "max"):
+            raise ValueError(f"recommend_basket_batch: combine must be 'sum' or 'max', got {combine!r}")
+        basket = basket.to(self.device).contiguous()
+        p = int(self.type_idx.shape[0])
+        # (padding is served for product 0, an id outside the catalogue for the nearest one inside: the fusion drops both rows)
+        _, idx, sc = self.recommend_batch(basket.reshape(-1).clamp(0, p - 1), per_item)
+        idx, sc, support = ops.fuse_lists(idx.reshape(b, items, -1), sc.reshape(b, items, -1), n, combine, source=basket,
+                                          exclude=self.exclusions, num_products=p)
+        types = torch.where(idx >= 0, self.type_idx[idx.clamp(min=0).long()].long(), -1)
+        return idx, sc, types, support
 
     def _rank_guard(self, what):
         """rank_targets and evaluate_catalogue ask here first: a bf16 catalogue is refused, before the model runs or the

@@ -2496,6 +2496,75 @@ def cap_lists(idx, score, n, group=None, cap=1, row_ban=None, bad=None):
     return out_idx, out_sc
 
 
+FUSE_LISTS_MAX_POOL, FUSE_LISTS_MAX_N = 1024, 256
+
+
+def fuse_lists(idx, score, n, combine="sum", source=None, exclude=None, num_products=None, bad=None):
+    """pc_fuse_lists: the lists served for the items of a basket fused into one list.  idx [B, S, w] int32 / score [B, S, w]
+    fp32, 1 <= S w <= FUSE_LISTS_MAX_POOL: S source rows of w slots per basket, each row what a grouped retrieval returned for
+    one basket item (its K type lists side by side), in any order (a slot with id -1 or a score that is not finite is no
+    candidate) -> (idx [B, n] int32, score [B, n] fp32, support [B, n] int32), 1 <= n <= min(S w, FUSE_LISTS_MAX_N): the first n
+    products of the basket under (fused score descending, product index ascending), -1 / -inf / 0 past the end.  All candidate
+    slots of a basket with one id are one product; with its slot scores in descending order s1 >= s2 >= ..., combine="sum":
+    f = s1, f = fl(f + s2), ... (sequential fp32, the largest first: the pinned order makes the bits independent of the slot
+    order); combine="max": f = s1, a dedupe.  support = the number of slots fused.  source [B, S] int32: the product id of the
+    item behind each row, -1 = no item here (the row is dropped); the sources are banned from their basket's list.  exclude =
+    (ex_rowptr [P + 1], ex_col) as exclusion_csr returns them (needs source): every id in the rows of a basket's sources is
+    banned too, whichever row offered it.  num_products: ids at or above it are bad; taken from ex_rowptr where given, else the
+    argument, else 2^31 - 1.  An id or a source outside [-1, num_products) is never used as an index and is counted in `bad`
+    (a [1] int32 device counter the caller passes to see the count; added to).  Bitwise deterministic; a permutation of a
+    basket's rows (with their sources) or of the slots inside rows changes nothing.  Nothing is read back."""
+    _req(idx, torch.int32, "idx")
+    _req(score, torch.float32, "score")
+    if idx.dim() != 3 or tuple(score.shape) != tuple(idx.shape):
+        raise ValueError(f"fuse_lists: expected idx and score of one shape [B, S, w], got {tuple(idx.shape)} and "
+                         f"{tuple(score.shape)}")
+    b, s, w = idx.shape
+    if not 1 <= s * w <= FUSE_LISTS_MAX_POOL:
+        raise ValueError(f"fuse_lists: the pool S * w must be in [1, {FUSE_LISTS_MAX_POOL}], got {s} * {w}")
+    n = int(n)
+    if not 1 <= n <= min(s * w, FUSE_LISTS_MAX_N):
+        raise ValueError(f"fuse_lists: n must be in [1, min(S * w, {FUSE_LISTS_MAX_N}) = {min(s * w, FUSE_LISTS_MAX_N)}], got {n}")
+    if combine not in ("sum", "max"):
+        raise ValueError(f"fuse_lists: combine must be 'sum' or 'max', got {combine!r}")
+    if source is not None:
+        if not isinstance(source, torch.Tensor):
+            raise ValueError(f"fuse_lists: source must be a [B, S] int32 device tensor, got {type(source).__name__}")
+        _req(source, torch.int32, "source", (b, s))
+    ex_rowptr = ex_col = None
+    if exclude is not None:
+        if source is None:
+            raise ValueError("fuse_lists: exclude is keyed by the rows' source ids and needs source")
+        if not isinstance(exclude, (tuple, list)) or len(exclude) != 2 or not all(isinstance(t, torch.Tensor) for t in exclude):
+            raise ValueError("fuse_lists: exclude must be the pair (ex_rowptr, ex_col) of int32 device tensors")
+        ex_rowptr, ex_col = exclude
+        _req(ex_rowptr, torch.int32, "ex_rowptr")
+        _req(ex_col, torch.int32, "ex_col")
+        if ex_rowptr.dim() != 1 or ex_rowptr.numel() < 2 or ex_col.dim() != 1:
+            raise ValueError(f"fuse_lists: expected ex_rowptr [P + 1] with P >= 1 and a 1-D ex_col, got "
+                             f"{tuple(ex_rowptr.shape)} and {tuple(ex_col.shape)}")
+        if num_products is not None and int(num_products) != ex_rowptr.numel() - 1:
+            raise ValueError(f"fuse_lists: num_products {int(num_products)} does not match the exclusion set's "
+                             f"{ex_rowptr.numel() - 1} keys")
+        num_products = ex_rowptr.numel() - 1
+        if ex_col.numel() == 0:                           # (every row empty: one unread entry, so that the pointer is not null)
+            ex_col = torch.zeros(1, dtype=torch.int32, device=idx.device)
+    num_products = 2 ** 31 - 1 if num_products is None else int(num_products)
+    if not 1 <= num_products <= 2 ** 31 - 1:
+        raise ValueError(f"fuse_lists: num_products must be in [1, 2^31 - 1], got {num_products}")
+    if bad is not None:
+        _req(bad, torch.int32, "bad", (1,))
+    out_idx = torch.empty(b, n, dtype=torch.int32, device=idx.device)
+    out_sc = torch.empty(b, n, dtype=torch.float32, device=idx.device)
+    out_sup = torch.empty(b, n, dtype=torch.int32, device=idx.device)
+    if b == 0:
+        return out_idx, out_sc, out_sup
+    check(_lib.lib().pc_fuse_lists(_p(idx), _p(score), _p(source), b, s, w, _p(ex_rowptr), _p(ex_col), num_products, n,
+                                   0 if combine == "sum" else 1, _p(out_idx), _p(out_sc), _p(out_sup), _p(bad), _stream()),
+          "pc_fuse_lists")
+    return out_idx, out_sc, out_sup
+
+
 class CompactCatalogue:
     """The bf16 copy of a catalogue as a serving table of its own: everything PCompanionInference needs to serve lists of up
     to RETRIEVE_LIST_MAX_N products per type and diversified lists without the fp32 features (catalogue=CompactCatalogue(...)).
