@@ -1516,6 +1516,67 @@ int pc_fuse_lists(const int32_t *idx, const float *score, const int32_t *source,
                   const int32_t *ex_rowptr, const int32_t *ex_col, int num_products, int n, int combine, int32_t *out_idx,
                   float *out_score, int32_t *out_support, int32_t *bad_count, void *stream);
 
+/* Per-query attribute filters (ABI 8, additive; csrc/where_list.hip, csrc/where_list_bf16.hip; ops.RowWhere,
+ * ops.retrieve_list_grouped_where, PCompanionInference.recommend_where_batch, SimilarProducts.similar_where_batch): lists
+ * narrowed by a condition on both the query and a property of the candidate -- complements within 0.5x to 2x of the query's
+ * price, only what ships to this shopper's region, nothing from a blocked seller tier.
+ *
+ * pc_row_where: per-product attributes, installed once per catalogue, either may be NULL:
+ *   value [num_products] fp32 (a price, a rating, a delivery time), flags [num_products] int32 read as 32 bits;
+ * and the per-row predicate, one entry per row of the call:
+ *   lo, hi [rows] fp32:      p passes iff lo[r] <= value[p] && value[p] <= hi[r], two fp32 compares: the ends are inclusive, a
+ *                            NaN value or bound passes nothing, lo > hi passes nothing, -inf / +inf pass every non-NaN value,
+ *                            -0.0 == 0.0.  Both with value, neither without: a one-sided caller passes an infinite bound.
+ *   need, deny [rows] int32: p passes iff (flags[p] & need[r]) == need[r] && (flags[p] & deny[r]) == 0; bit 31 is a bit like
+ *                            the others.  Only with flags; with flags either may be NULL (read as 0).
+ * A product that fails is treated exactly as an excluded product is: never buffered, the row's threshold does not move.  A
+ * row's list is the unfiltered order (score descending, product index ascending) with the failing products taken out, -1 / -inf
+ * past its end; the score bits are those of the entry underneath (the predicate reads no score).  It composes with the
+ * exclusion lists (both must let a product through) and with an eligibility CSR.  Every array NULL: the entry underneath's
+ * output, bit for bit.
+ *
+ * pc_retrieve_list_grouped_where / _bf16_where / _biased_where / _bf16_biased_where: the contract and argument list of
+ * pc_retrieve_list_grouped / _bf16 / _biased / _bf16_biased for every 1 <= n <= 256, with `where` in front of ws.  The kernel
+ * body, the merge and the host path are pc_retrieve_list_grouped's own code with the body's filter hook: value[p] and flags[p]
+ * are gathered per chunk column a chunk ahead and staged on chip, a candidate that beat the row's threshold is tested before
+ * the exclusion search.  Bitwise deterministic and independent of `slices`, of the placement of the rows and of the order of
+ * type_col inside a type; no float atomics, no host readback.  The workspace (NAME_workspace_bytes, 0 for arguments out of
+ * range) is pc_retrieve_list_grouped's size.
+ * PC_EINVAL: a null where; lo or hi without value, value without both; need or deny without flags; and everything the entry
+ * underneath answers with PC_EINVAL; PC_ESHAPE and PC_EWORKSPACE as there -- each checked before anything is launched: the
+ * outputs are untouched. */
+typedef struct pc_row_where {
+    const float   *value, *lo, *hi;
+    const int32_t *flags, *need, *deny;
+} pc_row_where;
+
+size_t pc_retrieve_list_grouped_where_workspace_bytes(int rows, int n_types, int n, int slices);
+int pc_retrieve_list_grouped_where(const float *proj, const int32_t *types, const int32_t *row_key, int rows,
+                                   const int32_t *type_rowptr, const int32_t *type_col, const float *table, int n_types,
+                                   const int32_t *ex_rowptr, const int32_t *ex_col, int n_keys, int n, int dim, int slices,
+                                   int32_t *out_idx, float *out_score, int32_t *bad_count, const pc_row_where *where,
+                                   void *ws, size_t ws_bytes, void *stream);
+size_t pc_retrieve_list_grouped_bf16_where_workspace_bytes(int rows, int n_types, int n, int slices);
+int pc_retrieve_list_grouped_bf16_where(const float *proj, const int32_t *types, const int32_t *row_key, int rows,
+                                        const int32_t *type_rowptr, const int32_t *type_col, const uint16_t *table_bf16,
+                                        int n_types, const int32_t *ex_rowptr, const int32_t *ex_col, int n_keys, int n,
+                                        int dim, int slices, int32_t *out_idx, float *out_score, int32_t *bad_count,
+                                        const pc_row_where *where, void *ws, size_t ws_bytes, void *stream);
+size_t pc_retrieve_list_grouped_biased_where_workspace_bytes(int rows, int n_types, int n, int slices);
+int pc_retrieve_list_grouped_biased_where(const float *proj, const int32_t *types, const int32_t *row_key, int rows,
+                                          const int32_t *type_rowptr, const int32_t *type_col, const float *table,
+                                          const float *bias, int n_types, const int32_t *ex_rowptr, const int32_t *ex_col,
+                                          int n_keys, int n, int dim, int slices, int32_t *out_idx, float *out_score,
+                                          int32_t *bad_count, const pc_row_where *where, void *ws, size_t ws_bytes,
+                                          void *stream);
+size_t pc_retrieve_list_grouped_bf16_biased_where_workspace_bytes(int rows, int n_types, int n, int slices);
+int pc_retrieve_list_grouped_bf16_biased_where(const float *proj, const int32_t *types, const int32_t *row_key, int rows,
+                                               const int32_t *type_rowptr, const int32_t *type_col,
+                                               const uint16_t *table_bf16, const float *bias, int n_types,
+                                               const int32_t *ex_rowptr, const int32_t *ex_col, int n_keys, int n, int dim,
+                                               int slices, int32_t *out_idx, float *out_score, int32_t *bad_count,
+                                               const pc_row_where *where, void *ws, size_t ws_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -76,6 +76,12 @@ class AdamFused(ctypes.Structure):
                 ("lr", ctypes.c_double), ("beta1", ctypes.c_double), ("beta2", ctypes.c_double), ("eps", ctypes.c_double)]
 
 
+class RowWhere(ctypes.Structure):
+    """pc_row_where (ABI 8): the per-product attributes and the per-row predicate of the filtered long-list entries; a part
+    that is absent is a null pointer."""
+    _fields_ = [(n, ctypes.c_void_p) for n in ("value", "lo", "hi", "flags", "need", "deny")]
+
+
 PC_OPT_SIDE_QUEUE = 1      # pc_set_option: the fused Product2Vec step's side queue (include/pcompanion_hip.h)
 PC_OPT_FUSED_OUT_CHAIN = 5           # ... and the out-projection's forward chain in front of it in the same launch (default 1)
 PC_OPT_FUSED_LOSS = 4                # ... the triplet hinge inside the attention backward's first launch (default 1)
@@ -263,6 +269,20 @@ SIGNATURES = {
                                   _sz, _vp]),
     # basket recommendations (csrc/fuse_lists.hip; ABI 8, additive)
     "pc_fuse_lists": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    # per-query attribute filters (csrc/where_list.hip, csrc/where_list_bf16.hip: grouped_list.h's body with its filter hook;
+    # the four long-list entries' lists with a pc_row_where in front of the workspace; ABI 8, additive)
+    "pc_retrieve_list_grouped_where_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "pc_retrieve_list_grouped_where": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp,
+                                            _P(RowWhere), _vp, _sz, _vp]),
+    "pc_retrieve_list_grouped_bf16_where_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "pc_retrieve_list_grouped_bf16_where": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp,
+                                                 _P(RowWhere), _vp, _sz, _vp]),
+    "pc_retrieve_list_grouped_biased_where_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "pc_retrieve_list_grouped_biased_where": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _vp, _vp,
+                                                   _vp, _P(RowWhere), _vp, _sz, _vp]),
+    "pc_retrieve_list_grouped_bf16_biased_where_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "pc_retrieve_list_grouped_bf16_biased_where": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _vp,
+                                                        _vp, _vp, _P(RowWhere), _vp, _sz, _vp]),
     "pc_hadamard_forward":(_i, [_vp, _vp, _i, _i, _vp, _vp]),
     "pc_hadamard_forward_dim": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
     "pc_hadamard_backward": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp]),

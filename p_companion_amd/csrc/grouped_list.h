@@ -1,5 +1,6 @@
 // The long-list family's header (retrieve_list.hip: the fp32 table; retrieve_list_bf16.hip: the bf16 copy; nearest_list.hip:
-// the fp32 table under a per-product bias; nearest_list_bf16.hip: the bf16 copy under one), the way grouped_select.h is the
+// the fp32 table under a per-product bias; nearest_list_bf16.hip: the bf16 copy under one; where_list.hip and
+// where_list_bf16.hip: all four under a per-row predicate on per-product attributes), the way grouped_select.h is the
 // 16-entry kernels': the list and buffer sizes, the score kernel's body and the host path, one text each.  A unit supplies its
 // score chain (a policy, below), its kernels as one-line wrappers of rl_score_body and its entries.
 //
@@ -63,8 +64,23 @@ void rl_merge_launch(const RgWs& w, const int32_t* types, int rows, const int32_
 // bias[pid] is a 4-byte gather per column, issued with the column's product id a chunk ahead (nb_score_kernel's scheme).  A
 // column past the slice's end (pid -1) reads bias[0]; nothing of it is used: its id in LDS is RG_NONE.  Without BIAS the
 // pointer is not read and the body is the text it was.
-template <class Chain, int NE, bool EX, bool BIAS = false>
-__device__ __forceinline__ void rl_score_body(RL_SCORE_PARAMS(typename Chain::Table), const float* __restrict__ bias = nullptr) {
+// WHERE: a per-row predicate on per-product attributes (RlWhere, below; where_list.hip, where_list_bf16.hip).  The h == 0 lanes
+// gather value[pid] and flags[pid] with the column's product id a chunk ahead, as the bias is gathered, and stage them in LDS
+// beside cid (wval / wflg, RG_CHUNK words each, the same lanes under the same barrier): 64 gathers a chunk whatever the
+// selectivity.  A selection thread holds its row's lo / hi / need / deny in registers for the work item and tests a candidate
+// that beat the threshold before the exclusion bisection; a candidate that fails is dropped as an excluded one is: never
+// buffered, the threshold stays.  An absent array is a null pointer: the branch on it is wave-uniform, the array is never read,
+// and the staged word / the row's bound is the one that passes everything (0 within [-inf, +inf]; need = deny = 0).  A column
+// past the slice's end reads entry 0 and nothing of it is used.  The predicate reads no score: the score bits are the body's
+// without it.  Without WHERE nothing of this is instantiated and the body is the text it was.
+struct RlWhere : pc_row_where {
+    // (rl_list_entry's required-pointer test of what travels behind bad_count: the pairing rule of the filter's parts)
+    explicit operator bool() const { return (value ? lo && hi : !lo && !hi) && (flags || (!need && !deny)); }
+};
+
+template <class Chain, int NE, bool EX, bool BIAS = false, bool WHERE = false>
+__device__ __forceinline__ void rl_score_body(RL_SCORE_PARAMS(typename Chain::Table), const float* __restrict__ bias = nullptr,
+                                              RlWhere wh = RlWhere{}) {
     using B = typename Chain::B;
     constexpr int D = Chain::D, NB = Chain::NB;
     constexpr int TM = RL_TM;
@@ -82,6 +98,14 @@ __device__ __forceinline__ void rl_score_body(RL_SCORE_PARAMS(typename Chain::Ta
     __shared__ int bcnt[TM];                 // entries in a row's buffer
     __shared__ float thv[TM];                // the row's threshold: its n-th entry at the last compaction
     __shared__ int thi[TM];
+    float* wval = nullptr;                   // (WHERE) the chunk's columns' value / flags, beside cid
+    int* wflg = nullptr;
+    if constexpr (WHERE) {
+        __shared__ float wval_[RG_CHUNK];
+        __shared__ int wflg_[RG_CHUNK];
+        wval = wval_;
+        wflg = wflg_;
+    }
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, c = lane & 15, h = lane >> 4;
     const int rr = tid / TPR, qq = tid % TPR;
     const int64_t n_items = item_start[n_types];
@@ -103,6 +127,16 @@ __device__ __forceinline__ void rl_score_body(RL_SCORE_PARAMS(typename Chain::Ta
             const int key = row_key[order[p0 + rr]];
             if (key >= 0 && key < n_keys) { elo = ex_rowptr[key]; ehi = ex_rowptr[key + 1]; }
         }
+        float wlo = -INFINITY, whi = INFINITY;            // (WHERE) this thread's row's predicate
+        int wneed = 0, wdeny = 0;
+        if constexpr (WHERE) {
+            if (rr < valid) {
+                const int r = order[p0 + rr];
+                if (wh.value) { wlo = wh.lo[r]; whi = wh.hi[r]; }
+                if (wh.need) wneed = wh.need[r];
+                if (wh.deny) wdeny = wh.deny[r];
+            }
+        }
 
         auto load_pid = [&](int cb) { const int cc = cb + wv * 16 + c; return cc < ce ? type_col[cc] : -1; };
         auto load_b = [&](B* b, int pid) {
@@ -121,6 +155,12 @@ __device__ __forceinline__ void rl_score_body(RL_SCORE_PARAMS(typename Chain::Ta
         int pidnn = load_pid(cb0 + RG_CHUNK);
         float bsn = 0.f;                                  // (BIAS) the term of the chunk in bn
         if constexpr (BIAS) bsn = bias[max(pidn, 0)];
+        float wvn = 0.f;                                  // (WHERE) the attributes of the chunk in bn, in the h == 0 lanes
+        int wfn = 0;
+        if constexpr (WHERE) {
+            if (h == 0 && wh.value) wvn = wh.value[max(pidn, 0)];
+            if (h == 0 && wh.flags) wfn = wh.flags[max(pidn, 0)];
+        }
         __syncthreads();                                  // query image, counters and thresholds in LDS
 
         for (int cb = cb0;; cb += RG_CHUNK) {
@@ -131,6 +171,8 @@ __device__ __forceinline__ void rl_score_body(RL_SCORE_PARAMS(typename Chain::Ta
                 for (int k = 0; k < NB; k++) b[k] = bn[k];
                 const int pid = pidn;
                 const float bs = bsn;
+                const float wvc = wvn;
+                const int wfc = wfn;
                 pidn = pidnn;
                 if (cb + RG_CHUNK < ce) load_b(bn, pidn); // the next chunk's rows in flight while this one is scored
                 pidnn = load_pid(cb + 2 * RG_CHUNK);
@@ -143,6 +185,14 @@ __device__ __forceinline__ void rl_score_body(RL_SCORE_PARAMS(typename Chain::Ta
 #pragma unroll
                 for (int k = 0; k < 4; k++) sc[4 * h + k][wv * 16 + c] = acc[k];
                 if (h == 0) cid[wv * 16 + c] = pid < 0 ? RG_NONE : pid;
+                if constexpr (WHERE) {
+                    if (h == 0) {
+                        wval[wv * 16 + c] = wvc;
+                        wflg[wv * 16 + c] = wfc;
+                        if (wh.value) wvn = wh.value[max(pidn, 0)];       // the next chunk's: in flight through the selection
+                        if (wh.flags) wfn = wh.flags[max(pidn, 0)];
+                    }
+                }
                 __syncthreads();                          // (also: the last compaction's threshold and count are visible)
                 if (rr < valid) {
                     const float hv = thv[rr];
@@ -153,6 +203,11 @@ __device__ __forceinline__ void rl_score_body(RL_SCORE_PARAMS(typename Chain::Ta
                         const int xi = cid[col];
                         const float x = sc[rr][col];
                         if (xi == RG_NONE || !rg_better(x, xi, hv, hix)) continue;
+                        if constexpr (WHERE) {            // two fp32 compares (a NaN passes nothing) and two masks
+                            const float a = wval[col];
+                            const int f = wflg[col];
+                            if (!(wlo <= a && a <= whi) || (f & wneed) != wneed || (f & wdeny) != 0) continue;
+                        }
                         if (EX) {
                             int a = elo, e = ehi;         // the first list entry >= xi
                             while (a < e) {
@@ -216,7 +271,8 @@ __device__ __forceinline__ void rl_score_body(RL_SCORE_PARAMS(typename Chain::Ta
 // The host path of an entry.  K names the unit's kernels: K::kernel<D, NE, EX>() is the score kernel over a table of T.
 // The entry looks at its lists before its counts (a list without keys is a caller's slip), then -- the bf16 entry's refusal
 // alone -- at the alignment a lane's 16-byte reads of a row need, then plans.  more: what the unit's kernels take behind
-// bad_count (the biased unit's bias), required pointers of the entry like the table.
+// bad_count (the biased unit's bias, the filtered units' RlWhere), required pointers of the entry like the table: each is
+// tested as a bool.
 template <class K, int D, int NE, class T, class... More>
 void rl_launch_score(dim3 grid, hipStream_t st, const float* proj, const int32_t* type_rowptr, const int32_t* type_col,
                      const T* table, int n_types, int n, int S, const RgWs& w, const int32_t* row_key, int rows,

@@ -28,6 +28,9 @@ recommend_page_batch merges a query's K lists into one row under a per-type quot
 recommend_batch's own pool.  SimilarProducts.similar_capped_batch does the same for substitutes, without the query's variants.
 recommend_basket_batch answers for a whole basket: the items' lists fused into one on the device (pc_fuse_lists), without the
 basket's own products and the substitutes of any of them.
+set_attributes / recommend_where_batch / similar_where_batch narrow a list by a per-QUERY predicate on per-product attributes -- a
+band on a value (price), masks on 32 flag bits (regions, seller tiers) -- tested inside the long-list kernel
+(pc_retrieve_list_grouped_where and its bf16 / biased twins): what set_eligible would serve per predicate, in one call.
 
 SimilarProducts is the substitute side: the nearest products of a query under Euclidean distance over any [P, D] fp32 table
 (Product2Vec's export), the grouped retrieval and rank with the per-product term -|e_p|^2 / 2 on the score
@@ -114,6 +117,67 @@ class _CandidateFilters:
         self.eligible = mask
         self.cand_type = torch.where(mask, cand, torch.full_like(cand, -1))
         return self
+
+    attributes = None                          # (value [P] fp32 or None, flags [P] int32 or None): set_attributes
+
+    def set_attributes(self, value=None, flags=None):
+        """Install the per-product attributes that the *_where_batch methods filter on: value [P] float32 (a price, a rating, a
+        delivery time) and / or flags [P] int32 read as 32 bits (ships-to-region bits, a seller tier), device tensors.  Once
+        per catalogue, off the serving path; set_attributes() removes them.  Nothing is rebuilt: the predicate is per query
+        (ops.RowWhere), the attributes are read by the list kernel as it scores."""
+        p = int(self.type_idx.shape[0])
+        for name, t, dtype in (("value", value, torch.float32), ("flags", flags, torch.int32)):
+            if t is not None and (not torch.is_tensor(t) or t.dtype != dtype or tuple(t.shape) != (p,)):
+                raise ValueError(f"set_attributes: {name} must be a {dtype} tensor of shape ({p},), got "
+                                 f"{(t.dtype, tuple(t.shape)) if torch.is_tensor(t) else type(t).__name__}")
+        if value is None and flags is None:
+            self.attributes = None
+            return self
+        self.attributes = tuple(None if t is None else t.to(self.device).contiguous() for t in (value, flags))
+        return self
+
+    def band_around(self, query_idx, below=0.5, above=2.0):
+        """(lo, hi) = (value[q] * below, value[q] * above) as [B] fp32 device tensors: the band of the common case -- complements
+        within 0.5x to 2x of the query's price.  Two multiplications."""
+        if self.attributes is None or self.attributes[0] is None:
+            raise ValueError("band_around: no per-product value is installed (set_attributes(value=...))")
+        v = self.attributes[0][query_idx.to(self.device).long()]
+        return v * below, v * above
+
+    def _row_predicate(self, what, rows, lo, hi, need, deny):
+        """The ops.RowWhere of `rows` queries from the installed attributes and the per-query arrays [rows] (a missing end of a
+        band is infinite); ValueError where no attributes are installed, none of the four is given, or an array has no
+        attribute to test -- before anything is computed."""
+        if self.attributes is None:
+            raise ValueError(f"{what}: no per-product attributes are installed (set_attributes)")
+        if lo is None and hi is None and need is None and deny is None:
+            raise ValueError(f"{what}: give at least one of lo, hi, need, deny (the unfiltered lists are the other methods')")
+        value, flags = self.attributes
+        band, masks = lo is not None or hi is not None, need is not None or deny is not None
+        if band and value is None:
+            raise ValueError(f"{what}: lo / hi bound the per-product value, and none is installed (set_attributes(value=...))")
+        if masks and flags is None:
+            raise ValueError(f"{what}: need / deny test the per-product flags, and none are installed (set_attributes(flags=...))")
+        parts = {}
+        for name, t, dtype in (("lo", lo, torch.float32), ("hi", hi, torch.float32), ("need", need, torch.int32),
+                               ("deny", deny, torch.int32)):
+            if t is None:
+                continue
+            if not torch.is_tensor(t) or t.dtype != dtype or tuple(t.shape) != (rows,):
+                raise ValueError(f"{what}: {name} must be a {dtype} tensor of one entry per query ({rows},), got "
+                                 f"{(t.dtype, tuple(t.shape)) if torch.is_tensor(t) else type(t).__name__}")
+            parts[name] = t.to(self.device).contiguous()
+        if band:
+            parts.setdefault("lo", torch.full((rows,), float("-inf"), device=self.device))
+            parts.setdefault("hi", torch.full((rows,), float("inf"), device=self.device))
+        return ops.RowWhere(value=value if band else None, flags=flags if masks else None, **parts)
+
+    @staticmethod
+    def _repeat_predicate(where, repeat):
+        """`where` with every per-query entry repeated over `repeat` consecutive rows (a query's K slots), as _exclude_rows
+        repeats the keys."""
+        rep = lambda t: None if t is None else t.repeat_interleave(repeat).contiguous()
+        return ops.RowWhere(where.value, where.flags, rep(where.lo), rep(where.hi), rep(where.need), rep(where.deny))
 
     def _group_covers(self, what, group):
         """a product-group array names every product of the catalogue (a shorter one would turn served ids into bad ids)"""
@@ -294,6 +358,37 @@ class PCompanionInference(_CandidateFilters):
             idx, sc = ops.retrieve_topk_grouped(*rows, self.features, n, exclude=exclude)
         else:
             idx, sc = ops.retrieve_topk(*rows, self.features, n)
+        return types, idx.reshape(b, k, -1), sc.reshape(b, k, -1)
+
+    @torch.no_grad()
+    def recommend_where_batch(self, query_idx: torch.Tensor, num_recommendations: int = 10, lo: torch.Tensor = None,
+                              hi: torch.Tensor = None, need: torch.Tensor = None, deny: torch.Tensor = None):
+        """recommend_batch's lists over the products that pass a per-QUERY predicate on the installed attributes
+        (set_attributes): lo / hi [B] float32 pass product p iff lo[b] <= value[p] <= hi[b] (band_around gives the band around
+        the query's own value; a missing end is infinite), need / deny [B] int32 pass it iff (flags[p] & need[b]) == need[b] and
+        (flags[p] & deny[b]) == 0.  The per-query arrays are repeated over the query's K slots as the exclusion keys are; the
+        exclusions and the eligibility installed on this object apply as in recommend_batch.  One call of
+        ops.retrieve_list_grouped_where for any 1 <= num_recommendations <= 256: what recommend_batch would serve under
+        set_eligible(mask of the predicate), bit for bit, for predicates that differ per query.  Returns recommend_batch's
+        triple.  Served from the fp32 features or an ops.CompactCatalogue; a bare bf16 catalogue stops at 16, as it does for
+        recommend_batch.  ValueError before the model runs where no attributes are installed or none of the four is given."""
+        n = self._list_length(num_recommendations)
+        if n < 1:
+            raise ValueError(f"recommend_where_batch: at least 1 recommendation per (query, type), got {n}")
+        if self.catalogue is not None and n > 16 and self.compact is None:
+            raise ValueError(f"recommend_where_batch: a bf16 catalogue serves at most 16 recommendations per (query, type), got "
+                             f"{n}; longer lists need the fp32 catalogue (catalogue=None) or an ops.CompactCatalogue")
+        where = self._row_predicate("recommend_where_batch", int(query_idx.shape[0]), lo, hi, need, deny)
+        query_idx = query_idx.to(self.device).to(torch.int32).contiguous()
+        batch = {"query_idx": query_idx, "query_types": self.type_idx[query_idx.long()]}
+        out = self.model(batch)
+        types = out["complementary_types"]
+        b, k = types.shape
+        proj = out["projected_embeddings"].contiguous().reshape(b * k, -1)
+        row_types = types.to(torch.int32).reshape(-1).contiguous()
+        table = self.catalogue if self.catalogue is not None else self.features
+        idx, sc = ops.retrieve_list_grouped_where(proj, row_types, self.type_rowptr, self.type_col, table, n,
+                                                  self._repeat_predicate(where, k), exclude=self._exclude_rows(query_idx, k))
         return types, idx.reshape(b, k, -1), sc.reshape(b, k, -1)
 
     _inv_norm = None                           # ops.inv_norm of the fp32 features: recommend_diverse_batch, formed on first use
@@ -756,6 +851,26 @@ class SimilarProducts(_CandidateFilters):
         return idx, self._list_distances(q, idx)
 
     @torch.no_grad()
+    def similar_where_batch(self, query_idx: torch.Tensor, n: int = 10, lo: torch.Tensor = None, hi: torch.Tensor = None,
+                            need: torch.Tensor = None, deny: torch.Tensor = None):
+        """similar_list_batch's contract (1 <= n <= MAX_LIST; idx [B, n] int32, dist [B, n] fp32, -1 / +inf past the end) over
+        the candidates that pass a per-query predicate on the installed attributes (set_attributes): lo / hi [B] float32 a band
+        on value[p] (band_around: substitutes around the query's price; hi = value[q]: cheaper ones), need / deny [B] int32
+        masks on flags[p].  ops.retrieve_list_grouped_where under this object's bias, in both scopes: what similar_list_batch
+        serves under set_eligible(mask of the predicate), ids and distances bit for bit, for predicates that differ per query.
+        ValueError before anything is computed where no attributes are installed or none of the four is given."""
+        n = self._list_length("similar_where_batch", n)
+        where = self._row_predicate("similar_where_batch", int(query_idx.shape[0]) if query_idx.dim() else -1, lo, hi, need, deny)
+        query_idx = self._queries("similar_where_batch", query_idx)
+        if query_idx.shape[0] == 0:
+            return self._no_neighbours(n)
+        q = self._rows(query_idx.long())
+        idx, _ = ops.retrieve_list_grouped_where(q, self._scope_type[query_idx.long()].contiguous(), self.type_rowptr,
+                                                 self.type_col, self.table, n, where, exclude=self._exclude_rows(query_idx),
+                                                 bias=self.bias)
+        return idx, self._list_distances(q, idx)
+
+    @torch.no_grad()
     def similar_capped_list_batch(self, query_idx: torch.Tensor, n: int = 10, group: torch.Tensor = None, cap: int = 1,
                                   own_group: bool = False, pool: int = 64):
         """similar_capped_batch's rule over a longer pool: ops.cap_lists on the negated reported distances of this object's
@@ -1010,6 +1125,11 @@ class IndexedSimilarProducts(SimilarProducts):
         q = self.table[query_idx.long()]
         idx, _ = self._search(query_idx, q, n, nprobe, long=True)
         return idx, self._list_distances(q, idx)
+
+    def similar_where_batch(self, query_idx, n=10, lo=None, hi=None, need=None, deny=None):
+        """Not served through the cell index: the per-query attribute filter is the exact classes'."""
+        raise NotImplementedError("IndexedSimilarProducts.similar_where_batch: the per-query attribute filter is not served "
+                                  "through the cell index; SimilarProducts / CompactSimilarProducts serve it")
 
     @torch.no_grad()
     def recall(self, query_idx: torch.Tensor, n: int = 10, nprobe: int = None):

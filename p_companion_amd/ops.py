@@ -2019,8 +2019,9 @@ def _grouped_call(name, tag, device, sizes, args, sized_as=None):
 
 
 def _retrieve_grouped(name, proj, types, type_rowptr, type_col, table, n, slices, exclude, bad, *, bias=None,
-                      what="retrieve_topk_grouped", tag="retrieve_grouped", table_dtype=torch.float32):
-    """retrieve_topk_grouped / retrieve_list_grouped behind the choice of the entry."""
+                      what="retrieve_topk_grouped", tag="retrieve_grouped", table_dtype=torch.float32, where=None):
+    """retrieve_topk_grouped / retrieve_list_grouped behind the choice of the entry (where: a RowWhere, for the entries that
+    take a pc_row_where behind bad_count)."""
     if exclude is not None:
         exclude = _check_exclude(what, exclude, types.shape[0] if isinstance(types, torch.Tensor) else -1)
     elif bad is not None:
@@ -2039,6 +2040,8 @@ def _retrieve_grouped(name, proj, types, type_rowptr, type_col, table, n, slices
         bias = () if bias is None else (_req(bias, torch.float32, "bias", (table.shape[0],)).data_ptr(),)
         args = (proj.data_ptr(), types.data_ptr(), _p(row_key), r, type_rowptr.data_ptr(), type_col.data_ptr(), table.data_ptr(),
                 *bias, t, _p(ex_rowptr), _p(ex_col), n_keys, n, d, slices, out_idx.data_ptr(), out_sc.data_ptr(), _p(bad))
+        if where is not None:
+            args += (ctypes.byref(where._struct(what, table.shape[0], r)),)
     _grouped_call(name, tag, device, (r, t, n, slices), args)
     return out_idx, out_sc
 
@@ -2217,6 +2220,91 @@ def retrieve_list_grouped_bf16_biased(proj, types, type_rowptr, type_col, table,
     _check_bias_bf16(what, bias, table)
     return _retrieve_grouped("pc_retrieve_list_grouped_bf16_biased", proj, types, type_rowptr, type_col, table, n, slices, exclude,
                              bad, bias=bias, what=what, tag="retrieve_list", table_dtype=torch.bfloat16)
+
+
+class RowWhere:
+    """pc_row_where, checked: the per-product attributes of a catalogue and a per-row predicate over them, for
+    retrieve_list_grouped_where.  Every part may be None.
+      value [P] float32, flags [P] int32 (read as 32 bits): the attributes, installed once per catalogue;
+      lo, hi [R] float32: product p passes row r iff lo[r] <= value[p] <= hi[r] -- two fp32 compares: the ends are inclusive,
+                          a NaN value or bound passes nothing, lo > hi passes nothing, -inf / +inf pass every non-NaN value;
+                          both with value and neither without (a one-sided caller passes an infinite bound);
+      need, deny [R] int32: p passes iff (flags[p] & need[r]) == need[r] and (flags[p] & deny[r]) == 0; only with flags, an
+                          absent one is 0.
+    Dtypes, 1-D shapes, one device for all parts and the pairing rule are checked here, on the host side alone (ValueError);
+    the lengths against P and R at the call."""
+
+    ATTRIBUTES = (("value", torch.float32), ("flags", torch.int32))
+    PREDICATE = (("lo", torch.float32), ("hi", torch.float32), ("need", torch.int32), ("deny", torch.int32))
+
+    def __init__(self, value=None, flags=None, lo=None, hi=None, need=None, deny=None):
+        parts = dict(value=value, flags=flags, lo=lo, hi=hi, need=need, deny=deny)
+        device = None
+        for name, dtype in self.ATTRIBUTES + self.PREDICATE:
+            t = parts[name]
+            if t is None:
+                continue
+            if not isinstance(t, torch.Tensor):
+                raise ValueError(f"RowWhere: {name} must be None or a 1-D {dtype} device tensor, got {type(t).__name__}")
+            if t.dtype != dtype:
+                raise ValueError(f"RowWhere: {name} of dtype {t.dtype} is not supported: it must be {dtype}")
+            if t.dim() != 1:
+                raise ValueError(f"RowWhere: {name} must be 1-D, got shape {tuple(t.shape)}")
+            if device is not None and t.device != device:
+                raise ValueError(f"RowWhere: {name} is on {t.device}, the parts before it on {device}: one device for all")
+            device = t.device
+        if value is None and (lo is not None or hi is not None):
+            raise ValueError("RowWhere: lo / hi bound `value`, which is absent")
+        if value is not None and (lo is None or hi is None):
+            raise ValueError("RowWhere: value needs both lo and hi (a one-sided band passes an infinite bound)")
+        if flags is None and (need is not None or deny is not None):
+            raise ValueError("RowWhere: need / deny test `flags`, which is absent")
+        self.__dict__.update(parts)
+
+    def _struct(self, what, p, r):
+        """The _lib.RowWhere of a call over p products and r rows: lengths (ValueError), device and layout (_req) checked."""
+        st = _lib.RowWhere()
+        for names, length, of in ((self.ATTRIBUTES, p, "product"), (self.PREDICATE, r, "row")):
+            for name, dtype in names:
+                t = getattr(self, name)
+                if t is None:
+                    continue
+                if t.shape[0] != length:
+                    raise ValueError(f"{what}: where.{name} must hold one entry per {of} ({length}), got {t.shape[0]}")
+                setattr(st, name, _req(t, dtype, "where." + name).data_ptr())
+        return st
+
+
+def retrieve_list_grouped_where(proj, types, type_rowptr, type_col, table, n, where, slices=0, exclude=None, bad=None,
+                                bias=None):
+    """pc_retrieve_list_grouped_where and its three twins: retrieve_list_grouped's contract (idx [R,n] int32, -1 = none; scores
+    [R,n] fp32, -inf = none; 1 <= n <= RETRIEVE_LIST_MAX_N; exclude and `bad` as there) over the products that pass the row's
+    predicate `where` (a RowWhere: a band on a per-product value, masks on per-product flags).  A product that fails is treated
+    exactly as an excluded one: the list is the unfiltered order (score descending, product index ascending) with the failing
+    products taken out -- what retrieve_list_grouped serves over a CSR of the passing products, bit for bit, in ONE call for
+    rows that each have their own predicate.  The score bits are the underlying entry's; a RowWhere() with every part absent
+    gives that entry's output.  The entry goes by the table and the bias:
+      table [P, D] fp32, bias None          pc_retrieve_list_grouped_where           (retrieve_list_grouped)
+      table [P, D] bfloat16, bias None      pc_retrieve_list_grouped_bf16_where      (retrieve_list_grouped, bf16 copy)
+      table fp32, bias [P] fp32             pc_retrieve_list_grouped_biased_where    (retrieve_list_grouped_biased's checks)
+      table bfloat16, bias [P] fp32         pc_retrieve_list_grouped_bf16_biased_where (retrieve_list_grouped_bf16_biased's)
+    The same kernel body, merge and determinism: the same bits for every `slices`.  Nothing is read back to the host."""
+    what = "retrieve_list_grouped_where"
+    n = int(n)
+    if not 1 <= n <= RETRIEVE_LIST_MAX_N:
+        raise ValueError(f"{what}: n must be in [1, {RETRIEVE_LIST_MAX_N}], got {n}")
+    if not isinstance(where, RowWhere):
+        raise ValueError(f"{what}: where must be an ops.RowWhere, got {type(where).__name__}")
+    bf16 = isinstance(table, torch.Tensor) and table.dtype == torch.bfloat16
+    if bias is not None:
+        if bf16:
+            _check_bf16_table(what, table, "retrieve_list_grouped_biased")
+            _check_bias_bf16(what, bias, table)
+        else:
+            _check_bias(what, bias, table)
+    name = "pc_retrieve_list_grouped" + ("_bf16" if bf16 else "") + ("_biased" if bias is not None else "") + "_where"
+    return _retrieve_grouped(name, proj, types, type_rowptr, type_col, table, n, slices, exclude, bad, bias=bias, what=what,
+                             tag="retrieve_list", table_dtype=torch.bfloat16 if bf16 else torch.float32, where=where)
 
 
 def rank_grouped_bf16(proj, types, targets, type_rowptr, type_col, table, slices=0, bad=None, exclude=None, cand_type=None,
