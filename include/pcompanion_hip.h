@@ -1516,6 +1516,55 @@ int pc_fuse_lists(const int32_t *idx, const float *score, const int32_t *source,
                   const int32_t *ex_rowptr, const int32_t *ex_col, int num_products, int n, int combine, int32_t *out_idx,
                   float *out_score, int32_t *out_support, int32_t *bad_count, void *stream);
 
+/* Session recommendations (ABI 8, additive; csrc/fuse_sessions.hip; ops.fuse_sessions,
+ * PCompanionInference.recommend_session_batch): pc_fuse_lists' fusion for ragged sessions with a weight per item, built on a
+ * walk that is linear in the pool.
+ *
+ * pc_fuse_sessions: idx / score [rows, w], 1 <= w <= 1024: row r is what a grouped retrieval returned for item r -- its K type
+ * lists side by side --, the slots in any order, -1 ids and non-finite scores anywhere.  source [rows] int32 or NULL: the
+ * item's product id, -1 = no item; NULL: every row qualifies and nothing is banned.  weight [rows] fp32 or NULL: NULL means
+ * every weight is 1.  seg_rowptr [sessions + 1] int32: session b owns the rows [seg_rowptr[b], seg_rowptr[b + 1]).  ex_rowptr
+ * [num_products + 1] / ex_col: an exclusion CSR keyed by product id with strictly ascending rows (ops.exclusion_csr), both or
+ * neither, and only with source.
+ *   live rows     L = min(1024 / w, max_items if max_items != 0).  Only the LAST L rows of a session -- its most recent items --
+ *                 offer candidates; a session with more rows adds one to *truncated_count (int32 [1], optional, added to).
+ *                 Every row of the session still bans, however long the session is.
+ *   offering row  a live row whose source lies in [0, num_products) (without source every row qualifies) and whose weight is
+ *                 finite and > 0.  A row with weight 0, a negative weight, NaN or +-inf offers nothing; its source still bans:
+ *                 the "already bought" case.
+ *   term          t = fl(weight[r] * score): one fp32 multiplication, rounded, formed before anything is added and never
+ *                 contracted with an addition.  A slot is a candidate iff its row offers, its id lies in [0, num_products) and
+ *                 t is finite: an overflowed term is no candidate.  Terms in the subnormal range are outside the contract
+ *                 (whether they are flushed is the device's floating-point mode, not this entry's).
+ *   ban set       the sources of all rows of the session and, with the CSR, every id in the exclusion rows of those sources:
+ *                 pc_fuse_lists' rule.  A banned product is no candidate, whichever row offered it.
+ *   fusion        all candidate slots of a session that hold one product id are one product.  With its terms in descending
+ *                 order t1 >= t2 >= ... (+0.0 before -0.0) -- combine 0 (sum): f = t1, then f = fl(f + t2), and so on:
+ *                 sequential fp32, the largest first.  combine 1 (max): f = t1.  support = the number of slots fused.  A sum
+ *                 that overflows is served as the infinity it became.
+ *   order         out_idx / out_score / out_support [sessions, n], 1 <= n <= 256: the first n products under (fused score
+ *                 descending, product index ascending); -1 / -inf / 0 past the end; an empty session is all padding.
+ *   bad inputs    an id of a live row or a source of any row outside [-1, num_products) is never used as an index and adds one
+ *                 to *bad_count (int32 [1], optional, added to); such a source's row offers nothing; the slots of rows that
+ *                 are not live are not read.  A seg_rowptr entry outside [0, rows] or below its predecessor adds one and is
+ *                 clamped -- lo to [0, rows], hi to [lo, rows] --: nothing outside the arrays is read.
+ * One wave per session; 64 lanes x 2, 4, 8 or 16 register slots serve effective pools min(len, L) * w of up to 128, 256, 512
+ * and 1024.  The pools differ per session and are not read back: every variant that L * w can reach is launched on the one
+ * stream, and a wave passes over the sessions of the other variants, so every session is written by exactly one launch.  The
+ * slots are sorted by (id ascending, term descending), so that a product's slots are adjacent; the head of each run adds the
+ * run in that order; the heads are sorted again under their fused scores and compacted.  No workspace, no float atomics
+ * (integer atomics for the two counters only), no host readback; the result does not depend on the launch geometry, the run,
+ * the variant that served the session, a permutation of a session's rows together with their sources and weights among the
+ * rows of one truncation status, or a permutation of the slots inside rows.
+ * PC_ESHAPE: rows < 0, sessions < 0, w outside [1, 1024], n outside [1, 256], max_items < 0, combine not 0 / 1, num_products
+ * < 1, one of ex_rowptr / ex_col without the other or without source, and, when sessions > 0, a null seg_rowptr / out_idx /
+ * out_score / out_support or (when rows > 0) a null idx / score -- each checked before anything is launched; sessions == 0
+ * succeeds without a launch. */
+int pc_fuse_sessions(const int32_t *idx, const float *score, const int32_t *source, const float *weight,
+                     const int32_t *seg_rowptr, int rows, int sessions, int w, int max_items, const int32_t *ex_rowptr,
+                     const int32_t *ex_col, int num_products, int n, int combine, int32_t *out_idx, float *out_score,
+                     int32_t *out_support, int32_t *bad_count, int32_t *truncated_count, void *stream);
+
 /* Per-query attribute filters (ABI 8, additive; csrc/where_list.hip, csrc/where_list_bf16.hip; ops.RowWhere,
  * ops.retrieve_list_grouped_where, PCompanionInference.recommend_where_batch, SimilarProducts.similar_where_batch): lists
  * narrowed by a condition on both the query and a property of the candidate -- complements within 0.5x to 2x of the query's

@@ -269,6 +269,8 @@ SIGNATURES = {
                                   _sz, _vp]),
     # basket recommendations (csrc/fuse_lists.hip; ABI 8, additive)
     "pc_fuse_lists": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    # session recommendations (csrc/fuse_sessions.hip: ragged, weighted sessions on a linear walk; ABI 8, additive)
+    "pc_fuse_sessions": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     # per-query attribute filters (csrc/where_list.hip, csrc/where_list_bf16.hip: grouped_list.h's body with its filter hook;
     # the four long-list entries' lists with a pc_row_where in front of the workspace; ABI 8, additive)
     "pc_retrieve_list_grouped_where_workspace_bytes": (_sz, [_i, _i, _i, _i]),

@@ -27,7 +27,8 @@ recommend_capped_batch keeps at most `cap` products of one product group (a pare
 recommend_page_batch merges a query's K lists into one row under a per-type quota and that cap: one pc_cap_lists pass over
 recommend_batch's own pool.  SimilarProducts.similar_capped_batch does the same for substitutes, without the query's variants.
 recommend_basket_batch answers for a whole basket: the items' lists fused into one on the device (pc_fuse_lists), without the
-basket's own products and the substitutes of any of them.
+basket's own products and the substitutes of any of them.  recommend_session_batch is the same for ragged sessions (a CSR of
+items, no padding rows) with a weight per item -- recency, quantity, "purchased, so only ban it" -- (pc_fuse_sessions).
 set_attributes / recommend_where_batch / similar_where_batch narrow a list by a per-QUERY predicate on per-product attributes -- a
 band on a value (price), masks on 32 flag bits (regions, seller tiers) -- tested inside the long-list kernel
 (pc_retrieve_list_grouped_where and its bf16 / biased twins): what set_eligible would serve per predicate, in one call.
@@ -553,6 +554,64 @@ class PCompanionInference(_CandidateFilters):
         _, idx, sc = self.recommend_batch(basket.reshape(-1).clamp(0, p - 1), per_item)
         idx, sc, support = ops.fuse_lists(idx.reshape(b, items, -1), sc.reshape(b, items, -1), n, combine, source=basket,
                                           exclude=self.exclusions, num_products=p)
+        types = torch.where(idx >= 0, self.type_idx[idx.clamp(min=0).long()].long(), -1)
+        return idx, sc, types, support
+
+    @torch.no_grad()
+    def recommend_session_batch(self, items: torch.Tensor, seg_rowptr: torch.Tensor, num_recommendations: int = 10,
+                                per_item: int = 8, weight: torch.Tensor = None, combine: str = "sum", max_items: int = None):
+        """recommend_basket_batch for RAGGED sessions with a weight per item: (idx [B, n] int32, score [B, n] fp32, types
+        [B, n] int64 = the product's type, -1 where idx is -1, support [B, n] int32).  items [R] int32: the product ids of all
+        sessions' items, one after the other, each session's oldest first; seg_rowptr [B + 1] int32: session b owns
+        items[seg_rowptr[b]:seg_rowptr[b + 1]] (an empty session is served as all padding).  There are no padding rows: ONE
+        recommend_batch(items.clamp(0, P - 1), per_item) serves the R real items -- its catalogue, its per-item exclusions and
+        eligibility, its choice of retrieval entry and its refusals (a bare bf16 catalogue stops at per_item 16) --, and ONE
+        ops.fuse_sessions call (source=items, exclude=the installed exclusion set) fuses each session's rows of K per_item
+        slots as recommend_basket_batch fuses a basket's: the same ids, score bits and supports as that method serves for the
+        sessions padded with -1.  weight [R] fp32 (None: every weight is 1): a slot's score is multiplied by its item's weight
+        (one rounded fp32 product) before the fusion; an item whose weight is not finite and > 0 -- 0: "purchased, so only
+        ban it" -- offers nothing, but it and its excluded products are still kept out of the list.  Recency decay is a torch
+        one-liner that does not synchronise, e.g. for half a point per step back from the session's last item:
+            length = (seg_rowptr[1:] - seg_rowptr[:-1]).long()
+            age = seg_rowptr[1:].repeat_interleave(length, output_size=R) - 1 - torch.arange(R, device=length.device)
+            weight = torch.pow(0.5, age.float())
+        Only the last min(1024 // (K per_item), max_items) items of a session offer (max_items None: no cap); every item
+        bans.  Needs K per_item <= ops.FUSE_SESSIONS_MAX_POOL and 1 <= num_recommendations <= ops.FUSE_SESSIONS_MAX_N, checked
+        before the model runs.  Nothing is read back."""
+        n, per_item, k = int(num_recommendations), int(per_item), int(self.config.NUM_COMP_TYPES)
+        if not torch.is_tensor(items) or items.dim() != 1 or items.dtype != torch.int32:
+            raise ValueError(f"recommend_session_batch: items must be a [R] int32 tensor, got "
+                             f"{tuple(items.shape) if torch.is_tensor(items) else type(items).__name__}"
+                             f"{' ' + str(items.dtype) if torch.is_tensor(items) else ''}")
+        if (not torch.is_tensor(seg_rowptr) or seg_rowptr.dim() != 1 or seg_rowptr.dtype != torch.int32
+                or seg_rowptr.numel() < 1):
+            raise ValueError(f"recommend_session_batch: seg_rowptr must be a [B + 1] int32 tensor, got "
+                             f"{tuple(seg_rowptr.shape) if torch.is_tensor(seg_rowptr) else type(seg_rowptr).__name__}"
+                             f"{' ' + str(seg_rowptr.dtype) if torch.is_tensor(seg_rowptr) else ''}")
+        r = items.shape[0]
+        if weight is not None and (not torch.is_tensor(weight) or weight.dtype != torch.float32
+                                   or tuple(weight.shape) != (r,)):
+            raise ValueError(f"recommend_session_batch: weight must be a [R = {r}] float32 tensor, got "
+                             f"{tuple(weight.shape) if torch.is_tensor(weight) else type(weight).__name__}"
+                             f"{' ' + str(weight.dtype) if torch.is_tensor(weight) else ''}")
+        if per_item < 1 or k * per_item > ops.FUSE_SESSIONS_MAX_POOL:
+            raise ValueError(f"recommend_session_batch: need 1 <= per_item and K * per_item <= {ops.FUSE_SESSIONS_MAX_POOL}, "
+                             f"got K = {k} and per_item {per_item}")
+        if not 1 <= n <= ops.FUSE_SESSIONS_MAX_N:
+            raise ValueError(f"recommend_session_batch: need 1 <= num_recommendations <= {ops.FUSE_SESSIONS_MAX_N}, got {n}")
+        if combine not in ("sum", "max"):
+            raise ValueError(f"recommend_session_batch: combine must be 'sum' or 'max', got {combine!r}")
+        if max_items is not None and int(max_items) < 0:
+            raise ValueError(f"recommend_session_batch: max_items must be None or at least 0 (0: no cap), got {max_items}")
+        items = items.to(self.device).contiguous()
+        seg_rowptr = seg_rowptr.to(self.device).contiguous()
+        if weight is not None:
+            weight = weight.to(self.device).contiguous()
+        p = int(self.type_idx.shape[0])
+        # (an id outside the catalogue is served for the nearest one inside: the fusion lets its row offer nothing)
+        _, idx, sc = self.recommend_batch(items.clamp(0, p - 1), per_item)
+        idx, sc, support = ops.fuse_sessions(idx.reshape(r, k * per_item), sc.reshape(r, k * per_item), seg_rowptr, n, combine, source=items,
+                                             weight=weight, exclude=self.exclusions, num_products=p, max_items=max_items)
         types = torch.where(idx >= 0, self.type_idx[idx.clamp(min=0).long()].long(), -1)
         return idx, sc, types, support
 

@@ -2653,6 +2653,97 @@ def fuse_lists(idx, score, n, combine="sum", source=None, exclude=None, num_prod
     return out_idx, out_sc, out_sup
 
 
+FUSE_SESSIONS_MAX_POOL, FUSE_SESSIONS_MAX_N = 1024, 256
+
+
+def fuse_sessions(idx, score, seg_rowptr, n, combine="sum", source=None, weight=None, exclude=None, num_products=None,
+                  max_items=None, bad=None, truncated=None):
+    """pc_fuse_sessions: fuse_lists for ragged sessions with a weight per item.  idx [R, w] int32 / score [R, w] fp32,
+    1 <= w <= FUSE_SESSIONS_MAX_POOL: row r is what a grouped retrieval returned for item r (its K type lists side by side), in
+    any order (a slot with id -1 or a score that is not finite is no candidate); seg_rowptr [B + 1] int32: session b owns the
+    rows [seg_rowptr[b], seg_rowptr[b + 1]) -> (idx [B, n] int32, score [B, n] fp32, support [B, n] int32), 1 <= n <=
+    FUSE_SESSIONS_MAX_N: the first n products of the session under (fused score descending, product index ascending), -1 /
+    -inf / 0 past the end; an empty session is all padding.  Only the LAST L = min(FUSE_SESSIONS_MAX_POOL // w, max_items)
+    rows of a session offer candidates (max_items None or 0: no cap); a longer session is counted in `truncated`; every row
+    still bans.  weight [R] fp32 (None: every weight is 1): a slot's term is t = fl(weight[r] * score), one rounded fp32
+    multiplication formed before anything is added; a row whose weight is not finite and > 0 offers nothing, but its source
+    still bans ("already bought"); a term that is not finite is no candidate.  All candidate slots of a session with one id are
+    one product; with its terms in descending order t1 >= t2 >= ..., combine="sum": f = t1, f = fl(f + t2), ... (sequential
+    fp32, the largest first); combine="max": f = t1.  support = the number of slots fused.  source [R] int32: the product id
+    of the item behind each row, -1 = no item (the row offers nothing); the sources of ALL rows are banned from their session's
+    list.  exclude = (ex_rowptr [P + 1], ex_col) as exclusion_csr returns them (needs source): every id in the rows of a
+    session's sources is banned too, whichever row offered it.  num_products: ids at or above it are bad; taken from ex_rowptr
+    where given, else the argument, else 2^31 - 1.  An id of a live row or a source outside [-1, num_products) is never used
+    as an index and is counted in `bad` (a [1] int32 device counter the caller passes to see the count; added to), and so is a
+    seg_rowptr entry outside [0, R] or below its predecessor, which is clamped.  `truncated`: a [1] int32 device counter,
+    added to.  Bitwise deterministic; a permutation of a session's rows (with their sources and weights, among the rows of one
+    truncation status) or of the slots inside rows changes nothing.  Nothing is read back."""
+    _req(idx, torch.int32, "idx")
+    _req(score, torch.float32, "score")
+    if idx.dim() != 2 or tuple(score.shape) != tuple(idx.shape):
+        raise ValueError(f"fuse_sessions: expected idx and score of one shape [R, w], got {tuple(idx.shape)} and "
+                         f"{tuple(score.shape)}")
+    r, w = idx.shape
+    if not 1 <= w <= FUSE_SESSIONS_MAX_POOL:
+        raise ValueError(f"fuse_sessions: the row width w must be in [1, {FUSE_SESSIONS_MAX_POOL}], got {w}")
+    _req(seg_rowptr, torch.int32, "seg_rowptr")
+    if seg_rowptr.dim() != 1 or seg_rowptr.numel() < 1:
+        raise ValueError(f"fuse_sessions: expected seg_rowptr [B + 1] with B >= 0, got {tuple(seg_rowptr.shape)}")
+    b = seg_rowptr.numel() - 1
+    n = int(n)
+    if not 1 <= n <= FUSE_SESSIONS_MAX_N:
+        raise ValueError(f"fuse_sessions: n must be in [1, {FUSE_SESSIONS_MAX_N}], got {n}")
+    if combine not in ("sum", "max"):
+        raise ValueError(f"fuse_sessions: combine must be 'sum' or 'max', got {combine!r}")
+    if source is not None:
+        if not isinstance(source, torch.Tensor):
+            raise ValueError(f"fuse_sessions: source must be a [R] int32 device tensor, got {type(source).__name__}")
+        _req(source, torch.int32, "source", (r,))
+    if weight is not None:
+        if not isinstance(weight, torch.Tensor):
+            raise ValueError(f"fuse_sessions: weight must be a [R] float32 device tensor, got {type(weight).__name__}")
+        _req(weight, torch.float32, "weight", (r,))
+    ex_rowptr = ex_col = None
+    if exclude is not None:
+        if source is None:
+            raise ValueError("fuse_sessions: exclude is keyed by the rows' source ids and needs source")
+        if not isinstance(exclude, (tuple, list)) or len(exclude) != 2 or not all(isinstance(t, torch.Tensor) for t in exclude):
+            raise ValueError("fuse_sessions: exclude must be the pair (ex_rowptr, ex_col) of int32 device tensors")
+        ex_rowptr, ex_col = exclude
+        _req(ex_rowptr, torch.int32, "ex_rowptr")
+        _req(ex_col, torch.int32, "ex_col")
+        if ex_rowptr.dim() != 1 or ex_rowptr.numel() < 2 or ex_col.dim() != 1:
+            raise ValueError(f"fuse_sessions: expected ex_rowptr [P + 1] with P >= 1 and a 1-D ex_col, got "
+                             f"{tuple(ex_rowptr.shape)} and {tuple(ex_col.shape)}")
+        if num_products is not None and int(num_products) != ex_rowptr.numel() - 1:
+            raise ValueError(f"fuse_sessions: num_products {int(num_products)} does not match the exclusion set's "
+                             f"{ex_rowptr.numel() - 1} keys")
+        num_products = ex_rowptr.numel() - 1
+        if ex_col.numel() == 0:                           # (every row empty: one unread entry, so that the pointer is not null)
+            ex_col = torch.zeros(1, dtype=torch.int32, device=idx.device)
+    num_products = 2 ** 31 - 1 if num_products is None else int(num_products)
+    if not 1 <= num_products <= 2 ** 31 - 1:
+        raise ValueError(f"fuse_sessions: num_products must be in [1, 2^31 - 1], got {num_products}")
+    max_items = 0 if max_items is None else int(max_items)
+    if not 0 <= max_items <= 2 ** 31 - 1:
+        raise ValueError(f"fuse_sessions: max_items must be None or in [0, 2^31 - 1] (0: no cap), got {max_items}")
+    if bad is not None:
+        _req(bad, torch.int32, "bad", (1,))
+    if truncated is not None:
+        _req(truncated, torch.int32, "truncated", (1,))
+    out_idx = torch.empty(b, n, dtype=torch.int32, device=idx.device)
+    out_sc = torch.empty(b, n, dtype=torch.float32, device=idx.device)
+    out_sup = torch.empty(b, n, dtype=torch.int32, device=idx.device)
+    if b == 0:
+        return out_idx, out_sc, out_sup
+    if r == 0:                                            # (no rows: nothing offers and nothing bans; every pointer is null)
+        source = weight = ex_rowptr = ex_col = None
+    check(_lib.lib().pc_fuse_sessions(_p(idx), _p(score), _p(source), _p(weight), _p(seg_rowptr), r, b, w, max_items,
+                                      _p(ex_rowptr), _p(ex_col), num_products, n, 0 if combine == "sum" else 1, _p(out_idx),
+                                      _p(out_sc), _p(out_sup), _p(bad), _p(truncated), _stream()), "pc_fuse_sessions")
+    return out_idx, out_sc, out_sup
+
+
 class CompactCatalogue:
     """The bf16 copy of a catalogue as a serving table of its own: everything PCompanionInference needs to serve lists of up
     to RETRIEVE_LIST_MAX_N products per type and diversified lists without the fp32 features (catalogue=CompactCatalogue(...)).
