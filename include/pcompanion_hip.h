@@ -490,7 +490,9 @@ int pc_joint_forward(const pc_joint_tensors *p, const int32_t *query_idx,
  * loss = alpha*item + (1-alpha)*type.  losses[3] = {loss, type, item}.
  * dsims is SPARSE: dsims_val[B,2] holds d(loss)/dS at columns (pos_b, neg_b) -- the only
  * non-zeros (the reference materialises a dense [B,T] zero gradient: SURVEY section 6).
- * dsims_val / dproj may be NULL (forward only).  partials: device scratch float[2*B]. */
+ * dsims_val / dproj may be NULL (forward only).  partials: device scratch float[2*B].
+ * At the kinks the gradients are torch's: a hinge of exactly 0 is active (clamp: slope 1 at 0), a
+ * norm of exactly 0 sends nothing (subgradient 0). */
 int pc_joint_loss(const float *sims, const float *proj, const int32_t *pos_types,
                   const int32_t *neg_types, const float *pos_items, const float *neg_items,
                   int batch, int num_types, int k, float margin, float alpha, float *losses,
@@ -1255,7 +1257,7 @@ int pc_rank_grouped_biased(const float *proj, const int32_t *types, const int32_
  *   np = |x_bk - pos_b|, nn = |x_bk - neg_b| (no eps), l = margin - np + nn, g = l > 0 ? alpha / (B K) : 0
  *   dx_bk = -(x_bk - pos_b) (np > 0 ? g / np : 0) + (x_bk - neg_b) (nn > 0 ? g / nn : 0)
  *   dq_b = W_item^T sum_k dx_bk * tp_bk
- * -- pc_joint_loss's conventions (strict hinge, subgradient 0 at a zero norm).  p: the step's parameters with product_table
+ * -- the fused joint step's conventions (strict hinge, subgradient 0 at a zero norm).  p: the step's parameters with product_table
  * [num_products, dim] set; dim 128 or 256; dq is written for every row.  A query_idx outside [0, num_products) or a topk id
  * outside [0, T) never indexes anything: the sample's dq row is zero and every such id adds one to *bad (int32 [1], added to).
  * Six launches on `stream` (id check, the two projections, W_item^T, the row-wise pass, the product with W_item^T), no host

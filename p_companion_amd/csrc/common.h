@@ -427,7 +427,8 @@ __device__ __forceinline__ void triplet_sample16(const float* __restrict__ a, co
     if (!grads) return;
     const bool active = (margin - dpos + dneg) > 0.f;      // relu'(0) = 0 as in torch
     const float gs = (active && live) ? 1.0f / (float)B : 0.f;        // d(mean)/d(l_b)
-    const float ip = gs / dpos;                            // d l / d d+ = -1 ; d l / d d-_j = 1/K
+    // d l / d d+ = -1 ; d l / d d-_j = 1/K; a distance of exactly 0 sends nothing (torch's norm: subgradient 0 at 0)
+    const float ip = dpos > 0.f ? gs / dpos : 0.f;
 #pragma unroll
     for (int c = 0; c < 8; c++) ga[c] = -dpv[c] * ip;
     if (live) {
@@ -437,7 +438,7 @@ __device__ __forceinline__ void triplet_sample16(const float* __restrict__ a, co
 #pragma unroll
     for (int j = 0; j < PC_LOSS_MAX_K; j++)
         if (j < K) {
-            const float in = gs / ((float)K * dn_j[j]);
+            const float in = dn_j[j] > 0.f ? gs / ((float)K * dn_j[j]) : 0.f;
 #pragma unroll
             for (int c = 0; c < 8; c++) ga[c] += dnv[j][c] * in;
             if (live) {

@@ -227,7 +227,7 @@ __global__ __launch_bounds__(256) void joint_loss_kernel(const float* sims, cons
     if (lane == 0) {
         part_type[b] = lt > 0.f ? lt : 0.f;
         if (dsims_val) {
-            const float g = lt > 0.f ? (1.0f - alpha) / (float)B : 0.f;
+            const float g = lt >= 0.f ? (1.0f - alpha) / (float)B : 0.f;   // torch.clamp(min=0): subgradient 1 at 0
             dsims_val[2 * b] = -g;
             dsims_val[2 * b + 1] = g;
         }
@@ -253,7 +253,7 @@ __global__ __launch_bounds__(256) void joint_loss_kernel(const float* sims, cons
         const float l = margin - np_ + nn_;
         li += l > 0.f ? l : 0.f;
         if (dproj) {
-            const float g = l > 0.f ? alpha / ((float)B * (float)K) : 0.f;
+            const float g = l >= 0.f ? alpha / ((float)B * (float)K) : 0.f;       // torch.clamp(min=0): subgradient 1 at 0
             const float ip = np_ > 0.f ? g / np_ : 0.f, in = nn_ > 0.f ? g / nn_ : 0.f;   // torch.norm: subgradient 0 at 0
 #pragma unroll
             for (int ch = 0; ch < NCH; ch++)

@@ -47,8 +47,8 @@ __global__ __launch_bounds__(256) void triplet_loss_kernel(const float* a, const
     if (!da) return;
     const bool active = (margin - dpos + dneg) > 0.f;      // relu'(0) = 0 as in torch
     const float gs = active ? 1.0f / (float)B : 0.f;        // d(mean)/d(l_b)
-    // d l / d d+ = -1 ; d l / d d-_j = 1/K
-    const float ip = gs / dpos;
+    // d l / d d+ = -1 ; d l / d d-_j = 1/K; a distance of exactly 0 sends nothing (torch's norm: subgradient 0 at 0)
+    const float ip = dpos > 0.f ? gs / dpos : 0.f;
     float ga[VW];
 #pragma unroll
     for (int c = 0; c < VW; c++) {
@@ -58,7 +58,7 @@ __global__ __launch_bounds__(256) void triplet_loss_kernel(const float* a, const
 #pragma unroll
     for (int j = 0; j < LOSS_MAX_K; j++) {
         if (j < K) {
-            const float in = gs / ((float)K * dn_j[j]);
+            const float in = dn_j[j] > 0.f ? gs / ((float)K * dn_j[j]) : 0.f;
 #pragma unroll
             for (int c = 0; c < VW; c++) {
                 ga[c] += dnv[j][c] * in;
