@@ -100,9 +100,14 @@ int pc_abi_version(void);
  * PC_OPT_FUSED_OUT_CHAIN (ABI 8; needs PC_OPT_FUSED_LOSS): 1 (default) = the attention forward's last launch (ctx and the
  * out-projection, MultiheadAttention of product2vec.py:23-28,48-68) runs in front of that prologue in the same launch -- per
  * 16-sample tile: out-projection forward, hinge, out-projection backward; 0 = its own launch.  Same bits.
+ * PC_OPT_DW0_STAGED_H (ABI 8, additive): how the weight-gradient kernel of Linear0 (dW0, rows >= 8192, no dx consumer) gets the
+ * H0 values its loader needs for the BatchNorm backward of dZ1 (product2vec.py:15-16).  0 (default) = from global memory into
+ * the registers of the thread that transforms the element; the LDS stage holds dZ1 and the gathered rows only.  1 = staged
+ * through LDS beside dZ1 (the form before; 16-row chunks in three stages at PRODUCT_EMB_DIM = 128), kept for comparison.
+ * The same expression on the same rows in the same order: the same bits.
  * Unknown option / value: PC_EINVAL.  Thread-safe. */
 enum { PC_OPT_SIDE_QUEUE = 1, PC_OPT_SORTED_TABLE_GRADIENTS = 2, PC_OPT_BN_FINALIZE_SIDE = 3, PC_OPT_FUSED_LOSS = 4,
-       PC_OPT_FUSED_OUT_CHAIN = 5, PC_OPT_BN_FINALIZE_RIDES = 6 };
+       PC_OPT_FUSED_OUT_CHAIN = 5, PC_OPT_BN_FINALIZE_RIDES = 6, PC_OPT_DW0_STAGED_H = 7 };
 int pc_set_option(int option, int value);
 int pc_get_option(int option, int* value);
 /* Destroys the library-owned device state (side queues and their events) of every device; 0 or a hipError_t. */

@@ -87,7 +87,8 @@ PC_OPT_FUSED_OUT_CHAIN = 5           # ... and the out-projection's forward chai
 PC_OPT_FUSED_LOSS = 4                # ... the triplet hinge inside the attention backward's first launch (default 1)
 PC_OPT_BN_FINALIZE_SIDE = 3          # ... the BatchNorm-backward finalize of the fused Product2Vec step on the side queue (default 0: on the step's own)
 PC_OPT_BN_FINALIZE_RIDES = 6         # ... that finalize as rider workgroups of the dW3 launch at rows >= 8192 (default 1)
-PC_OPT_SORTED_TABLE_GRADIENTS = 2    # ... the [T,64] table gradients of the fused joint step through the sorted form wherever it fits (default 1)
+PC_OPT_DW0_STAGED_H = 7              # ... dW0's loader takes H0 through an LDS image beside dZ1 instead of through registers (default 0)
+PC_OPT_SORTED_TABLE_GRADIENTS = 2   # ... the [T,64] table gradients of the fused joint step through the sorted form wherever it fits (default 1)
 
 # name -> (restype, argtypes).  Must list every symbol include/pcompanion_hip.h declares
 # (tests/test_abi.py parses the header and checks this table and the .so against it).

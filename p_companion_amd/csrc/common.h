@@ -109,6 +109,20 @@ __device__ __forceinline__ float row_multiplicity(const SegInfo& si, int r) {
     return r == si.wrow ? si.wmult : 1.f;
 }
 
+// row_multiplicity() in two halves for a loader that fetches a chunk ahead of its use: where the listed multiplicity of row r
+// lies (`none`, any readable float, when the row has none listed), and what the row stands for given the float read there --
+// the select needs the loaded value, so it stays with the use and the load waits for nothing
+__device__ __forceinline__ const float* row_multiplicity_src(const SegInfo& si, int r, const float* none) {
+    return (si.roww && (unsigned)(r - si.w0) < (unsigned)si.wn) ? si.roww + (r - si.w0) : none;
+}
+__device__ __forceinline__ float row_multiplicity_from(const SegInfo& si, int r, float listed) {
+#ifdef PC_EXP_NO_ROWMULT
+    return 1.f;
+#endif
+    if (si.roww && (unsigned)(r - si.w0) < (unsigned)si.wn) return listed;
+    return r == si.wrow ? si.wmult : 1.f;
+}
+
 __device__ __forceinline__ int seg_of_tile(const SegInfo& si, int t) {
     int s = 0;
 #pragma unroll
@@ -626,6 +640,7 @@ int pc_opt_bn_finalize_side();
 int pc_opt_bn_finalize_rides();
 int pc_opt_fused_loss();
 int pc_opt_fused_out_chain();
+int pc_opt_dw0_staged_h();
 // misc.hip
 int triplet_loss_launch(const float* a, const float* p, const float* n, int batch, int k_neg, int dim, float margin,
                         float* loss, float* d_pos, float* d_neg, float* da, float* dp, float* dn, void* stream, int with_mean);

@@ -20,6 +20,18 @@
 #define TM 128
 #define TK 32
 
+// BatchNorm backward of four columns of one dZ1 row on load: Z' = scale (Z - m (c1 + (H - mean) invstd c2)), m the row's
+// multiplicity.  ONE function for every loader that applies it (few-row, staged H, register H): the same expression tree, so
+// floating-point contraction cannot differ between them.
+__device__ __forceinline__ float4 bn_bwd_z4(float4 z, const float4& h, float zm, const float4& mu, const float4& is,
+                                            const float4& sc, const float4& c1, const float4& c2) {
+    z.x = sc.x * (z.x - zm * (c1.x + (h.x - mu.x) * is.x * c2.x));
+    z.y = sc.y * (z.y - zm * (c1.y + (h.y - mu.y) * is.y * c2.y));
+    z.z = sc.z * (z.z - zm * (c1.z + (h.z - mu.z) * is.z * c2.z));
+    z.w = sc.w * (z.w - zm * (c1.w + (h.w - mu.w) * is.w * c2.w));
+    return z;
+}
+
 __device__ __forceinline__ void tn_small_body(const TnArgs& a, int tiles_i, int nsplit, int rows_per_split, int bid) {
     __shared__ __attribute__((aligned(16))) float smem[2][2][TK * TM];
 
@@ -63,10 +75,7 @@ __device__ __forceinline__ void tn_small_body(const TnArgs& a, int tiles_i, int 
                 }
                 const float4 h = *reinterpret_cast<const float4*>(a.zaux + (size_t)r * a.ldzaux + o0 + lcol);
                 const float zm = row_multiplicity(a.seg, r);
-                rz[p].x = zsc.x * (rz[p].x - zm * (zc1.x + (h.x - zmu.x) * zis.x * zc2.x));
-                rz[p].y = zsc.y * (rz[p].y - zm * (zc1.y + (h.y - zmu.y) * zis.y * zc2.y));
-                rz[p].z = zsc.z * (rz[p].z - zm * (zc1.z + (h.z - zmu.z) * zis.z * zc2.z));
-                rz[p].w = zsc.w * (rz[p].w - zm * (zc1.w + (h.w - zmu.w) * zis.w * zc2.w));
+                rz[p] = bn_bwd_z4(rz[p], h, zm, zmu, zis, zsc, zc1, zc2);
             }
             int src = r;
             bool av = rv && acol_ok;
@@ -183,8 +192,10 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_group_kernel(TnGroup g) {
 // of consecutive row floats and the MFMA fragments are conflict-free ds_read_b32 (32 consecutive
 // floats per half-wave).  The fused loaders run IN PLACE on the landed stage:
 //   APRO  A' = tanh(A * scale_s + shift_s)                       (dW3: A1 recomputed from H0)
-//   ZPRO  Z' = scale_s * (Z - m (c1_s + (H - mean_s) invstd_s c2_s))  (dW0: BatchNorm backward of dZ1,
-//         H = H0 staged beside Z)
+//   ZPRO  Z' = scale_s * (Z - m (c1_s + (H - mean_s) invstd_s c2_s))  (dW0: BatchNorm backward of dZ1, H = H0)
+//         REGH (the default): no MFMA fragment reads H and the thread that transforms an element is a fixed function of tid, so
+//         H goes from global memory straight into that thread's registers, one chunk ahead of its use; the stage is Z and A.
+//         !REGH (PC_OPT_DW0_STAGED_H): H staged through LDS beside Z -- a stage of three images, which forced 16-row chunks.
 // db is folded from the Z fragments the wi == 0 waves read anyway.
 __device__ __attribute__((aligned(64))) float pc_tn_zero_chunk[16];
 
@@ -196,10 +207,26 @@ __device__ __attribute__((aligned(64))) float pc_tn_zero_chunk[16];
 // scratch is the stage memory.  The launcher gives them the places of slices that own no rows, or appends them.  (Its own
 // instantiation: read in front of every launch of this family, the rider's arguments cost each one a dependent fetch, 1.4 us.)
 struct TnNoRider {};
+typedef float tn_v4f __attribute__((ext_vector_type(4)));
+// Placed right behind the hand-kept s_waitcnt: every later use of the register-H values depends on this statement (they are
+// loaded by inline asm, which the compiler does not count), so none moves above the wait.  ONE statement on every path to the
+// uses: two of them (one per wait count) meet in a phi, and the compiler then copies the registers in front of the wait.
+__device__ __forceinline__ void tn_tie_h(tn_v4f (&h)[4]) { asm volatile("" : "+v"(h[0]), "+v"(h[1]), "+v"(h[2]), "+v"(h[3])::"memory"); }
+__device__ __forceinline__ void tn_tie_h(tn_v4f (&h)[2]) { asm volatile("" : "+v"(h[0]), "+v"(h[1])::"memory"); }
+// REGH is no template parameter: a ZPRO stage of three 32-row images does not fit the LDS twice (166 KB), so the ZPRO loader with
+// 32-row chunks IS the register form and the one with 16-row chunks the staged one.  (-DPC_EXP_DW0_REGH_16X3, a developer
+// build for the comparison in DESIGN 7: register H at the staged form's 16 x 3 geometry as well.)
+#ifdef PC_EXP_DW0_REGH_16X3
+#define PC_TN_REGH_ALL 1
+#else
+#define PC_TN_REGH_ALL 0
+#endif
 template <int WO, int WI, int TO, int TI, int TKC, int NST, bool APRO, bool ZPRO, bool RIDER = false>
 __global__ __launch_bounds__(64 * WO * WI, WO * WI / 4) void gemm_tn8_kernel(TnArgs a, int nsplit, int rows_per_split, int halves,
                                                                              size_t slab_half_off,
                                                                              std::conditional_t<RIDER, TnRider, TnNoRider> rider) {
+    constexpr bool REGH = ZPRO && (TKC == 32 || (PC_TN_REGH_ALL && WO == 4));
+    static_assert(!REGH || (!APRO && !RIDER), "register H is a form of the ZPRO loader");
     constexpr int NWV = WO * WI, THREADS = 64 * NWV;            // 8 waves (2 per SIMD) or 16 (4 per SIMD)
     constexpr int NO = WO * TO * 32, NI = WI * TI * 32;
     // Image rows must not start on the same LDS bank two rows apart in the MFMA's k pair (lanes 0-31 read row k,
@@ -214,10 +241,11 @@ __global__ __launch_bounds__(64 * WO * WI, WO * WI / 4) void gemm_tn8_kernel(TnA
     constexpr bool ZSW = NO == 128, ASW = NI == 128;                          // half swap of rows with bit 3 set
     static_assert((NO == 128 || NO == 256) && (NI == 128 || NI == 256), "image widths");
     constexpr int ZF = TKC * ZRS, AF = TKC * ARS;                // floats per stage image
-    constexpr int STAGE = ZF * (ZPRO ? 2 : 1) + AF;              // Z [, H], A
+    constexpr int ZIMG = (ZPRO && !REGH) ? 2 : 1;                // Z-shaped images per stage: Z [, H staged]
+    constexpr int STAGE = ZF * ZIMG + AF;                        // Z [, H], A
     constexpr int JZ = TKC * NO / 256 / NWV, JA = TKC * NI / 256 / NWV;      // DMA instructions per wave and image
     static_assert((TKC * NO) % (256 * NWV) == 0 && (TKC * NI) % (256 * NWV) == 0, "images must split into whole wave instructions over the waves");
-    constexpr int JALL = JZ * (ZPRO ? 2 : 1) + JA;              // DMA instructions per wave and stage
+    constexpr int JALL = JZ * ZIMG + JA;                         // DMA instructions per wave and stage
     __shared__ __attribute__((aligned(1024))) float smem[NST * STAGE];
 
     const int tid = threadIdx.x, lane = tid & 63;
@@ -277,13 +305,13 @@ __global__ __launch_bounds__(64 * WO * WI, WO * WI / 4) void gemm_tn8_kernel(TnA
             const int r = r0 + zr[j];
             const bool v = r < r_end && zc[j] < a.No;
             dma16(v ? a.Z + (size_t)r * a.ldz + zc[j] : zsrc0, base + zd[j]);
-            if (ZPRO) dma16(v ? a.zaux + (size_t)r * a.ldzaux + zc[j] : zsrc0, base + ZF * 4 + zd[j]);
+            if (ZIMG == 2) dma16(v ? a.zaux + (size_t)r * a.ldzaux + zc[j] : zsrc0, base + ZF * 4 + zd[j]);
         }
 #pragma unroll
         for (int j = 0; j < JA; j++) {
             const int r = r0 + ar[j];
             const bool v = r < r_end && ac[j] < a.Ni && gidx[j] >= 0;
-            dma16(v ? a.A + (size_t)gidx[j] * a.lda + ac[j] : zsrc0, base + (ZPRO ? 2 : 1) * ZF * 4 + ad[j]);
+            dma16(v ? a.A + (size_t)gidx[j] * a.lda + ac[j] : zsrc0, base + ZIMG * ZF * 4 + ad[j]);
         }
     };
 
@@ -292,12 +320,32 @@ __global__ __launch_bounds__(64 * WO * WI, WO * WI / 4) void gemm_tn8_kernel(TnA
     const int zrow = tid / ZT, zcol = (tid % ZT) * 4, arow = tid / AT, acol = (tid % AT) * 4;
     int zseg = -1;
     float4 zmu, zis, zsc, zc1, zc2;
+    // REGH: the H values of the elements this thread transforms, one float4 per pass of the transform.  The loads are inline
+    // asm: the compiler neither counts them nor parks a vmcnt(0) in front of their use (it would drain the stage DMA in
+    // flight); the wait is the hand-placed one at the top of a chunk, and tn_tie_h behind it keeps every use below it.
+    // Loaded AFTER the transform has consumed the previous chunk's values and BEFORE the DMA of the same step, so they are
+    // older than every DMA request the counted wait leaves in flight.  No store goes out in that window.
+    // The rows' listed multiplicities travel with them (plain loads the compiler counts: it waits for them where the transform
+    // first uses one, with everything landed; fetched inside the transform, each pass waited for its own round trip).
+    constexpr int HP = TKC / (THREADS / ZT);
+    [[maybe_unused]] tn_v4f hreg[HP];
+    [[maybe_unused]] float hmult[HP];
+    [[maybe_unused]] auto load_h = [&](int r0) {
+#pragma unroll
+        for (int p = 0; p < HP; p++) {
+            const int r = r0 + zrow + (THREADS / ZT) * p;
+            const bool v = r < r_end && zcol < a.No;
+            const float* src = v ? a.zaux + (size_t)r * a.ldzaux + zcol : zsrc0;     // (dead rows / columns: never transformed)
+            asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(hreg[p]) : "v"(src) : "memory");
+            hmult[p] = *(v ? row_multiplicity_src(a.seg, r, zsrc0) : zsrc0);
+        }
+    };
     auto transform = [&](float* stage, int r0) {
         if (ZPRO && zcol < a.No) {
             float* Zs = stage;
             const float* Hs = stage + ZF;
 #pragma unroll
-            for (int p = 0; p < TKC / (THREADS / ZT); p++) {
+            for (int p = 0; p < HP; p++) {
                 const int rr = zrow + (THREADS / ZT) * p, r = r0 + rr;
                 if (r < r_end) {
                     const int s = seg_of_row(a.seg, r);
@@ -311,19 +359,19 @@ __global__ __launch_bounds__(64 * WO * WI, WO * WI / 4) void gemm_tn8_kernel(TnA
                         zseg = s;
                     }
                     const int zp = rr * ZRS + ((ZSW && (rr & 8)) ? zcol ^ 32 : zcol);
-                    float4 z = *reinterpret_cast<const float4*>(&Zs[zp]);
-                    const float4 h = *reinterpret_cast<const float4*>(&Hs[zp]);
-                    const float zm = row_multiplicity(a.seg, r);
-                    z.x = zsc.x * (z.x - zm * (zc1.x + (h.x - zmu.x) * zis.x * zc2.x));
-                    z.y = zsc.y * (z.y - zm * (zc1.y + (h.y - zmu.y) * zis.y * zc2.y));
-                    z.z = zsc.z * (z.z - zm * (zc1.z + (h.z - zmu.z) * zis.z * zc2.z));
-                    z.w = zsc.w * (z.w - zm * (zc1.w + (h.w - zmu.w) * zis.w * zc2.w));
-                    *reinterpret_cast<float4*>(&Zs[zp]) = z;
+                    const float4 z = *reinterpret_cast<const float4*>(&Zs[zp]);
+                    float4 h;
+                    if constexpr (REGH) h = make_float4(hreg[p].x, hreg[p].y, hreg[p].z, hreg[p].w);
+                    else h = *reinterpret_cast<const float4*>(&Hs[zp]);
+                    float zm;
+                    if constexpr (REGH) zm = row_multiplicity_from(a.seg, r, hmult[p]);
+                    else zm = row_multiplicity(a.seg, r);
+                    *reinterpret_cast<float4*>(&Zs[zp]) = bn_bwd_z4(z, h, zm, zmu, zis, zsc, zc1, zc2);
                 }
             }
         }
         if (APRO && acol < a.Ni) {
-            float* As = stage + (ZPRO ? 2 : 1) * ZF;
+            float* As = stage + ZIMG * ZF;
             // scale / shift are re-fetched per chunk (L1 hits) instead of living in 8 registers across the MFMA phase
             int aseg = -1;
             float4 asc, ash;
@@ -371,6 +419,15 @@ __global__ __launch_bounds__(64 * WO * WI, WO * WI / 4) void gemm_tn8_kernel(TnA
     for (int i = 0; i < NST - 1; i++)
         if (i < nchunk) { load_gather(r_begin + i * TKC); issue(i, r_begin + i * TKC); }
     if (NST - 1 < nchunk) load_gather(r_begin + (NST - 1) * TKC);
+    if constexpr (REGH) {
+        // chunk 0's H, waited for at once: whatever the compiler does with these registers between here and the loop (the
+        // loop's own loads are another statement) happens to landed values.  Chunk 0 is needed before anything else anyway.
+        if (nchunk > 0) {
+            load_h(r_begin);
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            tn_tie_h(hreg);
+        }
+    }
     // lanes 32-63 read the odd row of each pair: in a half-swapped image their columns have bit 5 flipped
     // bf16 products (see common.h): one MFMA k group = 16 rows; lane (column lane & 31, half lane >> 5) holds the 8
     // rows 8 (lane >> 5) .. + 7 of its column, read one by one (row stride), split into three bf16 pieces once and
@@ -387,11 +444,25 @@ __global__ __launch_bounds__(64 * WO * WI, WO * WI / 4) void gemm_tn8_kernel(TnA
 #ifndef PC_EXP_NO_VMWAIT
         if (c + NST - 1 <= nchunk) { asm volatile("s_waitcnt vmcnt(%0)" ::"n"((NST - 2) * JALL) : "memory"); }
         else { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
+        // (REGH: this chunk's H loads went out in front of the DMA of the step that issued them -- older than all that stays in flight)
+        if constexpr (REGH) {
+            tn_tie_h(hreg);
+            // the gather indices of the chunk about to be issued (loaded a chunk ago) are taken HERE, where everything has landed:
+            // the compiler's wait for them otherwise sits in issue(), behind the H loads of this step, and waits for those too
+#pragma unroll
+            for (int j = 0; j < JA; j++) asm volatile("" : "+v"(gidx[j]));
+        }
 #endif
 #ifndef PC_EXP_NO_BARRIER
         __syncthreads();
 #endif
                                           // chunk c visible to all; slot of chunk c-1 free again
+        if constexpr (REGH) {
+            // transform first: it frees the H registers for the next chunk's loads, and its own counted loads (row multiplicities,
+            // a new segment's coefficients) then wait with nothing of this step in flight behind them
+            transform(smem + cur * STAGE, r_begin + c * TKC);
+            if (c + 1 < nchunk) load_h(r_begin + (c + 1) * TKC);
+        }
 #ifndef PC_EXP_NO_DMA
         if (c + NST - 1 < nchunk) {
             issue(cur == 0 ? NST - 1 : cur - 1, r_begin + (c + NST - 1) * TKC);
@@ -399,9 +470,10 @@ __global__ __launch_bounds__(64 * WO * WI, WO * WI / 4) void gemm_tn8_kernel(TnA
         }
 #endif
         float* stage = smem + cur * STAGE;
-        if (APRO || ZPRO) { transform(stage, r_begin + c * TKC); lds_sync(); }
+        if constexpr (REGH) lds_sync();
+        else if (APRO || ZPRO) { transform(stage, r_begin + c * TKC); lds_sync(); }
         const float* Zs = stage + fz;
-        const float* As = stage + (ZPRO ? 2 : 1) * ZF + fa;
+        const float* As = stage + ZIMG * ZF + fa;
 #pragma unroll
         for (int g = 0; g < TKC / 16; g++) {
             // rows 16 g + 8 (lane >> 5) + t; in a half-swapped 128-wide image the swap follows bit 3 of the row, i.e.
@@ -618,11 +690,19 @@ int launch_gemm_tn(const TnArgs& a, hipStream_t st, TnDefer* defer) {
     if (tn_full_tile(a.R, a.No, a.Ni) && !(apro && zpro)) {
         // (TKC, NST): chunks of 32 rows in two stages, except the 256 x 256 tile -- 128 accumulator registers per lane: its DMA
         // geometry and gather indices for 32-row chunks do not fit beside them (7-14 VGPRs went to scratch), so it takes 16-row
-        // chunks in three stages like the ZPRO forms (same steady-state rate: these kernels do not wait for HBM)
+        // chunks in three stages like the staged-H ZPRO forms (same steady-state rate: these kernels do not wait for HBM).
+        // ZPRO with Ni <= 128 (dW0): H through registers leaves a stage of two images, so it takes 32-row chunks in two stages
+        // like its mirror dW5; pc_set_option(PC_OPT_DW0_STAGED_H, 1) selects the staged form (16 x 3) again.
+#if PC_TN_REGH_ALL
+#define TN8_REGH gemm_tn8_kernel<4, 2, 2, 2, 16, 3, false, true>     /* developer build: register H at the staged form's chunk geometry */
+#else
+#define TN8_REGH gemm_tn8_kernel<4, 2, 2, 2, 32, 2, false, true>
+#endif
 #define TN8(WO, WI, TO, TI, TKC, NST)                                                                         \
     do {                                                                                                      \
         if (apro) PC_LAUNCH((gemm_tn8_kernel<WO, WI, TO, TI, TKC, NST, true, false>), dim3(nsplit), dim3(64 * WO * WI), 0, st, a, nsplit, rps, 1, (size_t)0, TnNoRider{});    \
         else if (zpro && a.Ni > 128) PC_LAUNCH((gemm_tn8_kernel<2, 4, 4, 2, 16, 3, false, true>), dim3(nsplit), dim3(512), 0, st, a, nsplit, rps, 1, (size_t)0, TnNoRider{});  \
+        else if (zpro && !pc_opt_dw0_staged_h()) PC_LAUNCH((TN8_REGH), dim3(nsplit), dim3(512), 0, st, a, nsplit, rps, 1, (size_t)0, TnNoRider{});  \
         else if (zpro) PC_LAUNCH((gemm_tn8_kernel<4, 2, 2, 2, 16, 3, false, true>), dim3(nsplit), dim3(512), 0, st, a, nsplit, rps, 1, (size_t)0, TnNoRider{});  \
         else PC_LAUNCH((gemm_tn8_kernel<WO, WI, TO, TI, TKC, NST, false, false>), dim3(nsplit), dim3(64 * WO * WI), 0, st, a, nsplit, rps, 1, (size_t)0, TnNoRider{});        \
     } while (0)
@@ -630,6 +710,7 @@ int launch_gemm_tn(const TnArgs& a, hipStream_t st, TnDefer* defer) {
         else if (a.No > 128) TN8(4, 2, 2, 2, 32, 2);
         else TN8(2, 4, 2, 2, 32, 2);
 #undef TN8
+#undef TN8_REGH
     } else {
         PC_LAUNCH(gemm_tn_kernel, dim3(tiles_o * tiles_i * nsplit), dim3(256), 0, st, a, tiles_i, nsplit, rps);
     }
@@ -704,8 +785,10 @@ std::atomic<int> g_opt_bn_finalize_side{0};
 std::atomic<int> g_opt_bn_finalize_rides{1};
 std::atomic<int> g_opt_fused_loss{1};
 std::atomic<int> g_opt_fused_out_chain{1};
+std::atomic<int> g_opt_dw0_staged_h{0};
 std::atomic<int>* opt_slot(int option) {
     switch (option) {
+        case PC_OPT_DW0_STAGED_H: return &g_opt_dw0_staged_h;
         case PC_OPT_SIDE_QUEUE: return &g_opt_side_queue;
         case PC_OPT_SORTED_TABLE_GRADIENTS: return &g_opt_sorted_tables;
         case PC_OPT_BN_FINALIZE_SIDE: return &g_opt_bn_finalize_side;
@@ -721,6 +804,7 @@ int pc_opt_bn_finalize_side() { return g_opt_bn_finalize_side.load(std::memory_o
 int pc_opt_bn_finalize_rides() { return g_opt_bn_finalize_rides.load(std::memory_order_relaxed); }
 int pc_opt_fused_loss() { return g_opt_fused_loss.load(std::memory_order_relaxed); }
 int pc_opt_fused_out_chain() { return g_opt_fused_out_chain.load(std::memory_order_relaxed); }
+int pc_opt_dw0_staged_h() { return g_opt_dw0_staged_h.load(std::memory_order_relaxed); }
 
 extern "C" int pc_set_option(int option, int value) {
     std::atomic<int>* o = opt_slot(option);
