@@ -1320,6 +1320,24 @@ int pc_cell_means(const float *table, const int32_t *cell_rowptr, const int32_t 
 int pc_merge_lists(const int32_t *idx, const float *score, int rows, int L, int n, int32_t *out_idx, float *out_score,
                    void *stream);
 
+/* The cell index over the bf16 copy of the catalogue (ABI 8, additive; csrc/cells_bf16.hip; ops.cell_means_bf16,
+ * ops.build_cell_index_bf16, inference.IndexedCompactSimilarProducts).
+ *
+ * pc_cell_means_bf16: pc_cell_means' contract over table [num_products, dim] bf16 (the patterns of ops.catalogue_bf16, 8-byte
+ * aligned); cell_rowptr, cell_col and centroids [n_cells, dim] fp32 (read and written, 16-byte aligned) as there:
+ *   centroids[c] = (sum of widen(table[cell_col[i]]), i in [cell_rowptr[c], cell_rowptr[c + 1])) / m_c   in fp32,
+ * widen the exact bf16 -> fp32 conversion (the pattern shifted left by 16), m_c the number of those ids inside
+ * [0, num_products).  A cell with m_c == 0 keeps the centroid it had; an id outside [0, num_products) is passed over: never
+ * read, not summed, not counted in m_c, not reported.  The ownership and the order are pc_cell_means': lane c of a group of
+ * dim / 4 lanes owns the columns 4 c .. 4 c + 3 (here one 8-byte load of four patterns), the 1024 / dim groups take the
+ * members g, g + G, .. in turn (sequential fp32 additions from zero), the same tree in LDS, one correctly rounded division by
+ * (float) m_c -- every addition is pc_cell_means' addition of the same operands, so centroids are bit for bit pc_cell_means'
+ * on the widened table, which is never formed.  The same bits on every run and for every grid; no atomics.
+ * PC_EINVAL: null pointer, n_cells or num_products <= 0; then PC_ESHAPE: dim not 128 / 256; then PC_ESHAPE: table not 8-byte
+ * or centroids not 16-byte aligned -- each checked before anything is launched. */
+int pc_cell_means_bf16(const void *table, const int32_t *cell_rowptr, const int32_t *cell_col, int n_cells, int num_products,
+                       int dim, float *centroids, void *stream);
+
 /* Diversified lists (ABI 8, additive; csrc/diversify.hip; ops.diversify_lists, ops.inv_norm,
  * PCompanionInference.recommend_diverse_batch): a greedy maximal-marginal-relevance re-rank of a served pool, on the device.
  *

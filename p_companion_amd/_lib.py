@@ -286,6 +286,8 @@ SIGNATURES = {
     "pc_retrieve_list_grouped_bf16_biased_where_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "pc_retrieve_list_grouped_bf16_biased_where": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _vp,
                                                         _vp, _vp, _P(RowWhere), _vp, _sz, _vp]),
+    # the cell index over the bf16 copy (csrc/cells_bf16.hip: cells.hip's centroid update reading bf16 rows; ABI 8, additive)
+    "pc_cell_means_bf16": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
     "pc_hadamard_forward":(_i, [_vp, _vp, _i, _i, _vp, _vp]),
     "pc_hadamard_forward_dim": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
     "pc_hadamard_backward": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp]),

@@ -40,7 +40,9 @@ serves up to 256 neighbours (pc_retrieve_list_grouped_biased) and similar_capped
 CompactSimilarProducts is SimilarProducts over the bf16 copy of the table alone (pc_retrieve_list_grouped_bf16_biased,
 pc_rank_grouped_bf16, pc_half_sq_norm_bias_bf16): distances to the stored rows, no fp32 table.
 IndexedSimilarProducts serves its whole-catalogue scope through a k-means cell index (ops.build_cell_index): the same retrieval
-over the products of a query's nearest cells, the probe lists of a query merged by pc_merge_lists."""
+over the products of a query's nearest cells, the probe lists of a query merged by pc_merge_lists.
+IndexedCompactSimilarProducts is that index over the bf16 copy alone (ops.build_cell_index_bf16, pc_cell_means_bf16): the scan is
+CompactSimilarProducts' entry, the index is built without the fp32 table, and a query probes up to 64 cells."""
 import os
 from typing import Any, Dict, List
 
@@ -1089,21 +1091,35 @@ class IndexedSimilarProducts(SimilarProducts):
     MAX_NPROBE = 16
 
     def __init__(self, table, bpg, index=None, n_cells=None, nprobe=8, iters=10, seed=0):
+        name = type(self).__name__
         if (index is None) == (n_cells is None):
-            raise ValueError("IndexedSimilarProducts: pass an index, or n_cells to build one (not both)")
-        if index is not None and torch.is_tensor(table) and table.dim() == 2 \
-                and (index.num_products, index.dim) != tuple(table.shape):
-            raise ValueError(f"IndexedSimilarProducts: the index is over [{index.num_products}, {index.dim}], the table is "
-                             f"{tuple(table.shape)}")
+            raise ValueError(f"{name}: pass an index, or n_cells to build one (not both)")
+        rows = table.table if isinstance(table, ops.CompactCatalogue) else table
+        if index is not None and torch.is_tensor(rows) and rows.dim() == 2 \
+                and (index.num_products, index.dim) != tuple(rows.shape):
+            raise ValueError(f"{name}: the index is over [{index.num_products}, {index.dim}], the table is {tuple(rows.shape)}")
         cells = int(n_cells) if index is None else int(index.n_cells)
-        self._check_nprobe("IndexedSimilarProducts", nprobe, cells)
+        self._check_nprobe(name, nprobe, cells)
         super().__init__(table, bpg, scope="catalogue")
         if index is None:
-            index = ops.build_cell_index(table, cells, iters=iters, seed=seed)
+            index = self._build_index(cells, iters, seed)
         self.index, self.n_cells, self.nprobe = index, cells, int(nprobe)
         self.cell_rowptr, self.cell_col = index.cell_rowptr, index.cell_col
         self._one_cell_type = (torch.tensor([0, cells], dtype=torch.int32, device=self.device),
                                torch.arange(cells, dtype=torch.int32, device=self.device))
+
+    # What differs over the bf16 copy (IndexedCompactSimilarProducts) beyond the parent's hooks: the index build and the scan of
+    # the probed cells.
+    def _build_index(self, n_cells, iters, seed):
+        return ops.build_cell_index(self.table, n_cells, iters=iters, seed=seed)
+
+    def _scan(self, rows, cells, n, exclude, long):
+        """The grouped retrieval over the B nprobe rows, a probed cell in the place of a type."""
+        if long:
+            return ops.retrieve_list_grouped_biased(rows, cells, self.cell_rowptr, self.cell_col, self.table, self.bias, n,
+                                                    exclude=exclude)
+        return ops.retrieve_topk_grouped(rows, cells, self.cell_rowptr, self.cell_col, self.table, n, exclude=exclude,
+                                         bias=self.bias)
 
     @classmethod
     def _check_nprobe(cls, what, nprobe, n_cells):
@@ -1127,6 +1143,10 @@ class IndexedSimilarProducts(SimilarProducts):
     def _probe(self, q, nprobe):
         rowptr, col = self._one_cell_type
         zeros = torch.zeros(q.shape[0], dtype=torch.int32, device=self.device)
+        if nprobe > self.MAX_N:                           # (above the 16-entry kernel: the same total order, the long-list entry)
+            cells, _ = ops.retrieve_list_grouped_biased(q, zeros, rowptr, col, self.index.centroids, self.index.centroid_bias,
+                                                        nprobe)
+            return cells
         cells, _ = ops.retrieve_topk_grouped(q, zeros, rowptr, col, self.index.centroids, nprobe, bias=self.index.centroid_bias)
         return cells
 
@@ -1138,12 +1158,7 @@ class IndexedSimilarProducts(SimilarProducts):
         cells = self._probe(q, nprobe)                                            # [B, nprobe]
         rows = q.repeat_interleave(nprobe, dim=0)                                 # [B nprobe, D]
         exclude = self._exclude_rows(query_idx, nprobe)
-        if long:
-            idx, score = ops.retrieve_list_grouped_biased(rows, cells.reshape(-1), self.cell_rowptr, self.cell_col, self.table,
-                                                          self.bias, n, exclude=exclude)
-        else:
-            idx, score = ops.retrieve_topk_grouped(rows, cells.reshape(-1), self.cell_rowptr, self.cell_col, self.table, n,
-                                                   exclude=exclude, bias=self.bias)
+        idx, score = self._scan(rows, cells.reshape(-1), n, exclude, long)
         return ops.merge_lists(idx.view(b, nprobe, n), score.view(b, nprobe, n))
 
     @torch.no_grad()
@@ -1154,7 +1169,7 @@ class IndexedSimilarProducts(SimilarProducts):
         query_idx = self._queries("probe_cells", query_idx)
         if query_idx.shape[0] == 0:
             return torch.empty(0, nprobe, dtype=torch.int32, device=self.device)
-        return self._probe(self.table[query_idx.long()], nprobe)
+        return self._probe(self._rows(query_idx.long()), nprobe)
 
     @torch.no_grad()
     def similar_batch(self, query_idx: torch.Tensor, n: int = 10, nprobe: int = None):
@@ -1167,7 +1182,7 @@ class IndexedSimilarProducts(SimilarProducts):
         query_idx = self._queries("similar_batch", query_idx)
         if query_idx.shape[0] == 0:
             return self._no_neighbours(n)
-        q = self.table[query_idx.long()]
+        q = self._rows(query_idx.long())
         idx, _ = self._search(query_idx, q, n, nprobe)
         return idx, self._distances(q, idx)
 
@@ -1181,13 +1196,13 @@ class IndexedSimilarProducts(SimilarProducts):
         query_idx = self._queries("similar_list_batch", query_idx)
         if query_idx.shape[0] == 0:
             return self._no_neighbours(n)
-        q = self.table[query_idx.long()]
+        q = self._rows(query_idx.long())
         idx, _ = self._search(query_idx, q, n, nprobe, long=True)
         return idx, self._list_distances(q, idx)
 
     def similar_where_batch(self, query_idx, n=10, lo=None, hi=None, need=None, deny=None):
         """Not served through the cell index: the per-query attribute filter is the exact classes'."""
-        raise NotImplementedError("IndexedSimilarProducts.similar_where_batch: the per-query attribute filter is not served "
+        raise NotImplementedError(f"{type(self).__name__}.similar_where_batch: the per-query attribute filter is not served "
                                   "through the cell index; SimilarProducts / CompactSimilarProducts serve it")
 
     @torch.no_grad()
@@ -1200,3 +1215,34 @@ class IndexedSimilarProducts(SimilarProducts):
         held = ((exact[:, :, None] == got[:, None, :]) & (exact[:, :, None] >= 0)).any(dim=2).sum()
         total = (exact >= 0).sum()
         return torch.where(total > 0, held.float() / total.clamp(min=1).float(), torch.ones((), device=self.device))
+
+
+class IndexedCompactSimilarProducts(IndexedSimilarProducts, CompactSimilarProducts):
+    """CompactSimilarProducts(scope="catalogue") served through a k-means cell index, from the bf16 copy of the catalogue alone:
+    IndexedSimilarProducts' four steps for a deployment that gave the fp32 table back.  catalogue: an ops.CompactCatalogue or a
+    contiguous [P, 128 | 256] torch.bfloat16 device tensor.  index: a CellIndex over these P products and D -- from
+    ops.build_cell_index_bf16, or from ops.build_cell_index on the fp32 table before it was given back --; or n_cells (with
+    iters, seed) to build one here through ops.build_cell_index_bf16.  nprobe: 1 .. min(MAX_NPROBE = 64, n_cells).
+      probe       the query row is the stored row widened (exactly) to fp32; the probe runs over the fp32 centroids with the fp32
+                  biased entries: for nprobe <= 16 the 16-entry retrieval (IndexedSimilarProducts.probe_cells' bits for the same
+                  index and rows), for 17 <= nprobe <= 64 ops.retrieve_list_grouped_biased -- the same total order, so the
+                  first 16 columns agree;
+      scan        ops.retrieve_list_grouped_bf16_biased over the cell CSR at every n, bias = the catalogue's .half_sq_norm: a
+                  (row, product) score comes from the kernel and chain of CompactSimilarProducts;
+      merge       ops.merge_lists (up to 64 lists of up to 256);
+      distances   the compact parent's, over widened gathered rows, chunked.
+    The cells partition the products and every selection is under (score descending, index ascending): the served list is the
+    exact compact list restricted to the non-excluded, eligible products of the probed cells, and with nprobe == n_cells that
+    list bit for bit, ids and distances.  similar_batch (n <= 16), similar_list_batch (n <= 256), the capped methods,
+    probe_cells, set_eligible and similar_where_batch (NotImplementedError) are IndexedSimilarProducts'; recall is relative
+    to the exact list over the ROUNDED rows; rank_pairs / evaluate_pairs are the exact inherited ones (ops.rank_grouped_bf16).
+    An fp32 table is never materialised."""
+
+    MAX_NPROBE = 64                   # ops.MERGE_MAX_LISTS: what merge_lists takes; the probe above 16 is the long-list entry
+
+    def _build_index(self, n_cells, iters, seed):
+        return ops.build_cell_index_bf16(self.compact, n_cells, iters=iters, seed=seed)
+
+    def _scan(self, rows, cells, n, exclude, long):
+        return ops.retrieve_list_grouped_bf16_biased(rows, cells, self.cell_rowptr, self.cell_col, self.table, self.bias, n,
+                                                     exclude=exclude)

@@ -2428,6 +2428,30 @@ def cell_means(table, cell_rowptr, cell_col, centroids):
     return centroids
 
 
+def cell_means_bf16(table, cell_rowptr, cell_col, centroids):
+    """pc_cell_means_bf16: cell_means for the [P, D] torch.bfloat16 copy of a catalogue (catalogue_bf16; a CompactCatalogue's
+    .table), in place: centroids[c] = the fp32 mean of the stored rows table[cell_col[i]] widened (exactly) to fp32 -- the
+    same lanes, order, tree and division, so the bits of cell_means(table.float(), ...) without the fp32 table ever being
+    formed.  cell_rowptr / cell_col / centroids [C, D] fp32, the empty cell and ids outside [0, P) as there.  Returns
+    centroids."""
+    if isinstance(table, torch.Tensor) and table.dtype == torch.float32:
+        raise ValueError("cell_means_bf16: an fp32 table is cell_means's; this function reads the bf16 copy (catalogue_bf16)")
+    d = _table_width(table, rows=True, dtype=torch.bfloat16)
+    _req(centroids, torch.float32, "centroids")
+    if centroids.dim() != 2 or centroids.shape[1] != d or centroids.shape[0] < 1:
+        raise ValueError(f"centroids: expected [C, {d}] with C >= 1, got shape {tuple(centroids.shape)}")
+    c = centroids.shape[0]
+    _req(cell_rowptr, torch.int32, "cell_rowptr", (c + 1,))
+    _req(cell_col, torch.int32, "cell_col")
+    if cell_col.dim() != 1:
+        raise ValueError(f"cell_col: expected a 1-D tensor, got shape {tuple(cell_col.shape)}")
+    if cell_col.numel() == 0:                             # (every cell empty: one unread entry)
+        cell_col = torch.zeros(1, dtype=torch.int32, device=table.device)
+    check(_lib.lib().pc_cell_means_bf16(_p(table), _p(cell_rowptr), _p(cell_col), c, table.shape[0], d, _p(centroids),
+                                        _stream()), "pc_cell_means_bf16")
+    return centroids
+
+
 def merge_lists(idx, score):
     """pc_merge_lists: idx [R, L, n] int32 / score [R, L, n] fp32, L lists per row as the grouped retrievals return them (sorted
     under (score descending, product index ascending), -1 / -inf behind the last entry), the lists of a row over disjoint
@@ -2797,7 +2821,8 @@ class CellIndex:
 def _assign_cells(table, centroids, centroid_bias=None, chunk_rows=1 << 20):
     """cell_of [P] int32: the nearest centroid of every row of table under Euclidean distance -- the biased grouped retrieval
     with the centroids as the candidates of one type and n = 1, in chunks of chunk_rows rows; the total order (score
-    descending, index ascending) gives a tie to the lowest cell."""
+    descending, index ascending) gives a tie to the lowest cell.  A bf16 table (build_cell_index_bf16) travels one chunk of
+    rows widened (exactly) to fp32 at a time: a row's cell does not depend on its chunk."""
     p, c = table.shape[0], centroids.shape[0]
     dev = table.device
     if centroid_bias is None:
@@ -2809,9 +2834,42 @@ def _assign_cells(table, centroids, centroid_bias=None, chunk_rows=1 << 20):
     cell_of = torch.empty(p, dtype=torch.int32, device=dev)
     for lo in range(0, p, chunk_rows):
         hi = min(lo + chunk_rows, p)
-        idx, _ = retrieve_topk_grouped(table[lo:hi], zeros[:hi - lo], rowptr, col, centroids, 1, bias=centroid_bias)
+        rows = table[lo:hi] if table.dtype == torch.float32 else table[lo:hi].float()
+        idx, _ = retrieve_topk_grouped(rows, zeros[:hi - lo], rowptr, col, centroids, 1, bias=centroid_bias)
         cell_of[lo:hi] = idx[:, 0]
+        del rows, idx                                     # (one widened chunk at a time)
     return cell_of
+
+
+def _lloyd(what, table, d, means, n_cells, iters, seed, init, chunk_rows):
+    """build_cell_index's argument checks and Lloyd loop over a checked [P, d] table; means: the centroid update of the
+    table's element type (cell_means / cell_means_bf16)."""
+    p = table.shape[0]
+    n_cells, iters, chunk_rows = int(n_cells), int(iters), int(chunk_rows)
+    if not 1 <= n_cells <= p:
+        raise ValueError(f"{what}: n_cells must be in [1, P = {p}], got {n_cells}")
+    if iters < 0:
+        raise ValueError(f"{what}: iters must not be negative, got {iters}")
+    if chunk_rows < 1:
+        raise ValueError(f"{what}: chunk_rows must be positive, got {chunk_rows}")
+    if init is not None:
+        _req(init, torch.float32, "init")
+        if tuple(init.shape) != (n_cells, d):
+            raise ValueError(f"{what}: init must be [{n_cells}, {d}], got shape {tuple(init.shape)}")
+        centroids = init.clone()
+    else:
+        gen = torch.Generator(device="cpu")
+        gen.manual_seed(int(seed))
+        first = torch.randperm(p, generator=gen)[:n_cells].to(table.device)
+        centroids = table[first].float().contiguous()     # (fp32 rows as they are; bf16 rows widened)
+    for _ in range(iters):
+        cell_of = _assign_cells(table, centroids, None, chunk_rows)
+        rowptr, col = type_csr(cell_of, n_cells)
+        means(table, rowptr, col, centroids)
+    bias = half_sq_norm_bias(centroids)
+    cell_of = _assign_cells(table, centroids, bias, chunk_rows)
+    rowptr, col = type_csr(cell_of, n_cells)
+    return CellIndex(centroids, bias, cell_of, rowptr, col)
 
 
 def build_cell_index(table, n_cells, iters=10, seed=0, init=None, chunk_rows=1 << 20):
@@ -2823,29 +2881,22 @@ def build_cell_index(table, n_cells, iters=10, seed=0, init=None, chunk_rows=1 <
     assignment under the stored centroids.  Every step is bitwise deterministic, so equal arguments give equal bits in every
     field.  Nothing is read back to the host but type_csr's range check of the assignment."""
     d = _table_width(table)
-    p = table.shape[0]
-    n_cells, iters, chunk_rows = int(n_cells), int(iters), int(chunk_rows)
-    if not 1 <= n_cells <= p:
-        raise ValueError(f"build_cell_index: n_cells must be in [1, P = {p}], got {n_cells}")
-    if iters < 0:
-        raise ValueError(f"build_cell_index: iters must not be negative, got {iters}")
-    if chunk_rows < 1:
-        raise ValueError(f"build_cell_index: chunk_rows must be positive, got {chunk_rows}")
-    if init is not None:
-        _req(init, torch.float32, "init")
-        if tuple(init.shape) != (n_cells, d):
-            raise ValueError(f"build_cell_index: init must be [{n_cells}, {d}], got shape {tuple(init.shape)}")
-        centroids = init.clone()
-    else:
-        gen = torch.Generator(device="cpu")
-        gen.manual_seed(int(seed))
-        first = torch.randperm(p, generator=gen)[:n_cells].to(table.device)
-        centroids = table[first].contiguous()
-    for _ in range(iters):
-        cell_of = _assign_cells(table, centroids, None, chunk_rows)
-        rowptr, col = type_csr(cell_of, n_cells)
-        cell_means(table, rowptr, col, centroids)
-    bias = half_sq_norm_bias(centroids)
-    cell_of = _assign_cells(table, centroids, bias, chunk_rows)
-    rowptr, col = type_csr(cell_of, n_cells)
-    return CellIndex(centroids, bias, cell_of, rowptr, col)
+    return _lloyd("build_cell_index", table, d, cell_means, n_cells, iters, seed, init, chunk_rows)
+
+
+def build_cell_index_bf16(catalogue, n_cells, iters=10, seed=0, init=None, chunk_rows=1 << 18):
+    """build_cell_index over the bf16 copy of a catalogue alone: catalogue an ops.CompactCatalogue or a contiguous
+    [P, 128 | 256] torch.bfloat16 device tensor -> CellIndex (fp32 centroids and centroid_bias, as there: C x D floats).  The
+    same Lloyd loop: the assignment is the biased 16-entry retrieval with n = 1 over the fp32 centroids, its query rows ONE
+    chunk of at most chunk_rows stored rows widened (exactly) to fp32 at a time -- no fp32 tensor of more than chunk_rows rows
+    is ever made (a catalogue of at most chunk_rows rows travels as its one chunk) --; the update is type_csr + cell_means_bf16; the final centroids get one more assignment.  init: [n_cells, D] fp32; None: the
+    widened rows at the first n_cells entries of the same CPU torch.randperm(P) seeded with `seed`.  Every field has the bits
+    of build_cell_index(catalogue.table.float(), same arguments), for any chunk_rows: a row's assignment does not depend on
+    the chunk it travels in, and cell_means_bf16 is cell_means on the widened table bit for bit.  A function of its own:
+    build_cell_index refuses a bf16 table."""
+    table = catalogue.table if isinstance(catalogue, CompactCatalogue) else catalogue
+    if isinstance(table, torch.Tensor) and table.dtype == torch.float32:
+        raise ValueError("build_cell_index_bf16: an fp32 table is build_cell_index's; this function reads the bf16 copy "
+                         "(catalogue_bf16, CompactCatalogue)")
+    d = _table_width(table, dtype=torch.bfloat16)
+    return _lloyd("build_cell_index_bf16", table, d, cell_means_bf16, n_cells, iters, seed, init, chunk_rows)
