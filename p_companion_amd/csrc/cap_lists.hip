@@ -13,15 +13,15 @@
 //                as (-inf, RG_NONE) so that a NaN never reaches a comparison, and through rl_sort<NE> (wave_sort.h): slot
 //                NE lane + e is then in serving order.  group[id] is gathered for the real slots alone, the wave's groups go to
 //                LDS, and every lane walks them as 16-byte broadcast reads, counting for each of its slots the earlier slots of
-//                the same group: m / 4 reads and NE m integer compares per lane.  The kept flags are counted per lane, a
-//                shuffle scan over the wave gives each kept slot its place, places below n are stored, and the tail [kept, n)
-//                is filled with -1 / -inf.
+//                the same group: m / 4 reads and NE m integer compares per lane.  lp_store_row (list_pool.h) compacts and
+//                stores the kept slots with the -1 / -inf tail.
 //   variants     NE = 2 (m <= 128) and NE = 4 (m <= 256).  Both sort under one total order in which equal keys are equal slots
 //                (same id, same score bits up to the sign of zero, see below), so the bits do not depend on the variant.
 // Integer compares and float compares only: no workspace, no float atomics, nothing read back; the result does not depend on
 // the grid or the run.  Two slots equal in (score, id) -- duplicate ids, outside the contract, or +0.0 / -0.0 under one id --
 // are served in an unspecified order; with distinct ids every comparison is strict and every output bit is determined.
 #include "common.h"
+#include "list_pool.h"             // lp_store_row, lp_i32x4
 #include "wave_sort.h"             // rl_sort; grouped_plan.h: rg_better, RG_NONE, RG_MAX_GRID
 
 #define CL_MAX_POOL 256
@@ -36,7 +36,6 @@ __global__ __launch_bounds__(64 * CL_ROWS_PER_WG) void cl_cap_kernel(const int32
                                                                      float* __restrict__ out_score,
                                                                      int32_t* __restrict__ bad_count) {
     typedef int ivec __attribute__((ext_vector_type(NE)));
-    typedef int i32x4 __attribute__((ext_vector_type(4)));
     __shared__ __attribute__((aligned(16))) int lg[CL_ROWS_PER_WG][64 * NE];     // a wave's groups in serving order
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     int* wg = lg[wave];
@@ -85,7 +84,7 @@ __global__ __launch_bounds__(64 * CL_ROWS_PER_WG) void cl_cap_kernel(const int32
             for (int e = 0; e < NE; e++) c[e] = 0;
             const int nq = (m + 3) >> 2;                  // (<= 16 NE: inside the wave's row, every entry of which is written)
             for (int q = 0; q < nq; q++) {
-                const i32x4 x = *reinterpret_cast<const i32x4*>(&wg[4 * q]);      // (one address per wave: a broadcast)
+                const lp_i32x4 x = *reinterpret_cast<const lp_i32x4*>(&wg[4 * q]);  // (one address per wave: a broadcast)
 #pragma unroll
                 for (int t = 0; t < 4; t++)
 #pragma unroll
@@ -96,32 +95,8 @@ __global__ __launch_bounds__(64 * CL_ROWS_PER_WG) void cl_cap_kernel(const int32
             for (int e = 0; e < NE; e++)
                 if (g[e] >= 0 && c[e] >= cap) keep[e] = false;
         }
-        // ---- compaction: the kept slots' places, in serving order
-        int mine = 0;
-#pragma unroll
-        for (int e = 0; e < NE; e++) mine += keep[e];
-        int inc = mine;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const int t = __shfl_up(inc, o, 64);
-            if (lane >= o) inc += t;
-        }
-        const int kept = __shfl(inc, 63, 64);
-        int pos = inc - mine;
-#pragma unroll
-        for (int e = 0; e < NE; e++) {
-            if (keep[e]) {
-                if (pos < n) {
-                    out_idx[(size_t)r * n + pos] = ix[e];
-                    out_score[(size_t)r * n + pos] = v[e];
-                }
-                pos++;
-            }
-        }
-        for (int k = kept + lane; k < n; k += 64) {
-            out_idx[(size_t)r * n + k] = -1;
-            out_score[(size_t)r * n + k] = -INFINITY;
-        }
+        // ---- compaction and store (list_pool.h): the kept slots' places, in serving order; no support column (ix stands in)
+        lp_store_row<NE, false>(keep, ix, v, ix, lane, n, (size_t)r * n, out_idx, out_score, nullptr);
     }
 }
 

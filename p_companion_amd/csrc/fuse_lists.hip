@@ -16,15 +16,14 @@
 //                slots fused.  A sum that overflows is served as the infinity it became, where rg_better puts it.
 //   kernel       one wave per basket, four baskets per workgroup, grid-stride over baskets; the waves of a workgroup never meet
 //                (every wave has its own LDS rows).  The slots go into NE registers per lane, non-candidates as
-//                (-inf, RG_NONE).  The ban ids -- 64 sources at a time, then their exclusion rows as one flat list, a bisection
-//                over the lanes' scanned row lengths finding the row of a flat position -- stream through a 256-entry LDS chunk
-//                that every lane walks as 16-byte broadcast reads against its own slots.  rlw_sort<NE> (wave_sort.h) sorts the
+//                (-inf, RG_NONE).  The ban set is struck out of them by list_pool.h's lp_ban_pass, written out below (see
+//                there; why this unit keeps its text: HISTORY.md "Shared list post-pass blocks").  rlw_sort<NE> sorts the
 //                survivors under the strict order of (score bits, id) -- rg_better with +0.0 before -0.0 --, ids and scores go
 //                to the wave's LDS rows, and every lane walks the candidates' part of them: for each of its slots it counts the
 //                earlier slots of the same id (a slot with any is not the head of its product) and, for sum, adds the later
 //                ones' scores to its own in slot order, which is already descending.  A second sort (rlw_sort_with: the support
-//                travels as payload) puts the heads under rg_better of their fused scores, a shuffle scan compacts them, places
-//                below n are stored, and the tail is filled with -1 / -inf / 0.
+//                travels as payload) puts the heads under rg_better of their fused scores, and list_pool.h's lp_store_row,
+//                written out below as well, compacts and stores them with the -1 / -inf / 0 tail.
 //   variants     NE = 2, 4, 8, 16 for S w <= 128, 256, 512, 1024.  Both sorts run under strict orders -- slots that compare
 //                equal are the same bits --, so the output bits do not depend on the variant.
 // Integer compares, float compares and the fp32 additions above: no workspace, no float atomics, nothing read back; the result
@@ -105,7 +104,7 @@ __global__ __launch_bounds__(64 * FL_WAVES) void fl_fuse_kernel(const int32_t* _
                 }
             }
         }
-        // ---- the ban set: the sources, 64 at a time, and behind them their exclusion rows as one flat list
+        // ---- the ban set: the sources, 64 at a time, and behind them their exclusion rows as one flat list (lp_ban_pass's text)
         if (source) {                                     // (uniform)
             for (int s0 = 0; s0 < S; s0 += 64) {
                 int src = -1;
@@ -186,7 +185,7 @@ __global__ __launch_bounds__(64 * FL_WAVES) void fl_fuse_kernel(const int32_t* _
             if (c[e] != 0) { v[e] = -INFINITY; ix[e] = RG_NONE; }                             // not the head of its product
         // the heads under rg_better of their fused scores (distinct ids: a strict order), each with its support
         rlw_sort_with<NE>(v, ix, sup, lane);
-        // ---- compaction: the heads' places, in serving order
+        // ---- compaction: the heads' places, in serving order (lp_store_row's text)
         bool keep[NE];
         int mine = 0;
 #pragma unroll

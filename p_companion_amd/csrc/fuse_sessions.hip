@@ -29,18 +29,16 @@
 //                without reading them back, so it launches every variant that L w can reach on the one stream, and a wave
 //                passes over, wave-uniformly, a session whose pool belongs to another variant (the smallest takes the empty
 //                ones): every session is written by exactly one launch.  The live slots go into the registers lane-interleaved
-//                (row of slot j: j / w), the term is formed there.  The ban ids -- 64 sources at a time, then their exclusion
-//                rows as one flat list, a bisection over the lanes' scanned row lengths finding the row of a flat position --
-//                stream through a 256-entry LDS chunk that every lane walks as 16-byte broadcast reads against its own slots
-//                (fl_fuse_kernel's block, over all rows of the session).  rlw_sort<NE> (wave_sort.h) then sorts ints with the
-//                keys swapped -- value ~id (INT_MIN for a non-candidate), index ~rlw_key(t) --: id ascending, then term
+//                (row of slot j: j / w), the term is formed there.  lp_ban_pass (list_pool.h) strikes the ban set out of them,
+//                over all rows of the session.  rlw_sort<NE> (wave_sort.h) then sorts ints with the keys swapped -- value
+//                ~id (INT_MIN for a non-candidate), index ~rlw_key(t) --: id ascending, then term
 //                descending with +0.0 before -0.0, a strict order in which equal slots are equal bits, so a product's slots
 //                are ADJACENT.  Ids and terms go to the wave's LDS rows; a slot is the head of its product iff it is a
 //                candidate and its predecessor's id differs; each head walks forward while the id matches, adding in position
 //                order -- the pinned one -- and counting its support.  The walk is bounded by the candidate count and costs the
 //                longest run, not the pool.  A second sort (rlw_sort_with: the support travels as payload) puts the heads
-//                under rg_better of their fused scores, a shuffle scan compacts them, places below n are stored, and the
-//                tail is filled with -1 / -inf / 0.
+//                under rg_better of their fused scores, and lp_store_row (list_pool.h) compacts and stores them with the
+//                -1 / -inf / 0 tail.
 // Both sorts run under strict orders, so the output bits do not depend on the variant.  Integer compares, float compares, one
 // fp32 multiplication per slot and the fp32 additions above: no workspace, no float atomics (integer atomics for the two
 // counters only), nothing read back; the result does not depend on the grid, the run, the variant, a permutation of a
@@ -48,15 +46,13 @@
 #include <climits>
 
 #include "common.h"
+#include "list_pool.h"             // lp_ban_pass, lp_store_row, LP_CHUNK
 #include "wave_sort.h"             // rlw_sort, rlw_sort_with, rlw_key; grouped_plan.h: rg_better, RG_NONE, RG_MAX_GRID
 
 #define FUSE_SESSIONS_MAX_POOL 1024
 #define FS_MAX_N 256
 #define FS_WAVES 4                 // sessions per workgroup, one wave each
-#define FS_CHUNK 256               // ban ids per pass through LDS
 #define FS_OUT INT_MIN             // the sort value of a slot that is no candidate (~id of a candidate is in [-2^31 + 1, -1])
-
-typedef int fs_i32x4 __attribute__((ext_vector_type(4)));
 
 // The variant that serves a pool of m slots.
 __host__ __device__ __forceinline__ int fs_class(int m) { return m <= 128 ? 2 : (m <= 256 ? 4 : (m <= 512 ? 8 : 16)); }
@@ -72,7 +68,7 @@ __global__ __launch_bounds__(64 * FS_WAVES) void fs_fuse_kernel(
     typedef float fvec __attribute__((ext_vector_type(NE)));
     __shared__ __attribute__((aligned(16))) int lid_all[FS_WAVES][64 * NE];       // a wave's ~ids, equal ids adjacent
     __shared__ __attribute__((aligned(16))) float lsc_all[FS_WAVES][64 * NE];     // ... and their terms
-    __shared__ __attribute__((aligned(16))) int lban_all[FS_WAVES][FS_CHUNK];     // a chunk of the session's ban ids
+    __shared__ __attribute__((aligned(16))) int lban_all[FS_WAVES][LP_CHUNK];     // a chunk of the session's ban ids
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     int* lid = lid_all[wave];
     float* lsc = lsc_all[wave];
@@ -114,58 +110,10 @@ __global__ __launch_bounds__(64 * FS_WAVES) void fs_fuse_kernel(
                 }
             }
         }
-        // ---- the ban set: the sources of ALL rows, 64 at a time, and behind them their exclusion rows as one flat list
-        if (source) {                                     // (uniform)
-            for (int64_t s0 = 0; s0 < len; s0 += 64) {
-                int src = -1;
-                if (s0 + lane < len) {
-                    src = source[(size_t)lo + s0 + lane];
-                    if (src < -1 || src >= num_products) { // never used as an index; its row offered nothing above
-                        if (bad_count) atomicAdd(bad_count, 1);
-                        src = -1;
-                    }
-                }
-                int xlo = 0, xlen = 0;
-                if (ex_rowptr && src >= 0) {              // (src < num_products: rowptr has num_products + 1 entries)
-                    xlo = ex_rowptr[src];
-                    xlen = max(ex_rowptr[src + 1] - xlo, 0);
-                }
-                int inc = xlen;                           // the inclusive scan of the lanes' row lengths
-#pragma unroll
-                for (int o = 1; o < 64; o <<= 1) {
-                    const int t = __shfl_up(inc, o, 64);
-                    if (lane >= o) inc += t;
-                }
-                const int total = __shfl(inc, 63, 64);
-                for (int base = 0; base < 64 + total; base += FS_CHUNK) {         // flat: 64 sources, then `total` row entries
-#pragma unroll
-                    for (int k = 0; k < FS_CHUNK / 64; k++) {
-                        const int p = base + lane + 64 * k - 64;                  // the flat position among the row entries
-                        int owner = 0;                    // the lanes whose rows end at or before p: the row that holds p
-#pragma unroll
-                        for (int step = 32; step >= 1; step >>= 1)
-                            if (__shfl(inc, owner + step - 1, 64) <= p) owner += step;          // (owner + step - 1 <= 63)
-                        const int o_inc = __shfl(inc, owner, 64), o_len = __shfl(xlen, owner, 64), o_lo = __shfl(xlo, owner, 64);
-                        int x = -1;                       // equal to no candidate's id
-                        if (p < 0) x = src;               // (base 0, k 0: the lane's own source)
-                        else if (p < total) x = ex_col[(size_t)o_lo + (p - (o_inc - o_len))];
-                        lban[lane + 64 * k] = ~x;         // (0 for -1: no candidate's value, which is negative)
-                    }
-                    // Same-wave LDS instructions execute in order: the lanes' stores are in LDS before any lane's read-back.
-                    __builtin_amdgcn_wave_barrier();
-                    const int nq = (min(FS_CHUNK, 64 + total - base) + 3) >> 2;
-                    for (int q = 0; q < nq; q++) {
-                        const fs_i32x4 x = *reinterpret_cast<const fs_i32x4*>(&lban[4 * q]);    // (a broadcast)
-#pragma unroll
-                        for (int t = 0; t < 4; t++)
-#pragma unroll
-                            for (int e = 0; e < NE; e++)
-                                if (x[t] == val[e]) { val[e] = FS_OUT; tk[e] = RG_NONE; }       // (x: 0 or ~(a product id))
-                    }
-                    __builtin_amdgcn_wave_barrier();      // the reads are done before the next chunk's stores
-                }
-            }
-        }
+        // ---- the ban set: the sources of ALL rows and their exclusion rows (list_pool.h), matched as ~id
+        if (source)                                       // (uniform)
+            lp_ban_pass<NE, true>(source + (size_t)lo, len, ex_rowptr, ex_col, num_products, bad_count, lban, lane, val, tk,
+                                  FS_OUT, RG_NONE);
         // slot NE * lane + e: id ascending, inside an id the term descending (+0.0 before -0.0), the non-candidates last
         rlw_sort<NE>(val, tk, lane);
         int cnt = 0;                                      // the candidates: the positions below cnt
@@ -206,38 +154,11 @@ __global__ __launch_bounds__(64 * FS_WAVES) void fs_fuse_kernel(
         __builtin_amdgcn_wave_barrier();                  // the reads are done before the next session's stores
         // the heads under rg_better of their fused scores (distinct ids: a strict order), each with its support
         rlw_sort_with<NE>(v, ix, sup, lane);
-        // ---- compaction: the heads' places, in serving order
+        // ---- compaction and store (list_pool.h): the heads' places, in serving order
         bool keep[NE];
-        int mine = 0;
 #pragma unroll
-        for (int e = 0; e < NE; e++) {
-            keep[e] = ix[e] != RG_NONE;
-            mine += keep[e];
-        }
-        int inc = mine;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const int t = __shfl_up(inc, o, 64);
-            if (lane >= o) inc += t;
-        }
-        const int kept = __shfl(inc, 63, 64);
-        int pos = inc - mine;
-#pragma unroll
-        for (int e = 0; e < NE; e++) {
-            if (keep[e]) {
-                if (pos < n) {
-                    out_idx[(size_t)b * n + pos] = ix[e];
-                    out_score[(size_t)b * n + pos] = v[e];
-                    out_support[(size_t)b * n + pos] = sup[e];
-                }
-                pos++;
-            }
-        }
-        for (int k = kept + lane; k < n; k += 64) {
-            out_idx[(size_t)b * n + k] = -1;
-            out_score[(size_t)b * n + k] = -INFINITY;
-            out_support[(size_t)b * n + k] = 0;
-        }
+        for (int e = 0; e < NE; e++) keep[e] = ix[e] != RG_NONE;
+        lp_store_row<NE, true>(keep, ix, v, sup, lane, n, (size_t)b * n, out_idx, out_score, out_support);
     }
 }
 

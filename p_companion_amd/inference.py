@@ -55,6 +55,13 @@ from .metrics import Metrics
 from .p_companion import PCompanion
 
 
+def _refuse_tensor(what, name, wanted, t):
+    """The refusal of an argument that is not the tensor asked for: '<what>: <name> must be <wanted>, got <shape> <dtype>' (the
+    type's name for anything but a tensor)."""
+    got = f"{tuple(t.shape)} {t.dtype}" if torch.is_tensor(t) else type(t).__name__
+    raise ValueError(f"{what}: {name} must be {wanted}, got {got}")
+
+
 def _check_group(what, group, cap):
     """cap as an int, and the shape of a product-group array (ops.cap_lists): cap >= 1, group None or a 1-D int32 tensor --
     ValueError before anything of the serving object is read."""
@@ -62,9 +69,7 @@ def _check_group(what, group, cap):
     if cap < 1:
         raise ValueError(f"{what}: cap must be at least 1, got {cap}")
     if group is not None and (not torch.is_tensor(group) or group.dtype != torch.int32 or group.dim() != 1):
-        raise ValueError(f"{what}: group must be None or a [P] int32 device tensor (the product's group, negative = ungrouped), "
-                         f"got {tuple(group.shape) if torch.is_tensor(group) else type(group).__name__}"
-                         f"{' ' + str(group.dtype) if torch.is_tensor(group) else ''}")
+        _refuse_tensor(what, "group", "None or a [P] int32 device tensor (the product's group, negative = ungrouped)", group)
     return cap
 
 
@@ -189,6 +194,10 @@ class _CandidateFilters:
         p = int(self.type_idx.shape[0])
         if group.shape[0] != p:
             raise ValueError(f"{what}: group must hold one entry per product ({p}), got {group.shape[0]}")
+
+    def _served_types(self, idx):
+        """the served products' types: int64, idx's shape, -1 where idx is -1"""
+        return torch.where(idx >= 0, self.type_idx[idx.clamp(min=0).long()].long(), -1)
 
     def _exclude_rows(self, query_idx, repeat=None):
         """The `exclude` triple of the grouped entries for rows keyed by their query's id -- `repeat` consecutive rows per query
@@ -516,8 +525,7 @@ class PCompanionInference(_CandidateFilters):
         _, idx, sc = self.recommend_batch(query_idx, per_type)
         b = idx.shape[0]
         idx, sc = ops.cap_lists(idx.reshape(b, -1), sc.reshape(b, -1), n, group, cap)
-        types = torch.where(idx >= 0, self.type_idx[idx.clamp(min=0).long()].long(), -1)
-        return idx, sc, types
+        return idx, sc, self._served_types(idx)
 
     @torch.no_grad()
     def recommend_basket_batch(self, basket: torch.Tensor, num_recommendations: int = 10, per_item: int = 8,
@@ -537,9 +545,7 @@ class PCompanionInference(_CandidateFilters):
         fusion), so bucket baskets by length.  Nothing is read back."""
         n, per_item, k = int(num_recommendations), int(per_item), int(self.config.NUM_COMP_TYPES)
         if not torch.is_tensor(basket) or basket.dim() != 2 or basket.dtype != torch.int32 or basket.shape[1] < 1:
-            raise ValueError(f"recommend_basket_batch: basket must be a [B, I] int32 tensor with I >= 1 (-1 = no item), got "
-                             f"{tuple(basket.shape) if torch.is_tensor(basket) else type(basket).__name__}"
-                             f"{' ' + str(basket.dtype) if torch.is_tensor(basket) else ''}")
+            _refuse_tensor("recommend_basket_batch", "basket", "a [B, I] int32 tensor with I >= 1 (-1 = no item)", basket)
         b, items = basket.shape
         if per_item < 1 or items * k * per_item > ops.FUSE_LISTS_MAX_POOL:
             raise ValueError(f"recommend_basket_batch: need 1 <= per_item and I * K * per_item <= {ops.FUSE_LISTS_MAX_POOL}, got "
@@ -556,8 +562,7 @@ class PCompanionInference(_CandidateFilters):
         _, idx, sc = self.recommend_batch(basket.reshape(-1).clamp(0, p - 1), per_item)
         idx, sc, support = ops.fuse_lists(idx.reshape(b, items, -1), sc.reshape(b, items, -1), n, combine, source=basket,
                                           exclude=self.exclusions, num_products=p)
-        types = torch.where(idx >= 0, self.type_idx[idx.clamp(min=0).long()].long(), -1)
-        return idx, sc, types, support
+        return idx, sc, self._served_types(idx), support
 
     @torch.no_grad()
     def recommend_session_batch(self, items: torch.Tensor, seg_rowptr: torch.Tensor, num_recommendations: int = 10,
@@ -582,20 +587,14 @@ class PCompanionInference(_CandidateFilters):
         before the model runs.  Nothing is read back."""
         n, per_item, k = int(num_recommendations), int(per_item), int(self.config.NUM_COMP_TYPES)
         if not torch.is_tensor(items) or items.dim() != 1 or items.dtype != torch.int32:
-            raise ValueError(f"recommend_session_batch: items must be a [R] int32 tensor, got "
-                             f"{tuple(items.shape) if torch.is_tensor(items) else type(items).__name__}"
-                             f"{' ' + str(items.dtype) if torch.is_tensor(items) else ''}")
+            _refuse_tensor("recommend_session_batch", "items", "a [R] int32 tensor", items)
         if (not torch.is_tensor(seg_rowptr) or seg_rowptr.dim() != 1 or seg_rowptr.dtype != torch.int32
                 or seg_rowptr.numel() < 1):
-            raise ValueError(f"recommend_session_batch: seg_rowptr must be a [B + 1] int32 tensor, got "
-                             f"{tuple(seg_rowptr.shape) if torch.is_tensor(seg_rowptr) else type(seg_rowptr).__name__}"
-                             f"{' ' + str(seg_rowptr.dtype) if torch.is_tensor(seg_rowptr) else ''}")
+            _refuse_tensor("recommend_session_batch", "seg_rowptr", "a [B + 1] int32 tensor", seg_rowptr)
         r = items.shape[0]
         if weight is not None and (not torch.is_tensor(weight) or weight.dtype != torch.float32
                                    or tuple(weight.shape) != (r,)):
-            raise ValueError(f"recommend_session_batch: weight must be a [R = {r}] float32 tensor, got "
-                             f"{tuple(weight.shape) if torch.is_tensor(weight) else type(weight).__name__}"
-                             f"{' ' + str(weight.dtype) if torch.is_tensor(weight) else ''}")
+            _refuse_tensor("recommend_session_batch", "weight", f"a [R = {r}] float32 tensor", weight)
         if per_item < 1 or k * per_item > ops.FUSE_SESSIONS_MAX_POOL:
             raise ValueError(f"recommend_session_batch: need 1 <= per_item and K * per_item <= {ops.FUSE_SESSIONS_MAX_POOL}, "
                              f"got K = {k} and per_item {per_item}")
@@ -614,8 +613,7 @@ class PCompanionInference(_CandidateFilters):
         _, idx, sc = self.recommend_batch(items.clamp(0, p - 1), per_item)
         idx, sc, support = ops.fuse_sessions(idx.reshape(r, k * per_item), sc.reshape(r, k * per_item), seg_rowptr, n, combine, source=items,
                                              weight=weight, exclude=self.exclusions, num_products=p, max_items=max_items)
-        types = torch.where(idx >= 0, self.type_idx[idx.clamp(min=0).long()].long(), -1)
-        return idx, sc, types, support
+        return idx, sc, self._served_types(idx), support
 
     def _rank_guard(self, what):
         """rank_targets and evaluate_catalogue ask here first: a bf16 catalogue is refused, before the model runs or the

@@ -1970,6 +1970,68 @@ def _filter_args(exclude, bad, device, counted=False):
     return row_key, ex_rowptr, ex_col, ex_rowptr.numel() - 1, _bad_counter(bad, device)
 
 
+def _list_pair(what, idx, score, shape):
+    """idx int32 / score fp32 of one shape, as many dimensions as `shape` ("[R, m]": the function's own wording) names -> the
+    shape."""
+    _req(idx, torch.int32, "idx")
+    _req(score, torch.float32, "score")
+    if idx.dim() != shape.count(",") + 1 or tuple(score.shape) != tuple(idx.shape):
+        raise ValueError(f"{what}: expected idx and score of one shape {shape}, got {tuple(idx.shape)} and "
+                         f"{tuple(score.shape)}")
+    return tuple(idx.shape)
+
+
+def _optional(what, t, dtype, name, wording, shape=None):
+    """An optional device tensor argument (None passes): anything but a tensor is refused under the function's name with the
+    wording of the shape ("[P]"), a tensor goes through _req."""
+    if t is None:
+        return
+    if not isinstance(t, torch.Tensor):
+        raise ValueError(f"{what}: {name} must be a {wording} {str(dtype)[6:]} device tensor, got {type(t).__name__}")
+    _req(t, dtype, name, shape)
+
+
+def _counters(**counters):
+    """The [1] int32 device counters a caller may pass to see a count (None: not asked for)."""
+    for name, t in counters.items():
+        if t is not None:
+            _req(t, torch.int32, name, (1,))
+
+
+def _exclusion_pair(what, exclude, source, num_products, device):
+    """fuse_lists' / fuse_sessions' exclude = (ex_rowptr [P + 1], ex_col) beside their num_products -> (ex_rowptr, ex_col,
+    num_products) as device arguments: without a pair (None, None, the argument or 2^31 - 1); with one, num_products is the
+    pair's P (an argument that disagrees is refused) and an empty ex_col is one unread entry, so that the pointer is not null."""
+    ex_rowptr = ex_col = None
+    if exclude is not None:
+        if source is None:
+            raise ValueError(f"{what}: exclude is keyed by the rows' source ids and needs source")
+        if not isinstance(exclude, (tuple, list)) or len(exclude) != 2 or not all(isinstance(t, torch.Tensor) for t in exclude):
+            raise ValueError(f"{what}: exclude must be the pair (ex_rowptr, ex_col) of int32 device tensors")
+        ex_rowptr, ex_col = exclude
+        _req(ex_rowptr, torch.int32, "ex_rowptr")
+        _req(ex_col, torch.int32, "ex_col")
+        if ex_rowptr.dim() != 1 or ex_rowptr.numel() < 2 or ex_col.dim() != 1:
+            raise ValueError(f"{what}: expected ex_rowptr [P + 1] with P >= 1 and a 1-D ex_col, got "
+                             f"{tuple(ex_rowptr.shape)} and {tuple(ex_col.shape)}")
+        if num_products is not None and int(num_products) != ex_rowptr.numel() - 1:
+            raise ValueError(f"{what}: num_products {int(num_products)} does not match the exclusion set's "
+                             f"{ex_rowptr.numel() - 1} keys")
+        num_products = ex_rowptr.numel() - 1
+        if ex_col.numel() == 0:
+            ex_col = torch.zeros(1, dtype=torch.int32, device=device)
+    num_products = 2 ** 31 - 1 if num_products is None else int(num_products)
+    if not 1 <= num_products <= 2 ** 31 - 1:
+        raise ValueError(f"{what}: num_products must be in [1, 2^31 - 1], got {num_products}")
+    return ex_rowptr, ex_col, num_products
+
+
+def _list_out(rows, n, device, support=False):
+    """The served lists' outputs: (idx [rows, n] int32, score [rows, n] fp32) and, with support, support [rows, n] int32."""
+    out = (torch.empty(rows, n, dtype=torch.int32, device=device), torch.empty(rows, n, dtype=torch.float32, device=device))
+    return out + (torch.empty(rows, n, dtype=torch.int32, device=device),) if support else out
+
+
 def half_sq_norm_bias(table):
     """pc_half_sq_norm_bias: bias[p] = -0.5 * |table[p]|^2 for a [P, D] fp32 device table -> [P] fp32, the per-product term under
     which retrieve_topk_grouped / rank_grouped (bias=) order by Euclidean distance: |q - e|^2 = |q|^2 - 2 (<q, e> + bias).  One
@@ -2457,18 +2519,12 @@ def merge_lists(idx, score):
     under (score descending, product index ascending), -1 / -inf behind the last entry), the lists of a row over disjoint
     products -> (idx [R, n] int32, score [R, n] fp32): the first n of the row's union under the same total order, the scores'
     bits unchanged, -1 / -inf past the end.  1 <= L <= 64, 1 <= n <= 256."""
-    _req(idx, torch.int32, "idx")
-    _req(score, torch.float32, "score")
-    if idx.dim() != 3 or tuple(score.shape) != tuple(idx.shape):
-        raise ValueError(f"merge_lists: expected idx and score of one shape [R, L, n], got {tuple(idx.shape)} and "
-                         f"{tuple(score.shape)}")
-    r, l, n = idx.shape
+    r, l, n = _list_pair("merge_lists", idx, score, "[R, L, n]")
     if not 1 <= l <= MERGE_MAX_LISTS:
         raise ValueError(f"merge_lists: L must be in [1, {MERGE_MAX_LISTS}], got {l}")
     if not 1 <= n <= MERGE_MAX_N:
         raise ValueError(f"merge_lists: n must be in [1, {MERGE_MAX_N}], got {n}")
-    out_idx = torch.empty(r, n, dtype=torch.int32, device=idx.device)
-    out_sc = torch.empty(r, n, dtype=torch.float32, device=idx.device)
+    out_idx, out_sc = _list_out(r, n, idx.device)
     if r == 0:
         return out_idx, out_sc
     check(_lib.lib().pc_merge_lists(_p(idx), _p(score), r, l, n, _p(out_idx), _p(out_sc), _stream()), "pc_merge_lists")
@@ -2523,12 +2579,7 @@ def diversify_lists_bf16(idx, score, table, n, lam, scale=None, bad=None):
 
 def _diversify(what, name, dtype, idx, score, table, n, lam, scale, bad):
     """diversify_lists / diversify_lists_bf16 behind the choice of the entry: the checks (host side alone), then the call."""
-    _req(idx, torch.int32, "idx")
-    _req(score, torch.float32, "score")
-    if idx.dim() != 2 or tuple(score.shape) != tuple(idx.shape):
-        raise ValueError(f"{what}: expected idx and score of one shape [R, m], got {tuple(idx.shape)} and "
-                         f"{tuple(score.shape)}")
-    r, m = idx.shape
+    r, m = _list_pair(what, idx, score, "[R, m]")
     if not 1 <= m <= DIVERSIFY_MAX_POOL:
         raise ValueError(f"{what}: the pool m must be in [1, {DIVERSIFY_MAX_POOL}], got {m}")
     n = int(n)
@@ -2538,14 +2589,9 @@ def _diversify(what, name, dtype, idx, score, table, n, lam, scale, bad):
     if not 0.0 <= lam <= 1.0:                             # (a NaN fails the comparison)
         raise ValueError(f"{what}: lam must be in [0, 1], got {lam}")
     d = _table_width(table, rows=True, dtype=dtype)
-    if scale is not None:
-        if not isinstance(scale, torch.Tensor):
-            raise ValueError(f"{what}: scale must be a [P] float32 device tensor, got {type(scale).__name__}")
-        _req(scale, torch.float32, "scale", (table.shape[0],))
-    if bad is not None:
-        _req(bad, torch.int32, "bad", (1,))
-    out_idx = torch.empty(r, n, dtype=torch.int32, device=idx.device)
-    out_sc = torch.empty(r, n, dtype=torch.float32, device=idx.device)
+    _optional(what, scale, torch.float32, "scale", "[P]", (table.shape[0],))
+    _counters(bad=bad)
+    out_idx, out_sc = _list_out(r, n, idx.device)
     if r == 0:
         return out_idx, out_sc
     check(getattr(_lib.lib(), name)(_p(idx), _p(score), r, m, _p(table), _p(scale), table.shape[0], d, n, lam, _p(out_idx),
@@ -2569,12 +2615,7 @@ def cap_lists(idx, score, n, group=None, cap=1, row_ban=None, bad=None):
     counter the caller passes to see the count; added to).  cap >= m or group=None returns the pool's first n: of a grouped
     entry's list its own first n, bit for bit.  Bitwise deterministic; a permutation of a row's slots changes nothing.  Nothing
     is read back."""
-    _req(idx, torch.int32, "idx")
-    _req(score, torch.float32, "score")
-    if idx.dim() != 2 or tuple(score.shape) != tuple(idx.shape):
-        raise ValueError(f"cap_lists: expected idx and score of one shape [R, m], got {tuple(idx.shape)} and "
-                         f"{tuple(score.shape)}")
-    r, m = idx.shape
+    r, m = _list_pair("cap_lists", idx, score, "[R, m]")
     if not 1 <= m <= CAP_LISTS_MAX_POOL:
         raise ValueError(f"cap_lists: the pool m must be in [1, {CAP_LISTS_MAX_POOL}], got {m}")
     n, cap = int(n), int(cap)
@@ -2584,22 +2625,15 @@ def cap_lists(idx, score, n, group=None, cap=1, row_ban=None, bad=None):
         raise ValueError(f"cap_lists: cap must be at least 1, got {cap}")
     num_products = 2 ** 31 - 1                            # without groups every non-negative id is a candidate
     if group is not None:
-        if not isinstance(group, torch.Tensor):
-            raise ValueError(f"cap_lists: group must be a [P] int32 device tensor, got {type(group).__name__}")
-        _req(group, torch.int32, "group")
+        _optional("cap_lists", group, torch.int32, "group", "[P]")
         if group.dim() != 1 or group.shape[0] < 1:
             raise ValueError(f"cap_lists: group must be [P] with at least one product, got {tuple(group.shape)}")
         num_products = group.shape[0]
-    if row_ban is not None:
-        if group is None:
-            raise ValueError("cap_lists: row_ban names a group per row and needs group")
-        if not isinstance(row_ban, torch.Tensor):
-            raise ValueError(f"cap_lists: row_ban must be a [R] int32 device tensor, got {type(row_ban).__name__}")
-        _req(row_ban, torch.int32, "row_ban", (r,))
-    if bad is not None:
-        _req(bad, torch.int32, "bad", (1,))
-    out_idx = torch.empty(r, n, dtype=torch.int32, device=idx.device)
-    out_sc = torch.empty(r, n, dtype=torch.float32, device=idx.device)
+    if row_ban is not None and group is None:
+        raise ValueError("cap_lists: row_ban names a group per row and needs group")
+    _optional("cap_lists", row_ban, torch.int32, "row_ban", "[R]", (r,))
+    _counters(bad=bad)
+    out_idx, out_sc = _list_out(r, n, idx.device)
     if r == 0:
         return out_idx, out_sc
     # (a group holds at most m of a row's slots: every cap >= m is the cap m, whatever fits a C int)
@@ -2626,12 +2660,7 @@ def fuse_lists(idx, score, n, combine="sum", source=None, exclude=None, num_prod
     argument, else 2^31 - 1.  An id or a source outside [-1, num_products) is never used as an index and is counted in `bad`
     (a [1] int32 device counter the caller passes to see the count; added to).  Bitwise deterministic; a permutation of a
     basket's rows (with their sources) or of the slots inside rows changes nothing.  Nothing is read back."""
-    _req(idx, torch.int32, "idx")
-    _req(score, torch.float32, "score")
-    if idx.dim() != 3 or tuple(score.shape) != tuple(idx.shape):
-        raise ValueError(f"fuse_lists: expected idx and score of one shape [B, S, w], got {tuple(idx.shape)} and "
-                         f"{tuple(score.shape)}")
-    b, s, w = idx.shape
+    b, s, w = _list_pair("fuse_lists", idx, score, "[B, S, w]")
     if not 1 <= s * w <= FUSE_LISTS_MAX_POOL:
         raise ValueError(f"fuse_lists: the pool S * w must be in [1, {FUSE_LISTS_MAX_POOL}], got {s} * {w}")
     n = int(n)
@@ -2639,36 +2668,10 @@ def fuse_lists(idx, score, n, combine="sum", source=None, exclude=None, num_prod
         raise ValueError(f"fuse_lists: n must be in [1, min(S * w, {FUSE_LISTS_MAX_N}) = {min(s * w, FUSE_LISTS_MAX_N)}], got {n}")
     if combine not in ("sum", "max"):
         raise ValueError(f"fuse_lists: combine must be 'sum' or 'max', got {combine!r}")
-    if source is not None:
-        if not isinstance(source, torch.Tensor):
-            raise ValueError(f"fuse_lists: source must be a [B, S] int32 device tensor, got {type(source).__name__}")
-        _req(source, torch.int32, "source", (b, s))
-    ex_rowptr = ex_col = None
-    if exclude is not None:
-        if source is None:
-            raise ValueError("fuse_lists: exclude is keyed by the rows' source ids and needs source")
-        if not isinstance(exclude, (tuple, list)) or len(exclude) != 2 or not all(isinstance(t, torch.Tensor) for t in exclude):
-            raise ValueError("fuse_lists: exclude must be the pair (ex_rowptr, ex_col) of int32 device tensors")
-        ex_rowptr, ex_col = exclude
-        _req(ex_rowptr, torch.int32, "ex_rowptr")
-        _req(ex_col, torch.int32, "ex_col")
-        if ex_rowptr.dim() != 1 or ex_rowptr.numel() < 2 or ex_col.dim() != 1:
-            raise ValueError(f"fuse_lists: expected ex_rowptr [P + 1] with P >= 1 and a 1-D ex_col, got "
-                             f"{tuple(ex_rowptr.shape)} and {tuple(ex_col.shape)}")
-        if num_products is not None and int(num_products) != ex_rowptr.numel() - 1:
-            raise ValueError(f"fuse_lists: num_products {int(num_products)} does not match the exclusion set's "
-                             f"{ex_rowptr.numel() - 1} keys")
-        num_products = ex_rowptr.numel() - 1
-        if ex_col.numel() == 0:                           # (every row empty: one unread entry, so that the pointer is not null)
-            ex_col = torch.zeros(1, dtype=torch.int32, device=idx.device)
-    num_products = 2 ** 31 - 1 if num_products is None else int(num_products)
-    if not 1 <= num_products <= 2 ** 31 - 1:
-        raise ValueError(f"fuse_lists: num_products must be in [1, 2^31 - 1], got {num_products}")
-    if bad is not None:
-        _req(bad, torch.int32, "bad", (1,))
-    out_idx = torch.empty(b, n, dtype=torch.int32, device=idx.device)
-    out_sc = torch.empty(b, n, dtype=torch.float32, device=idx.device)
-    out_sup = torch.empty(b, n, dtype=torch.int32, device=idx.device)
+    _optional("fuse_lists", source, torch.int32, "source", "[B, S]", (b, s))
+    ex_rowptr, ex_col, num_products = _exclusion_pair("fuse_lists", exclude, source, num_products, idx.device)
+    _counters(bad=bad)
+    out_idx, out_sc, out_sup = _list_out(b, n, idx.device, support=True)
     if b == 0:
         return out_idx, out_sc, out_sup
     check(_lib.lib().pc_fuse_lists(_p(idx), _p(score), _p(source), b, s, w, _p(ex_rowptr), _p(ex_col), num_products, n,
@@ -2702,12 +2705,7 @@ def fuse_sessions(idx, score, seg_rowptr, n, combine="sum", source=None, weight=
     seg_rowptr entry outside [0, R] or below its predecessor, which is clamped.  `truncated`: a [1] int32 device counter,
     added to.  Bitwise deterministic; a permutation of a session's rows (with their sources and weights, among the rows of one
     truncation status) or of the slots inside rows changes nothing.  Nothing is read back."""
-    _req(idx, torch.int32, "idx")
-    _req(score, torch.float32, "score")
-    if idx.dim() != 2 or tuple(score.shape) != tuple(idx.shape):
-        raise ValueError(f"fuse_sessions: expected idx and score of one shape [R, w], got {tuple(idx.shape)} and "
-                         f"{tuple(score.shape)}")
-    r, w = idx.shape
+    r, w = _list_pair("fuse_sessions", idx, score, "[R, w]")
     if not 1 <= w <= FUSE_SESSIONS_MAX_POOL:
         raise ValueError(f"fuse_sessions: the row width w must be in [1, {FUSE_SESSIONS_MAX_POOL}], got {w}")
     _req(seg_rowptr, torch.int32, "seg_rowptr")
@@ -2719,45 +2717,14 @@ def fuse_sessions(idx, score, seg_rowptr, n, combine="sum", source=None, weight=
         raise ValueError(f"fuse_sessions: n must be in [1, {FUSE_SESSIONS_MAX_N}], got {n}")
     if combine not in ("sum", "max"):
         raise ValueError(f"fuse_sessions: combine must be 'sum' or 'max', got {combine!r}")
-    if source is not None:
-        if not isinstance(source, torch.Tensor):
-            raise ValueError(f"fuse_sessions: source must be a [R] int32 device tensor, got {type(source).__name__}")
-        _req(source, torch.int32, "source", (r,))
-    if weight is not None:
-        if not isinstance(weight, torch.Tensor):
-            raise ValueError(f"fuse_sessions: weight must be a [R] float32 device tensor, got {type(weight).__name__}")
-        _req(weight, torch.float32, "weight", (r,))
-    ex_rowptr = ex_col = None
-    if exclude is not None:
-        if source is None:
-            raise ValueError("fuse_sessions: exclude is keyed by the rows' source ids and needs source")
-        if not isinstance(exclude, (tuple, list)) or len(exclude) != 2 or not all(isinstance(t, torch.Tensor) for t in exclude):
-            raise ValueError("fuse_sessions: exclude must be the pair (ex_rowptr, ex_col) of int32 device tensors")
-        ex_rowptr, ex_col = exclude
-        _req(ex_rowptr, torch.int32, "ex_rowptr")
-        _req(ex_col, torch.int32, "ex_col")
-        if ex_rowptr.dim() != 1 or ex_rowptr.numel() < 2 or ex_col.dim() != 1:
-            raise ValueError(f"fuse_sessions: expected ex_rowptr [P + 1] with P >= 1 and a 1-D ex_col, got "
-                             f"{tuple(ex_rowptr.shape)} and {tuple(ex_col.shape)}")
-        if num_products is not None and int(num_products) != ex_rowptr.numel() - 1:
-            raise ValueError(f"fuse_sessions: num_products {int(num_products)} does not match the exclusion set's "
-                             f"{ex_rowptr.numel() - 1} keys")
-        num_products = ex_rowptr.numel() - 1
-        if ex_col.numel() == 0:                           # (every row empty: one unread entry, so that the pointer is not null)
-            ex_col = torch.zeros(1, dtype=torch.int32, device=idx.device)
-    num_products = 2 ** 31 - 1 if num_products is None else int(num_products)
-    if not 1 <= num_products <= 2 ** 31 - 1:
-        raise ValueError(f"fuse_sessions: num_products must be in [1, 2^31 - 1], got {num_products}")
+    _optional("fuse_sessions", source, torch.int32, "source", "[R]", (r,))
+    _optional("fuse_sessions", weight, torch.float32, "weight", "[R]", (r,))
+    ex_rowptr, ex_col, num_products = _exclusion_pair("fuse_sessions", exclude, source, num_products, idx.device)
     max_items = 0 if max_items is None else int(max_items)
     if not 0 <= max_items <= 2 ** 31 - 1:
         raise ValueError(f"fuse_sessions: max_items must be None or in [0, 2^31 - 1] (0: no cap), got {max_items}")
-    if bad is not None:
-        _req(bad, torch.int32, "bad", (1,))
-    if truncated is not None:
-        _req(truncated, torch.int32, "truncated", (1,))
-    out_idx = torch.empty(b, n, dtype=torch.int32, device=idx.device)
-    out_sc = torch.empty(b, n, dtype=torch.float32, device=idx.device)
-    out_sup = torch.empty(b, n, dtype=torch.int32, device=idx.device)
+    _counters(bad=bad, truncated=truncated)
+    out_idx, out_sc, out_sup = _list_out(b, n, idx.device, support=True)
     if b == 0:
         return out_idx, out_sc, out_sup
     if r == 0:                                            # (no rows: nothing offers and nothing bans; every pointer is null)

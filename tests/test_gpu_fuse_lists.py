@@ -269,6 +269,27 @@ def test_the_ban_set():
         assert same(check(idx, score, top, combine, source, empty), without)
 
 
+def test_the_ban_set_past_64_sources_and_past_one_chunk_of_exclusion_ids():
+    """S = 65, w = 1, four ids per source: the 64 sources of the first round bring 256 ids -- behind the 64 sources the first
+    256-entry chunk holds the ids 0 .. 191, a second one 192 .. 255 --, and the 65th source makes a second round (256 .. 259)."""
+    rng = np.random.default_rng(65)
+    b, s = 5, 65
+    source = np.tile(np.arange(700, 700 + s, dtype=np.int32), (b, 1))             # source j excludes 4 j .. 4 j + 3
+    ex = (np.zeros(P + 1, np.int32), np.arange(4 * s, dtype=np.int32))
+    ex[0][701:] = np.minimum(4 * np.arange(1, P - 699), 4 * s)
+    assert ex[0][700] == 0 and ex[0][764] == 256 and ex[0][765] == ex[0][P] == 260
+    idx = rng.integers(0, 330, (b, s, 1)).astype(np.int32)                        # banned by a row (< 260) or not
+    score = (rng.permutation(b * s).reshape(b, s, 1) / 4).astype(np.float32)
+    planted = (191, 192, 200, 255, 256, 259, 764, 700)    # the chunks' and rounds' edges, a source of either round
+    idx[:, :len(planted), 0], idx[:, len(planted), 0] = planted, 300
+    for combine in ("sum", "max"):
+        with_ex = check(idx, score, s, combine, source, ex)[0].cpu().numpy()
+        without = check(idx, score, s, combine, source, num_products=P)[0].cpu().numpy()
+        for r in range(b):
+            assert set(planted[:6]) | {300} <= set(without[r].tolist()) and not {764, 700} & set(without[r].tolist())
+            assert 300 in with_ex[r] and (with_ex[r][with_ex[r] >= 0] >= 260).all() and not {764, 700} & set(with_ex[r].tolist())
+
+
 def test_short_baskets_end_in_minus_one_minus_inf_and_zero():
     s, w = 3, 10
     idx = np.full((4, s, w), -1, np.int32)

@@ -305,6 +305,34 @@ def test_a_long_session_offers_its_last_rows_and_bans_with_all_of_them():
             assert int(t) == want[4]
 
 
+def test_the_ban_set_past_64_rows_and_past_one_chunk_of_exclusion_ids():
+    """w = 1.  A session of 65 rows, four ids per source: the 64 sources of the first round bring 256 ids -- behind the 64
+    sources the first 256-entry chunk holds the ids 0 .. 191, a second one 192 .. 255 --, and the 65th row makes a second round
+    (256 .. 259).  A session of 3 rows whose sources exclude 100 ids each: what it offers is among the last 40 of the 300, all
+    of them in the second chunk."""
+    rng = np.random.default_rng(65)
+    long, short = 65, 3
+    ptr = ragged([long, short])
+    source = np.concatenate([np.arange(700, 700 + long), [900, 901, 902]]).astype(np.int32)
+    sets = [np.array([], np.int64)] * P
+    for j in range(long):
+        sets[700 + j] = np.arange(4 * j, 4 * j + 4)
+    for t in range(short):
+        sets[900 + t] = np.arange(300 + 100 * t, 400 + 100 * t)
+    ex = (np.concatenate([[0], np.cumsum([len(r) for r in sets])]).astype(np.int32), np.concatenate(sets).astype(np.int32))
+    idx = rng.integers(0, 300, (long + short, 1)).astype(np.int32)                # the long session: banned by a row (< 260) or not
+    score = (rng.permutation(long + short).reshape(-1, 1) / 4).astype(np.float32)
+    planted = (191, 192, 200, 255, 256, 259, 764, 700)    # the chunks' and rounds' edges, a source of either round
+    idx[:len(planted), 0], idx[len(planted), 0] = planted, 299
+    idx[long:, 0] = (560, 580, 599)
+    for combine in ("sum", "max"):
+        with_ex = check(idx, score, ptr, 64, combine, source, None, ex)[0].cpu().numpy()
+        without = check(idx, score, ptr, 64, combine, source, num_products=P)[0].cpu().numpy()
+        assert set(planted[:6]) | {299} <= set(without[0].tolist()) and not {764, 700} & set(without[0].tolist())
+        assert 299 in with_ex[0] and (with_ex[0][with_ex[0] >= 0] >= 260).all() and not {764, 700} & set(with_ex[0].tolist())
+        assert sorted(without[1][:3].tolist()) == [560, 580, 599] and (with_ex[1] == -1).all()
+
+
 def test_max_items_counts_exactly():
     lengths = [0, 1, 2, 3, 1, 2, 5, 1]
     rng = np.random.default_rng(9)
