@@ -40,7 +40,9 @@ class Stream:
         return r
 
 
-def build_batch(pair_ids, sim_pairs, cv_rowptr, cv_col, sim_rowptr, sim_col, n_products, n_pad, k, seed, step):
+def build_batch(pair_ids, sim_pairs, cv_rowptr, cv_col, sim_rowptr, sim_col, n_products, n_pad, k, seed, step, on_draw=None):
+    """on_draw (optional): called as on_draw(b, c, stream) for every candidate c of sample b BEFORE it is judged -- what
+    tests/batch_builder_cases.traced_oracle counts draws and rejection reasons with.  It changes no output."""
     B = len(pair_ids)
     a = sim_pairs[pair_ids, 0].astype(np.int32)
     p = sim_pairs[pair_ids, 1].astype(np.int32)
@@ -52,6 +54,8 @@ def build_batch(pair_ids, sim_pairs, cv_rowptr, cv_col, sim_rowptr, sim_col, n_p
         got = []
         while len(got) < k:
             c = s.below(n_products)
+            if on_draw is not None:
+                on_draw(b, c, s)
             if c != a[b] and c not in pos and c not in got:
                 got.append(c)
         neg[b] = got
