@@ -1651,6 +1651,49 @@ int pc_retrieve_list_grouped_bf16_biased_where(const float *proj, const int32_t 
                                                int slices, int32_t *out_idx, float *out_score, int32_t *bad_count,
                                                const pc_row_where *where, void *ws, size_t ws_bytes, void *stream);
 
+/* Ranks under a predicate (ABI 8, additive; csrc/where_rank.hip, csrc/where_rank_bf16.hip; ops.rank_grouped_where,
+ * PCompanionInference.rank_targets_where / evaluate_catalogue_where, SimilarProducts.rank_pairs_where / evaluate_pairs_where):
+ * the rank twin of the filtered lists above -- where a known product stands in the list a row is served under its predicate,
+ * over the whole type, from the list's own score bits.
+ *
+ * pc_rank_grouped_where (fp32 table) / pc_rank_grouped_bf16_where (table_bf16): pc_rank_grouped_bf16's argument list -- row_key,
+ * a bias that may be NULL (then s = d), the exclusion CSR, cand_type, dim, slices -- with `where` in front of ws.  For row r
+ * with type c = types[r], target y = targets[r] and predicate w_r, s the score pc_retrieve_list_grouped[_bf16][_biased]_where
+ * gives the pair, bit for bit:
+ *   rank_out[r] = #{ p of type c : p passes w_r, p not in the row's list : s_p > s_y or (s_p == s_y and p < y) }.
+ * The predicate is pc_row_where's as stated above, unchanged: inclusive fp32 ends, a NaN value or bound passes nothing, lo > hi
+ * passes nothing, infinite bounds pass every non-NaN value, -0.0 == 0.0, need / deny on 32 bits, every part optional.
+ * rank_out[r] = -1 wherever pc_rank_grouped_bf16 / pc_rank_grouped_biased give -1 -- types[r] < 0; a type or target out of range
+ * (counted in *bad_count); with lists, the target in the row's list or cand_type[y] != c -- and where the target itself fails
+ * its row's predicate.  row_key, ex_rowptr, ex_col and cand_type all four or none.  So rank_out[r] < n exactly when
+ * pc_retrieve_list_grouped[_bf16][_biased]_where with the same lists, bias and table holds y at position rank_out[r]; over rows
+ * that share one predicate it is pc_rank_grouped_biased / pc_rank_grouped_bf16 over a type CSR and cand_type rebuilt from the
+ * passing products; with every array of the filter NULL it is those entries' output bit for bit.
+ * pc_rank_grouped's plan and work items; the test sits inside the count: value[p] and flags[p] are gathered per chunk column a
+ * chunk ahead with the product id, the rows' lo / hi / need / deny are staged on chip once per work item, a candidate is counted
+ * where it beats (or ties and precedes) the target AND passes that row's predicate.  A row post-pass (one wave per row, in every
+ * call) writes the -1 of a failing target after all slices' counts have landed and, with lists, takes out the list entries that
+ * pass the predicate and were counted.  Integer counts, one integer atomic per (row, slice); bitwise deterministic, the same for
+ * every `slices`, placement of the rows and order of type_col inside a type; no float atomics, no host readback.
+ * Workspace: NAME_workspace_bytes(rows, n_types, slices) = pc_rank_grouped_workspace_bytes.
+ * PC_EINVAL: a null where; lo or hi without value, value without both; need or deny without flags; a null pointer (bias apart),
+ * rows, n_types or num_products <= 0, n_keys < 0, half-given exclusion arguments; PC_ESHAPE: dim not 128 / 256, slices outside
+ * [0, 64], table_bf16 not 16-byte aligned; PC_EWORKSPACE: ws_bytes too small -- each checked before anything is launched: the
+ * outputs are untouched. */
+size_t pc_rank_grouped_where_workspace_bytes(int rows, int n_types, int slices);
+int pc_rank_grouped_where(const float *proj, const int32_t *types, const int32_t *targets, const int32_t *row_key, int rows,
+                          const int32_t *type_rowptr, const int32_t *type_col, const float *table, const float *bias,
+                          int n_types, int num_products, const int32_t *ex_rowptr, const int32_t *ex_col, int n_keys,
+                          const int32_t *cand_type, int dim, int slices, int32_t *rank_out, int32_t *bad_count,
+                          const pc_row_where *where, void *ws, size_t ws_bytes, void *stream);
+size_t pc_rank_grouped_bf16_where_workspace_bytes(int rows, int n_types, int slices);
+int pc_rank_grouped_bf16_where(const float *proj, const int32_t *types, const int32_t *targets, const int32_t *row_key,
+                               int rows, const int32_t *type_rowptr, const int32_t *type_col, const uint16_t *table_bf16,
+                               const float *bias, int n_types, int num_products, const int32_t *ex_rowptr,
+                               const int32_t *ex_col, int n_keys, const int32_t *cand_type, int dim, int slices,
+                               int32_t *rank_out, int32_t *bad_count, const pc_row_where *where, void *ws, size_t ws_bytes,
+                               void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -286,6 +286,14 @@ SIGNATURES = {
     "pc_retrieve_list_grouped_bf16_biased_where_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "pc_retrieve_list_grouped_bf16_biased_where": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _vp,
                                                         _vp, _vp, _P(RowWhere), _vp, _sz, _vp]),
+    # ranks under a predicate (csrc/where_rank.hip, csrc/where_rank_bf16.hip: the rank twins of the filtered lists;
+    # pc_rank_grouped_bf16's list with a pc_row_where in front of the workspace; ABI 8, additive)
+    "pc_rank_grouped_where_workspace_bytes": (_sz, [_i, _i, _i]),
+    "pc_rank_grouped_where": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _vp, _i, _i, _vp, _vp,
+                                   _P(RowWhere), _vp, _sz, _vp]),
+    "pc_rank_grouped_bf16_where_workspace_bytes": (_sz, [_i, _i, _i]),
+    "pc_rank_grouped_bf16_where": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _vp, _i, _i, _vp, _vp,
+                                        _P(RowWhere), _vp, _sz, _vp]),
     # the cell index over the bf16 copy (csrc/cells_bf16.hip: cells.hip's centroid update reading bf16 rows; ABI 8, additive)
     "pc_cell_means_bf16": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
     "pc_hadamard_forward":(_i, [_vp, _vp, _i, _i, _vp, _vp]),

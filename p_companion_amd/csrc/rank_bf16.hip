@@ -16,7 +16,7 @@
 //            counts per lane; at the end a 16-lane sum, the four waves' sums through LDS, one integer atomic per (row, slice)
 //   exclude  rb_rank_exclude_kernel: rk_exclude_kernel's post-pass, one wave per row, through the same chain
 //
-// Determinism: d is rg_score_bf16_kernel's chain through rb_chain, the one text of this unit: k-block 0 .. D / 32 - 1, inside
+// Determinism: d is rg_score_bf16_kernel's chain through rb_chain (rank_chain_bf16.h), the one text of the bf16 ranks: k-block 0 .. D / 32 - 1, inside
 // a k-block the pieces p0, p1, p2, one v_mfma_f32_16x16x32_bf16 each into ONE accumulator per row group; an MFMA's output
 // (row, column) depends on its A row and B column alone.  So a (row, product) score has the bits pc_retrieve_topk_grouped_bf16,
 // pc_retrieve_list_grouped_bf16 and, with a bias, pc_retrieve_list_grouped_bf16_biased give it, s_y and g are the same bits,
@@ -26,41 +26,7 @@
 #include "grouped_select.h"        // the item decode
 #include "grouped_plan.h"          // rg_better
 
-// THE k-chain: NG row groups from g0 on of a query image with TM rows per operand column block against the 16 columns whose
-// rows the lanes hold in b.  Image piece p, operand (d8, row) at q[p][d8 * TM + row] = the dimensions 8 d8 .. + 7 of the row's
-// piece p (rg_score_bf16_kernel's layout: the 16 lanes of an LDS cycle read 16 consecutive operands, no padding).
-// For one accumulator the MFMAs run k-block ascending and inside a k-block p0, p1, p2; unit u = (k-block u / (3 NG), piece
-// (u / NG) % 3, group u % NG) is one MFMA on one ds_read_b128 of the image, read PD units ahead.  The fence after each unit
-// keeps the scheduler from hoisting all 3 NG D / 32 image reads (4 registers each), which would push the rank kernel's
-// registers into scratch (rk_chain's reason).
-template <int D, int TM, int NG>
-__device__ __forceinline__ void rb_chain(const bf16x8 (&q)[3][(D / 8) * TM], int g0, const bf16x8 (&b)[D / 32], f32x4 (&acc)[NG],
-                                         int c, int h) {
-    constexpr int U = (D / 32) * 3 * NG, PD = 4;
-    auto load_a = [&](int u) { return q[(u / NG) % 3][(4 * (u / (3 * NG)) + h) * TM + (g0 + u % NG) * 16 + c]; };
-    bf16x8 ar[PD + 1];
-#pragma unroll
-    for (int u = 0; u < PD && u < U; u++) ar[u] = load_a(u);
-#pragma unroll
-    for (int u = 0; u < U; u++) {
-        if (u + PD < U) ar[(u + PD) % (PD + 1)] = load_a(u + PD);
-        acc[u % NG] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ar[u % (PD + 1)], b[u / (3 * NG)], acc[u % NG], 0, 0, 0);
-        __builtin_amdgcn_sched_barrier(0);
-    }
-}
-
-// the 16 bytes h + 4 k of product pid's row for every k-block k (pid < 0: zeros, nothing is read)
-template <int D>
-__device__ __forceinline__ void rb_load_b(bf16x8 (&b)[D / 32], const uint16_t* __restrict__ table, int pid, int h) {
-    if (pid >= 0) {
-        const bf16x8* f = reinterpret_cast<const bf16x8*>(table + (size_t)pid * D) + h;
-#pragma unroll
-        for (int k = 0; k < D / 32; k++) b[k] = f[4 * k];
-    } else {
-#pragma unroll
-        for (int k = 0; k < D / 32; k++) b[k] = bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
-    }
-}
+#include "rank_chain_bf16.h"      // rb_chain, rb_load_b: THE k-chain (where_rank_bf16.hip scores through it too)
 
 // One work item's candidate stream for a tile of NG 16-row groups (NG a template argument: the loop body is straight-line
 // code).  Lane l of wave wv: column c = l & 15 (candidate wv * 16 + c of the chunk), k-lane h = l >> 4; accumulator register k

@@ -638,14 +638,34 @@ class PCompanionInference(_CandidateFilters):
         Returns (slot int32 [B], rank int32 [B]) on the device; nothing is read back."""
         self._rank_guard("rank_targets")
         rank_grouped, table = self._rank_entry()
+        rows = self._target_rows("rank_targets", query_idx, target_idx, take, table)
+        if rows is None:
+            e = torch.empty(0, dtype=torch.int32, device=self.device)
+            return e, e.clone()
+        query_idx, target_idx, slot, proj, row_type = rows
+        exclude = self._exclude_rows(query_idx)
+        if exclude is not None:
+            # a target in the query's list, or not eligible: -1 from the entry itself
+            rank, _ = rank_grouped(proj, row_type, target_idx, self.type_rowptr, self.type_col, table, exclude=exclude,
+                                   cand_type=self.cand_type)
+            return slot, rank
+        rank, _ = rank_grouped(proj, row_type, target_idx, self.type_rowptr, self.type_col, table)
+        if self.eligible is not None:
+            kept = self.eligible[target_idx.long().clamp(0, table.shape[0] - 1)]
+            rank = torch.where(kept, rank, torch.full_like(rank, -1))
+        return slot, rank
+
+    def _target_rows(self, what, query_idx, target_idx, take, table):
+        """rank_targets' rows: the model in eval mode on the queries and the slot whose predicted type is the target's ->
+        (query_idx, target_idx -- int32 on the device --, slot [B] int32, proj [B, D] of that slot, row_type [B] int32, -1
+        where no slot matches or `take` is False); None for no pair."""
         query_idx = query_idx.to(self.device).to(torch.int32).contiguous()
         target_idx = target_idx.to(self.device).to(torch.int32).contiguous()
         if query_idx.dim() != 1 or query_idx.shape != target_idx.shape:
-            raise ValueError("rank_targets: query_idx and target_idx must be 1-D and of equal length")
+            raise ValueError(f"{what}: query_idx and target_idx must be 1-D and of equal length")
         b = query_idx.shape[0]
         if b == 0:
-            e = torch.empty(0, dtype=torch.int32, device=self.device)
-            return e, e.clone()
+            return None
         out = self.model({"query_idx": query_idx, "query_types": self.type_idx[query_idx.long()]})
         types = out["complementary_types"]                                        # [B, K], distinct in a row
         inside = (target_idx >= 0) & (target_idx < table.shape[0])
@@ -658,17 +678,80 @@ class PCompanionInference(_CandidateFilters):
         slot = torch.where(found, k, torch.full_like(k, -1)).to(torch.int32)
         proj = out["projected_embeddings"][torch.arange(b, device=self.device), k].contiguous()      # [B, D]
         row_type = torch.where(found, target_type, torch.full_like(target_type, -1)).to(torch.int32)
+        return query_idx, target_idx, slot, proj, row_type
+
+    @torch.no_grad()
+    def rank_targets_where(self, query_idx: torch.Tensor, target_idx: torch.Tensor, lo: torch.Tensor = None,
+                           hi: torch.Tensor = None, need: torch.Tensor = None, deny: torch.Tensor = None,
+                           take: torch.Tensor = None):
+        """rank_targets under a per-QUERY predicate on the installed attributes (set_attributes; lo / hi / need / deny [B] as
+        in recommend_where_batch): rank[b] = the number of products of the matched slot's type that PASS query b's predicate
+        and that the slot's projected embedding scores above the target -- the target's position in recommend_where_batch's
+        list of that slot, were the list the whole type: rank < n exactly when recommend_where_batch(query, n, ...) holds the
+        target at that position.  The installed exclusions and eligibility apply as in rank_targets; a target they keep out,
+        or that fails its own query's predicate, keeps its slot and has rank -1.  One call of ops.rank_grouped_where, over the
+        fp32 features (CompactInference: the bf16 copy).  Returns (slot int32 [B], rank int32 [B]) on the device.  ValueError
+        before the model runs where no attributes are installed, none of the four is given, or an array has no attribute."""
+        self._rank_guard("rank_targets_where")
+        where = self._row_predicate("rank_targets_where", int(query_idx.shape[0]) if query_idx.dim() else -1, lo, hi, need, deny)
+        table = self._rank_entry()[1]
+        rows = self._target_rows("rank_targets_where", query_idx, target_idx, take, table)
+        if rows is None:
+            e = torch.empty(0, dtype=torch.int32, device=self.device)
+            return e, e.clone()
+        query_idx, target_idx, slot, proj, row_type = rows
         exclude = self._exclude_rows(query_idx)
         if exclude is not None:
-            # a target in the query's list, or not eligible: -1 from the entry itself
-            rank, _ = rank_grouped(proj, row_type, target_idx, self.type_rowptr, self.type_col, table, exclude=exclude,
-                                   cand_type=self.cand_type)
+            rank, _ = ops.rank_grouped_where(proj, row_type, target_idx, self.type_rowptr, self.type_col, table, where,
+                                             exclude=exclude, cand_type=self.cand_type)
             return slot, rank
-        rank, _ = rank_grouped(proj, row_type, target_idx, self.type_rowptr, self.type_col, table)
+        rank, _ = ops.rank_grouped_where(proj, row_type, target_idx, self.type_rowptr, self.type_col, table, where)
         if self.eligible is not None:
             kept = self.eligible[target_idx.long().clamp(0, table.shape[0] - 1)]
             rank = torch.where(kept, rank, torch.full_like(rank, -1))
         return slot, rank
+
+    def _fails_predicate(self, target_idx, parts):
+        """[B] bool: target_idx[b] fails the predicate `parts` (lo / hi / need / deny [B], any of them) of its own pair --
+        ops.RowWhere's test on value[y] / flags[y] as vector operations: two inclusive fp32 compares (a NaN passes nothing),
+        two masks."""
+        value, flags = self.attributes
+        y = target_idx.long().clamp(0, int(self.type_idx.shape[0]) - 1)
+        fails = torch.zeros_like(y, dtype=torch.bool)
+        if parts.get("lo") is not None:
+            fails |= ~(parts["lo"].to(self.device) <= value[y])
+        if parts.get("hi") is not None:
+            fails |= ~(value[y] <= parts["hi"].to(self.device))
+        if parts.get("need") is not None:
+            need = parts["need"].to(self.device)
+            fails |= (flags[y] & need) != need
+        if parts.get("deny") is not None:
+            fails |= (flags[y] & parts["deny"].to(self.device)) != 0
+        return fails
+
+    def _predicate_parts(self, what, predicate, query_idx):
+        """predicate(query_idx) as a dict with any of lo, hi, need, deny (ValueError for anything else)"""
+        parts = predicate(query_idx)
+        if not isinstance(parts, dict) or not set(parts) <= {"lo", "hi", "need", "deny"}:
+            raise ValueError(f"{what}: predicate(query_idx) must return a dict with any of lo, hi, need, deny, got "
+                             f"{sorted(parts) if isinstance(parts, dict) else type(parts).__name__}")
+        return parts
+
+    def evaluate_catalogue_where(self, dataset: ComplementaryIndexDataset, predicate, ks=(1, 3, 10, 100),
+                                 chunk: int = 65536) -> Dict[str, Any]:
+        """evaluate_catalogue of what recommend_where_batch serves: predicate(query_idx) -- query_idx an int32 device vector, a
+        chunk's queries -- returns a dict with any of lo, hi, need, deny ([chunk] tensors), for instance
+        lambda q: dict(zip(("lo", "hi"), inf.band_around(q))); the chunks go through rank_targets_where.  Returns
+        evaluate_catalogue's dict: hit@k for k <= 256 is the share of the +1 pairs whose target is among
+        recommend_where_batch(query, k, **predicate(query))'s lists.  "filtered_targets" is always there and also counts the
+        pairs whose target fails its own query's predicate (value[y] / flags[y] tested in torch): such a pair is a miss."""
+        what = "evaluate_catalogue_where"
+        self._rank_guard(what)
+        if self.attributes is None:
+            raise ValueError(f"{what}: no per-product attributes are installed (set_attributes)")
+        if not callable(predicate):
+            raise ValueError(f"{what}: predicate must be a callable of the chunk's query ids, got {type(predicate).__name__}")
+        return self._evaluate(what, dataset, ks, chunk, predicate)
 
     def evaluate_catalogue(self, dataset: ComplementaryIndexDataset, ks=(1, 3, 10, 100), chunk: int = 65536) -> Dict[str, Any]:
         """Are the held-out complements among what is served?  `dataset`: a ComplementaryIndexDataset over this object's
@@ -682,31 +765,39 @@ class PCompanionInference(_CandidateFilters):
         of the type, the query included, as in serving.  With set_exclusions / set_eligible the candidates are what is then
         served; a pair whose target the filters keep out (it is in its query's list, or not eligible) is a miss -- it keeps its
         slot, its rank is -1 -- and the dict gains "filtered_targets", the number of such pairs."""
+        return self._evaluate("evaluate_catalogue", dataset, ks, chunk)
+
+    def _evaluate(self, what, dataset, ks, chunk, predicate=None):
+        """evaluate_catalogue; with a predicate evaluate_catalogue_where (the chunks through rank_targets_where)"""
+        self._rank_guard(what)
         bpg = self.bpg
-        self._rank_guard("evaluate_catalogue")
         if isinstance(bpg, DeviceBPG) and bpg.world != 1:
-            raise ValueError(f"evaluate_catalogue: this DeviceBPG holds a cyclic 1/{bpg.world} shard of the features")
+            raise ValueError(f"{what}: this DeviceBPG holds a cyclic 1/{bpg.world} shard of the features")
         if not isinstance(dataset, ComplementaryIndexDataset) or dataset.bpg is not bpg:
-            raise ValueError("evaluate_catalogue: the dataset was built over another graph than this object serves")
+            raise ValueError(f"{what}: the dataset was built over another graph than this object serves")
         chunk = int(chunk)
         if chunk < 1:
-            raise ValueError("evaluate_catalogue: chunk must be positive")
+            raise ValueError(f"{what}: chunk must be positive")
         pairs = dataset.pairs
         if not torch.is_tensor(pairs):
             pairs = np.asarray(pairs)
             pairs = torch.from_numpy(np.ascontiguousarray(pairs[pairs[:, 2] == 1], dtype=np.int32))
         if pairs.shape[0] == 0:
-            raise ValueError("evaluate_catalogue: the dataset holds no +1 pair")
+            raise ValueError(f"{what}: the dataset holds no +1 pair")
         pairs = pairs.to(self.device)
         n = pairs.shape[0]
         take = pairs[:, 2] == 1
         slot = torch.empty(n, dtype=torch.int32, device=self.device)
         rank = torch.empty(n, dtype=torch.int32, device=self.device)
-        filtering = self.exclusions is not None or self.eligible is not None
+        filtering = self.exclusions is not None or self.eligible is not None or predicate is not None
         filtered = torch.zeros((), dtype=torch.int64, device=self.device)
         for lo in range(0, n, chunk):
             hi = min(lo + chunk, n)
-            slot[lo:hi], rank[lo:hi] = self.rank_targets(pairs[lo:hi, 0], pairs[lo:hi, 1], take[lo:hi])
+            if predicate is None:
+                slot[lo:hi], rank[lo:hi] = self.rank_targets(pairs[lo:hi, 0], pairs[lo:hi, 1], take[lo:hi])
+            else:
+                parts = self._predicate_parts(what, predicate, pairs[lo:hi, 0].contiguous())
+                slot[lo:hi], rank[lo:hi] = self.rank_targets_where(pairs[lo:hi, 0], pairs[lo:hi, 1], take=take[lo:hi], **parts)
             if filtering:
                 q, y = pairs[lo:hi, 0], pairs[lo:hi, 1]
                 out = torch.zeros_like(take[lo:hi])
@@ -714,11 +805,13 @@ class PCompanionInference(_CandidateFilters):
                     out |= self._excluded(q, y)
                 if self.eligible is not None:
                     out |= ~self.eligible[y.long()]
+                if predicate is not None:
+                    out |= self._fails_predicate(y, parts)
                 filtered += (out & take[lo:hi]).sum()
         try:
             res = Metrics.catalogue_metrics(slot, rank, ks, take)
         except ValueError as e:
-            raise ValueError("evaluate_catalogue: the dataset holds no +1 pair") from e
+            raise ValueError(f"{what}: the dataset holds no +1 pair") from e
         if filtering:
             res["filtered_targets"] = int(filtered)
         return res
@@ -986,10 +1079,19 @@ class SimilarProducts(_CandidateFilters):
         similar_batch's list, were the list the whole scope -- rank < n exactly when similar_batch(anchor, n) holds the target
         at that position -- and -1 as ops.rank_grouped defines: no candidate of the scope, in the anchor's exclusion list (the
         anchor itself by default), outside the catalogue.  (slot, rank) int32 [B] on the device; nothing is read back."""
+        return self._rank_pairs("rank_pairs", anchor_idx, target_idx)
+
+    def _rank_where(self, q, row_type, target_idx, where, **lists):
+        return ops.rank_grouped_where(q, row_type, target_idx, self.type_rowptr, self.type_col, self.table, where, bias=self.bias,
+                                      **lists)
+
+    def _rank_pairs(self, what, anchor_idx, target_idx, where=None):
+        """rank_pairs; with an ops.RowWhere rank_pairs_where (ops.rank_grouped_where in _rank's place)"""
+        rank_rows = self._rank if where is None else (lambda *rows, **lists: self._rank_where(*rows, where, **lists))
         anchor_idx = anchor_idx.to(self.device).to(torch.int32).contiguous()
         target_idx = target_idx.to(self.device).to(torch.int32).contiguous()
         if anchor_idx.dim() != 1 or anchor_idx.shape != target_idx.shape:
-            raise ValueError("rank_pairs: anchor_idx and target_idx must be 1-D and of equal length")
+            raise ValueError(f"{what}: anchor_idx and target_idx must be 1-D and of equal length")
         if anchor_idx.shape[0] == 0:
             e = torch.empty(0, dtype=torch.int32, device=self.device)
             return e, e.clone()
@@ -1001,32 +1103,67 @@ class SimilarProducts(_CandidateFilters):
         q = self._rows(anchor_idx.long())
         exclude = self._exclude_rows(anchor_idx)
         if exclude is not None:
-            rank, _ = self._rank(q, row_type.contiguous(), target_idx, exclude=exclude, cand_type=self.cand_type)
+            rank, _ = rank_rows(q, row_type.contiguous(), target_idx, exclude=exclude, cand_type=self.cand_type)
             return slot, rank
         # no lists: a target that is no candidate costs no search
         row_type = torch.where(candidate, row_type, torch.full_like(row_type, -1)).contiguous()
-        rank, _ = self._rank(q, row_type, target_idx)
+        rank, _ = rank_rows(q, row_type, target_idx)
         return slot, rank
+
+    @torch.no_grad()
+    def rank_pairs_where(self, anchor_idx: torch.Tensor, target_idx: torch.Tensor, lo: torch.Tensor = None,
+                         hi: torch.Tensor = None, need: torch.Tensor = None, deny: torch.Tensor = None):
+        """rank_pairs under a per-anchor predicate on the installed attributes (set_attributes; lo / hi / need / deny [B] as in
+        similar_where_batch): rank[b] = the number of candidates of the anchor's scope that PASS anchor b's predicate and stand
+        in front of the target -- rank < n exactly when similar_where_batch(anchor, n, ...) holds the target at that position
+        -- under this object's bias, scope, exclusions and eligibility; -1 as in rank_pairs and where the target fails its own
+        anchor's predicate (its slot stays).  One call of ops.rank_grouped_where, the entry by the table's dtype.  (slot, rank)
+        int32 [B] on the device.  ValueError before anything is computed where no attributes are installed or none of the
+        four is given."""
+        where = self._row_predicate("rank_pairs_where", int(anchor_idx.shape[0]) if anchor_idx.dim() else -1, lo, hi, need, deny)
+        return self._rank_pairs("rank_pairs_where", anchor_idx, target_idx, where)
+
+    def evaluate_pairs_where(self, pairs, predicate, ks=(1, 3, 10, 100), chunk: int = 65536) -> Dict[str, Any]:
+        """evaluate_pairs of what similar_where_batch serves: predicate(anchor_idx) -- an int32 device vector, a chunk's
+        anchors -- returns a dict with any of lo, hi, need, deny ([chunk] tensors); the chunks go through rank_pairs_where.
+        Returns evaluate_pairs' dict; a pair whose target fails its own anchor's predicate is a miss."""
+        what = "evaluate_pairs_where"
+        if self.attributes is None:
+            raise ValueError(f"{what}: no per-product attributes are installed (set_attributes)")
+        if not callable(predicate):
+            raise ValueError(f"{what}: predicate must be a callable of the chunk's anchor ids, got {type(predicate).__name__}")
+        return self._evaluate_pairs(what, pairs, ks, chunk, predicate)
 
     def evaluate_pairs(self, pairs, ks=(1, 3, 10, 100), chunk: int = 65536) -> Dict[str, Any]:
         """Are held-out similar pairs among the neighbours that are served?  pairs [M, 2] (anchor, target) int -- whatever the
         caller held out, e.g. the co-view pairs of a later window of edges.  Chunks of `chunk` pairs go through rank_pairs
         into two device vectors; Metrics.catalogue_metrics folds them and reads back once: {"pairs", "type_hit" (the share
         whose target is a candidate of the anchor's scope), "hit@k" for k in ks, "mrr", "median_rank"}."""
+        return self._evaluate_pairs("evaluate_pairs", pairs, ks, chunk)
+
+    def _evaluate_pairs(self, what, pairs, ks, chunk, predicate=None):
+        """evaluate_pairs; with a predicate evaluate_pairs_where (the chunks through rank_pairs_where)"""
         chunk = int(chunk)
         if chunk < 1:
-            raise ValueError("evaluate_pairs: chunk must be positive")
+            raise ValueError(f"{what}: chunk must be positive")
         if not torch.is_tensor(pairs):
             pairs = torch.from_numpy(np.ascontiguousarray(np.asarray(pairs), dtype=np.int32))
         if pairs.dim() != 2 or pairs.shape[1] != 2 or pairs.shape[0] == 0:
-            raise ValueError(f"evaluate_pairs: expected a non-empty [M, 2] array of (anchor, target), got {tuple(pairs.shape)}")
+            raise ValueError(f"{what}: expected a non-empty [M, 2] array of (anchor, target), got {tuple(pairs.shape)}")
         pairs = pairs.to(self.device).to(torch.int32)
         m = pairs.shape[0]
         slot = torch.empty(m, dtype=torch.int32, device=self.device)
         rank = torch.empty(m, dtype=torch.int32, device=self.device)
         for lo in range(0, m, chunk):
             hi = min(lo + chunk, m)
-            slot[lo:hi], rank[lo:hi] = self.rank_pairs(pairs[lo:hi, 0], pairs[lo:hi, 1])
+            if predicate is None:
+                slot[lo:hi], rank[lo:hi] = self.rank_pairs(pairs[lo:hi, 0], pairs[lo:hi, 1])
+            else:
+                parts = predicate(pairs[lo:hi, 0].contiguous())
+                if not isinstance(parts, dict) or not set(parts) <= {"lo", "hi", "need", "deny"}:
+                    raise ValueError(f"{what}: predicate(anchor_idx) must return a dict with any of lo, hi, need, deny, got "
+                                     f"{sorted(parts) if isinstance(parts, dict) else type(parts).__name__}")
+                slot[lo:hi], rank[lo:hi] = self.rank_pairs_where(pairs[lo:hi, 0], pairs[lo:hi, 1], **parts)
         return Metrics.catalogue_metrics(slot, rank, ks)
 
 

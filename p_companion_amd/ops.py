@@ -2409,6 +2409,64 @@ def rank_grouped_bf16(proj, types, targets, type_rowptr, type_col, table, slices
     return rank, bad
 
 
+def rank_grouped_where(proj, types, targets, type_rowptr, type_col, table, where, slices=0, bad=None, exclude=None,
+                       cand_type=None, bias=None):
+    """pc_rank_grouped_where / pc_rank_grouped_bf16_where: the rank twin of retrieve_list_grouped_where -- for row r the number
+    of products of type types[r] that PASS the row's predicate `where` (a RowWhere: a band on a per-product value, masks on
+    per-product flags) and that retrieve_list_grouped_where orders in front of targets[r], from that call's own score bits:
+    rank < n exactly when retrieve_list_grouped_where(..., n, where, ...) with the same exclude / bias / table holds the target
+    at position rank.  Returns (rank [R] int32, bad [1] int32): rank -1 wherever rank_grouped / rank_grouped_bf16 give -1
+    (types[r] < 0; a type or target out of range, which `bad` counts; with exclude, a target in the row's list or no candidate
+    of the row's type) and where the target itself fails its row's predicate.  The entry goes by the table's dtype:
+      table [P, D] fp32      pc_rank_grouped_where       (rank_grouped's checks; bias None or [P] fp32)
+      table [P, D] bfloat16  pc_rank_grouped_bf16_where  (rank_grouped_bf16's checks; bias None or [P] fp32)
+    exclude = (row_key, ex_rowptr, ex_col) with cand_type [P] int32, `bad` and `slices` as in rank_grouped.  Over rows that
+    share one predicate it is rank_grouped / rank_grouped_bf16 over a type CSR (and cand_type) rebuilt from the passing
+    products; a RowWhere() with every part absent gives those functions' output bit for bit.  Bitwise deterministic, the same
+    for every `slices`.  Every host-side check (ValueError) happens before any launch; nothing is read back to the host."""
+    what = "rank_grouped_where"
+    if not isinstance(where, RowWhere):
+        raise ValueError(f"{what}: where must be an ops.RowWhere, got {type(where).__name__}")
+    bf16 = isinstance(table, torch.Tensor) and table.dtype == torch.bfloat16
+    if bf16:
+        _check_bf16_table(what, table, "rank_grouped")
+        if bias is not None:
+            _check_bias_bf16(what, bias, table)
+    else:
+        if not isinstance(table, torch.Tensor) or table.dtype != torch.float32 or table.dim() != 2:
+            raise ValueError(f"{what}: table must be a [P, D] float32 or bfloat16 device tensor, got "
+                             f"{(table.dtype, tuple(table.shape)) if isinstance(table, torch.Tensor) else type(table).__name__}")
+        if bias is not None:
+            _check_bias(what, bias, table)
+    if exclude is not None:
+        exclude = _check_exclude(what, exclude, types.shape[0] if isinstance(types, torch.Tensor) else -1)
+        if cand_type is None:
+            raise ValueError(f"{what}: exclude needs cand_type (the type under which each product is a candidate)")
+        if not isinstance(cand_type, torch.Tensor) or cand_type.dtype != torch.int32 or cand_type.dim() != 1 \
+                or cand_type.shape[0] != table.shape[0]:
+            raise ValueError(f"{what}: cand_type must be an int32 tensor of one entry per product")
+    elif cand_type is not None:
+        raise ValueError(f"{what}: cand_type is read with an exclude triple only")
+    proj, r, t, d, slices = _grouped_rows(proj, types, type_rowptr, type_col, table, torch.bfloat16 if bf16 else torch.float32,
+                                          slices)
+    _req(targets, torch.int32, "targets", (r,))
+    p, device = table.shape[0], proj.device
+    st = where._struct(what, p, r)                        # (the lengths against P and R, before anything is allocated)
+    if exclude is not None:
+        _req(cand_type, torch.int32, "cand_type", (p,))
+    if bias is not None:
+        _req(bias, torch.float32, "bias", (p,))
+    rank = torch.empty(r, dtype=torch.int32, device=device)
+    row_key, ex_rowptr, ex_col, n_keys, bad = _filter_args(exclude, bad, device, counted=True)
+    # (pc_rank_grouped_bf16's list; without a triple row_key, ex_rowptr, ex_col and cand_type are None, without a bias it too:
+    # null pointers, n_keys 0)
+    args = (proj.data_ptr(), types.data_ptr(), targets.data_ptr(), _p(row_key), r, type_rowptr.data_ptr(), type_col.data_ptr(),
+            table.data_ptr(), _p(bias), t, p, _p(ex_rowptr), _p(ex_col), n_keys, _p(cand_type), d, slices, rank.data_ptr(),
+            bad.data_ptr(), ctypes.byref(st))
+    _grouped_call("pc_rank_grouped_bf16_where" if bf16 else "pc_rank_grouped_where", "rank_grouped", device, (r, t, slices), args)
+    return rank, bad
+
+
 def type_csr(type_idx, n_types):
     """The type-grouped product CSR of PCompanionInference (bpg.get_products_by_type, bpg.py:40-43), built on the device from
     an int32 CUDA type_idx [P]: rowptr [T+1] int32, col [P] int32 = the products of each type in ascending node order (the
