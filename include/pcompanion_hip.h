@@ -1694,6 +1694,40 @@ int pc_rank_grouped_bf16_where(const float *proj, const int32_t *types, const in
                                int32_t *rank_out, int32_t *bad_count, const pc_row_where *where, void *ws, size_t ws_bytes,
                                void *stream);
 
+/* Score moments (ABI 8, additive; csrc/score_moments.hip, csrc/score_moments_bf16.hip; ops.score_moments_grouped,
+ * PCompanionInference.score_moments and the normalise="zscore" keyword of the serving methods): the mean and the standard
+ * deviation of a row's scores over ALL candidates of its type -- what a served score is standardised against before the lists of
+ * different types are merged into a page or fused into a basket's list, whose raw dot products differ in scale from type to type.
+ *
+ * pc_score_moments_grouped (fp32 table) / pc_score_moments_grouped_bf16 (table_bf16): pc_rank_grouped's rows, type CSR, dim and
+ * slices, without targets.  For row r with type c = types[r], n = type_rowptr[c+1] - type_rowptr[c] candidates, s the score
+ * pc_retrieve_list_grouped[_bf16] gives a (row, product) pair, bit for bit, and the pivot g = s of the type's FIRST candidate
+ * type_col[type_rowptr[c]]:
+ *   count[r] = n,   pivot[r] = g,   s1[r] = sum_p fl(s_p - g),   s2[r] = sum_p fl(s_p - g)^2   over the products p of type c,
+ *   mean[r] = g + s1 / n,   std[r] = sqrt(max(s2 / n - (s1 / n)^2, 0))   (the population form; fp32, one rounding per operation
+ *   in this order, nothing fused).
+ * The sums are centred on a score of the type itself, so s2 carries no term of the size of mean^2 and keeps its digits where
+ * |mean| >> std.  types[r] < 0 ("no type matched"): the row is skipped, count 0 and zeros.  A type >= n_types never reaches
+ * memory: count 0 and zeros, and *bad_count (a device counter the caller owns) is incremented.  An empty type: count 0 and zeros.
+ * pc_rank_grouped's plan and work items and its kernel's shape -- the pivot formed as the rank forms its target's score, the
+ * candidates through the same chain -- with a subtraction, an addition and a fused multiply-add per (row, candidate) where the
+ * rank compares and counts; the (row, slice) partial sums go to the workspace as plain stores and a finishing kernel adds them
+ * in slice order.  No float atomics, no host readback.  Bitwise reproducible from run to run for a given `slices`; across
+ * different `slices`, or orders of type_col inside a type (its first entry apart: the pivot), the fp32 sums may differ in their
+ * last bits -- unlike the rank's integer count -- and are identical where every sum is exact.
+ * Workspace: pc_score_moments_grouped_workspace_bytes(rows, n_types, slices), for both entries (0 for arguments out of range).
+ * PC_EINVAL: null pointer, rows or n_types <= 0; PC_ESHAPE: dim not 128 / 256, slices outside [0, 64], table_bf16 not 16-byte
+ * aligned; PC_EWORKSPACE: ws_bytes too small -- each checked before anything is launched: the outputs are untouched. */
+size_t pc_score_moments_grouped_workspace_bytes(int rows, int n_types, int slices);
+int pc_score_moments_grouped(const float *proj, const int32_t *types, int rows, const int32_t *type_rowptr,
+                             const int32_t *type_col, const float *table, int n_types, int dim, int slices, int32_t *count,
+                             float *pivot, float *s1, float *s2, float *mean, float *std_out, int32_t *bad_count, void *ws,
+                             size_t ws_bytes, void *stream);
+int pc_score_moments_grouped_bf16(const float *proj, const int32_t *types, int rows, const int32_t *type_rowptr,
+                                  const int32_t *type_col, const uint16_t *table_bf16, int n_types, int dim, int slices,
+                                  int32_t *count, float *pivot, float *s1, float *s2, float *mean, float *std_out,
+                                  int32_t *bad_count, void *ws, size_t ws_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

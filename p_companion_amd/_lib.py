@@ -294,6 +294,12 @@ SIGNATURES = {
     "pc_rank_grouped_bf16_where_workspace_bytes": (_sz, [_i, _i, _i]),
     "pc_rank_grouped_bf16_where": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _vp, _i, _i, _vp, _vp,
                                         _P(RowWhere), _vp, _sz, _vp]),
+    # score moments (csrc/score_moments.hip, csrc/score_moments_bf16.hip: the mean and std of a row's scores over its whole type,
+    # for standardised pages; ABI 8, additive)
+    "pc_score_moments_grouped_workspace_bytes": (_sz, [_i, _i, _i]),
+    "pc_score_moments_grouped": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "pc_score_moments_grouped_bf16": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz,
+                                           _vp]),
     # the cell index over the bf16 copy (csrc/cells_bf16.hip: cells.hip's centroid update reading bf16 rows; ABI 8, additive)
     "pc_cell_means_bf16": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
     "pc_hadamard_forward":(_i, [_vp, _vp, _i, _i, _vp, _vp]),

@@ -32,6 +32,9 @@ items, no padding rows) with a weight per item -- recency, quantity, "purchased,
 set_attributes / recommend_where_batch / similar_where_batch narrow a list by a per-QUERY predicate on per-product attributes -- a
 band on a value (price), masks on 32 flag bits (regions, seller tiers) -- tested inside the long-list kernel
 (pc_retrieve_list_grouped_where and its bf16 / biased twins): what set_eligible would serve per predicate, in one call.
+score_moments / normalise="zscore" make the scores of different types comparable before a page or a basket merges them: the
+mean and spread of every (query, type) slot's score over its whole type (pc_score_moments_grouped and its bf16 twin: the rank's
+pass with two sums in the count's place), and z = (s - mean) / std on what recommend_batch serves.
 
 SimilarProducts is the substitute side: the nearest products of a query under Euclidean distance over any [P, D] fp32 table
 (Product2Vec's export), the grouped retrieval and rank with the per-product term -|e_p|^2 / 2 on the score
@@ -43,6 +46,7 @@ IndexedSimilarProducts serves its whole-catalogue scope through a k-means cell i
 over the products of a query's nearest cells, the probe lists of a query merged by pc_merge_lists.
 IndexedCompactSimilarProducts is that index over the bf16 copy alone (ops.build_cell_index_bf16, pc_cell_means_bf16): the scan is
 CompactSimilarProducts' entry, the index is built without the fp32 table, and a query probes up to 64 cells."""
+import functools
 import os
 from typing import Any, Dict, List
 
@@ -71,6 +75,33 @@ def _check_group(what, group, cap):
     if group is not None and (not torch.is_tensor(group) or group.dtype != torch.int32 or group.dim() != 1):
         _refuse_tensor(what, "group", "None or a [P] int32 device tensor (the product's group, negative = ungrouped)", group)
     return cap
+
+
+def _check_normalise(what, normalise):
+    """normalise=None (the raw dot products) or "zscore"; anything else: ValueError, before the model runs."""
+    if normalise is not None and normalise != "zscore":
+        raise ValueError(f"{what}: normalise must be None or 'zscore', got {normalise!r}")
+
+
+def _takes_normalise(method):
+    """The keyword normalise=None | "zscore" of the five serving methods that end in recommend_batch's pool, in one place: the
+    value is checked before anything of the method runs, None calls the method as it is (today's path, nothing set, nothing
+    read), and "zscore" holds self._normalise for the length of the call, which recommend_batch -- the one place where served
+    scores are made -- reads.  The keyword belongs to this wrapper, not to the method: inspect.signature follows
+    functools.wraps to the method's own parameters, which the host tests of those methods pin; help() shows it in the
+    docstrings.  The mode lives on the object: two threads that share one serving object must not mix normalised and raw
+    calls."""
+    @functools.wraps(method)
+    def call(self, *args, normalise=None, **kwargs):
+        _check_normalise(method.__name__, normalise)
+        if normalise is None:
+            return method(self, *args, **kwargs)
+        before, self._normalise = self._normalise, normalise
+        try:
+            return method(self, *args, **kwargs)
+        finally:
+            self._normalise = before
+    return call
 
 
 class _CandidateFilters:
@@ -339,24 +370,55 @@ class PCompanionInference(_CandidateFilters):
             raise ValueError(f"recommend_batch: at most {ops.RETRIEVE_LIST_MAX_N} recommendations per (query, type), got {n}")
         return n
 
-    @torch.no_grad()
-    def recommend_batch(self, query_idx: torch.Tensor, num_recommendations: int = 10):
-        """All queries at once.  Returns complementary_types [B,K] int64, product indices [B,K,n] int32
-        (-1 past the end of a short type) and scores [B,K,n].  Up to 16 recommendations: the entries with a sorted list per
-        thread; from 17 to ops.RETRIEVE_LIST_MAX_N (256): pc_retrieve_list_grouped, whatever the graph's kind -- an uploaded
-        IntBPG's arrays are on the device, and the per-row kernel stops at 16.  A bf16 catalogue serves up to 16
-        (pc_retrieve_topk_grouped_bf16); given as an ops.CompactCatalogue also 17 to 256 (pc_retrieve_list_grouped_bf16)."""
-        n = self._list_length(num_recommendations)
-        if self.catalogue is not None and n > 16 and self.compact is None:
-            raise ValueError(f"recommend_batch: a bf16 catalogue serves at most 16 recommendations per (query, type), got {n}; "
-                             "longer lists need the fp32 catalogue (catalogue=None)")
+    _normalise = None                          # "zscore" while a call with normalise="zscore" runs (_takes_normalise)
+
+    def _slot_rows(self, query_idx):
+        """The model in eval mode on the queries -> (query_idx int32 on the device, complementary types [B, K] int64, the B K
+        slots' projected embeddings [B K, D] and their types [B K] int32)."""
         query_idx = query_idx.to(self.device).to(torch.int32).contiguous()
         batch = {"query_idx": query_idx, "query_types": self.type_idx[query_idx.long()]}
         out = self.model(batch)
         types = out["complementary_types"]
         b, k = types.shape
         proj = out["projected_embeddings"].contiguous().reshape(b * k, -1)
-        row_types = types.to(torch.int32).reshape(-1).contiguous()
+        return query_idx, types, proj, types.to(torch.int32).reshape(-1).contiguous()
+
+    def _moments(self, proj, row_types):
+        """ops.score_moments_grouped of the slots over the installed type CSR and the table this object serves from"""
+        table = self.catalogue if self.catalogue is not None else self.features
+        return ops.score_moments_grouped(proj, row_types, self.type_rowptr, self.type_col, table)
+
+    @torch.no_grad()
+    def score_moments(self, query_idx: torch.Tensor):
+        """The distribution behind recommend_batch's lists: (types [B, K] int64, count [B, K] int32, mean [B, K], std [B, K]
+        fp32) -- for every slot the number of candidates of its predicted type and the mean and (population) standard deviation
+        of the slot's score over ALL of them, one call of ops.score_moments_grouped over whatever table this object serves from:
+        the fp32 features, a bare bf16 catalogue or an ops.CompactCatalogue's rows (CompactInference too).  The candidates are
+        those of the installed type CSR, so set_eligible is honoured as it is for the lists.  The per-query exclusion lists
+        (set_exclusions) are NOT subtracted: a handful of products among a whole type do not move its mean or spread.  Nothing is
+        read back."""
+        _, types, proj, row_types = self._slot_rows(query_idx)
+        m = self._moments(proj, row_types)
+        return types, m.count.reshape(types.shape), m.mean.reshape(types.shape), m.std.reshape(types.shape)
+
+    @_takes_normalise
+    @torch.no_grad()
+    def recommend_batch(self, query_idx: torch.Tensor, num_recommendations: int = 10):
+        """All queries at once.  Returns complementary_types [B,K] int64, product indices [B,K,n] int32
+        (-1 past the end of a short type) and scores [B,K,n].  Up to 16 recommendations: the entries with a sorted list per
+        thread; from 17 to ops.RETRIEVE_LIST_MAX_N (256): pc_retrieve_list_grouped, whatever the graph's kind -- an uploaded
+        IntBPG's arrays are on the device, and the per-row kernel stops at 16.  A bf16 catalogue serves up to 16
+        (pc_retrieve_topk_grouped_bf16); given as an ops.CompactCatalogue also 17 to 256 (pc_retrieve_list_grouped_bf16).
+        normalise="zscore": the same model run and lists, the scores standardised per (query, type) --
+        ops.standardise_scores against the moments of the slot's score over its whole type (score_moments, taken for all B K
+        slots in one call) -- so that the lists of different types can be compared; a list keeps its order.  None: the raw dot
+        products, today's path and bits."""
+        n = self._list_length(num_recommendations)
+        if self.catalogue is not None and n > 16 and self.compact is None:
+            raise ValueError(f"recommend_batch: a bf16 catalogue serves at most 16 recommendations per (query, type), got {n}; "
+                             "longer lists need the fp32 catalogue (catalogue=None)")
+        query_idx, types, proj, row_types = self._slot_rows(query_idx)
+        b, k = types.shape
         exclude = self._exclude_rows(query_idx, k)
         rows = (proj, row_types, self.type_rowptr, self.type_col)
         if self.catalogue is not None and n > 16:         # (a CompactCatalogue) the bf16 list entry
@@ -370,6 +432,9 @@ class PCompanionInference(_CandidateFilters):
             idx, sc = ops.retrieve_topk_grouped(*rows, self.features, n, exclude=exclude)
         else:
             idx, sc = ops.retrieve_topk(*rows, self.features, n)
+        if self._normalise is not None:
+            m = self._moments(proj, row_types)
+            sc = ops.standardise_scores(sc, m.mean[:, None], m.std[:, None], m.count[:, None])
         return types, idx.reshape(b, k, -1), sc.reshape(b, k, -1)
 
     @torch.no_grad()
@@ -462,6 +527,7 @@ class PCompanionInference(_CandidateFilters):
             scale = self._inv_norm
         return ops.diversify_lists(idx, sc, table, n, 1.0 - diversity, scale=scale)
 
+    @_takes_normalise
     @torch.no_grad()
     def recommend_capped_batch(self, query_idx: torch.Tensor, num_recommendations: int = 10, group: torch.Tensor = None,
                                cap: int = 1, pool: int = 64, diversity: float = None, similarity: str = "cosine"):
@@ -476,7 +542,8 @@ class PCompanionInference(_CandidateFilters):
         num_recommendations products: the cap is on a POOL, and a pool that is mostly one group gives a short list -- take a
         longer pool.  1 <= num_recommendations <= pool <= ops.CAP_LISTS_MAX_POOL and cap >= 1, checked before the model runs.
         group=None and diversity=None is recommend_batch(query_idx, num_recommendations), bit for bit, wherever the pool comes
-        through a grouped entry."""
+        through a grouped entry.  normalise="zscore": the pool is recommend_batch(query_idx, pool, normalise="zscore") -- the
+        cap and the re-rank see the standardised scores and return them; None: today's path and bits."""
         n, pool = int(num_recommendations), int(pool)
         if not 1 <= n <= pool <= ops.CAP_LISTS_MAX_POOL:
             raise ValueError(f"recommend_capped_batch: need 1 <= num_recommendations <= pool <= {ops.CAP_LISTS_MAX_POOL}, got "
@@ -501,6 +568,7 @@ class PCompanionInference(_CandidateFilters):
             idx, sc = self._rerank(idx, sc, table, n, diversity, similarity)
         return types, idx.reshape(b, k, n), sc.reshape(b, k, n)
 
+    @_takes_normalise
     @torch.no_grad()
     def recommend_page_batch(self, query_idx: torch.Tensor, num_recommendations: int = 10, per_type: int = 4,
                              group: torch.Tensor = None, cap: int = 1):
@@ -513,7 +581,10 @@ class PCompanionInference(_CandidateFilters):
         product of that type's projected query with the product's features, and nothing normalises one type against another --
         a type whose projections score higher takes the head of the page.  Needs K per_type <= ops.CAP_LISTS_MAX_POOL and
         1 <= num_recommendations <= K per_type (and cap >= 1), checked before the model runs; -1 / -inf where fewer products
-        are kept."""
+        are kept.  normalise="zscore" is the remedy: the pool is recommend_batch(query_idx, per_type, normalise="zscore"), every
+        score standardised against the mean and spread of its own (query, type) slot over the whole type, so the page is
+        ordered by how exceptional a product is for its slot and no longer by which type projects loudest; the returned scores
+        are the standardised ones.  None: today's path and bits."""
         n, per_type, k = int(num_recommendations), int(per_type), int(self.config.NUM_COMP_TYPES)
         if per_type < 1 or k * per_type > ops.CAP_LISTS_MAX_POOL:
             raise ValueError(f"recommend_page_batch: need 1 <= per_type and K * per_type <= {ops.CAP_LISTS_MAX_POOL}, got K = {k} "
@@ -527,6 +598,7 @@ class PCompanionInference(_CandidateFilters):
         idx, sc = ops.cap_lists(idx.reshape(b, -1), sc.reshape(b, -1), n, group, cap)
         return idx, sc, self._served_types(idx)
 
+    @_takes_normalise
     @torch.no_grad()
     def recommend_basket_batch(self, basket: torch.Tensor, num_recommendations: int = 10, per_item: int = 8,
                                combine: str = "sum"):
@@ -542,7 +614,9 @@ class PCompanionInference(_CandidateFilters):
         (fused score descending, product index ascending), -1 / -inf / -1 / 0 where fewer products are left.  Needs
         I K per_item <= ops.FUSE_LISTS_MAX_POOL and 1 <= num_recommendations <= min(I K per_item, ops.FUSE_LISTS_MAX_N), checked
         before the model runs.  A padding slot still costs a retrieval row (it is served for product 0 and dropped by the
-        fusion), so bucket baskets by length.  Nothing is read back."""
+        fusion), so bucket baskets by length.  Nothing is read back.  normalise="zscore": the items are served by
+        recommend_batch(items, per_item, normalise="zscore"), so the fusion adds (or takes the largest of) standardised scores
+        and no type's scale outweighs the agreement of several items; None: today's path and bits."""
         n, per_item, k = int(num_recommendations), int(per_item), int(self.config.NUM_COMP_TYPES)
         if not torch.is_tensor(basket) or basket.dim() != 2 or basket.dtype != torch.int32 or basket.shape[1] < 1:
             _refuse_tensor("recommend_basket_batch", "basket", "a [B, I] int32 tensor with I >= 1 (-1 = no item)", basket)
@@ -564,6 +638,7 @@ class PCompanionInference(_CandidateFilters):
                                           exclude=self.exclusions, num_products=p)
         return idx, sc, self._served_types(idx), support
 
+    @_takes_normalise
     @torch.no_grad()
     def recommend_session_batch(self, items: torch.Tensor, seg_rowptr: torch.Tensor, num_recommendations: int = 10,
                                 per_item: int = 8, weight: torch.Tensor = None, combine: str = "sum", max_items: int = None):
@@ -584,7 +659,9 @@ class PCompanionInference(_CandidateFilters):
             weight = torch.pow(0.5, age.float())
         Only the last min(1024 // (K per_item), max_items) items of a session offer (max_items None: no cap); every item
         bans.  Needs K per_item <= ops.FUSE_SESSIONS_MAX_POOL and 1 <= num_recommendations <= ops.FUSE_SESSIONS_MAX_N, checked
-        before the model runs.  Nothing is read back."""
+        before the model runs.  Nothing is read back.  normalise="zscore": the items are served by recommend_batch(...,
+        normalise="zscore") and the weights multiply standardised scores, as in recommend_basket_batch; None: today's path and
+        bits."""
         n, per_item, k = int(num_recommendations), int(per_item), int(self.config.NUM_COMP_TYPES)
         if not torch.is_tensor(items) or items.dim() != 1 or items.dtype != torch.int32:
             _refuse_tensor("recommend_session_batch", "items", "a [R] int32 tensor", items)

@@ -2467,6 +2467,72 @@ def rank_grouped_where(proj, types, targets, type_rowptr, type_col, table, where
     return rank, bad
 
 
+class ScoreMoments:
+    """What score_moments_grouped returns, one entry per row, on the device: count [R] int32 (the candidates of the row's type),
+    mean / std [R] fp32 of the row's scores over them (the population form), and the sums behind them -- pivot (the score of the
+    type's first candidate), s1 = sum(s - pivot), s2 = sum((s - pivot)^2) -- with `bad` [1] int32."""
+    __slots__ = ("count", "mean", "std", "pivot", "s1", "s2", "bad")
+
+    def __init__(self, count, mean, std, pivot, s1, s2, bad):
+        self.count, self.mean, self.std, self.pivot, self.s1, self.s2, self.bad = count, mean, std, pivot, s1, s2, bad
+
+
+def score_moments_grouped(proj, types, type_rowptr, type_col, table, slices=0, bad=None):
+    """pc_score_moments_grouped / pc_score_moments_grouped_bf16: for row r the mean and the standard deviation of the scores of
+    ALL products of type types[r] under proj[r] -- the distribution retrieve_list_grouped's list is the head of, from that call's
+    own score bits -- as a ScoreMoments: count = the type's size n, pivot g = the score of the type's first candidate
+    type_col[type_rowptr[t]], s1 = sum fl(s - g), s2 = sum fl(s - g)^2, mean = g + s1 / n, std = sqrt(max(s2 / n - (s1 / n)^2, 0)).
+    A row with types[r] < 0, with a type >= the CSR's (which `bad` counts: a device counter to add to, a fresh zero otherwise) or
+    of an empty type: count 0 and zeros.  The entry goes by the table's dtype:
+      table [P, D] fp32      pc_score_moments_grouped
+      table [P, D] bfloat16  pc_score_moments_grouped_bf16  (the unrounded proj against the ROUNDED rows)
+    The rank entries' plan, query tile, score chain and candidate stream, and `slices` as there.  Bitwise reproducible for a given
+    `slices`; across `slices` the fp32 sums may differ in their last bits (where they are exact they do not).  Every host-side
+    check (ValueError) happens before any launch; nothing is read back to the host."""
+    what = "score_moments_grouped"
+    if not isinstance(table, torch.Tensor) or table.dtype not in (torch.float32, torch.bfloat16) or table.dim() != 2:
+        raise ValueError(f"{what}: table must be a [P, D] float32 or bfloat16 device tensor, got "
+                         f"{(table.dtype, tuple(table.shape)) if isinstance(table, torch.Tensor) else type(table).__name__}")
+    bf16 = table.dtype == torch.bfloat16
+    if table.shape[0] < 1 or table.shape[1] not in (128, 256):
+        raise ValueError(f"{what}: table must hold at least one row of 128 or 256 columns, got shape {tuple(table.shape)}")
+    if not isinstance(proj, torch.Tensor) or proj.numel() == 0 or proj.numel() % table.shape[1]:
+        raise ValueError(f"{what}: proj must be a non-empty tensor of rows of {table.shape[1]} columns")
+    rows = proj.numel() // table.shape[1]
+    if not isinstance(types, torch.Tensor) or types.dtype != torch.int32 or tuple(types.shape) != (rows,):
+        raise ValueError(f"{what}: types must be an int32 tensor of one entry per row ({rows},), got "
+                         f"{(types.dtype, tuple(types.shape)) if isinstance(types, torch.Tensor) else type(types).__name__}")
+    if not isinstance(type_rowptr, torch.Tensor) or type_rowptr.dim() != 1 or type_rowptr.numel() < 2:
+        raise ValueError(f"{what}: type_rowptr must be a [T + 1] int32 tensor with T >= 1")
+    proj, r, t, d, slices = _grouped_rows(proj, types, type_rowptr, type_col, table, torch.bfloat16 if bf16 else torch.float32,
+                                          slices)
+    _counters(bad=bad)
+    device = proj.device
+    count = torch.empty(r, dtype=torch.int32, device=device)
+    pivot, s1, s2, mean, std = torch.empty(5, r, dtype=torch.float32, device=device).unbind(0)
+    bad = _bad_counter(bad, device)
+    args = (proj.data_ptr(), types.data_ptr(), r, type_rowptr.data_ptr(), type_col.data_ptr(), table.data_ptr(), t, d, slices,
+            count.data_ptr(), pivot.data_ptr(), s1.data_ptr(), s2.data_ptr(), mean.data_ptr(), std.data_ptr(), bad.data_ptr())
+    _grouped_call("pc_score_moments_grouped_bf16" if bf16 else "pc_score_moments_grouped", "score_moments", device,
+                  (r, t, slices), args, "pc_score_moments_grouped")
+    return ScoreMoments(count, mean, std, pivot, s1, s2, bad)
+
+
+def standardise_scores(score, mean, std, count):
+    """z = (score - mean) / std in fp32, as torch operations on the tensors' device: how exceptional a served product is among
+    ALL candidates of its slot (mean / std / count: score_moments_grouped's, broadcast against score -- [R, 1] beside [R, n]).
+    z = 0 where count < 2 or std == 0 (one candidate, or all alike: nothing stands out); -inf (the padding of a short list)
+    stays -inf.  Inside one row the map is monotone: a list keeps its order."""
+    if not all(isinstance(t, torch.Tensor) for t in (score, mean, std, count)):
+        raise ValueError("standardise_scores: score, mean, std and count must be tensors")
+    if score.dtype != torch.float32 or mean.dtype != torch.float32 or std.dtype != torch.float32:
+        raise ValueError(f"standardise_scores: score, mean and std must be float32, got {score.dtype}, {mean.dtype}, {std.dtype}")
+    flat = (count < 2) | (std == 0)
+    z = (score - mean) / torch.where(flat, torch.ones_like(std), std)
+    z = torch.where(flat, torch.zeros_like(z), z)
+    return torch.where(score == float("-inf"), score, z)
+
+
 def type_csr(type_idx, n_types):
     """The type-grouped product CSR of PCompanionInference (bpg.get_products_by_type, bpg.py:40-43), built on the device from
     an int32 CUDA type_idx [P]: rowptr [T+1] int32, col [P] int32 = the products of each type in ascending node order (the
