@@ -1010,6 +1010,42 @@ int pc_ingest_emit(int64_t n_products, int32_t *src, const int32_t *src_rowptr, 
                    const int32_t *out_rowptr, int32_t *out_col, int32_t *out_pairs, int32_t *out_deg,
                    const int32_t *deg_rowptr, int clear, void *stream);
 
+/* ---- The three edge lists above DERIVED from a shopper event log on the device (csrc/events.hip, ABI 8, additive).
+ * events [N][4] int32, 16-byte aligned, rows (session, product, kind, time) in any order: session in [0, n_sessions), product in
+ * [0, n_products), kind 0 = view / 1 = purchase, time >= 0; N < 2^31.  Semantics (DESIGN.md "Edge lists from shopper
+ * events"): a session with more than max_events (2..1024) raw rows is skipped whole; the items of a kept session are its distinct
+ * products, fv(x) = the earliest view time of item x, lp(x) = its latest purchase time (-1 = none), V(x) = fv(x) >= 0, U(x) =
+ * lp(x) >= 0; per kept session and ordered pair of items a != b: co_purchase U(a) & U(b); co_view V(a) & V(b) [exclusive: and not
+ * (U(a) & U(b))]; purchase_after_view V(a) & U(b) & fv(a) <= lp(b) [exclusive: and not U(a)].  Each list is written as (a, b)
+ * rows ordered by (session, a, b): an edge appears once per session that shows it.  Integer atomics only; every output is a
+ * function of the log as a multiset of rows.  Call order (ops.event_edges): pc_events_count -> read *bad -> pc_exclusive_scan_i32
+ * (rowptr) -> pc_events_scatter -> pc_events_sessions -> read totals -> pc_exclusive_scan_i32 per list -> pc_events_emit. */
+/* the largest max_events, and the number of int64 words of pc_events_sessions' totals */
+int pc_events_limits(int *max_events, int *n_totals);
+/* cnt[session] += 1 (cnt zeroed by the caller) for every row.  Every field is compared with its range BEFORE it indexes
+ * anything: an offending row is skipped (by pc_events_scatter too) and ORs 1 (session), 2 (product), 4 (kind), 8 (time) into
+ * the device word *bad, which the caller reads once.  n_events = 0: nothing is launched.  PC_ESHAPE: events not 16-byte
+ * aligned. */
+int pc_events_count(const int32_t *events, int64_t n_events, int64_t n_sessions, int64_t n_products, int32_t *cnt,
+                    int32_t *bad, void *stream);
+/* bucket[rowptr[s] + j][2] = (product, (kind ^ 1) << 31 | time) of the rows of session s in arbitrary order, through the
+ * integer cursor cursor[s] (the counts of pc_events_count on entry; rowptr = their exclusive scan).  The rows of a session
+ * longer than max_events are not written. */
+int pc_events_scatter(const int32_t *events, int64_t n_events, int64_t n_sessions, int64_t n_products, int max_events,
+                      const int32_t *rowptr, int32_t *cursor, int32_t *bucket, void *stream);
+/* Every kept session in place, one wave each: its items ascending by product as (product, fv) in bucket[rowptr[s] + i][2] and
+ * lp in last_purchase[rowptr[s] + i], i < n_items[s]; count_cv / count_pv / count_cp [s] = its rows of co_view,
+ * purchase_after_view, co_purchase (0 for an empty or a skipped session).  totals[5] (int64, zeroed by the caller): the three
+ * lists' rows over all sessions, the items, the skipped sessions -- 64-bit sums the caller checks before it scans offsets. */
+int pc_events_sessions(int64_t n_sessions, const int32_t *rowptr, int32_t *bucket, int32_t *last_purchase, int max_events,
+                       int exclusive, int32_t *n_items, int32_t *count_cv, int32_t *count_pv, int32_t *count_cp,
+                       int64_t *totals, void *stream);
+/* out_cv / out_pv / out_cp [.][2]: the (a, b) rows of every session at off_*[s] onwards (off_* [n_sessions + 1] = the exclusive
+ * scans of pc_events_sessions' counts), a ascending, inside a the b ascending.  max_events and exclusive as given there. */
+int pc_events_emit(int64_t n_sessions, const int32_t *rowptr, const int32_t *bucket, const int32_t *last_purchase,
+                   const int32_t *n_items, int max_events, int exclusive, const int32_t *off_cv, const int32_t *off_pv,
+                   const int32_t *off_cp, int32_t *out_cv, int32_t *out_pv, int32_t *out_cp, void *stream);
+
 /* The epoch order of DataLoader(shuffle=True) (scripts/pretrain_product2vec.py:24-30, train.py:115-121) as a keyed
  * bijection: out[i] = perm_{seed,epoch}(i), i in [0, n) -- a six-round balanced Feistel network over the even number of
  * bits covering n, cycle-walked into [0, n).  No sort, no storage, deterministic in (seed, epoch); restated in

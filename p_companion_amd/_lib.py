@@ -329,6 +329,12 @@ SIGNATURES = {
     "pc_ingest_rows": (_i, [_i64, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "pc_ingest_flag": (_i, [_i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "pc_ingest_emit": (_i, [_i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
+    # the edge lists from a shopper event log (csrc/events.hip; ABI 8, additive)
+    "pc_events_limits": (_i, [_P(ctypes.c_int), _P(ctypes.c_int)]),
+    "pc_events_count": (_i, [_vp, _i64, _i64, _i64, _vp, _vp, _vp]),
+    "pc_events_scatter": (_i, [_vp, _i64, _i64, _i64, _i, _vp, _vp, _vp, _vp]),
+    "pc_events_sessions": (_i, [_i64, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "pc_events_emit": (_i, [_i64, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "pc_shuffle_rows_i32": (_i, [_vp, _i, _i, _u64, _u64, _vp, _vp]),
     "pc_comp_split_pairs": (_i, [_vp, _i64, _vp, _i64, _i64, _i64, _u64, _i, _vp, _vp]),
     "pc_epoch_plan": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),

@@ -116,6 +116,13 @@ class IntBPG:
                    similarity_pairs=pairs(sim), complementary_pairs=pairs(comp),
                    n_types=int(type_idx.max()) + 1 if P else 0)
 
+    @classmethod
+    def from_events(cls, features, type_idx, events, n_sessions=None, degree_cap=None, max_events=256, exclusive=True):
+        """From a raw shopper event log, int [N, 4] rows of (session, product, kind, time): event_edges_host's three lists
+        through from_edges.  The host twin of device_bpg_from_events, equal bit for bit."""
+        e = event_edges_host(events, int(np.asarray(type_idx).shape[0]), n_sessions, max_events, exclusive)
+        return cls.from_edges(features, type_idx, e.co_view, e.purchase_after_view, e.co_purchase, degree_cap=degree_cap)
+
     def cuda(self, device="cuda"):
         if self._dev is None:
             t = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a)).to(dt).to(device)
@@ -125,6 +132,72 @@ class IntBPG:
                 "sim_pairs": t(self.similarity_pairs, torch.int32), "sim_rowptr": t(self.sim_rowptr, torch.int32),
                 "sim_col": t(self.sim_col, torch.int32), "n_products": self.num_products}
         return self._dev
+
+
+def event_edges_host(events, n_products, n_sessions=None, max_events=256, exclusive=True):
+    """The numpy twin of ops.event_edges, equal bit for bit (DESIGN.md "Edge lists from shopper events"): an ops.EventEdges
+    of int32 [E, 2] numpy arrays, each ordered by (session, a, b), from an integer [N, 4] log of (session, product, kind 0
+    view / 1 purchase, time >= 0) rows in any order.  Session ids are dense in [0, n_sessions) (None: the largest id + 1); a
+    caller with sparse ids densifies them first (np.unique(ids, return_inverse=True)).  A session with more than max_events
+    raw rows is skipped whole.  Per kept session, over its distinct products with fv = earliest view time and lp = latest
+    purchase time, and per ordered pair a != b: co_purchase U(a) & U(b); co_view V(a) & V(b) [exclusive: and not both
+    purchased]; purchase_after_view V(a) & U(b) & fv(a) <= lp(b) [exclusive: and not U(a)].  It forms every ordered pair of a
+    session's items at once: the definition for tests and small logs, not a tool for large ones."""
+    from .ops import EVENT_COLUMNS, EVENT_EDGE_LIMIT, EVENT_MAX_EVENTS, INGEST_LISTS, EventEdges
+    ev = np.asarray(events)
+    if ev.ndim != 2 or ev.shape[1] != 4 or not np.issubdtype(ev.dtype, np.integer):
+        raise ValueError(f"event_edges_host: events must be an integer array of shape [N, 4], got {ev.dtype} {ev.shape}")
+    P = int(n_products)
+    if not 1 <= P < 2 ** 31:
+        raise ValueError(f"event_edges_host: n_products must be in 1..2^31 - 1, got {n_products!r}")
+    if n_sessions is not None and not 1 <= int(n_sessions) < 2 ** 31:
+        raise ValueError(f"event_edges_host: n_sessions must be None or in 1..2^31 - 1, got {n_sessions!r}")
+    if not 2 <= int(max_events) <= EVENT_MAX_EVENTS:
+        raise ValueError(f"event_edges_host: max_events must be in 2..{EVENT_MAX_EVENTS}, got {max_events!r}")
+    ev = ev.astype(np.int64)
+    N = ev.shape[0]
+    if n_sessions is None:
+        n_sessions = max(int(ev[:, 0].max()) + 1, 1) if N else 0
+    S = int(n_sessions)
+    s, p, kind, t = ev[:, 0], ev[:, 1], ev[:, 2], ev[:, 3]
+    wrong = [((s < 0) | (s >= S)).any(), ((p < 0) | (p >= P)).any(), ((kind < 0) | (kind > 1)).any(), (t < 0).any()]
+    if any(wrong):
+        names = ", ".join(n for n, w in zip(EVENT_COLUMNS, wrong) if w)
+        raise ValueError(f"event_edges_host: rows with {names} out of range (session in [0, {S}), product in [0, {P}), "
+                         "kind 0 or 1, time >= 0)")
+    empty = np.zeros((0, 2), np.int32)
+    if N == 0:
+        return EventEdges(empty, empty.copy(), empty.copy(), S, 0, 0)
+    rows = np.bincount(s, minlength=S)
+    keep = rows[s] <= int(max_events)
+    s, p, kind, t = s[keep], p[keep], kind[keep], t[keep]
+    # ---- the items: the distinct (session, product), ascending; fv / lp = -1 where there is no view / purchase
+    key, inv = np.unique(s * P + p, return_inverse=True)
+    inv = inv.reshape(-1)
+    fv = np.full(key.size, 2 ** 31, np.int64)
+    np.minimum.at(fv, inv[kind == 0], t[kind == 0])
+    fv[fv == 2 ** 31] = -1
+    lp = np.full(key.size, -1, np.int64)
+    np.maximum.at(lp, inv[kind == 1], t[kind == 1])
+    item_s, item_p = key // P, key % P
+    # ---- every ordered pair (a, b) of a session's items, a-major: already in (session, a, b) order
+    m = np.bincount(item_s, minlength=S)
+    start = np.concatenate([[0], np.cumsum(m)])[:-1]
+    per_a = m[item_s]                                        # partners of item a, itself included
+    a = np.repeat(np.arange(key.size), per_a)
+    b = start[item_s[a]] + np.arange(a.size) - np.repeat(np.cumsum(per_a) - per_a, per_a)
+    va, ua, vb, ub = fv[a] >= 0, lp[a] >= 0, fv[b] >= 0, lp[b] >= 0
+    other, both = a != b, ua & ub
+    masks = (other & va & vb & ~(both & bool(exclusive)),
+             other & va & ub & (fv[a] <= lp[b]) & ~(ua & bool(exclusive)),
+             other & both)
+    lists = []
+    for name, mask in zip(INGEST_LISTS, masks):
+        if int(mask.sum()) > EVENT_EDGE_LIMIT:
+            raise ValueError(f"event_edges_host: {name} would hold {int(mask.sum())} edges; a list is limited to "
+                             f"{EVENT_EDGE_LIMIT} -- lower max_events (the expansion is quadratic in a session's items)")
+        lists.append(np.stack([item_p[a[mask]], item_p[b[mask]]], 1).astype(np.int32).reshape(-1, 2))
+    return EventEdges(*lists, S, int((rows > int(max_events)).sum()), int(key.size))
 
 
 def generate_scaled_bpg(num_products=100_000, num_types=100, seed=0, mean_degree=16.0, degree_cap=32,
@@ -315,6 +388,38 @@ def device_bpg_from_edges(features, type_idx, n_types, co_view, purchase_after_v
     if n_types is None:
         n_types = int(arrays["type_idx"].max()) + 1
     return DeviceBPG(arrays, n_types, 0 if feats is None else feats.shape[1])
+
+
+def device_bpg_from_events(features, type_idx, n_types, events, n_sessions=None, degree_cap=32, max_events=256, exclusive=True,
+                           device="cuda") -> DeviceBPG:
+    """A DeviceBPG from a raw shopper event log, int32 [N, 4] rows of (session, product, kind 0 view / 1 purchase, time) in
+    any order: ops.event_edges (csrc/events.hip) derives the three edge lists in HBM -- an edge's multiplicity is the number
+    of sessions that show it, which is the weight degree_cap selects by -- and ops.build_catalogue builds the graph from them
+    (IntBPG.from_events is the host twin).  Session ids are dense; see ops.event_edges for n_sessions, max_events and
+    exclusive.  Host arrays (numpy or torch) are uploaded once; device tensors are used as they are.  The result carries
+    n_sessions, skipped_sessions and n_items of the derivation as attributes.  world = 1."""
+    from . import ops
+
+    def up(a, dtype):
+        if a is None:
+            return None
+        t = a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a))
+        if t.dtype != dtype:
+            raise ValueError(f"device_bpg_from_events: expected {dtype}, got {t.dtype}")
+        return t.to(device=device, dtype=dtype).contiguous()
+
+    ev = up(events, torch.int32)
+    if ev.numel() == 0:
+        ev = ev.reshape(0, 4)
+    types, feats = up(type_idx, torch.int32), up(features, torch.float32)
+    e = ops.event_edges(ev, int(types.shape[0]), n_sessions=n_sessions, max_events=max_events, exclusive=exclusive)
+    arrays = ops.build_catalogue(types, e.co_view, e.purchase_after_view, e.co_purchase, degree_cap=degree_cap, features=feats,
+                                 n_types=n_types)
+    if n_types is None:
+        n_types = int(arrays["type_idx"].max()) + 1
+    bpg = DeviceBPG(arrays, n_types, 0 if feats is None else feats.shape[1])
+    bpg.n_sessions, bpg.skipped_sessions, bpg.n_items = e.n_sessions, e.skipped_sessions, e.n_items
+    return bpg
 
 
 class _LazyCount:

@@ -5,6 +5,7 @@ HIP kernel of libpcompanion_hip.so.  All tensors must be CUDA(ROCm), contiguous,
 int32; anything else raises (no silent conversion on the hot path, no CPU fallback).
 """
 import ctypes
+from typing import NamedTuple
 
 import numpy as np
 import torch
@@ -1662,6 +1663,104 @@ def build_catalogue(type_idx, co_view, purchase_after_view, co_purchase, degree_
     out.update(cv_rowptr=cv_rowptr, cv_col=cv_col[:n_edges], sim_rowptr=sim_rowptr, sim_pairs=sim_pairs[:n_sim],
                sim_col=sim_col[:n_sim], pair_deg=pair_deg[:n_sim], max_degree=int(max_kept.item()), comp_pairs=comp[:n_comp])
     return out
+
+
+EVENT_MAX_EVENTS = 1024            # the longest session pc_events_sessions sorts (one wave, 16 register slots per lane);
+#                                    pc_events_limits reports the library's own value (tests/test_events_host.py compares)
+EVENT_EDGE_LIMIT = 2 ** 31 - 1     # rows of one derived edge list at most: offsets are int32 (and build_catalogue's limit)
+EVENT_COLUMNS = ("session", "product", "kind", "time")
+
+
+class EventEdges(NamedTuple):
+    """What event_edges (device tensors) and data.event_edges_host (numpy arrays) return: the three int32 [E, 2] lists of
+    (a, b), each ordered by (session, a, b), and the counts."""
+    co_view: object
+    purchase_after_view: object
+    co_purchase: object
+    n_sessions: int
+    skipped_sessions: int
+    n_items: int
+
+
+def _check_event_args(events, n_products, n_sessions, max_events, who="event_edges"):
+    """event_edges' checks that need neither the library nor a device; every refusal is a ValueError.  Returns N."""
+    if not isinstance(events, torch.Tensor) or not events.is_cuda:
+        raise ValueError(f"{who}: events must be a tensor on the device (the HIP path has no CPU fallback)")
+    if events.dtype != torch.int32:
+        raise ValueError(f"{who}: events must be int32, got {events.dtype}")
+    if events.dim() != 2 or events.shape[1] != 4:
+        raise ValueError(f"{who}: events must have shape [N, 4] (session, product, kind, time), got {tuple(events.shape)}")
+    if not events.is_contiguous():
+        raise ValueError(f"{who}: events must be contiguous")
+    if events.shape[0] >= 2 ** 31:
+        raise ValueError(f"{who}: {events.shape[0]} rows; a log is limited to 2^31 - 1")
+    if isinstance(n_products, bool) or not isinstance(n_products, (int, np.integer)) or not 1 <= n_products < 2 ** 31:
+        raise ValueError(f"{who}: n_products must be an integer in 1..2^31 - 1, got {n_products!r}")
+    if n_sessions is not None and (isinstance(n_sessions, bool) or not isinstance(n_sessions, (int, np.integer))
+                                   or not 1 <= n_sessions < 2 ** 31):
+        raise ValueError(f"{who}: n_sessions must be None or an integer in 1..2^31 - 1, got {n_sessions!r}")
+    if isinstance(max_events, bool) or not isinstance(max_events, (int, np.integer)) or not 2 <= max_events <= EVENT_MAX_EVENTS:
+        raise ValueError(f"{who}: max_events must be an integer in 2..{EVENT_MAX_EVENTS}, got {max_events!r}")
+    if events.shape[0] and events.data_ptr() % 16:
+        raise ValueError(f"{who}: events must be 16-byte aligned (a row is read as one word)")
+    return int(events.shape[0])
+
+
+def event_edges(events, n_products, n_sessions=None, max_events=256, exclusive=True):
+    """csrc/events.hip end to end: the co_view, purchase_after_view and co_purchase lists build_catalogue reads, derived from a
+    raw event log on the device (DESIGN.md "Edge lists from shopper events" has the semantics; data.event_edges_host is the
+    host twin, equal bit for bit).  events: int32 [N, 4] device tensor, rows (session, product, kind 0 view / 1 purchase,
+    time >= 0) in any order.  Session ids are dense in [0, n_sessions) (None: the largest id + 1, one more read-back); a
+    caller with sparse ids densifies them first (torch.unique(ids, return_inverse=True)).  A session with more than max_events
+    raw rows is skipped whole and counted.  Returns an EventEdges of device tensors.  A field outside its range raises
+    ValueError naming its column: the device compares every field before using it and reports through one flag word.  A
+    list of more than EVENT_EDGE_LIMIT rows raises ValueError before anything is emitted.  Host synchronisations: the flag
+    word and the 64-bit totals."""
+    N = _check_event_args(events, n_products, n_sessions, max_events)
+    P, cap, dev = int(n_products), int(max_events), events.device
+    i32 = lambda *s: torch.empty(*s, dtype=torch.int32, device=dev)
+    z32 = lambda *s: torch.zeros(*s, dtype=torch.int32, device=dev)
+    if n_sessions is None:
+        n_sessions = max(int(events[:, 0].max()) + 1, 1) if N else 0          # (a negative id is then reported by the device)
+    S = int(n_sessions)
+    if N == 0:
+        return EventEdges(i32(0, 2), i32(0, 2), i32(0, 2), S, 0, 0)
+    L = _lib.lib()
+    # ---- bucket the rows by session
+    cnt, bad = z32(S), z32(1)
+    check(L.pc_events_count(_p(events), N, S, P, _p(cnt), _p(bad), _stream()), "pc_events_count")
+    flag = int(bad.item())
+    if flag:
+        names = ", ".join(n for k, n in enumerate(EVENT_COLUMNS) if flag >> k & 1)
+        raise ValueError(f"event_edges: rows with {names} out of range (session in [0, {S}), product in [0, {P}), "
+                         "kind 0 or 1, time >= 0)")
+    nbytes = L.pc_scan_scratch_bytes(S)
+    scratch = torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=dev)
+
+    def scan(counts):                                        # (no total is read back: the rows, and the totals below)
+        out = i32(S + 1)
+        check(L.pc_exclusive_scan_i32(_p(counts), S, _p(out), None, _p(scratch), nbytes, _stream()), "pc_exclusive_scan_i32")
+        return out
+
+    rowptr = scan(cnt)
+    bucket, last = i32(N, 2), i32(N)
+    check(L.pc_events_scatter(_p(events), N, S, P, cap, _p(rowptr), _p(cnt), _p(bucket), _stream()), "pc_events_scatter")
+    # ---- every kept session sorted into its items; the rows it gives each list
+    n_items, count = i32(S), i32(3, S)
+    totals = torch.zeros(8, dtype=torch.int64, device=dev)
+    check(L.pc_events_sessions(S, _p(rowptr), _p(bucket), _p(last), cap, int(bool(exclusive)), _p(n_items), _p(count[0]),
+                               _p(count[1]), _p(count[2]), _p(totals), _stream()), "pc_events_sessions")
+    n_cv, n_pv, n_cp, items, skipped = totals[:5].tolist()
+    for name, n in zip(INGEST_LISTS, (n_cv, n_pv, n_cp)):
+        if n > EVENT_EDGE_LIMIT:
+            raise ValueError(f"event_edges: {name} would hold {n} edges; a list is limited to {EVENT_EDGE_LIMIT} -- "
+                             "lower max_events (the expansion is quadratic in a session's items)")
+    # ---- offsets, then the rows
+    off = [scan(count[k]) for k in range(3)]
+    out = [i32(max(n, 1), 2) for n in (n_cv, n_pv, n_cp)]
+    check(L.pc_events_emit(S, _p(rowptr), _p(bucket), _p(last), _p(n_items), cap, int(bool(exclusive)), _p(off[0]), _p(off[1]),
+                           _p(off[2]), _p(out[0]), _p(out[1]), _p(out[2]), _stream()), "pc_events_emit")
+    return EventEdges(out[0][:n_cv], out[1][:n_pv], out[2][:n_cp], S, int(skipped), int(items))
 
 
 def epoch_permutation(n, seed, epoch, device):
