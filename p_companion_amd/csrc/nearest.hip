@@ -28,7 +28,7 @@
 // integers, one integer atomic per (row, slice).  No float atomics.
 #include "common.h"
 #include "grouped_select.h"        // the item decode, the tile load, the dispatch on a tile's row groups, the selection, the write
-#include "rank_chain.h"
+#include "grouped_rank.h"          // rk_rank_body, rk_post: the rank skeleton and the row post-pass
 
 // Lane l of wave wv: column c = l & 15 (candidate wv * 16 + c of the chunk, query row g * 16 + c of the A operand), k-lane
 // h = l >> 4.  Partial lists: pv / pi [rows][S][n] at the row's grouped position.  EXCL: rg_score_excl_kernel's exclusion lists
@@ -142,69 +142,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(D == 128 ? 
     }
 }
 
-// One work item's candidate stream for a tile of NG 16-row groups (rk_stream with the biased score): accumulator register k of
-// row group g holds query row g * 16 + 4 h + k; gs / ys: the rows' target scores g = d(r, y) + bias[y] and targets.  b / pid /
-// bs: the first chunk's rows, product ids and terms, pidn: the second chunk's ids (-1: a column past the slice's end; its b is
-// product 0's row and its scores are not counted).  Leaves the wave's counts in part[wv][row].
-template <int D, int NG>
-__device__ __forceinline__ void nb_stream(const float* q, const float* gs, const int* ys, int (*part)[8192 / D],
-                                          const int32_t* __restrict__ type_col, const float* __restrict__ table,
-                                          const float* __restrict__ bias, int cb0, int ce, float4 (&b)[D / 16], int pid, int pidn,
-                                          float bs, int wv, int c, int h) {
-    float gv[NG][4];
-    int cn[NG][4];
-#pragma unroll
-    for (int g = 0; g < NG; g++) {
-        const float4 x = *reinterpret_cast<const float4*>(&gs[g * 16 + 4 * h]);
-        gv[g][0] = x.x; gv[g][1] = x.y; gv[g][2] = x.z; gv[g][3] = x.w;
-#pragma unroll
-        for (int k = 0; k < 4; k++) cn[g][k] = 0;
-    }
-    for (int cb = cb0; cb < ce; cb += RG_CHUNK) {
-        const int cc = cb + 2 * RG_CHUNK + wv * 16 + c;
-        const int pidnn = cc < ce ? type_col[cc] : -1;
-        const float4* next = reinterpret_cast<const float4*>(table + (size_t)max(pidn, 0) * D) + h;
-        f32x4 acc[NG];
-#pragma unroll
-        for (int g = 0; g < NG; g++) acc[g] = f32x4{0.f, 0.f, 0.f, 0.f};
-        rk_chain<D, NG>(q, 0, b, next, acc, c, h);
-        // s = fl(d + bias[pid]) above g is counted; equal to g: the product index decides (rare: ys is read only then)
-        if (pid >= 0) {
-            bool tie = false;
-#pragma unroll
-            for (int g = 0; g < NG; g++) {
-                acc[g] += bs;
-#pragma unroll
-                for (int k = 0; k < 4; k++) {
-                    cn[g][k] += acc[g][k] > gv[g][k] ? 1 : 0;
-                    tie |= acc[g][k] == gv[g][k];
-                }
-            }
-            if (tie) {
-#pragma unroll
-                for (int g = 0; g < NG; g++)
-#pragma unroll
-                    for (int k = 0; k < 4; k++)
-                        cn[g][k] += (acc[g][k] == gv[g][k] && pid < ys[g * 16 + 4 * h + k]) ? 1 : 0;
-            }
-        }
-        const float bsn = bias[max(pidn, 0)];             // the next chunk's term, with its product id, a chunk ahead
-        pid = pidn;
-        pidn = pidnn;
-        bs = bsn;
-    }
-    // the 16 columns of a (wave, k-lane) -> lane c == 0
-#pragma unroll
-    for (int g = 0; g < NG; g++)
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            int v = cn[g][k];
-#pragma unroll
-            for (int o = 8; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-            if (c == 0) part[wv][g * 16 + 4 * h + k] = v;
-        }
-}
-
 // rk_rank_kernel with the biased score: rank_out[r] += #{ p of the slice : s_p > g or (s_p == g and p < y) }, one integer atomic
 // per (row, slice).
 template <int D>
@@ -213,73 +150,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(D == 128 ? 
     const int32_t* __restrict__ type_col, const float* __restrict__ table, const float* __restrict__ bias, int n_types, int S,
     const int32_t* __restrict__ cnt, const int32_t* __restrict__ row_start, const int64_t* __restrict__ item_start,
     const int32_t* __restrict__ order, int32_t* __restrict__ rank_out) {
-    constexpr int TM = 8192 / D;
-    constexpr int RG = TM / 16;
-    constexpr int QS = RK_QS(D);
-    constexpr int NB = D / 16;
-    __shared__ __attribute__((aligned(16))) float q[TM * QS];
-    __shared__ __attribute__((aligned(16))) float gs[TM];            // the rows' target scores
-    __shared__ __attribute__((aligned(16))) int ys[TM];              // the rows' targets
-    __shared__ int part[4][TM];                                      // the waves' counts
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, c = lane & 15, h = lane >> 4;
-    const int64_t n_items = item_start[n_types];
-    for (int64_t w = blockIdx.x; w < n_items; w += gridDim.x) {
-        const RgItem it = rg_decode<TM>(w, item_start, cnt, row_start, type_rowptr, n_types, S);
-        const int p0 = it.p0, valid = it.valid, rg = it.rg, cb0 = it.cb0, ce = it.ce;
-
-        __syncthreads();                                  // the previous item's readers of q / part are done
-        rg_load_tile<D, QS>(q, proj, order, p0, valid, rg, tid);
-
-        auto load_pid = [&](int cb) { const int cc = cb + wv * 16 + c; return cc < ce ? type_col[cc] : -1; };
-        // (a lane without a product reads product 0's row and term: no branch, and nothing of it is used)
-        auto load_b = [&](float4* b, int pid) {
-            const float4* f = reinterpret_cast<const float4*>(table + (size_t)max(pid, 0) * D) + h;
-#pragma unroll
-            for (int k = 0; k < NB; k++) b[k] = f[4 * k];
-        };
-        float4 b[NB];
-        const int pid = load_pid(cb0);
-        load_b(b, pid);
-        const float bs = bias[max(pid, 0)];
-        const int pidn = load_pid(cb0 + RG_CHUNK);
-        // wave wv: column c = the target of query row wv * 16 + c
-        int ty = -1;
-        if (wv < rg && wv * 16 + c < valid) ty = targets[order[p0 + wv * 16 + c]];
-        __syncthreads();                                  // query tile in LDS
-        if (wv < rg) {                                    // (wave-uniform)
-            float4 bt[NB];
-            load_b(bt, ty);
-            const float by = bias[max(ty, 0)];
-            f32x4 ag[1] = {f32x4{0.f, 0.f, 0.f, 0.f}};
-            rk_chain<D, 1>(q, wv, bt, nullptr, ag, c, h);
-            const f32x4 acc = ag[0];
-            // C/D map of the 16x16 f32 MFMA: column lane & 15, row 4 (lane >> 4) + reg; the diagonal: row == column
-            if ((c >> 2) == h) {
-                const int k = c & 3;
-                gs[wv * 16 + c] = (k == 0 ? acc[0] : k == 1 ? acc[1] : k == 2 ? acc[2] : acc[3]) + by;
-                ys[wv * 16 + c] = ty;
-            }
-        }
-        __syncthreads();                                  // gs / ys in LDS
-        if (rg == 1) nb_stream<D, 1>(q, gs, ys, part, type_col, table, bias, cb0, ce, b, pid, pidn, bs, wv, c, h);
-        else if (rg == 2) nb_stream<D, 2>(q, gs, ys, part, type_col, table, bias, cb0, ce, b, pid, pidn, bs, wv, c, h);
-        else if constexpr (RG == 4) {
-            if (rg == 3) nb_stream<D, 3>(q, gs, ys, part, type_col, table, bias, cb0, ce, b, pid, pidn, bs, wv, c, h);
-            else nb_stream<D, 4>(q, gs, ys, part, type_col, table, bias, cb0, ce, b, pid, pidn, bs, wv, c, h);
-        }
-        __syncthreads();
-        if (tid < valid) {
-            const int v = part[0][tid] + part[1][tid] + part[2][tid] + part[3][tid];
-            if (v) atomicAdd(&rank_out[order[p0 + tid]], v);
-        }
-    }
+    rk_rank_body<D, true, false>(proj, targets, type_rowptr, type_col, table, bias, n_types, S, cnt, row_start, item_start, order,
+                                 rank_out, pc_row_where{});
 }
 
-// rk_exclude_kernel's post-pass with the biased score.  One wave per row: column 0 of the first block is the target y, then the
-// row's list ex_col[elo, ehi); g and every s_e are the bits nb_rank_kernel compared.  A list entry e with cand_type[e] ==
-// types[r] and rg_better(s_e, e, g, y) was counted there: one off.  e == y, or cand_type[y] != types[r]: rank -1.  A row the plan
-// left at -1 stays so; an id outside [0, num_products) is passed over; a key outside [-1, n_keys) is no list and is counted in
-// *bad_count.  Integer work, the row's wave the one writer.
+// rk_exclude_kernel's post-pass with the biased score (rk_post): g and every s_e are the bits nb_rank_kernel compared.
 template <int D>
 __global__ __launch_bounds__(64) void nb_rank_exclude_kernel(const float* __restrict__ proj, const int32_t* __restrict__ types,
                                                              const int32_t* __restrict__ targets,
@@ -290,56 +165,9 @@ __global__ __launch_bounds__(64) void nb_rank_exclude_kernel(const float* __rest
                                                              const float* __restrict__ table, const float* __restrict__ bias,
                                                              int num_products, int32_t* __restrict__ rank_out,
                                                              int32_t* __restrict__ bad_count) {
-    constexpr int QS = RK_QS(D), NB = D / 16;
-    __shared__ __attribute__((aligned(16))) float q[16 * QS];
-    const int lane = threadIdx.x, c = lane & 15, h = lane >> 4;
-    const int r = blockIdx.x;
-    int key = row_key[r];
-    if (key < -1 || key >= n_keys) {
-        if (lane == 0) atomicAdd(bad_count, 1);
-        key = -1;
-    }
-    const int base = rank_out[r];
-    if (base < 0) return;                                 // (wave-uniform, as every exit below) no type, or an id out of range
-    const int t = types[r], y = targets[r];               // both inside their ranges: the plan counted the row
-    if (cand_type[y] != t) {
-        if (lane == 0) rank_out[r] = -1;
-        return;
-    }
-    if (key < 0) return;
-    const int elo = ex_rowptr[key], len = ex_rowptr[key + 1] - elo;
-    if (len <= 0) return;
-    for (int e = lane; e < 16 * (QS / 4); e += 64) {
-        const int row = e / (QS / 4), d4 = e - row * (QS / 4);
-        float4 x = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (row == 0 && d4 < D / 4) x = reinterpret_cast<const float4*>(proj + (size_t)r * D)[d4];
-        *reinterpret_cast<float4*>(&q[row * QS + 4 * d4]) = x;
-    }
-    __syncthreads();
-    float g = 0.f;
-    int dec = 0;
-    bool hit = false;
-    for (int v0 = 0; v0 <= len; v0 += 16) {               // column v: the target (v == 0), list entry v - 1
-        const int v = v0 + c;
-        int id = -1;
-        if (v == 0) id = y;
-        else if (v <= len) id = ex_col[elo + v - 1];
-        if (id >= num_products) id = -1;
-        float4 b[NB];
-        const float4* f = reinterpret_cast<const float4*>(table + (size_t)max(id, 0) * D) + h;
-#pragma unroll
-        for (int k = 0; k < NB; k++) b[k] = f[4 * k];
-        const float bs = bias[max(id, 0)];
-        f32x4 acc[1] = {f32x4{0.f, 0.f, 0.f, 0.f}};
-        rk_chain<D, 1>(q, 0, b, nullptr, acc, c, h);
-        // C/D map of the 16x16 f32 MFMA: column lane & 15, row 4 (lane >> 4) + reg: row 0 is register 0 of lanes 0..15
-        const float s = acc[0][0] + bs;
-        if (v0 == 0) g = __shfl(s, 0, 64);
-        const bool mine = h == 0 && v > 0 && id >= 0;
-        hit |= __any(mine && id == y);
-        dec += __popcll(__ballot(mine && id != y && cand_type[max(id, 0)] == t && rg_better(s, id, g, y)));
-    }
-    if (lane == 0) rank_out[r] = hit ? -1 : base - dec;
+    __shared__ __attribute__((aligned(16))) typename RkScoreF32<D>::Image q;
+    rk_post<D, RkScoreF32<D>, true, false>(q, proj, types, targets, row_key, ex_rowptr, ex_col, n_keys, cand_type, table, bias,
+                                           num_products, pc_row_where{}, rank_out, bad_count);
 }
 
 // out[p] = -0.5f * sum_d e[p][d]^2.  ONE summation order per row, whatever the grid: a group of 16 lanes owns a row; lane l of
@@ -420,33 +248,17 @@ extern "C" int pc_rank_grouped_biased(const float* proj, const int32_t* types, c
                                       const float* bias, int n_types, int num_products, const int32_t* ex_rowptr,
                                       const int32_t* ex_col, int n_keys, const int32_t* cand_type, int dim, int slices,
                                       int32_t* rank_out, int32_t* bad_count, void* ws, size_t ws_bytes, void* stream) {
-    if (!proj || !types || !targets || !type_rowptr || !type_col || !table || !bias || !rank_out || !bad_count || !ws)
-        return PC_EINVAL;
-    if (rows <= 0 || n_types <= 0 || num_products <= 0) return PC_EINVAL;
-    // the lists and the products' types: all or none
-    if (!rg_lists_ok(row_key, ex_rowptr, ex_col, bad_count, n_keys) || !row_key != !cand_type) return PC_EINVAL;
-    if ((dim != 128 && dim != 256) || slices < 0 || slices > RG_MAX_SLICES) return PC_ESHAPE;
-    const int S = rg_slices(slices);
-    hipStream_t st = (hipStream_t)stream;
-    RgWs w;
-    unsigned grid;
-    PC_TRY(rg_begin(w, grid, ws, ws_bytes, types, targets, rows, type_rowptr, n_types, num_products, 0, S, 8192 / dim, rank_out,
-                    bad_count, st));
-    const RgPlan& pl = w.plan;
-    if (dim == 128)
-        PC_LAUNCH(nb_rank_kernel<128>, dim3(grid), dim3(256), 0, st, proj, targets, type_rowptr, type_col, table, bias, n_types, S,
-                  pl.cnt, pl.row_start, pl.item_start, pl.order, rank_out);
-    else
-        PC_LAUNCH(nb_rank_kernel<256>, dim3(grid), dim3(256), 0, st, proj, targets, type_rowptr, type_col, table, bias, n_types, S,
-                  pl.cnt, pl.row_start, pl.item_start, pl.order, rank_out);
-    if (row_key) {
-        if (dim == 128)
-            PC_LAUNCH(nb_rank_exclude_kernel<128>, dim3(rows), dim3(64), 0, st, proj, types, targets, row_key, ex_rowptr, ex_col,
+    RkStart s;
+    PC_TRY(rk_begin(s, proj && table && bias, nullptr, types, targets, row_key, rows, type_rowptr, type_col, n_types, num_products,
+                    ex_rowptr, ex_col, n_keys, cand_type, dim, slices, rank_out, bad_count, ws, ws_bytes, stream));
+    const RgPlan& pl = s.w.plan;
+    rk_dispatch(dim, false, [&](auto d, auto) {
+        constexpr int D = decltype(d)::value;
+        PC_LAUNCH(nb_rank_kernel<D>, dim3(s.grid), dim3(256), 0, s.st, proj, targets, type_rowptr, type_col, table, bias, n_types,
+                  s.S, pl.cnt, pl.row_start, pl.item_start, pl.order, rank_out);
+        if (row_key)
+            PC_LAUNCH(nb_rank_exclude_kernel<D>, dim3(rows), dim3(64), 0, s.st, proj, types, targets, row_key, ex_rowptr, ex_col,
                       n_keys, cand_type, table, bias, num_products, rank_out, bad_count);
-        else
-            PC_LAUNCH(nb_rank_exclude_kernel<256>, dim3(rows), dim3(64), 0, st, proj, types, targets, row_key, ex_rowptr, ex_col,
-                      n_keys, cand_type, table, bias, num_products, rank_out, bad_count);
-    }
+    });
     return pc_launch_status();
 }
-

@@ -23,10 +23,7 @@
 // and the count is a sum of integers: it does not depend on the slices, on the order of the rows in a tile or on the order of
 // type_col inside a type.  No float atomics.
 #include "common.h"
-#include "grouped_select.h"        // the item decode
-#include "grouped_plan.h"          // rg_better
-
-#include "rank_chain_bf16.h"      // rb_chain, rb_load_b: THE k-chain (where_rank_bf16.hip scores through it too)
+#include "grouped_rank.h"          // rk_post: the row post-pass; rk_begin, rk_dispatch
 
 // One work item's candidate stream for a tile of NG 16-row groups (NG a template argument: the loop body is straight-line
 // code).  Lane l of wave wv: column c = l & 15 (candidate wv * 16 + c of the chunk), k-lane h = l >> 4; accumulator register k
@@ -178,14 +175,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void r
     }
 }
 
-// rk_exclude_kernel's post-pass over the bf16 table: rb_rank_kernel counted over the whole type; this takes the excluded
-// products out again.  One wave per row: the row's split query is row 0 of a 16-row image (rows 1..15 are zero: an MFMA's
-// output row depends on its own A row alone), the B operand is blocks of 16 columns -- column 0 of the first block the target
-// y, then the row's list ex_col[elo, ehi) -- through rb_chain, so g and every s_e are the bits rb_rank_kernel compared.  A list
-// entry e with cand_type[e] == types[r] and rg_better(s_e, e, g, y) was counted there: one off.  e == y, or cand_type[y] !=
-// types[r]: the target is no candidate of the row, rank -1.  A row the plan left at -1 stays so; an id outside
-// [0, num_products) is passed over; a key outside [-1, n_keys) is no list and is counted in *bad_count.  Integer work, the
-// row's wave the one writer.
+// rk_exclude_kernel's post-pass over the bf16 table (rk_post through rb_chain): rb_rank_kernel counted over the whole type; this
+// takes the excluded products out again, and g and every s_e are the bits rb_rank_kernel compared.
 template <int D, bool BIAS>
 __global__ __launch_bounds__(64) void rb_rank_exclude_kernel(const float* __restrict__ proj, const int32_t* __restrict__ types,
                                                              const int32_t* __restrict__ targets,
@@ -196,62 +187,9 @@ __global__ __launch_bounds__(64) void rb_rank_exclude_kernel(const float* __rest
                                                              const uint16_t* __restrict__ table, const float* __restrict__ bias,
                                                              int num_products, int32_t* __restrict__ rank_out,
                                                              int32_t* __restrict__ bad_count) {
-    constexpr int NB = D / 32;
-    __shared__ __attribute__((aligned(16))) bf16x8 q[3][(D / 8) * 16];
-    const int lane = threadIdx.x, c = lane & 15, h = lane >> 4;
-    const int r = blockIdx.x;
-    int key = row_key[r];
-    if (key < -1 || key >= n_keys) {
-        if (lane == 0) atomicAdd(bad_count, 1);
-        key = -1;
-    }
-    const int base = rank_out[r];
-    if (base < 0) return;                                 // (wave-uniform, as every exit below) no type, or an id out of range
-    const int t = types[r], y = targets[r];               // both inside their ranges: the plan counted the row
-    if (cand_type[y] != t) {
-        if (lane == 0) rank_out[r] = -1;
-        return;
-    }
-    if (key < 0) return;
-    const int elo = ex_rowptr[key], len = ex_rowptr[key + 1] - elo;
-    if (len <= 0) return;
-    for (int e = lane; e < 16 * (D / 8); e += 64) {
-        const int d8 = e >> 4, row = e & 15;
-        float4 x0 = make_float4(0.f, 0.f, 0.f, 0.f), x1 = x0;
-        if (row == 0) {
-            const float4* f = reinterpret_cast<const float4*>(proj + (size_t)r * D) + 2 * d8;
-            x0 = f[0];
-            x1 = f[1];
-        }
-        const Split3 sp = split3(x0, x1);
-        q[0][d8 * 16 + row] = sp.p0;
-        q[1][d8 * 16 + row] = sp.p1;
-        q[2][d8 * 16 + row] = sp.p2;
-    }
-    __syncthreads();
-    float g = 0.f;
-    int dec = 0;
-    bool hit = false;
-    for (int v0 = 0; v0 <= len; v0 += 16) {               // column v: the target (v == 0), list entry v - 1
-        const int v = v0 + c;
-        int id = -1;
-        if (v == 0) id = y;
-        else if (v <= len) id = ex_col[elo + v - 1];
-        if (id >= num_products) id = -1;
-        bf16x8 b[NB];
-        rb_load_b<D>(b, table, id, h);
-        float bs = 0.f;
-        if constexpr (BIAS) bs = bias[max(id, 0)];
-        f32x4 acc[1] = {f32x4{0.f, 0.f, 0.f, 0.f}};
-        rb_chain<D, 16, 1>(q, 0, b, acc, c, h);
-        // C/D map of the 16x16 MFMAs: column lane & 15, row 4 (lane >> 4) + reg: row 0 is register 0 of lanes 0..15
-        const float s = BIAS ? acc[0][0] + bs : acc[0][0];
-        if (v0 == 0) g = __shfl(s, 0, 64);
-        const bool mine = h == 0 && v > 0 && id >= 0;
-        hit |= __any(mine && id == y);
-        dec += __popcll(__ballot(mine && id != y && cand_type[max(id, 0)] == t && rg_better(s, id, g, y)));
-    }
-    if (lane == 0) rank_out[r] = hit ? -1 : base - dec;
+    __shared__ __attribute__((aligned(16))) typename RkScoreBf16<D>::Image q;
+    rk_post<D, RkScoreBf16<D>, BIAS, false>(q, proj, types, targets, row_key, ex_rowptr, ex_col, n_keys, cand_type, table, bias,
+                                            num_products, pc_row_where{}, rank_out, bad_count);
 }
 
 extern "C" size_t pc_rank_grouped_bf16_workspace_bytes(int rows, int n_types, int slices) {
@@ -263,33 +201,18 @@ extern "C" int pc_rank_grouped_bf16(const float* proj, const int32_t* types, con
                                     const float* bias, int n_types, int num_products, const int32_t* ex_rowptr,
                                     const int32_t* ex_col, int n_keys, const int32_t* cand_type, int dim, int slices,
                                     int32_t* rank_out, int32_t* bad_count, void* ws, size_t ws_bytes, void* stream) {
-    if (!proj || !types || !targets || !type_rowptr || !type_col || !table_bf16 || !rank_out || !bad_count || !ws)
-        return PC_EINVAL;
-    if (rows <= 0 || n_types <= 0 || num_products <= 0) return PC_EINVAL;
-    // the lists and the products' types: all or none
-    if (!rg_lists_ok(row_key, ex_rowptr, ex_col, bad_count, n_keys) || !row_key != !cand_type) return PC_EINVAL;
-    if ((dim != 128 && dim != 256) || slices < 0 || slices > RG_MAX_SLICES) return PC_ESHAPE;
-    if ((uintptr_t)table_bf16 & 15) return PC_ESHAPE;     // a lane reads 16 bytes of a row at once
-    const int S = rg_slices(slices);
-    hipStream_t st = (hipStream_t)stream;
-    RgWs w;
-    unsigned grid;
-    PC_TRY(rg_begin(w, grid, ws, ws_bytes, types, targets, rows, type_rowptr, n_types, num_products, 0, S, 8192 / dim, rank_out,
-                    bad_count, st));
-    const RgPlan& pl = w.plan;
-#define RB_RANK(D, BIAS)                                                                                                        \
-    do {                                                                                                                        \
-        PC_LAUNCH((rb_rank_kernel<D, BIAS>), dim3(grid), dim3(256), 0, st, proj, targets, type_rowptr, type_col, table_bf16, bias, \
-                  n_types, S, pl.cnt, pl.row_start, pl.item_start, pl.order, rank_out);                                         \
-        if (row_key)                                                                                                            \
-            PC_LAUNCH((rb_rank_exclude_kernel<D, BIAS>), dim3(rows), dim3(64), 0, st, proj, types, targets, row_key, ex_rowptr,  \
-                      ex_col, n_keys, cand_type, table_bf16, bias, num_products, rank_out, bad_count);                          \
-    } while (0)
-    if (dim == 128) {
-        if (bias) RB_RANK(128, true); else RB_RANK(128, false);
-    } else {
-        if (bias) RB_RANK(256, true); else RB_RANK(256, false);
-    }
-#undef RB_RANK
+    RkStart s;
+    PC_TRY(rk_begin(s, proj && table_bf16, table_bf16, types, targets, row_key, rows, type_rowptr, type_col, n_types, num_products,
+                    ex_rowptr, ex_col, n_keys, cand_type, dim, slices, rank_out, bad_count, ws, ws_bytes, stream));
+    const RgPlan& pl = s.w.plan;
+    rk_dispatch(dim, bias != nullptr, [&](auto d, auto b) {
+        constexpr int D = decltype(d)::value;
+        constexpr bool BIAS = decltype(b)::value;
+        PC_LAUNCH((rb_rank_kernel<D, BIAS>), dim3(s.grid), dim3(256), 0, s.st, proj, targets, type_rowptr, type_col, table_bf16, bias,
+                  n_types, s.S, pl.cnt, pl.row_start, pl.item_start, pl.order, rank_out);
+        if (row_key)
+            PC_LAUNCH((rb_rank_exclude_kernel<D, BIAS>), dim3(rows), dim3(64), 0, s.st, proj, types, targets, row_key, ex_rowptr,
+                      ex_col, n_keys, cand_type, table_bf16, bias, num_products, rank_out, bad_count);
+    });
     return pc_launch_status();
 }

@@ -21,10 +21,7 @@
 // [_where] and pc_rank_grouped_bf16 give it; the predicate reads no score; the count is a sum of integers.  With every array of
 // the filter absent: pc_rank_grouped_bf16's output.  No float atomics, no readback.
 #include "common.h"
-#include "grouped_select.h"        // the item decode
-#include "grouped_plan.h"          // rg_better
-#include "rank_chain_bf16.h"
-#include "where_rank.h"
+#include "grouped_rank.h"          // rk_post: the row post-pass; rk_begin, rk_dispatch
 
 // One work item's candidate stream for a tile of NG 16-row groups (rb_stream with the test in the count).  bn / pidn / bsn / an /
 // fn: the first chunk's rows, product ids, terms and attributes, pidnn: the second chunk's ids, all already in flight (-1: a
@@ -162,67 +159,9 @@ __global__ __launch_bounds__(64) void wrb_post_kernel(const float* __restrict__ 
                                                       const uint16_t* __restrict__ table, const float* __restrict__ bias,
                                                       int num_products, pc_row_where wh, int32_t* __restrict__ rank_out,
                                                       int32_t* __restrict__ bad_count) {
-    constexpr int NB = D / 32;
-    __shared__ __attribute__((aligned(16))) bf16x8 q[3][(D / 8) * 16];
-    const int lane = threadIdx.x, c = lane & 15, h = lane >> 4;
-    const int r = blockIdx.x;
-    int key = -1;
-    if (row_key) {
-        key = row_key[r];
-        if (key < -1 || key >= n_keys) {
-            if (lane == 0) atomicAdd(bad_count, 1);
-            key = -1;
-        }
-    }
-    const int base = rank_out[r];
-    if (base < 0) return;                                 // (wave-uniform, as every exit below) no type, or an id out of range
-    const int t = types[r], y = targets[r];               // both inside their ranges: the plan counted the row
-    const WrRow w = wr_row(wh, r);
-    if ((row_key && cand_type[y] != t) || !wr_pass(w, wr_value(wh, y), wr_flags(wh, y))) {
-        if (lane == 0) rank_out[r] = -1;
-        return;
-    }
-    if (key < 0) return;
-    const int elo = ex_rowptr[key], len = ex_rowptr[key + 1] - elo;
-    if (len <= 0) return;
-    for (int e = lane; e < 16 * (D / 8); e += 64) {
-        const int d8 = e >> 4, row = e & 15;
-        float4 x0 = make_float4(0.f, 0.f, 0.f, 0.f), x1 = x0;
-        if (row == 0) {
-            const float4* f = reinterpret_cast<const float4*>(proj + (size_t)r * D) + 2 * d8;
-            x0 = f[0];
-            x1 = f[1];
-        }
-        const Split3 sp = split3(x0, x1);
-        q[0][d8 * 16 + row] = sp.p0;
-        q[1][d8 * 16 + row] = sp.p1;
-        q[2][d8 * 16 + row] = sp.p2;
-    }
-    __syncthreads();
-    float g = 0.f;
-    int dec = 0;
-    bool hit = false;
-    for (int v0 = 0; v0 <= len; v0 += 16) {               // column v: the target (v == 0), list entry v - 1
-        const int v = v0 + c;
-        int id = -1;
-        if (v == 0) id = y;
-        else if (v <= len) id = ex_col[elo + v - 1];
-        if (id >= num_products) id = -1;
-        bf16x8 b[NB];
-        rb_load_b<D>(b, table, id, h);
-        float bs = 0.f;
-        if constexpr (BIAS) bs = bias[max(id, 0)];
-        const bool ok = wr_pass(w, wr_value(wh, id), wr_flags(wh, id));
-        f32x4 acc[1] = {f32x4{0.f, 0.f, 0.f, 0.f}};
-        rb_chain<D, 16, 1>(q, 0, b, acc, c, h);
-        // C/D map of the 16x16 MFMAs: column lane & 15, row 4 (lane >> 4) + reg: row 0 is register 0 of lanes 0..15
-        const float s = BIAS ? acc[0][0] + bs : acc[0][0];
-        if (v0 == 0) g = __shfl(s, 0, 64);
-        const bool mine = h == 0 && v > 0 && id >= 0;
-        hit |= __any(mine && id == y);
-        dec += __popcll(__ballot(mine && id != y && ok && cand_type[max(id, 0)] == t && rg_better(s, id, g, y)));
-    }
-    if (lane == 0) rank_out[r] = hit ? -1 : base - dec;
+    __shared__ __attribute__((aligned(16))) typename RkScoreBf16<D>::Image q;
+    rk_post<D, RkScoreBf16<D>, BIAS, true>(q, proj, types, targets, row_key, ex_rowptr, ex_col, n_keys, cand_type, table, bias,
+                                           num_products, wh, rank_out, bad_count);
 }
 
 extern "C" size_t pc_rank_grouped_bf16_where_workspace_bytes(int rows, int n_types, int slices) {
@@ -235,33 +174,19 @@ extern "C" int pc_rank_grouped_bf16_where(const float* proj, const int32_t* type
                                           const int32_t* ex_rowptr, const int32_t* ex_col, int n_keys, const int32_t* cand_type,
                                           int dim, int slices, int32_t* rank_out, int32_t* bad_count, const pc_row_where* where,
                                           void* ws, size_t ws_bytes, void* stream) {
-    if (!proj || !types || !targets || !type_rowptr || !type_col || !table_bf16 || !rank_out || !bad_count || !ws)
-        return PC_EINVAL;
-    if (!wr_where_ok(where)) return PC_EINVAL;            // a null filter, or a half-given one
-    if (rows <= 0 || n_types <= 0 || num_products <= 0) return PC_EINVAL;
-    // the lists and the products' types: all or none
-    if (!rg_lists_ok(row_key, ex_rowptr, ex_col, bad_count, n_keys) || !row_key != !cand_type) return PC_EINVAL;
-    if ((dim != 128 && dim != 256) || slices < 0 || slices > RG_MAX_SLICES) return PC_ESHAPE;
-    if ((uintptr_t)table_bf16 & 15) return PC_ESHAPE;     // a lane reads 16 bytes of a row at once
-    const int S = rg_slices(slices);
-    hipStream_t st = (hipStream_t)stream;
-    RgWs w;
-    unsigned grid;
-    PC_TRY(rg_begin(w, grid, ws, ws_bytes, types, targets, rows, type_rowptr, n_types, num_products, 0, S, 8192 / dim, rank_out,
-                    bad_count, st));
-    const RgPlan& pl = w.plan;
-#define WRB_RANK(D, BIAS)                                                                                                      \
-    do {                                                                                                                       \
-        PC_LAUNCH((wrb_rank_kernel<D, BIAS>), dim3(grid), dim3(256), 0, st, proj, targets, type_rowptr, type_col, table_bf16,  \
-                  bias, n_types, S, pl.cnt, pl.row_start, pl.item_start, pl.order, rank_out, *where);                          \
-        PC_LAUNCH((wrb_post_kernel<D, BIAS>), dim3(rows), dim3(64), 0, st, proj, types, targets, row_key, ex_rowptr, ex_col,   \
-                  n_keys, cand_type, table_bf16, bias, num_products, *where, rank_out, bad_count);                             \
-    } while (0)
-    if (dim == 128) {
-        if (bias) WRB_RANK(128, true); else WRB_RANK(128, false);
-    } else {
-        if (bias) WRB_RANK(256, true); else WRB_RANK(256, false);
-    }
-#undef WRB_RANK
+    RkStart s;
+    // (args_ok: a null filter, or a half-given one, too)
+    PC_TRY(rk_begin(s, proj && table_bf16 && wr_where_ok(where), table_bf16, types, targets, row_key, rows, type_rowptr, type_col,
+                    n_types, num_products, ex_rowptr, ex_col, n_keys, cand_type, dim, slices, rank_out, bad_count, ws, ws_bytes,
+                    stream));
+    const RgPlan& pl = s.w.plan;
+    rk_dispatch(dim, bias != nullptr, [&](auto d, auto b) {
+        constexpr int D = decltype(d)::value;
+        constexpr bool BIAS = decltype(b)::value;
+        PC_LAUNCH((wrb_rank_kernel<D, BIAS>), dim3(s.grid), dim3(256), 0, s.st, proj, targets, type_rowptr, type_col, table_bf16,
+                  bias, n_types, s.S, pl.cnt, pl.row_start, pl.item_start, pl.order, rank_out, *where);
+        PC_LAUNCH((wrb_post_kernel<D, BIAS>), dim3(rows), dim3(64), 0, s.st, proj, types, targets, row_key, ex_rowptr, ex_col,
+                  n_keys, cand_type, table_bf16, bias, num_products, *where, rank_out, bad_count);
+    });
     return pc_launch_status();
 }

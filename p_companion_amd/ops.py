@@ -2275,6 +2275,60 @@ def retrieve_list_grouped_biased(proj, types, type_rowptr, type_col, table, bias
                              bias=bias, what="retrieve_list_grouped_biased", tag="retrieve_list")
 
 
+def _check_rank_lists(what, exclude, cand_type, types, table):
+    """A rank function's exclude triple beside its cand_type, checked on the host side alone (ValueError): both or neither, the
+    triple as _check_exclude has it, cand_type an int32 tensor of one entry per product -> the checked triple (None: none)."""
+    if exclude is None:
+        if cand_type is not None:
+            raise ValueError(f"{what}: cand_type is read with an exclude triple only")
+        return None
+    exclude = _check_exclude(what, exclude, types.shape[0] if isinstance(types, torch.Tensor) else -1)
+    if cand_type is None:
+        raise ValueError(f"{what}: exclude needs cand_type (the type under which each product is a candidate)")
+    if not isinstance(cand_type, torch.Tensor) or cand_type.dtype != torch.int32 or cand_type.dim() != 1 \
+            or cand_type.shape[0] != table.shape[0]:
+        raise ValueError(f"{what}: cand_type must be an int32 tensor of one entry per product")
+    return exclude
+
+
+def _req_rank_extras(exclude, cand_type, bias, p):
+    """The device checks of a rank call's cand_type (read with a triple only) and bias."""
+    if exclude is not None:
+        _req(cand_type, torch.int32, "cand_type", (p,))
+    if bias is not None:
+        _req(bias, torch.float32, "bias", (p,))
+
+
+def _rank_call(name, what, proj, types, targets, type_rowptr, type_col, table, table_dtype, slices, bad, exclude, cand_type, bias,
+               where=None, sized_as=None):
+    """Rank entry `name` behind its function's own checks -> (rank [R] int32, bad [1] int32): the rows, the outputs, the lists
+    as device arguments and the device checks of cand_type and bias, then the arguments in the header's order --
+    pc_rank_grouped's short list, or the filtered entries' (bias behind table in every entry but pc_rank_grouped_excluding, a
+    pc_row_where behind bad_count).  Without a triple row_key, ex_rowptr, ex_col and cand_type are None, without a bias it
+    too: null pointers, n_keys 0.  where (a RowWhere): its lengths against P and R and the device checks come before anything
+    is allocated; the functions without one have always allocated first, and keep that order."""
+    proj, r, t, d, slices = _grouped_rows(proj, types, type_rowptr, type_col, table, table_dtype, slices)
+    _req(targets, torch.int32, "targets", (r,))
+    p, device = table.shape[0], proj.device
+    tail = ()
+    if where is not None:
+        tail = (ctypes.byref(where._struct(what, p, r)),)
+        _req_rank_extras(exclude, cand_type, bias, p)
+    rank = torch.empty(r, dtype=torch.int32, device=device)
+    row_key, ex_rowptr, ex_col, n_keys, bad = _filter_args(exclude, bad, device, counted=True)
+    if where is None:
+        _req_rank_extras(exclude, cand_type, bias, p)
+    if name == "pc_rank_grouped":
+        args = (proj.data_ptr(), types.data_ptr(), targets.data_ptr(), r, type_rowptr.data_ptr(), type_col.data_ptr(),
+                table.data_ptr(), t, p, d, slices, rank.data_ptr(), bad.data_ptr())
+    else:
+        args = (proj.data_ptr(), types.data_ptr(), targets.data_ptr(), _p(row_key), r, type_rowptr.data_ptr(), type_col.data_ptr(),
+                table.data_ptr(), *(() if name == "pc_rank_grouped_excluding" else (_p(bias),)), t, p, _p(ex_rowptr), _p(ex_col),
+                n_keys, _p(cand_type), d, slices, rank.data_ptr(), bad.data_ptr(), *tail)
+    _grouped_call(name, "rank_grouped", device, (r, t, slices), args, sized_as)
+    return rank, bad
+
+
 def rank_grouped(proj, types, targets, type_rowptr, type_col, table, slices=0, bad=None, exclude=None, cand_type=None,
                  bias=None):
     """pc_rank_grouped: for row r the number of products of type types[r] that retrieve_topk_grouped orders in front of
@@ -2293,38 +2347,13 @@ def rank_grouped(proj, types, targets, type_rowptr, type_col, table, slices=0, b
     position rank.  bias=None: exactly the calls above."""
     if bias is not None:
         _check_bias("rank_grouped", bias, table)
-    if exclude is not None:
-        exclude = _check_exclude("rank_grouped", exclude, types.shape[0] if isinstance(types, torch.Tensor) else -1)
-        if cand_type is None:
-            raise ValueError("rank_grouped: exclude needs cand_type (the type under which each product is a candidate)")
-        if not isinstance(cand_type, torch.Tensor) or cand_type.dtype != torch.int32 or cand_type.dim() != 1 \
-                or cand_type.shape[0] != table.shape[0]:
-            raise ValueError("rank_grouped: cand_type must be an int32 tensor of one entry per product")
-    elif cand_type is not None:
-        raise ValueError("rank_grouped: cand_type is read with an exclude triple only")
-    proj, r, t, d, slices = _grouped_rows(proj, types, type_rowptr, type_col, table, torch.float32, slices)
-    _req(targets, torch.int32, "targets", (r,))
-    p, device = table.shape[0], proj.device
-    rank = torch.empty(r, dtype=torch.int32, device=device)
-    row_key, ex_rowptr, ex_col, n_keys, bad = _filter_args(exclude, bad, device, counted=True)
-    if bias is None and exclude is None:
-        name, sized_as = "pc_rank_grouped", None
-        args = (proj.data_ptr(), types.data_ptr(), targets.data_ptr(), r, type_rowptr.data_ptr(), type_col.data_ptr(),
-                table.data_ptr(), t, p, d, slices, rank.data_ptr(), bad.data_ptr())
+    exclude = _check_rank_lists("rank_grouped", exclude, cand_type, types, table)
+    if bias is not None:
+        name, sized_as = "pc_rank_grouped_biased", None
     else:
-        # (the filtered entries' list, bias behind table where the entry has it; without a triple row_key, ex_rowptr, ex_col
-        # and cand_type are None: null pointers, n_keys 0)
-        if exclude is not None:
-            _req(cand_type, torch.int32, "cand_type", (p,))
-        if bias is None:
-            name, sized_as, bias = "pc_rank_grouped_excluding", "pc_rank_grouped", ()
-        else:
-            name, sized_as, bias = "pc_rank_grouped_biased", None, (_req(bias, torch.float32, "bias", (p,)).data_ptr(),)
-        args = (proj.data_ptr(), types.data_ptr(), targets.data_ptr(), _p(row_key), r, type_rowptr.data_ptr(),
-                type_col.data_ptr(), table.data_ptr(), *bias, t, p, _p(ex_rowptr), _p(ex_col), n_keys, _p(cand_type), d, slices,
-                rank.data_ptr(), bad.data_ptr())
-    _grouped_call(name, "rank_grouped", device, (r, t, slices), args, sized_as)
-    return rank, bad
+        name, sized_as = ("pc_rank_grouped" if exclude is None else "pc_rank_grouped_excluding"), "pc_rank_grouped"
+    return _rank_call(name, "rank_grouped", proj, types, targets, type_rowptr, type_col, table, torch.float32, slices, bad, exclude,
+                      cand_type, bias, sized_as=sized_as)
 
 
 def half_sq_norm_bias_bf16(table):
@@ -2481,31 +2510,9 @@ def rank_grouped_bf16(proj, types, targets, type_rowptr, type_col, table, slices
     _check_bf16_table(what, table, "rank_grouped")
     if bias is not None:
         _check_bias_bf16(what, bias, table)
-    if exclude is not None:
-        exclude = _check_exclude(what, exclude, types.shape[0] if isinstance(types, torch.Tensor) else -1)
-        if cand_type is None:
-            raise ValueError(f"{what}: exclude needs cand_type (the type under which each product is a candidate)")
-        if not isinstance(cand_type, torch.Tensor) or cand_type.dtype != torch.int32 or cand_type.dim() != 1 \
-                or cand_type.shape[0] != table.shape[0]:
-            raise ValueError(f"{what}: cand_type must be an int32 tensor of one entry per product")
-    elif cand_type is not None:
-        raise ValueError(f"{what}: cand_type is read with an exclude triple only")
-    proj, r, t, d, slices = _grouped_rows(proj, types, type_rowptr, type_col, table, torch.bfloat16, slices)
-    _req(targets, torch.int32, "targets", (r,))
-    p, device = table.shape[0], proj.device
-    rank = torch.empty(r, dtype=torch.int32, device=device)
-    row_key, ex_rowptr, ex_col, n_keys, bad = _filter_args(exclude, bad, device, counted=True)
-    if exclude is not None:
-        _req(cand_type, torch.int32, "cand_type", (p,))
-    if bias is not None:
-        _req(bias, torch.float32, "bias", (p,))
-    # (the biased entry's list; without a triple row_key, ex_rowptr, ex_col and cand_type are None, without a bias it too:
-    # null pointers, n_keys 0)
-    args = (proj.data_ptr(), types.data_ptr(), targets.data_ptr(), _p(row_key), r, type_rowptr.data_ptr(), type_col.data_ptr(),
-            table.data_ptr(), _p(bias), t, p, _p(ex_rowptr), _p(ex_col), n_keys, _p(cand_type), d, slices, rank.data_ptr(),
-            bad.data_ptr())
-    _grouped_call("pc_rank_grouped_bf16", "rank_grouped", device, (r, t, slices), args)
-    return rank, bad
+    exclude = _check_rank_lists(what, exclude, cand_type, types, table)
+    return _rank_call("pc_rank_grouped_bf16", what, proj, types, targets, type_rowptr, type_col, table, torch.bfloat16, slices, bad,
+                      exclude, cand_type, bias)
 
 
 def rank_grouped_where(proj, types, targets, type_rowptr, type_col, table, where, slices=0, bad=None, exclude=None,
@@ -2537,33 +2544,9 @@ def rank_grouped_where(proj, types, targets, type_rowptr, type_col, table, where
                              f"{(table.dtype, tuple(table.shape)) if isinstance(table, torch.Tensor) else type(table).__name__}")
         if bias is not None:
             _check_bias(what, bias, table)
-    if exclude is not None:
-        exclude = _check_exclude(what, exclude, types.shape[0] if isinstance(types, torch.Tensor) else -1)
-        if cand_type is None:
-            raise ValueError(f"{what}: exclude needs cand_type (the type under which each product is a candidate)")
-        if not isinstance(cand_type, torch.Tensor) or cand_type.dtype != torch.int32 or cand_type.dim() != 1 \
-                or cand_type.shape[0] != table.shape[0]:
-            raise ValueError(f"{what}: cand_type must be an int32 tensor of one entry per product")
-    elif cand_type is not None:
-        raise ValueError(f"{what}: cand_type is read with an exclude triple only")
-    proj, r, t, d, slices = _grouped_rows(proj, types, type_rowptr, type_col, table, torch.bfloat16 if bf16 else torch.float32,
-                                          slices)
-    _req(targets, torch.int32, "targets", (r,))
-    p, device = table.shape[0], proj.device
-    st = where._struct(what, p, r)                        # (the lengths against P and R, before anything is allocated)
-    if exclude is not None:
-        _req(cand_type, torch.int32, "cand_type", (p,))
-    if bias is not None:
-        _req(bias, torch.float32, "bias", (p,))
-    rank = torch.empty(r, dtype=torch.int32, device=device)
-    row_key, ex_rowptr, ex_col, n_keys, bad = _filter_args(exclude, bad, device, counted=True)
-    # (pc_rank_grouped_bf16's list; without a triple row_key, ex_rowptr, ex_col and cand_type are None, without a bias it too:
-    # null pointers, n_keys 0)
-    args = (proj.data_ptr(), types.data_ptr(), targets.data_ptr(), _p(row_key), r, type_rowptr.data_ptr(), type_col.data_ptr(),
-            table.data_ptr(), _p(bias), t, p, _p(ex_rowptr), _p(ex_col), n_keys, _p(cand_type), d, slices, rank.data_ptr(),
-            bad.data_ptr(), ctypes.byref(st))
-    _grouped_call("pc_rank_grouped_bf16_where" if bf16 else "pc_rank_grouped_where", "rank_grouped", device, (r, t, slices), args)
-    return rank, bad
+    exclude = _check_rank_lists(what, exclude, cand_type, types, table)
+    return _rank_call("pc_rank_grouped_bf16_where" if bf16 else "pc_rank_grouped_where", what, proj, types, targets, type_rowptr,
+                      type_col, table, torch.bfloat16 if bf16 else torch.float32, slices, bad, exclude, cand_type, bias, where=where)
 
 
 class ScoreMoments:

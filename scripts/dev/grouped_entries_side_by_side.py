@@ -2,9 +2,10 @@
 """Two builds of libpcompanion_hip.so side by side, no device involved: every workspace query of the type-grouped catalogue
 entries over a grid of (rows, n_types, n, slices) with each bound and one step past it, and the return code of refused calls
 of those entries -- the cases of the family's error-code tests (tests/test_gpu_retrieval_grouped.py, test_gpu_exclusions.py,
-test_gpu_retrieval_list.py, test_gpu_retrieval_bf16.py, test_gpu_compact_catalogue.py, test_gpu_nearest.py, test_gpu_rank_grouped.py and the *_host.py ones)
+test_gpu_retrieval_list.py, test_gpu_retrieval_bf16.py, test_gpu_compact_catalogue.py, test_gpu_nearest.py, test_gpu_rank_grouped.py, test_gpu_rank_bf16.py, test_gpu_where_rank.py and the *_host.py ones)
 and around them every single null pointer, every pair of two changed arguments out of the edge values below, and every
-combination of present / absent exclusion arguments.  No call here can launch: the workspace handed in is one byte short at
+combination of present / absent exclusion arguments, a bf16 table off its 16-byte alignment, and for the entries under a
+predicate every present / absent shape of the pc_row_where.  No call here can launch: the workspace handed in is one byte short at
 the most, and the pointers are never dereferenced before that check.
 
     python scripts/dev/grouped_entries_side_by_side.py PARENT.so CHILD.so
@@ -26,7 +27,7 @@ NS = (-1, 0, 1, 2, 15, 16, 17, 32, 33, 96, 97, 255, 256, 257)
 SLICES = (-1, 0, 1, 15, 16, 17, 63, 64, 65)
 TOPN = ("pc_retrieve_topk_grouped", "pc_retrieve_topk_grouped_excluding", "pc_retrieve_list_grouped",
         "pc_retrieve_topk_grouped_bf16", "pc_retrieve_list_grouped_bf16", "pc_retrieve_topk_grouped_biased")
-RANK = ("pc_rank_grouped", "pc_rank_grouped_biased")
+RANK = ("pc_rank_grouped", "pc_rank_grouped_biased", "pc_rank_grouped_bf16", "pc_rank_grouped_where", "pc_rank_grouped_bf16_where")
 
 # the entries' arguments in the order of the C ABI (include/pcompanion_hip.h)
 ARGS = {
@@ -47,6 +48,12 @@ ARGS = {
                                  "n_keys cand_type dim slices rank_out bad_count ws ws_bytes stream",
     "pc_rank_grouped_biased": "proj types targets row_key rows type_rowptr type_col table bias n_types num_products ex_rowptr ex_col "
                               "n_keys cand_type dim slices rank_out bad_count ws ws_bytes stream",
+    "pc_rank_grouped_bf16": "proj types targets row_key rows type_rowptr type_col table bias n_types num_products ex_rowptr ex_col "
+                            "n_keys cand_type dim slices rank_out bad_count ws ws_bytes stream",
+    "pc_rank_grouped_where": "proj types targets row_key rows type_rowptr type_col table bias n_types num_products ex_rowptr ex_col "
+                             "n_keys cand_type dim slices rank_out bad_count where ws ws_bytes stream",
+    "pc_rank_grouped_bf16_where": "proj types targets row_key rows type_rowptr type_col table bias n_types num_products ex_rowptr "
+                                  "ex_col n_keys cand_type dim slices rank_out bad_count where ws ws_bytes stream",
 }
 INTS = {"rows": (4, 0, -1), "n_types": (3, 0, -1), "num_products": (9, 0, -1), "n_keys": (2, 0, -1), "n": (10, 0, 1, 16, 17, 256, 257),
         "dim": (128, 256, 64, 192, 0), "slices": (0, 1, 64, -1, 65)}
@@ -94,10 +101,18 @@ def cases(entry, base):
                 kw["n_keys"] = nk
             for more in ({}, {"rows": 0}, {"n": 0}, {"dim": 192}):
                 yield {**kw, **{k: v for k, v in more.items() if k in names}}
-    if entry.endswith("bf16"):
+    if "bf16" in entry:                                               # a table that is not 16-byte aligned
         for off in (2, 8):
-            for more in ({}, {"n": 17}, {"row_key": None, "ex_rowptr": None, "ex_col": None, "n_keys": 0}):
-                yield {"table": ctypes.c_void_p(base["table"].value + off), **more}
+            for more in ({}, {"n": 17}, {"dim": 192}, {"slices": 65}, {"rows": 0}, {"bias": None},
+                         {"row_key": None, "ex_rowptr": None, "ex_col": None, "n_keys": 0},
+                         {"row_key": None, "ex_rowptr": None, "ex_col": None, "cand_type": None, "n_keys": 0}):
+                yield {"table": ctypes.c_void_p(base["table"].value + off), **{k: v for k, v in more.items() if k in names}}
+    if "where" in names:                                              # every present / absent shape of the pc_row_where
+        fields = [f for f, _ in _lib.RowWhere._fields_]
+        for present in itertools.product((False, True), repeat=len(fields)):
+            where = _lib.RowWhere(**{f: base["table"].value for f, on in zip(fields, present) if on})
+            for more in ({}, {"rows": 0}, {"dim": 192}, {"row_key": None}):
+                yield {"where": ctypes.pointer(where), **more}
 
 
 def run(L, entry, base, kw):
@@ -127,6 +142,8 @@ def main(parent, child):
         hist, diff, launched, count = collections.Counter(), 0, 0, 0
         for short in (0, None):                                        # a workspace of 0 bytes; one byte short
             base = {a: (INTS[a][0] if a in INTS else p) for a in names.split()}
+            if "where" in base:
+                base["where"] = ctypes.pointer(_lib.RowWhere())         # every part absent: every product passes
             base.update(ws_bytes=short, stream=None)
             for kw in cases(entry, base):
                 a, b = run(P, entry, base, kw), run(C, entry, base, kw)

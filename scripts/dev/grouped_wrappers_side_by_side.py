@@ -7,8 +7,8 @@ return at once, one fixed workspace and stream) -- so what is timed is the wrapp
 
     python scripts/dev/grouped_wrappers_side_by_side.py PARENT_TREE [CHILD_TREE] [--calls 4000] [--rounds 8] [--out FILE]
 
-Four cases (plain retrieval, biased + exclude retrieval, list + exclude, biased + exclude rank) at R = 6 rows, P = 9 products,
-D = 128; `--rounds` rounds, the two trees alternating inside a round, calls / rounds calls of a case at a time.  The subclass
+Six cases (plain retrieval, biased + exclude retrieval, list + exclude, and biased + exclude rank over the fp32 table, over the
+bf16 copy and under a full predicate) at R = 6 rows, P = 9 products, D = 128; `--rounds` rounds, the two trees alternating inside a round, calls / rounds calls of a case at a time.  The subclass
 inflates the absolute times and the rounds of one process vary by tens of per cent, so the times say little beside the counts;
 only parent against child means anything.  Prints ONE JSON line and, with --out, writes it.
 Exit status 1 when the public names or a signature differ."""
@@ -76,12 +76,18 @@ def cases(ops):
     proj, types, targets = dev(R, D), dev(R, dtype=i32), dev(R, dtype=i32)
     rowptr, col, table, bias, cand = dev(T + 1, dtype=i32), dev(P, dtype=i32), dev(P, D), dev(P), dev(P, dtype=i32)
     exclude = (dev(R, dtype=i32), dev(KEYS + 1, dtype=i32), dev(5, dtype=i32))
+    table16 = dev(P, D, dtype=torch.bfloat16)
+    where = ops.RowWhere(value=dev(P), flags=dev(P, dtype=i32), lo=dev(R), hi=dev(R), need=dev(R, dtype=i32), deny=dev(R, dtype=i32))
     return {
         "retrieve_plain": lambda: ops.retrieve_topk_grouped(proj, types, rowptr, col, table, 10),
         "retrieve_biased_exclude": lambda: ops.retrieve_topk_grouped(proj, types, rowptr, col, table, 10, exclude=exclude, bias=bias),
         "list_exclude": lambda: ops.retrieve_list_grouped(proj, types, rowptr, col, table, 100, exclude=exclude),
         "rank_biased_exclude": lambda: ops.rank_grouped(proj, types, targets, rowptr, col, table, exclude=exclude, cand_type=cand,
                                                         bias=bias),
+        "rank_bf16_biased_exclude": lambda: ops.rank_grouped_bf16(proj, types, targets, rowptr, col, table16, exclude=exclude,
+                                                                  cand_type=cand, bias=bias),
+        "rank_where_biased_exclude": lambda: ops.rank_grouped_where(proj, types, targets, rowptr, col, table, where, exclude=exclude,
+                                                                    cand_type=cand, bias=bias),
     }
 
 
