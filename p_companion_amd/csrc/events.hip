@@ -33,7 +33,7 @@
 // which the sort removes, or sums.  No floats.  Every output is a function of the log as a multiset of rows.
 #include <climits>
 
-#include "common.h"
+#include "block_ops.h"             // wave_sum, wave_exclusive_sum
 #include "wave_sort.h"             // rlw_sort; grouped_plan.h: RG_NONE
 
 #define EV_MAX_EVENTS 1024
@@ -118,17 +118,6 @@ __device__ __forceinline__ void ev_pairs(const int* prod, const int* fv, const i
     }
 }
 
-__device__ __forceinline__ int ev_wave_exclusive_sum(int x, int lane, int& total) {
-    int inc = x;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int y = __shfl_up(inc, d, 64);
-        inc += lane >= d ? y : 0;
-    }
-    total = __shfl(inc, 63, 64);
-    return inc - x;
-}
-
 // ---- sessions ---------------------------------------------------------------------------------------------------------
 template <int NE>
 __global__ __launch_bounds__(64) void ev_sessions_kernel(uint32_t S, const int32_t* __restrict__ rowptr, int2* bucket,
@@ -174,7 +163,7 @@ __global__ __launch_bounds__(64) void ev_sessions_kernel(uint32_t S, const int32
             mine += (head[e] ? 1 : 0) + (tail[e] ? 1 << 16 : 0);
         }
         int all;
-        const int first = ev_wave_exclusive_sum(mine, lane, all);
+        const int first = wave_exclusive_sum(mine, lane, all);
         const int m = all & 0xffff;                        // the session's items (= its tails)
         int h = first & 0xffff, t = first >> 16;
 #pragma unroll
@@ -220,9 +209,7 @@ __global__ __launch_bounds__(256) void ev_totals_kernel(uint32_t S, const int32_
     }
 #pragma unroll
     for (int k = 0; k < EV_TOTALS; k++) {
-        unsigned long long v = t[k];
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
+        const unsigned long long v = wave_sum(t[k]);
         if ((threadIdx.x & 63) == 0 && v) atomicAdd(&totals[k], v);
     }
 }

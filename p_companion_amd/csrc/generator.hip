@@ -14,7 +14,7 @@
 //             probability 1 (same category) / 2/3 (different) -- the 1.5x of [107-108]; distinct within a row
 //   similarity pair = co-view edge with purchase-after-view (0.2) and without co-purchase (0.075 same / 0.15)  [110-121]
 //   complementary pair = Poisson(4.5) targets per product, kept 0.5 (same) / 1.0 (different), not co-viewed    [122-127]
-#include "common.h"
+#include "block_ops.h"
 
 enum { GEN_TYPE = 1, GEN_FEAT = 2, GEN_DEG = 3, GEN_EDGE = 4, GEN_COMP = 5 };
 #define GEN_CAP_MAX 64
@@ -91,7 +91,7 @@ __global__ void gen_degrees_kernel(uint32_t P, double mean_degree, int cap, doub
     }
 }
 
-// ---- exclusive scan of int32 counts -> int32 offsets [n + 1] (three launches: chunk sums, scan of the sums, offsets)
+// ---- exclusive scan of int32 counts -> int32 offsets [n + 1] (chunk sums, scan of the sums, offsets; block_ops.h's pieces)
 #define SCAN_CHUNK 4096
 __global__ __launch_bounds__(1024) void scan_chunk_sums_kernel(const int32_t* in, uint32_t n, long long* sums) {
     __shared__ long long red[16];
@@ -99,8 +99,7 @@ __global__ __launch_bounds__(1024) void scan_chunk_sums_kernel(const int32_t* in
     long long s = 0;
 #pragma unroll
     for (int i = 0; i < 4; i++) s += base + i < n ? in[base + i] : 0;
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) s += __shfl_xor(s, o, 64);
+    s = wave_sum(s);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -116,15 +115,7 @@ __global__ __launch_bounds__(1024) void scan_sums_kernel(long long* sums, int nb
     const int lo = t * per, hi = min(nblocks, lo + per);
     long long s = 0;
     for (int i = lo; i < hi; i++) s += sums[i];
-    part[t] = s;
-    __syncthreads();
-    for (int o = 1; o < 1024; o <<= 1) {
-        const long long v = t >= o ? part[t - o] : 0;
-        __syncthreads();
-        part[t] += v;
-        __syncthreads();
-    }
-    long long run = part[t] - s;
+    long long run = block_scan_1024(s, part) - s;
     for (int i = lo; i < hi; i++) { const long long v = sums[i]; sums[i] = run; run += v; }
     if (t == 1023) *total = part[1023];
 }
@@ -134,22 +125,21 @@ __global__ __launch_bounds__(1024) void scan_offsets_kernel(const int32_t* in, u
     int v[4], s = 0;
 #pragma unroll
     for (int i = 0; i < 4; i++) { v[i] = base + i < n ? in[base + i] : 0; s += v[i]; }
-    int inc = s;                                             // inclusive scan of the thread sums inside the wave
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) { const int t = __shfl_up(inc, o, 64); if (lane >= o) inc += t; }
-    if (lane == 63) wsum[w] = inc;
+    int wtot;
+    const int before = wave_exclusive_sum(s, lane, wtot);   // the thread sums of the lower lanes
+    if (lane == 63) wsum[w] = wtot;
     __syncthreads();
     int woff = 0;
     for (int i = 0; i < w; i++) woff += wsum[i];
-    long long run = sums[blockIdx.x] + woff + (inc - s);
+    long long run = sums[blockIdx.x] + woff + before;
 #pragma unroll
     for (int i = 0; i < 4; i++) {
         if (base + i < n) out[base + i] = (int32_t)run;
         run += v[i];
     }
     if (base <= n && n < base + 4) {                        // the thread whose range holds position n writes out[n] = total
-        long long r2 = sums[blockIdx.x] + woff + (inc - s);
+        long long r2 = sums[blockIdx.x] + woff + before;
         for (uint32_t i = base; i < n; i++) r2 += v[i - base];
         out[n] = (int32_t)r2;
     }

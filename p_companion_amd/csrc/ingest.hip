@@ -13,7 +13,7 @@
 //             ascending, bit 31 set on the kept ones (the full set answers "is this edge co-viewed", the kept ones are the
 //             neighbour list).  Three row classes by RAW length n:
 //               n <= ING_WAVE_ROW_MAX   one wave per row, wave_sort.h's bitonic network in registers
-//               n <= ING_LDS_ROW_MAX    one workgroup per row, LSD radix sort (8-bit digits) between two LDS buffers
+//               n <= ING_LDS_ROW_MAX    one workgroup per row, block_ops.h's LSD radix sort (8-bit digits) between two LDS buffers
 //               longer                  one workgroup per row, the same radix sort between the bucket and a scratch buffer
 //             The selection needs no second sort: the threshold weight w* (largest w with at least cap ids of weight >= w)
 //             is bisected by counting, ids above it are kept, and of the ids AT it the first cap - #above in id order.
@@ -23,7 +23,7 @@
 //
 // Integer atomics only (counters, cursors, the flag word, a maximum), and they decide arrival order or nothing: every array
 // written is a function of the lists as SETS (co_view: as a multiset), so a permuted input gives identical bits.
-#include "common.h"
+#include "block_ops.h"             // block_rank, block_sum and the radix pass
 #include "wave_sort.h"
 
 #define ING_WAVE_ROW_MAX 128
@@ -71,89 +71,14 @@ __global__ __launch_bounds__(256) void ing_classify_kernel(uint32_t P, const int
 }
 
 // ---- the per-row pass -----------------------------------------------------------------------------------------------
-// Position of a thread's element among the tile's elements with `pred`, in thread order, and their number.  Every thread of
-// the workgroup calls it.  wsum: NT / 64 LDS ints.
-template <int NT>
-__device__ __forceinline__ int ing_tile_rank(bool pred, int* wsum, int& total) {
-    const unsigned long long m = __ballot(pred);
-    const int lane = threadIdx.x & 63;
-    int r = __popcll(m & ((1ull << lane) - 1ull));
-    if constexpr (NT > 64) {
-        const int w = threadIdx.x >> 6;
-        if (lane == 0) wsum[w] = __popcll(m);
-        __syncthreads();
-        int tot = 0;
-#pragma unroll
-        for (int i = 0; i < NT / 64; i++) { const int c = wsum[i]; r += i < w ? c : 0; tot += c; }
-        total = tot;
-        __syncthreads();
-    } else {
-        total = __popcll(m);
-    }
-    return r;
-}
-
-template <int NT>
-__device__ __forceinline__ int ing_block_sum(int c, int* wsum) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) c += __shfl_xor(c, o, 64);
-    if constexpr (NT > 64) {
-        if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = c;
-        __syncthreads();
-        c = 0;
-#pragma unroll
-        for (int i = 0; i < NT / 64; i++) c += wsum[i];
-        __syncthreads();
-    }
-    return c;
-}
-
-// One stable pass of the LSD radix sort over the 8-bit digit at `shift`: src[0, n) -> dst[0, n).  base: 256 LDS ints, wcnt:
-// NT / 64 x 256 LDS ints.  Tiles of NT elements in order; inside a tile an element's place among those of its digit is its
-// wave's offset (the waves' counts per digit) plus its rank in the wave (a ballot per digit bit).
-template <int NT>
+// One stable pass of the LSD radix sort over the 8-bit digit at `shift`: src[0, n) -> dst[0, n) (block_ops.h: the digit
+// histogram, the digit offsets, the tile scatter).  base: 256 LDS ints, wcnt: 4 x 256 LDS ints.
 __device__ __forceinline__ void ing_radix_pass(const int32_t* src, int32_t* dst, int n, int shift, int* base, int* wcnt) {
-    static_assert(NT == 256, "one thread per digit");
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    base[tid] = 0;
+    radix_hist<256>(src, 0, n, shift, base);
+    const int ex = radix_digit_offset(base, threadIdx.x);
     __syncthreads();
-    for (int i = tid; i < n; i += NT) atomicAdd(&base[((uint32_t)src[i] >> shift) & 255u], 1);
-    __syncthreads();
-    int ex = 0;
-    for (int d = 0; d < tid; d++) ex += base[d];
-    __syncthreads();
-    base[tid] = ex;
-    for (int b0 = 0; b0 < n; b0 += NT) {
-#pragma unroll
-        for (int q = 0; q < NT / 64; q++) wcnt[q * 256 + tid] = 0;
-        __syncthreads();                                      // (orders base[] of the previous tile / the scan as well)
-        const int i = b0 + tid;
-        const bool valid = i < n;
-        const uint32_t v = valid ? (uint32_t)src[i] : 0u;
-        const uint32_t d = (v >> shift) & 255u;
-        unsigned long long m = __ballot(valid);
-#pragma unroll
-        for (int b = 0; b < 8; b++) {
-            const bool bit = (d >> b) & 1u;
-            const unsigned long long bm = __ballot(valid && bit);
-            m &= bit ? bm : ~bm;
-        }
-        const int r = __popcll(m & ((1ull << lane) - 1ull));
-        if (valid && r == 0) wcnt[w * 256 + d] = __popcll(m);
-        __syncthreads();
-        if (valid) {
-            int pos = base[d] + r;
-#pragma unroll
-            for (int q = 0; q < NT / 64; q++) pos += q < w ? wcnt[q * 256 + d] : 0;
-            dst[pos] = (int32_t)v;
-        }
-        __syncthreads();
-        int t = 0;
-#pragma unroll
-        for (int q = 0; q < NT / 64; q++) t += wcnt[q * 256 + tid];
-        base[tid] += t;
-        __syncthreads();
-    }
+    base[threadIdx.x] = ex;
+    radix_scatter<256, false>(src, nullptr, dst, nullptr, 0, n, n, shift, base, wcnt);
 }
 
 // s[0, n): the row's raw targets sorted ascending; y[0, n): scratch.  Writes the row's D distinct ids ascending to dst[0, D)
@@ -173,7 +98,7 @@ __device__ __forceinline__ void ing_finish_row(int32_t* s, int32_t* y, int n, in
         if (i < n) { v = s[i]; head = i == 0 || s[i - 1] != v; }
         __syncthreads();
         int tot;
-        const int r = ing_tile_rank<NT>(head, wsum, tot);
+        const int r = block_rank<NT>(head, wsum, tot);
         if (head) { s[D + r] = v; y[D + r] = i; }
         D += tot;
         __syncthreads();
@@ -186,13 +111,13 @@ __device__ __forceinline__ void ing_finish_row(int32_t* s, int32_t* y, int n, in
             const int mid = lo + (hi - lo + 1) / 2;
             int c = 0;
             for (int p = tid; p < D; p += NT) c += ((p + 1 < D ? y[p + 1] : n) - y[p]) >= mid ? 1 : 0;
-            c = ing_block_sum<NT>(c, wsum);
+            c = block_sum<NT>(c, wsum);
             if (c >= cap) lo = mid; else hi = mid - 1;
         }
         wstar = lo;
         int c = 0;
         for (int p = tid; p < D; p += NT) c += ((p + 1 < D ? y[p + 1] : n) - y[p]) > wstar ? 1 : 0;
-        at = cap - ing_block_sum<NT>(c, wsum);
+        at = cap - block_sum<NT>(c, wsum);
     }
     int ties = 0;
     for (int b0 = 0; b0 < D; b0 += NT) {
@@ -206,7 +131,7 @@ __device__ __forceinline__ void ing_finish_row(int32_t* s, int32_t* y, int n, in
             tie = wgt == wstar;
         }
         int tot;
-        const int r = ing_tile_rank<NT>(tie, wsum, tot);
+        const int r = block_rank<NT>(tie, wsum, tot);
         if (p < D) {
             keep = keep || (tie && ties + r < at);
             dst[p] = (int32_t)((uint32_t)id | (cap > 0 && keep ? ING_FLAG : 0u));
@@ -276,9 +201,9 @@ __global__ __launch_bounds__(256) void ing_rows_block_kernel(const int32_t* __re
         if (IN_LDS) for (int i = threadIdx.x; i < n; i += 256) a[i] = bucket[(size_t)lo + i];
         __syncthreads();
         for (int p = 0; p < passes; p += 2) {
-            ing_radix_pass<256>(a, b, n, 8 * p, base, wcnt);
+            ing_radix_pass(a, b, n, 8 * p, base, wcnt);
             __syncthreads();
-            ing_radix_pass<256>(b, a, n, 8 * p + 8, base, wcnt);
+            ing_radix_pass(b, a, n, 8 * p + 8, base, wcnt);
             __syncthreads();
         }
         ing_finish_row<256>(a, b, n, cap, bucket + (size_t)lo, row, full_cnt, kept_cnt, max_kept, wsum);

@@ -6,7 +6,7 @@
 // The reference draws from CPython's sequential MT19937 stream (host path: host_mt.cpp, bit
 // exact).  This is the throughput path: the same rejection rules on a counter-based
 // Philox4x32-10 stream keyed by (seed; sample, step), so every sample draws independently.
-#include "common.h"
+#include "block_ops.h"             // block_scan_1024 (degree_scan_kernel)
 
 __device__ __forceinline__ void pairs_negatives_body(const int32_t* pair_ids, int B, const int32_t* sim_pairs,
                                                      const int32_t* sim_rowptr, const int32_t* sim_col, int n_products,
@@ -96,15 +96,7 @@ __global__ __launch_bounds__(1024) void degree_scan_kernel(const int32_t* anchor
 #pragma unroll
         for (int u = 0; u < 8; u++) s += d[u];
     }
-    part[t] = s;
-    __syncthreads();
-    for (int o = 1; o < 1024; o <<= 1) {                 // Hillis-Steele inclusive scan of the partials
-        const int v = t >= o ? part[t - o] : 0;
-        __syncthreads();
-        part[t] += v;
-        __syncthreads();
-    }
-    int run = part[t] - s;                               // exclusive prefix of this thread's chunk
+    int run = block_scan_1024(s, part) - s;              // exclusive prefix of this thread's chunk
     for (int b0 = lo; b0 < hi; b0 += 8) {
         int d[8];
         degrees8(b0, d);

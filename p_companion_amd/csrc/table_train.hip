@@ -8,13 +8,13 @@
 //                         [B, D] x [D, D] products and the type projection go through the library's NT GEMM; the row-wise
 //                         pass between them (x = pi * tp, both norms, the hinge, dpi) is one wave per sample -- the item half
 //                         of joint_rowwise_kernel, same expressions, for D = 128 and 256.
-//   pc_sparse_adam_rows   torch.optim.SparseAdam over the rows named by idx [R] (duplicates expected): an LSD radix sort of
-//                         (id, r) by id, 8-bit digits, stable -- so the sources of a row stay in ascending r -- then one wave per
+//   pc_sparse_adam_rows   torch.optim.SparseAdam over the rows named by idx [R] (duplicates expected): block_ops.h's LSD radix sort
+//                         of (id, r) by id, stable -- so the sources of a row stay in ascending r -- then one wave per
 //                         distinct row sums its sources in that order and updates the row's parameter and both moments.
 //                         No float atomics: the result is a function of the inputs alone.
 //
 // Integer atomics only (the `bad` counter, LDS digit counts), and none of them decides a value that is written.
-#include "common.h"
+#include "block_ops.h"
 
 #define TT_NT 1024                     // threads of the sorting workgroups
 #define TT_CHUNK 4096                  // keys per workgroup and pass of the multi-workgroup sort
@@ -35,54 +35,8 @@ __device__ __forceinline__ void tt_init_range(const int32_t* __restrict__ idx, u
         key[r] = ok ? (uint32_t)id : P;
         val[r] = r;
     }
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) nbad += __shfl_xor(nbad, o, 64);
+    nbad = wave_sum(nbad);
     if ((threadIdx.x & 63) == 0 && nbad) atomicAdd(bad, nbad);
-}
-
-// cnt[0, 256) (LDS, zeroed by the caller, barrier behind it) += the digit counts of key[lo, hi)
-__device__ __forceinline__ void tt_hist_range(const uint32_t* key, uint32_t lo, uint32_t hi, int shift, int* cnt) {
-    for (uint32_t i = lo + threadIdx.x; i < hi; i += TT_NT) atomicAdd(&cnt[(key[i] >> shift) & 255u], 1);
-}
-
-// One stable scatter of (key, val)[lo, hi) by the 8-bit digit at `shift`.  base[d] (LDS): where the next element of digit d
-// goes; wcnt: TT_NT / 64 x 256 LDS ints.  Tiles of TT_NT elements in order; inside a tile an element's place among those of
-// its digit is its wave's offset (the earlier waves' counts of the digit) plus its rank in the wave (a ballot per digit bit).
-__device__ __forceinline__ void tt_scatter_range(const uint32_t* skey, const uint32_t* sval, uint32_t* dkey, uint32_t* dval,
-                                                 uint32_t lo, uint32_t hi, uint32_t R, int shift, int* base, int* wcnt) {
-    constexpr int NW = TT_NT / 64;
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    for (uint32_t b0 = lo; b0 < hi; b0 += TT_NT) {
-        for (int q = tid; q < NW * 256; q += TT_NT) wcnt[q] = 0;
-        __syncthreads();                                      // (orders base[] of the previous tile / the caller's scan as well)
-        const uint32_t i = b0 + tid;
-        const bool valid = i < hi;
-        const uint32_t k = valid ? skey[i] : 0u, v = valid ? sval[i] : 0u;
-        const uint32_t d = (k >> shift) & 255u;
-        unsigned long long m = __ballot(valid);
-#pragma unroll
-        for (int b = 0; b < 8; b++) {
-            const bool bit = (d >> b) & 1u;
-            const unsigned long long bm = __ballot(valid && bit);
-            m &= bit ? bm : ~bm;
-        }
-        const int r = __popcll(m & ((1ull << lane) - 1ull));
-        if (valid && r == 0) wcnt[w * 256 + d] = __popcll(m);
-        __syncthreads();
-        if (valid) {
-            uint32_t pos = (uint32_t)(base[d] + r);
-            for (int q = 0; q < w; q++) pos += (uint32_t)wcnt[q * 256 + d];
-            if (pos < R) { dkey[pos] = k; dval[pos] = v; }    // (always, when base[] scans this pass's digit counts)
-        }
-        __syncthreads();
-        if (tid < 256) {
-            int t = 0;
-#pragma unroll
-            for (int q = 0; q < NW; q++) t += wcnt[q * 256 + tid];
-            base[tid] += t;
-        }
-        __syncthreads();
-    }
 }
 
 // R <= TT_SMALL_R: keys, every pass and nothing else, by one workgroup.  The sorted arrays end in buffer (passes & 1).
@@ -95,17 +49,10 @@ __global__ __launch_bounds__(TT_NT) void tt_sort_small_kernel(const int32_t* __r
     for (int p = 0; p < passes; p++) {
         const uint32_t* sk = (p & 1) ? key1 : key0; const uint32_t* sv = (p & 1) ? val1 : val0;
         uint32_t* dk = (p & 1) ? key0 : key1; uint32_t* dv = (p & 1) ? val0 : val1;
-        if (threadIdx.x < 256) cnt[threadIdx.x] = 0;
+        radix_hist<TT_NT>(sk, 0u, R, 8 * p, cnt);
+        if (threadIdx.x < 256) base[threadIdx.x] = radix_digit_offset(cnt, threadIdx.x);
         __syncthreads();
-        tt_hist_range(sk, 0, R, 8 * p, cnt);
-        __syncthreads();
-        if (threadIdx.x < 256) {
-            int ex = 0;
-            for (int d = 0; d < (int)threadIdx.x; d++) ex += cnt[d];
-            base[threadIdx.x] = ex;
-        }
-        __syncthreads();
-        tt_scatter_range(sk, sv, dk, dv, 0, R, R, 8 * p, base, wcnt);
+        radix_scatter<TT_NT, true>(sk, sv, dk, dv, 0u, R, R, 8 * p, base, wcnt);
         __syncthreads();
     }
 }
@@ -120,11 +67,8 @@ __global__ __launch_bounds__(TT_NT) void tt_init_kernel(const int32_t* __restric
 __global__ __launch_bounds__(TT_NT) void tt_hist_kernel(const uint32_t* __restrict__ key, uint32_t R, int shift, int nblk,
                                                        int32_t* counts) {
     __shared__ int cnt[256];
-    if (threadIdx.x < 256) cnt[threadIdx.x] = 0;
-    __syncthreads();
     const uint32_t lo = blockIdx.x * (uint32_t)TT_CHUNK, hi = min(R, lo + (uint32_t)TT_CHUNK);
-    tt_hist_range(key, lo, hi, shift, cnt);
-    __syncthreads();
+    radix_hist<TT_NT>(key, lo, hi, shift, cnt);
     if (threadIdx.x < 256) counts[threadIdx.x * nblk + blockIdx.x] = cnt[threadIdx.x];
 }
 
@@ -136,8 +80,7 @@ __global__ __launch_bounds__(256) void tt_scan_kernel(int nblk, int32_t* counts)
     for (int j = 0; j < nblk; j++) s += counts[d * nblk + j];
     tot[d] = s;
     __syncthreads();
-    int ex = 0;
-    for (int e = 0; e < d; e++) ex += tot[e];
+    int ex = radix_digit_offset(tot, d);
     for (int j = 0; j < nblk; j++) {
         const int c = counts[d * nblk + j];
         counts[d * nblk + j] = ex;
@@ -152,7 +95,7 @@ __global__ __launch_bounds__(TT_NT) void tt_scatter_kernel(const uint32_t* __res
     if (threadIdx.x < 256) base[threadIdx.x] = offsets[threadIdx.x * nblk + blockIdx.x];
     __syncthreads();
     const uint32_t lo = blockIdx.x * (uint32_t)TT_CHUNK, hi = min(R, lo + (uint32_t)TT_CHUNK);
-    tt_scatter_range(skey, sval, dkey, dval, lo, hi, R, shift, base, wcnt);
+    radix_scatter<TT_NT, true>(skey, sval, dkey, dval, lo, hi, R, shift, base, wcnt);
 }
 
 // ---- row-sparse Adam: the update -------------------------------------------------------------------------------------
@@ -324,8 +267,7 @@ __global__ __launch_bounds__(256) void tt_query_ids_kernel(const int32_t* __rest
         }
         zero[b] = nbad ? 1 : 0;
     }
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) nbad += __shfl_xor(nbad, o, 64);
+    nbad = wave_sum(nbad);
     if ((threadIdx.x & 63) == 0 && nbad) atomicAdd(bad, nbad);
 }
 

@@ -8,11 +8,14 @@
   100 k x 128 and 10 M x 128 products (a random table), B = 4096, K = 3, T = 100; the queries are drawn uniformly, and once more
   with a popular head (a fifth of the batch on 16 products) for the row-sparse Adam.
 
+  adam_1M     ops.sparse_adam_rows alone at R = 2^20 uniform rows of a 10 M x 128 table: the multi-workgroup sort (R > 8192;
+              the legs above run R = 4096, which one workgroup sorts) and the update over a million sources
+
 Host clock around a synchronised call, two untimed rounds first, median of `--reps` = 20; every single time is kept
 ("ms_all") so that the trained leg can be read against the frozen leg's own spread.  Prints ONE JSON line and, with --out,
 writes it.
 
-  python scripts/table_train_probe.py [--legs 100k,10M] [--reps 20] [--out profiles/table_train_probe.json]
+  python scripts/table_train_probe.py [--legs 100k,10M,adam_1M] [--reps 20] [--out profiles/table_train_probe.json]
 """
 import argparse
 import json
@@ -90,6 +93,25 @@ def leg(P, reps, dev):
     return out
 
 
+def adam_leg(reps, dev, P=10_000_000, R=1 << 20):
+    from p_companion_amd import ops
+    g = torch.Generator(device=dev).manual_seed(1)
+    table = torch.randn(P, D, generator=g, device=dev)
+    m, v = torch.zeros_like(table), torch.zeros_like(table)
+    idx = torch.randint(0, P, (R,), generator=g, device=dev, dtype=torch.int32)
+    grad = torch.randn(R, D, generator=g, device=dev)
+    bad = torch.zeros(1, dtype=torch.int32, device=dev)
+    step = [0]
+
+    def adam():
+        step[0] += 1
+        ops.sparse_adam_rows(table, m, v, idx, grad, step[0], bad=bad)
+
+    out = {"products": P, "dim": D, "rows": R, "entries": timed({"sparse_adam_uniform": adam}, reps)}
+    assert int(bad) == 0
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--legs", default="100k,10M")
@@ -101,7 +123,7 @@ def main():
     dev = torch.device("cuda")
     res = {"probe": "table_train", "device": torch.cuda.get_device_name(0), "legs": {}}
     for name in [s for s in args.legs.split(",") if s]:
-        res["legs"][name] = leg(LEGS[name], args.reps, dev)
+        res["legs"][name] = adam_leg(args.reps, dev) if name == "adam_1M" else leg(LEGS[name], args.reps, dev)
         torch.cuda.empty_cache()
     line = json.dumps(res)
     print(line, flush=True)

@@ -15,7 +15,7 @@ def cfg(dim=128):
                            MARGIN=1.0, DEVICE=torch.device("cuda"))
 
 
-@pytest.mark.parametrize("n", [1, 5, 4095, 4096, 4097, 8192, 1_000_003])
+@pytest.mark.parametrize("n", [1, 3, 4, 5, 255, 256, 257, 4095, 4096, 4097, 8192, 1_000_003])
 def test_exclusive_scan(n):
     from p_companion_amd import ops
     rng = np.random.default_rng(n)
